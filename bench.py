@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""bench.py — decode throughput of the RWKV hot path on MI355X, with roofline and CPU baseline.
+"""bench.py — decode throughput of the RWKV hot path on MI355X; with --full also roofline, CPU baseline and the other legs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload v6-3b] [--batch 32] [--quant int8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload v6-3b] [--batch 32] [--quant int8] [--dump-outputs DIR] [--full]
 
 A "step" is one decode step of the hot path over a batch of B slots (one token per slot: B tokens),
 inputs (weights, recurrent state, token ids) resident in HBM: the arg-max token is fed back on the device
@@ -14,9 +14,15 @@ from the environment) or by this file itself: `python bench.py --gpus N` with no
 ranks as child processes (gloo rendezvous on 127.0.0.1) and relays rank 0's line.  The barrier and the MAX of the timing go
 over gloo on the host; `n_gpus` in the line is the world size that actually ran, and it must equal `--gpus`.
 
-Legs of the default run (rank 0, N = 1; every leg carries its own roofline fraction and a verification flag):
-  * the headline: BASELINE config #3 (V6-3B Int8, 32 slots) + sweep B = 1, 8, PCIe-inclusive and on-device-sampling rates,
-    embeddings/s (256-token documents, state-only prefill, checked against a `Last` prefill of the same documents);
+A plain run does only what the headline needs: it synthesises the checkpoint, loads the engine, runs W warm-up steps, times EXACTLY K
+steps in one region (`value`, `ms_per_step`), writes that region's outputs when --dump-outputs is given, and prints the line.  The legs
+below are measured only with --full; in a plain run their keys are on the line with null values.
+
+Legs of a --full run (rank 0, N = 1; every leg carries its own roofline fraction and a verification flag):
+  * next to the headline (BASELINE config #3, V6-3B Int8, 32 slots): --repeats - 1 more timed regions for the spread (`timed_regions`),
+    the decode check (`tokens_verified`), the roofline, sweep B = 1, 8, PCIe-inclusive and on-device-sampling rates,
+    embeddings/s (256-token documents, state-only prefill, checked against a `Last` prefill of the same documents) — the serving
+    loops and the embeddings job on every rank when N > 1;
   * `configs`: #2 (V6-1.6B fp16, B = 1), V6-3B fp16 at B = 1 / 32, #4 (V7-2.9B NF4: B = 32 decode + `/embeddings` at
     token_chunk_size 256), #5 (V6-7B fp16: 8 x 4096-token prefill at chunk 2048 / 1024 + B = 8 decode);
   * `cpu_baseline`: the compiled restatement on the host cores (a reported baseline, never the target).
@@ -59,13 +65,20 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="fp16", choices=["fp16", "fp32", "fp16raw"],
                     help="rwkv_load_desc.precision: fp16 = the library's default (ABI 7: f16 operands, the error-carrying launches hi + lo; holds 1e-3 at "
                          "32 layers), fp32 = hi + lo everywhere, fp16raw = f16 operands on every launch (fastest, outside 1e-3 at depth)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps decode steps each; the line reports the MEDIAN region (and min / max)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well (spread, verification, roofline, sweep, serving loops, "
+                         "embeddings, other precisions, CPU baseline, other configurations); off: the headline decode only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed call computed in its last step as DIR/<name>.npy: every slot's greedy "
+                         "token id and a fixed seeded sample of the recurrent state it left in every slot")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: timed regions of --steps decode steps each, the headline's first; the line "
+                                                           "reports their spread under `timed_regions`")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--decode-only", action="store_true", help="headline decode + roofline only (profiling runs)")
+    ap.add_argument("--decode-only", action="store_true", help="--full: the headline decode + roofline only (profiling runs)")
     ap.add_argument("--sweep", default="1,8", help="extra batch sizes reported under 'sweep' (north_star: batch 1-32)")
     ap.add_argument("--verify-steps", type=int, default=8, help="decode steps re-run through rwkv_infer + host arg-max and compared")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (#2, #4, #5, V6-3B fp16)")
-    ap.add_argument("--config5", action="store_true", help="kept for old command lines: config #5 is part of the default run")
+    ap.add_argument("--config5", action="store_true", help="kept for old command lines: config #5 is part of the --full run")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="exercise launcher + rendezvous + barrier + MAX reduction with a stand-in workload (no GPU, no engine): CPU test of the N > 1 path")
     return ap.parse_args(argv)
@@ -318,27 +331,42 @@ def verify_decode(rt, eng, first, n_steps):
 
 
 def decode_point(job, eng, first, steps, warmup):
-    """EXACTLY `steps` timed decode steps bracketed by barrier + synchronize on both sides; MAX over ranks."""
+    """EXACTLY `steps` timed decode steps bracketed by barrier + synchronize on both sides; MAX over ranks.
+    Returns (MAX seconds, every rank's seconds, device ms, the token ids the timed call returned [steps, slots])."""
     if warmup > 0:
         eng.decode_greedy(first, warmup)
     job.barrier()
     t = time.perf_counter()
-    _, dev_ms = eng.decode_greedy(first, steps)
+    ids, dev_ms = eng.decode_greedy(first, steps)
     job.sync()
     dt = time.perf_counter() - t
     job.barrier()
     dt_max, dt_all = job.max_and_all(dt)
-    return dt_max, dt_all, dev_ms
+    return dt_max, dt_all, dev_ms, ids
 
 
-def decode_regions(job, eng, first, steps, warmup, repeats):
-    """`repeats` timed regions (each EXACTLY `steps` steps, bracketed like decode_point; the warm-up once in front of the first).  A 20-step
+def region_spread(job, eng, first, steps, repeats, head_ms):
+    """--full: `repeats` - 1 more timed regions after the headline's (each EXACTLY `steps` steps, bracketed like decode_point).  A 20-step
     region is 44 ms: one region's number moves by ~1 % from run to run, which is the size of most kernel A/B deltas —
-    so the line carries the MEDIAN region and the spread.  Returns (median region as decode_point's triple, [ms_per_step of every region])."""
-    regs = [decode_point(job, eng, first, steps, warmup if i == 0 else 0) for i in range(max(1, repeats))]
-    order = sorted(range(len(regs)), key=lambda i: regs[i][0])
-    med = regs[order[(len(regs) - 1) // 2]]
-    return med, [r[0] * 1e3 / steps for r in regs]
+    so the line carries the spread of the regions, the headline's included."""
+    ms = [head_ms] + [decode_point(job, eng, first, steps, 0)[0] * 1e3 / steps for _ in range(repeats - 1)]
+    s = sorted(ms)
+    return {"n": len(ms), "steps_each": steps, "ms_per_step": ms, "median": s[(len(s) - 1) // 2], "min": s[0], "max": s[-1],
+            "note": "`value` / `ms_per_step` are the first region's (each region: exactly --steps steps, barrier + synchronize on both sides)"}
+
+
+DUMP_STATE_ELEMS = 1 << 22      # --dump-outputs: state elements kept over all slots (16 MB of float32)
+
+
+def dump_outputs(out_dir, eng, ids):
+    """--dump-outputs: what the timed decode computed in its last step — every slot's greedy token id (the array the caller receives) and
+    the recurrent state the step left in the slot (read back with rwkv_state_back; the same seeded positions in every slot and every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "token_ids.npy"), np.asarray(ids[-1], dtype=np.float64))
+    B = ids.shape[1]
+    c, r, l, _ = eng.state.shape
+    pos = np.unique(np.random.default_rng(0).integers(0, c * r * l, DUMP_STATE_ELEMS // B))
+    np.save(os.path.join(out_dir, "state_sample.npy"), np.stack([eng.state.back(b).ravel()[pos] for b in range(B)]))
 
 
 def timed_on_all_ranks(job, fn, own_clock=False):
@@ -461,7 +489,7 @@ def config_leg(job, rt, R, name, quant, batches, steps, verify_steps, embed_chun
     V = info.num_vocab
     first = first_tokens(R, V, B)
     for nb in batches:
-        dt, _, _ = decode_point(job, eng, first[:nb], steps, min(5, steps))
+        dt = decode_point(job, eng, first[:nb], steps, min(5, steps))[0]
         ab = R.algorithmic_bytes(info, shapes, ql, qt, nb)
         out["decode"][str(nb)] = {"tokens_per_s": nb * steps / dt, "ms_per_step": dt * 1e3 / steps,
                                   "frac_of_hbm_peak": ab["per_step"] * (steps / dt) / HBM_PEAK}
@@ -502,7 +530,7 @@ def config_leg(job, rt, R, name, quant, batches, steps, verify_steps, embed_chun
         e.close()
     if raw:                                                  # the all-f16 opt-in next to the default: what the tolerance-holding default costs
         e = build_engine(rt, st, job.local_rank, ql, qt, B, embed_chunk or max(2048, B), "fp16raw")
-        dt, _, _ = decode_point(job, e, first, steps, min(5, steps))
+        dt = decode_point(job, e, first, steps, min(5, steps))[0]
         out["fp16_raw"] = {"precision": PRECISION_TEXT["fp16raw"], "decode": {str(B): {"tokens_per_s": B * steps / dt, "ms_per_step": dt * 1e3 / steps}},
                            "default_vs_raw_ms_per_step": out["decode"][str(B)]["ms_per_step"] / (dt * 1e3 / steps),
                            "tokens_verified": verify_decode(rt, e, first, verify_steps) if verify_steps > 0 else None}
@@ -607,13 +635,13 @@ def selftest_dist(job, args):
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "selftest", "data": "none",
                           "config": {"workload": "launcher self-test (sleep)"},
                           "per_rank_tokens_per_s": [B * args.steps / d for d in dt_all], "selftest": True,
-                          # the legs every rank of a real N > 1 run adds (same aggregation: all units over the slowest rank's time)
-                          "pcie_inclusive_tokens_per_s": B * job.world * args.steps / dt_max,
-                          "pcie_inclusive": {"value": B * job.world * args.steps / dt_max, "per_rank": [B * args.steps / d for d in dt_all]},
-                          "on_device_sampling_tokens_per_s": B * job.world * args.steps / dt_max,
-                          "on_device_sampling": {"value": B * job.world * args.steps / dt_max, "per_rank": [B * args.steps / d for d in dt_all]},
+                          # the legs every rank of a real N > 1 run adds with --full (same aggregation: all units over the slowest rank's time)
+                          "pcie_inclusive_tokens_per_s": B * job.world * args.steps / dt_max if args.full else None,
+                          "pcie_inclusive": {"value": B * job.world * args.steps / dt_max, "per_rank": [B * args.steps / d for d in dt_all]} if args.full else None,
+                          "on_device_sampling_tokens_per_s": B * job.world * args.steps / dt_max if args.full else None,
+                          "on_device_sampling": {"value": B * job.world * args.steps / dt_max, "per_rank": [B * args.steps / d for d in dt_all]} if args.full else None,
                           "embeddings": {"value": 8 * job.world / dt_max, "unit": "embeddings/s", "docs": 8 * job.world, "docs_per_rank": 8,
-                                         "per_rank_embeddings_per_s": [8 / d for d in dt_all]}}), flush=True)
+                                         "per_rank_embeddings_per_s": [8 / d for d in dt_all]} if args.full else None}), flush=True)
 
 
 def main(argv=None):
@@ -647,33 +675,39 @@ def main(argv=None):
     V = info.num_vocab
     first = first_tokens(R, V, B)
 
-    (dt, dt_all, dev_ms), region_ms = decode_regions(job, eng, first, args.steps, args.warmup, args.repeats)
+    dt, dt_all, dev_ms, ids = decode_point(job, eng, first, args.steps, args.warmup)
     ms_per_step = dt * 1e3 / args.steps
     value = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, ids)
 
-    tokens_verified = verify_decode(rt, eng, first, args.verify_steps) if rank == 0 and args.verify_steps > 0 else None
-    ab = R.algorithmic_bytes(info, shapes, ql, qt, B)
-    step_frac = ab["per_step"] * (args.steps / dt) / HBM_PEAK
+    full = args.full
     single = rank == 0 and world == 1
-    roof = roofline_leg(rt, R, eng, info, shapes, first, ms_per_step, args.workload, args.quant, step_frac, ab) if rank == 0 else None
+    timed_regions = region_spread(job, eng, first, args.steps, args.repeats, ms_per_step) if full else None
+    tokens_verified = verify_decode(rt, eng, first, args.verify_steps) if full and rank == 0 and args.verify_steps > 0 else None
+    roof = None
+    if full and rank == 0:
+        ab = R.algorithmic_bytes(info, shapes, ql, qt, B)
+        step_frac = ab["per_step"] * (args.steps / dt) / HBM_PEAK
+        roof = roofline_leg(rt, R, eng, info, shapes, first, ms_per_step, args.workload, args.quant, step_frac, ab)
 
     sweep = {}
-    if single and args.sweep:
+    if full and single and args.sweep:
         for nb in [int(x) for x in args.sweep.split(",") if x]:
             if nb > eng.max_batch:
                 continue
-            d2, _, _ = decode_point(job, eng, first[:nb], args.steps, min(args.warmup, 10))
+            d2 = decode_point(job, eng, first[:nb], args.steps, min(args.warmup, 10))[0]
             abn = R.algorithmic_bytes(info, shapes, ql, qt, nb)
             sweep[str(nb)] = {"tokens_per_s": nb * args.steps / d2, "ms_per_step": d2 * 1e3 / args.steps,
                               "frac_of_peak": abn["per_step"] * (args.steps / d2) / HBM_PEAK}
 
-    # On EVERY rank (the N > 1 line carries the whole metric, not only the device-resident loop — the host side is where replica
+    # --full, on EVERY rank (the N > 1 line carries the whole metric, not only the device-resident loop — the host side is where replica
     # scaling can break): the PCIe-inclusive rate through rwkv_infer (logits of every slot D2H every token, as
     # run.rs:809-832 receives them) — never `value`; the serving path with the on-device sampling front-end (rwkv_infer_sample: 8 bytes
     # per slot over PCIe); and the embeddings job.  Each is bracketed by barrier + synchronize like `value`, aggregated over the
     # slowest rank, with every rank's own rate beside it.
     pcie = sampled = emb = None
-    if not args.decode_only:
+    if full and not args.decode_only:
         nst = max(5, min(40, args.steps))
         d_max, d_all, _ = timed_on_all_ranks(job, lambda: eng.serve_loop_logits(first, nst), own_clock=True)
         pcie = {"value": B * nst * world / d_max, "unit": "tokens/s", "per_rank": [B * nst / d for d in d_all], "steps": nst}
@@ -698,7 +732,7 @@ def main(argv=None):
     # Precision::Fp32 — hi + lo f16 operands on every launch, measured <= 3e-5 at 32 layers — and RWKV_PRECISION_FP16_RAW — the fastest,
     # outside 1e-3 at depth.  What the tolerance-holding default costs is `default_vs_raw_ms_per_step`.
     others = None
-    if single and not args.decode_only and args.precision == "fp16":
+    if full and single and not args.decode_only and args.precision == "fp16":
         others = {}
         for mode in ("fp32", "fp16raw"):
             eo = build_engine(rt, st, job.local_rank, ql, qt, B, max(2048, B), mode)
@@ -706,7 +740,7 @@ def main(argv=None):
             for nb in sorted({B, 8, 1}, reverse=True):
                 if nb > B:
                     continue
-                d2, _, _ = decode_point(job, eo, first[:nb], args.steps, min(args.warmup, 10))
+                d2 = decode_point(job, eo, first[:nb], args.steps, min(args.warmup, 10))[0]
                 abn = R.algorithmic_bytes(info, shapes, ql, qt, nb)
                 rec["decode"][str(nb)] = {"tokens_per_s": nb * args.steps / d2, "ms_per_step": d2 * 1e3 / args.steps,
                                           "frac_of_hbm_peak": abn["per_step"] * (args.steps / d2) / HBM_PEAK}
@@ -722,12 +756,12 @@ def main(argv=None):
     del st
 
     cpu = None
-    if single and not args.no_cpu_baseline and not args.decode_only:
+    if full and single and not args.no_cpu_baseline and not args.decode_only:
         cpu = cpu_leg(R, tensors, ql, qt, first, args.workload, args.quant)
     del tensors
 
     configs = None
-    if single and not args.no_configs and not args.decode_only:
+    if full and single and not args.no_configs and not args.decode_only:
         vs, cs = args.verify_steps, min(args.steps, 50)
         configs = {}
         for key, kw in [("config2_v6-1.6b_fp16", dict(name="v6-1.6b", quant="none", batches=[1])),
@@ -748,9 +782,7 @@ def main(argv=None):
                 "per_rank_numa": numa,
                 "device_ms_per_step": dev_ms / args.steps,
                 "roofline": roof, "cpu_baseline": cpu, "embeddings": emb, "other_precisions": others,
-                "timed_regions": {"n": len(region_ms), "steps_each": args.steps, "ms_per_step": region_ms, "median": ms_per_step,
-                                  "min": min(region_ms), "max": max(region_ms),
-                                  "note": "`value` / `ms_per_step` are the MEDIAN region's (each region: exactly --steps steps, barrier + synchronize on both sides)"},
+                "timed_regions": timed_regions,
                 "pcie_inclusive_tokens_per_s": pcie["value"] if pcie else None, "pcie_inclusive": pcie,
                 "on_device_sampling_tokens_per_s": sampled["value"] if sampled else None, "on_device_sampling": sampled,
                 "sweep": sweep or None, "tokens_verified": tokens_verified,

@@ -14,7 +14,7 @@ for spec in sys.argv[1:]:
         env["RWKV_HIP_LIB"] = os.path.join(ROOT, lib)
     wl = env.get("AB_WORKLOAD", "v6-3b")
     q = env.get("AB_QUANT", "int8")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--decode-only", "--no-cpu-baseline", "--sweep", "8,1", "--steps", "40",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--decode-only", "--no-cpu-baseline", "--sweep", "8,1", "--steps", "40",
                         "--warmup", "5", "--workload", wl, "--quant", q], env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 // Round 6 dev tool (GPU box): what shader clock does the chip run at WHILE another process keeps it busy?  One wave spins ~1 ms and reports
 // clock64 (shader cycles) against wall_clock64 (the 100 MHz constant counter); sampled every 50 ms for `seconds`.  Run it beside the workload:
-//   ./clock_probe.bin 8 > idle.txt;   (./clock_probe.bin 20 > decode.txt &) ; python bench.py --decode-only ...
+//   ./clock_probe.bin 8 > idle.txt;   (./clock_probe.bin 20 > decode.txt &) ; python bench.py --full --decode-only ...
 // A wave's clock is its XCD's; the probe lands on whichever CU the dispatcher picks.
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd /tmp; export TMPDIR=/tmp
 python -c "import torch" 2>/dev/null   # (page the image in first)
 echo "idle:            $($R/scripts/clock_probe.bin 3)"
 $R/scripts/clock_probe.bin 16 > /tmp/clk_decode.txt & p=$!
-python $R/bench.py --decode-only --no-cpu-baseline --sweep= --verify-steps 0 --steps 1500 --warmup 5 --repeats 2 > /tmp/bench_clk.log 2>&1; echo "bench rc=$?"; wait $p
+python $R/bench.py --full --decode-only --no-cpu-baseline --sweep= --verify-steps 0 --steps 1500 --warmup 5 --repeats 2 > /tmp/bench_clk.log 2>&1; echo "bench rc=$?"; wait $p
 echo "decode B=32:     $(cat /tmp/clk_decode.txt)"
 $R/scripts/clock_probe.bin 16 > /tmp/clk_p2048.txt & p=$!
 for i in 1 2; do python $R/scripts/prefill_probe.py v6-3b 1 32 2048 2048 > /dev/null 2>&1; done; wait $p

@@ -23,7 +23,7 @@ run_stats () {   # name, then the command
   echo "stats $name rc=$? $(wc -c < $P/${TAG}_kernel_stats_$name.csv 2>/dev/null) bytes of summary"
   rm -rf $O/prof_$name                                     # the raw traces are hundreds of MB; gpurun_out/ is copied back only below 64 MiB
 }
-BENCH="python $R/bench.py --decode-only --no-cpu-baseline --sweep= --verify-steps 0 --steps 50 --warmup 5"
+BENCH="python $R/bench.py --full --decode-only --no-cpu-baseline --sweep= --verify-steps 0 --steps 50 --warmup 5"
 # every engine in the library's default precision (ABI 7: Precision::Fp16 = f16 operands, the error-carrying launches hi + lo); the other two modes of the
 # headline configuration and the raw mode of config #4 beside them
 run_stats v6-3b_int8_b32 $BENCH --workload v6-3b --quant int8 --batch 32

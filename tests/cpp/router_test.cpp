@@ -63,10 +63,13 @@ int main() {
         std::vector<FakeEngine *> es{&e0, &e1, &e2};
         ReplicaRouter<FakeEngine> router(es);
         RoutedRequest a, b, c;
-        a.tokens = {9, 8, 7, 6}; a.max_new = 3000;                        // long enough to still be in flight when b is routed
+        a.tokens = {9, 8, 7, 6}; a.max_new = 3000;
         b.tokens = {1, 2}; b.max_new = 2;
-        CHECK(router.submit(&a) == 0);                                   // all idle: lowest index
-        CHECK(router.submit(&b) == 1);                                   // replica 0 has one in flight: least busy is 1
+        e0.hold = true;                                                  // a is still in flight when b is routed, however the threads run
+        const int where_a = router.submit(&a), where_b = router.submit(&b);
+        e0.hold = false;                                                 // (released before any CHECK: a failed CHECK must not hang the thread)
+        CHECK(where_a == 0);                                             // all idle: lowest index
+        CHECK(where_b == 1);                                             // replica 0 has one in flight: least busy is 1
         router.drain();
         Tokens follow = a.tokens;
         follow.insert(follow.end(), a.generated.begin(), a.generated.end());       // what replica 0 cached at finish: prompt + every fed token
@@ -130,7 +133,10 @@ int main() {
         std::deque<RoutedRequest> probes;                                // stable addresses; declared before the router: they outlive its threads
         first[0].tokens = {1, 2}; first[0].max_new = 30; first[1].tokens = {3}; first[1].max_new = 30;
         ReplicaRouter<FakeEngine> router(es, 256, 2);
-        CHECK(router.submit(&first[0]) == 0 && router.submit(&first[1]) == 1);
+        e0.hold = true;                                                  // replica 0 cannot fail (and empty) before first[1] is placed
+        const int where0 = router.submit(&first[0]), where1 = router.submit(&first[1]);
+        e0.hold = false;
+        CHECK(where0 == 0 && where1 == 1);
         for (int spin = 0; spin < 20000 && router.healthy(0); ++spin) {  // keep feeding replica 0 until its failures add up
             probes.emplace_back();
             RoutedRequest *probe = &probes.back();
@@ -219,9 +225,19 @@ int main() {
             ReplicaRouter<FakeEngine> router(es);
             RoutedRequest other;
             other.tokens = Tokens{3, 1, 4}; other.max_new = 200;
-            CHECK(router.submit(&other) >= 0);
+            // no replica runs before every one of them holds work: a fast replica cannot take all the documents however the threads run
+            for (auto *e : es) e->hold = true;
+            std::thread release([&] {
+                for (int i = 0; i < 2000 && !(router.busy(0) > 0 && router.busy(1) > 0 && router.busy(2) > 0); ++i)
+                    std::this_thread::sleep_for(std::chrono::milliseconds(5));
+                for (auto *e : es) e->hold = false;
+            });
+            const int where_other = router.submit(&other);
             std::vector<float> out(docs.size() * 2, -1.f);
-            CHECK(router.embed_documents(docs, 5, out.data(), 2) == 0);
+            const size_t retried = router.embed_documents(docs, 5, out.data(), 2);
+            release.join();
+            CHECK(where_other >= 0);
+            CHECK(retried == 0);
             for (size_t d = 0; d < docs.size(); ++d) {
                 float want[2];
                 expect(docs[d], 5, want);
@@ -239,7 +255,14 @@ int main() {
             e2[1]->fail_from = 3;
             ReplicaRouter<FakeEngine> router(es2, 256, 2);
             std::vector<float> out(docs.size() * 2, -1.f);
+            // the other two replicas stay full until replica 1 is out, so that it reaches its fault however the threads are scheduled
+            e2[0]->hold = true; e2[2]->hold = true;
+            std::thread release([&] {
+                for (int i = 0; i < 2000 && router.healthy(1); ++i) std::this_thread::sleep_for(std::chrono::milliseconds(5));
+                e2[0]->hold = false; e2[2]->hold = false;
+            });
             const size_t retried = router.embed_documents(docs, 0, out.data(), 2, 4);
+            release.join();
             CHECK(retried > 0 && !router.healthy(1) && router.healthy_count() == 2);
             for (size_t d = 0; d < docs.size(); ++d) {
                 float want[2];
@@ -306,7 +329,15 @@ int main() {
         std::vector<Tokens> docs;
         for (uint32_t d = 0; d < 12; ++d) docs.push_back(Tokens{d % 7 + 1, (d * 3) % 5 + 1, 2});
         std::vector<float> out(docs.size() * 2, -1.f);
+        // the healthy replica stays full until the flaky one is out: otherwise a fast healthy replica can take every remaining document
+        // after the flaky one's first failure, and the flaky one never fails twice in a row
+        good.hold = true;
+        std::thread release([&] {
+            for (int i = 0; i < 2000 && router.healthy(1); ++i) std::this_thread::sleep_for(std::chrono::milliseconds(5));
+            good.hold = false;
+        });
         router.embed_documents(docs, 1, out.data(), 2, 6);
+        release.join();
         CHECK(!router.healthy(1) && router.healthy(0));
         for (size_t d = 0; d < docs.size(); ++d) {
             float h = 1.0f, n = 0.0f;

@@ -92,14 +92,18 @@ def test_tokenizer_matches_reference_algorithm(built_lib):
 
 
 REF_VOCAB = "/root/reference/assets/tokenizer/rwkv_vocab_v20230424.json"
+FULL_VOCAB = os.path.join(ROOT, "tests", "golden", "rwkv_vocab_v20230424.json.xz")     # that file, xz-compressed
 
 
-@pytest.mark.skipif(not os.path.exists(REF_VOCAB), reason="the reference checkout (and its full World vocabulary) is not on this machine")
 def test_tokenizer_on_the_full_reference_vocabulary(built_lib):
-    """The reference's own 65 529-entry vocabulary file (lib.rs:375 loads exactly this asset), read in place: table identical,
-    encode == greedy longest match over the whole vocabulary, decode round-trips, on the reference's README texts + random bytes."""
+    """The reference's own 65 529-entry vocabulary file (lib.rs:375 loads exactly this asset; a copy under tests/golden/, compared byte
+    for byte with the reference checkout's where one is present): table identical, encode == greedy longest match over the whole
+    vocabulary, decode round-trips, on the reference's README texts (where present) + random bytes + a seeded run of vocabulary entries."""
     import json
-    raw = open(REF_VOCAB, encoding="utf-8").read()
+    import lzma
+    raw = lzma.open(FULL_VOCAB, "rt", encoding="utf-8").read()
+    if os.path.exists(REF_VOCAB):
+        assert raw == open(REF_VOCAB, encoding="utf-8").read()
     tk = rt.Tokenizer(raw)
     vocab = {int(k): (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for k, v in json.loads(raw).items()}
     assert len(vocab) == 65529 and min(vocab) == 1 and max(vocab) == 65529
@@ -112,6 +116,7 @@ def test_tokenizer_on_the_full_reference_vocabulary(built_lib):
         if os.path.exists(path):
             texts.append(open(path, "rb").read())
     texts.append(np.random.default_rng(5).integers(0, 256, 5000, dtype=np.uint8).tobytes())
+    texts.append(b"".join(vocab[int(i)] for i in np.random.default_rng(6).integers(1, len(vocab) + 1, 2000)))
     # longest-match oracle with a first-byte index (the plain _py_encode is quadratic in the vocabulary size)
     by_first = {}
     for i, b in vocab.items():

@@ -24,7 +24,7 @@ def last_json(out: str) -> dict:
 
 
 def test_gpus_2_without_a_launcher_spawns_two_ranks():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "10", "--selftest-dist"], env=clean_env(),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "10", "--selftest-dist", "--full"], env=clean_env(),
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -112,7 +112,7 @@ def test_world_size_8_the_rank_count_the_metric_names():
     cpus = sorted(os.sched_getaffinity(0))
     half = max(1, len(cpus) // 2)
     fake = {str(g): [g // 4, (cpus[:half] if g < 4 else cpus[half:] or cpus[:half])] for g in range(8)}
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "4", "--selftest-dist"], env=clean_env(BENCH_FAKE_NUMA=json.dumps(fake)),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "4", "--selftest-dist", "--full"], env=clean_env(BENCH_FAKE_NUMA=json.dumps(fake)),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
@@ -182,7 +182,7 @@ def test_world_size_and_gpus_flag_must_agree():
 def test_real_bench_as_two_ranks_on_one_device():
     """Two ranks sharing the test box's one device: decode, the serving loops (logits over PCIe; on-device sampling) and the embeddings
     job (64 documents per rank here instead of 512) on BOTH ranks, each leg aggregated over the slower rank."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-configs", "--no-cpu-baseline", "--sweep", "",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-configs", "--no-cpu-baseline", "--sweep", "",
                         "--verify-steps", "4"], env=clean_env(BENCH_SHARE_GPU="1", BENCH_EMBED_DOCS="64"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
@@ -194,6 +194,33 @@ def test_real_bench_as_two_ranks_on_one_device():
     e = d["embeddings"]
     assert e["docs"] == 128 and e["docs_per_rank"] == 64 and len(e["per_rank_embeddings_per_s"]) == 2 and e["embeddings_verified"] is True
     assert e["token_chunk_size"] == 256 and 0 < e["value"] <= 2 * min(e["per_rank_embeddings_per_s"]) * (1 + 1e-6)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """A plain run: one timed region of exactly --steps steps, none of the --full legs on the line; --dump-outputs writes the last timed
+    step's token ids and state sample as float arrays (64 MB at most), the same from run to run for the same arguments."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "6", "--warmup", "2", "--dump-outputs", str(out)], env=clean_env(),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = last_json(r.stdout)
+        B = d["config"]["batch_per_gpu"]
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["n_gpus"] == 1
+        assert abs(d["value"] - B * 1000.0 / d["ms_per_step"]) / d["value"] < 1e-6
+        for k in ("timed_regions", "tokens_verified", "roofline", "sweep", "pcie_inclusive", "on_device_sampling", "embeddings",
+                  "other_precisions", "cpu_baseline", "configs"):
+            assert d[k] is None, k
+        ids, st = np.load(out / "token_ids.npy"), np.load(out / "state_sample.npy")
+        assert ids.dtype == np.float64 and ids.shape == (B,) and (ids == np.round(ids)).all() and ids.min() >= 0
+        assert st.dtype == np.float32 and st.ndim == 2 and st.shape[0] == B and np.isfinite(st).all() and np.abs(st).max() > 0
+        assert ids.nbytes + st.nbytes <= 64 << 20
+        dumps.append((ids, st))
+    assert np.array_equal(dumps[0][0], dumps[1][0])
+    assert np.allclose(dumps[0][1], dumps[1][1], rtol=1e-4, atol=1e-5)
 
 
 def test_committed_bench_line_keeps_the_contract():
