@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/rwkv_abi.h"
-#include "rwkv_kernels.h"
+#include "gemm_plan.h"
 #include "safetensors.hpp"
 
 using namespace rwkv;
@@ -176,24 +176,6 @@ static rwkv_model_info detect_info(const SafeTensors &st) {
 // ------------------------------------------------------------------------------------------------
 // engine
 // ------------------------------------------------------------------------------------------------
-struct Opd {                        // f16 hi/lo activation operand, B-tiled (rwkv_kernels.hip opd_off): ceil16(Tmax) x ld
-    _Float16 *hi = nullptr, *lo = nullptr;
-    int ld = 0;
-};
-
-struct ProbSpec {
-    const DMat *W = nullptr;
-    Opd x;
-    int xoff = 0;                   // column offset into x (multiple of 32)
-    int act = ACT_NONE, post = POST_NONE;
-    const float *bias = nullptr, *m0 = nullptr, *m1 = nullptr;
-    int ldm = 0;
-    float *out = nullptr;
-    int ldo = 0;
-    bool partial = false;           // out = partial-sum buffer, K may be split across blocks
-    Opd oh;                         // optional operand output
-};
-
 enum Family { FAM_GEMM = 0, FAM_HEAD = 1, FAM_ROW = 2, FAM_WKV = 3, FAM_SAMPLE = 4, FAM_COPY = 5 };
 static const char *kFamilyNames[RWKV_PROFILE_FAMILIES] = {"gemm_layers", "gemm_head", "row_ln_shift", "wkv", "sample", "copy", "", ""};
 
@@ -821,283 +803,25 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// GEMM planning: choose the K split per problem, the X chunk and launch
+// GEMM launch: gemm_plan.h decides (path, tile shape, K split, block geometry); this logs and launches
 // ------------------------------------------------------------------------------------------------
-
-// Decomposition of one launch (DESIGN.md "GEMM planning"): every wave owns KW = KSW*32 k of the block's K range;
-// linear ("partial") problems may split K across `ksb` blocks (the consumer row kernel sums the partials);
-// a block walks `spb` strips.  Aim: >= ~1.5 blocks per CU in flight, whole matrix in flight at once.
-static int plan_gemm(GemmLaunch &Lh, std::vector<ProbSpec> &ps, int T, bool hilo, long pstride, int force_spb = 0) {
-    if (ps.empty() || ps.size() > GEMM_MAXP) throw RwkvError(RWKV_ERR_INVALID, "gemm: bad problem count");
-    Lh = GemmLaunch{};
-    Lh.nprob = (int)ps.size();
-    Lh.T = T;
-    int NT, KSW;
-    gemm_variant(T, hilo, NT, KSW);
-    const int KW = KSW * 32;
-    long total_strips = 0;
-    for (auto &s : ps) total_strips += s.W->rows / 16;
-    int blocks = 0, np = 1, max_nw = 1, lds_items = 1;
-    bool shot = true, tail = false;
-    for (size_t i = 0; i < ps.size(); ++i) {
-        const ProbSpec &s = ps[i];
-        GemmProb &g = Lh.p[i];
-        const int K = s.W->K, strips = s.W->rows / 16;
-        const int align = s.W->fmt == W_F16 ? 32 : 256;
-        // K split across blocks: mandatory when the range needs more than 16 waves, optional (linear epilogues)
-        // to spread small matrices over more CUs
-        int ksb = 1;
-        auto valid = [&](int b) { return K % b == 0 && (K / b) % align == 0; };
-        if (s.partial) {
-            // smallest split that gives >= 1.5 blocks per CU (one strip per block), else the largest valid one <= 8
-            int best = 0;
-            // (round 6: capping the split at 1 or 2 — one or two partial slabs for the next row kernel to sum instead of five — costs 5 % of a 32-slot
-            // step: 2.274 -> 2.395 / 2.385 ms, profiles/r6_exp_decode_ab.log)
-            for (int b = 1; b <= 8; ++b) {
-                if (!valid(b)) continue;
-                best = b;
-                if ((long)strips * b >= 384) break;
-            }
-            if (!best) throw RwkvError(RWKV_ERR_UNSUPPORTED, "cannot split inner dimension");
-            ksb = best;
-        }
-        const int Kb = K / ksb;
-        const int nslice = (Kb + KW - 1) / KW;                 // balanced: every wave owns the same number of slices
-        const int maxw = gemm_variant_max_waves(NT, KSW, hilo), per_wave = (nslice + maxw - 1) / maxw;
-        int nw = (nslice + per_wave - 1) / per_wave;
-        // two-tile hi + lo launches run 512-thread blocks (8 waves): ten 256-k slices balance as five waves with two slices each, but what a CU
-        // pulls from HBM grows with its waves — eight waves, two of them with a second slice, stream the first 80 % of the block's bytes at once
-        // (Precision::Fp32 at 32 slots 2.587 -> 2.490 ms per step, Fp16 + RWKV_PROMOTE=1 2.307 -> 2.256)
-        if (hilo && NT == 2 && per_wave > 1) nw = std::min(maxw, nslice);
-        // (Round 6: the two slices beyond the eight waves dealt out as six (slice, strip) items — one strip of a slice per wave instead of two waves
-        // walking a whole second slice — is SLOWER: every item pulls its slice's whole operand for a third of the work; 32-slot step 2.274 -> 2.30 ms,
-        // Fp32 2.51 -> 2.59, V7 2.38 -> 2.41; profiles/r6_exp_hilo_ragged_items.log.  Not kept.)
-        // strips per block: the whole grid should be resident at once (~164 VGPRs -> 12 waves per CU), and a wave's
-        // rounds should fit in registers so that every load is issued up-front (single shot); the head matrix is too
-        // big for that and runs 8 strips per block, software-pipelined.
-        const int sub = KSW / 8, maxr = gemm_max_rounds(s.W->fmt, NT, hilo);
-        const long cap = 256L * std::max(1, 8 / nw);           // measured: 5-wave blocks are resident one per CU
-        int spb = (int)((total_strips * ksb + cap - 1) / cap);
-        if ((total_strips * ksb + spb - 1) / spb > 1024) spb = 8;            // huge matrices (head): long pipelined blocks
-        else if (spb * sub > maxr && strips * ksb <= 64) spb = std::max(1, maxr / sub);   // tiny member of a group
-        spb = std::max(1, std::min(spb, 8));
-        if (force_spb) spb = force_spb;
-        spb = std::min(spb, std::max(1, 150 / (nw * NT)));                     // LDS: spb*nw*NT KiB <= 150 KiB
-        g.W = s.W->data; g.S = s.W->scales; g.fmt = s.W->fmt; g.rows = s.W->rows; g.K = K;
-        g.xhi = s.x.hi + (s.xoff >> 5) * 512; g.xlo = s.x.lo ? s.x.lo + (s.xoff >> 5) * 512 : nullptr; g.ldx = s.x.ld;   // column offset = whole k-tiles
-        g.spb = spb; g.nw = nw; g.ksb = ksb;
-        g.Kb = Kb; g.nslice = nslice;
-        g.nblk_strip = (strips + spb - 1) / spb;
-        g.block_begin = blocks;
-        blocks += g.nblk_strip * ksb;
-        g.act = s.act; g.post = s.post; g.bias = s.bias; g.m0 = s.m0; g.m1 = s.m1; g.ldm = s.ldm;
-        g.out_f32 = s.out; g.ldo = s.ldo; g.partial_stride = pstride;
-        g.out_hi = s.oh.hi; g.out_lo = s.oh.lo; g.ldh = s.oh.ld;
-        max_nw = std::max(max_nw, nw);
-        if (spb * sub > maxr) shot = false;
-        if (Kb % 256) tail = true;
-        lds_items = std::max(lds_items, spb * nw);
-        if (s.partial) np = ksb;
-    }
-    Lh.total_blocks = blocks;
-    Lh.threads = max_nw * 64;
-    Lh.lds_items = lds_items;
-    // 17..32-row steps over quantised weights: a ring of two rounds in flight per wave instead of every load issued up-front.  A wave that
-    // has issued its 16 operand tiles and 12 weight tiles sits in the issue queue for ~3 us (profiles/r4_trace_gemm_timeline_t1_t32.log)
-    // and only then starts on a strip that landed long ago; with the ring its dequantisation starts a round earlier: r/k/v/g Int8 at
-    // T = 32 10.07 -> 9.74 us, Fk / Fr 10.70 -> 10.48, fp16 and T <= 16 unchanged or slower (profiles/r4_exp_gemm_ring_vs_shot.log).
-    {
-        bool all_quant = true;
-        for (auto &sp : ps) all_quant = all_quant && (sp.W->fmt != W_F16 || sp.W->rows <= 256);   // (the decay LoRA's 64 fp16 rows ride along)
-        if (NT == 2 && all_quant && !hilo) shot = false;
-    }
-    Lh.single_shot = shot ? 1 : 0;
-    Lh.tail = tail ? 1 : 0;
-    return np;
-}
-
 int rwkv_engine::gemm(std::vector<ProbSpec> &ps, int T, int fam, const ShiftCommit *commit, int cls) {
-    GemmLaunch Lh;
     const bool hilo = wide(cls);                                 // shadows the engine-wide flag: this launch's operand width
     if (hilo) for (auto &sp : ps) if (!sp.x.lo) throw RwkvError(RWKV_ERR_INVALID, "gemm: a hi + lo launch needs the lo part of every operand");
-    // launches whose every matrix is short in K (V7's second LoRA stage): the output-stationary small-K kernel, whatever the step's rows
-    // (a launch that has to carry a token-shift commit keeps the decode kernel: the commit rides on its extra block)
-    // Decode-shaped steps only: at 32 rows 6.4 -> ~5.5 us (V7-2.9B: -1.0 / -1.7 / -1.7 % per step at 32 / 8 / 1 slots); at 256 and 2048 rows
-    // the tile kernels, which share X through LDS, are as fast (profiles/r5_exp_smallk_ab.log).
-    if (T <= 64 && !(commit && commit->src) && !ps.empty() && ps.size() <= GEMM_MAXP) {
-        Lh = GemmLaunch{};
-        Lh.nprob = (int)ps.size();
-        Lh.T = T;
-        int items = 0;
-        bool ok = true;
-        for (size_t i = 0; i < ps.size() && ok; ++i) {
-            const ProbSpec &sp = ps[i];
-            GemmProb &g = Lh.p[i];
-            ok = !sp.partial && sp.xoff == 0;
-            g.W = sp.W->data; g.S = sp.W->scales; g.fmt = sp.W->fmt; g.rows = sp.W->rows; g.K = sp.W->K;
-            g.xhi = sp.x.hi; g.xlo = sp.x.lo; g.ldx = sp.x.ld;
-            g.spb = 1; g.nw = 1; g.ksb = 1; g.Kb = g.K; g.nslice = 1; g.nblk_strip = g.rows / 16;
-            g.block_begin = items;
-            items += g.rows / 16;
-            g.act = sp.act; g.post = sp.post; g.bias = sp.bias; g.m0 = sp.m0; g.m1 = sp.m1; g.ldm = sp.ldm;
-            g.out_f32 = sp.out; g.ldo = sp.ldo; g.partial_stride = pstride;
-            g.out_hi = sp.oh.hi; g.out_lo = sp.oh.lo; g.ldh = sp.oh.ld;
-        }
-        Lh.total_blocks = items;
-        if (ok && smallk_supported(Lh)) {
-            log_gemm(ps, T, fam, "smallk", 0, (items + 3) / 4, 1, 256);
-            launch(fam, [&] { launch_smallk(Lh, hilo, s_main); });
-            return 1;
-        }
-    }
-    const int no_tile = kn.no_tile;
-    if (T >= GEMM_TILE_MIN_T && !no_tile) {
-        // prefill: LDS-tiled MFMA GEMM, no K split (partial problems write one slab)
-        if (ps.empty() || ps.size() > GEMM_MAXP) throw RwkvError(RWKV_ERR_INVALID, "gemm: bad problem count");
-        Lh = GemmLaunch{};
-        Lh.nprob = (int)ps.size();
-        Lh.T = T;
-        // 64x64 tiles measured best everywhere (tile_bench): with 256-k chunks while the launch is latency-bound
-        // (few blocks: one L2 round trip per chunk dominates), with 128-k chunks (more blocks per CU) once it is
-        // throughput-bound.  RWKV_TILE_SHAPE overrides (0..10) for experiments.
-        const int f_shape = kn.tile_shape;                          // the parity tests force every shape (one engine per shape)
-        long tot64 = 0;
-        for (auto &s : ps) tot64 += gemm_tile_blocks(3, s.W->rows, T);
-        int shape = tot64 <= 1536 ? 4 : 3;
-        // fp16 weights fill a wave's registers twice as fast as Int8: the 128-k chunks (more blocks per CU) win at every grid size
-        // since the LDS image is in fragment order (rkvg fp16 T = 512: 489 -> 534 TFLOP/s, T = 256: 374 -> 456)
-        bool all_f16 = true;
-        for (auto &s : ps) all_f16 = all_f16 && s.W->fmt == W_F16;
-        if (all_f16) shape = 3;
-        // NF4 sits in between (a quarter of the bytes per weight, the most dequantisation work): the 128-k chunks win from ~500 tiles
-        // (isolated, 3 B width, 256 rows: r/k/v/g 42.0 -> 40.2 us, Fk + Fr 50.8 -> 47.4; Wo / Fv with 160 tiles lose 40 %),
-        // profiles/r3_exp_tile_128x64.log
-        bool all_nf4 = true;
-        for (auto &s : ps) all_nf4 = all_nf4 && s.W->fmt == W_NF4;
-        if (all_nf4 && tot64 >= 512) shape = 3;
-        // the direct-to-LDS 128x64 shape (7: two strips per wave, X tiles by global_load_lds) pays only for very large
-        // grids: 7B fp16 prefill at chunk 1024 25.9 -> 27.5 k tok/s, but 21.3 -> 17.8 k at chunk 512; the 256x128
-        // GLDS shape (9) wins isolated large fp16 GEMMs (404 -> 536 TFLOP/s) and loses the model (small matrices starve)
-        // (not for launches whose matrices are all short in K — V7's second-stage LoRA, K = 64..320, four [T][C] outputs: 88 us on that
-        // shape at 2048 rows; on the 64x64 shapes V7-2.9B NF4 prefill 74.4 -> 76.5 k tok/s, 64.7 -> 66.5 k at 1024; profiles/r3_exp_shape7_by_k.log)
-        int maxK = 0;
-        for (auto &s : ps) maxK = std::max(maxK, s.W->K);
-        if (T >= 1024 && tot64 >= 2500 && maxK >= 1024) shape = 7;
-        // The pipelined 128x128 kernel (shape 10) keeps two blocks per CU resident, 512 tiles a round, and runs ~820 TFLOP/s on
-        // whole rounds against ~540 for the 64x64 shapes whatever the grid (scripts/tile_bench2.py); a partial last round costs
-        // a whole one (blocks left alone on a CU are latency-bound), so it is used when its rounds are at least 60 % full and it has
-        // at least 300 tiles: V6-3B chunk 2048 60.8 -> 69.5 k prefill tok/s, V6-7B chunk 1024 30.4 -> 32.7 k.  (Round 3 moved the bar
-        // from 65 % / 400 tiles: Wo of the 3 B models at 2048 rows — 320 tiles, 62.5 % of a round — is 75 us on 64x64 tiles and one
-        // round of this kernel, ~64 us: 76.4 -> 78.3 k, V7-2.9B NF4 69.2 -> 71.8 k; profiles/r3_exp_tile3_thresholds.log.)
-        // RWKV_TILE3_FILL=<percent> (0 = never), RWKV_TILE3_MIN_TILES.
-        bool ok3 = true;
-        {
-            long t3 = 0;
-            for (auto &sp : ps) { t3 += gemm_tile_blocks(GEMM_TILE3, sp.W->rows, T); ok3 = ok3 && gemm_tile3_supported(hilo, sp.W->K); }
-            const long fill_min = 60;
-            const long rounds = (t3 + 511) / 512;
-            if (ok3 && t3 >= 300 && t3 * 100 >= fill_min * rounds * 512) shape = GEMM_TILE3;
-        }
-        // The pipelined kernel on 128 x 64 tiles (shape 11, round 4) for the NON-linear launches of steps the 128-token tile cannot fill:
-        // at 256 rows a 10304-row launch is 160 tiles of 128 x 128 (fewer than CUs) but 324 of 128 x 64, each prefetching four stages
-        // ahead where the 64 x 64 shapes prefetch one chunk: r/k/v/g/decay 49.7 -> 40.8 us, Fk / Fr 45.7 -> 40.0 (Int8, 256 rows).
-        // Where it pays, measured after the epilogue rewrite (profiles/r4_exp_tile3_128x64.log, last section; V6-3B Int8 / fp16, V7-2.9B
-        // NF4, V6-7B fp16): quantised launches at 256 rows (Int8 +5.8 %, NF4 even) and NF4 at 1024 rows (+2.7 %); fp16 at 512 rows (7 B
-        // +8 %, 3 B +1 %); everywhere else the 64 x 64 shapes or the 128 x 128 tile are as fast or faster (fp16 at 1024 rows -3 %).
-        // The linear launches (Wo, Fv) stay on K copies of 64 x 64 tiles (22 us at 256 rows against 30).  RWKV_TILE3_64=0 turns the rule off.
-        {
-            const bool linear_launch = ps.size() == 1 && ps[0].partial;
-            bool big_f16 = false, big_not_nf4 = false;
-            for (auto &sp : ps) {
-                if (sp.W->rows <= 512) continue;                       // (the fp16 LoRA stages — V6's decay, V7's w / a / g / v: 64..320 rows — ride along)
-                big_f16 = big_f16 || sp.W->fmt == W_F16;
-                big_not_nf4 = big_not_nf4 || sp.W->fmt != W_NF4;
-            }
-            const bool in_range = big_f16 ? (T > 320 && T <= 768) : (T <= 320 || (!big_not_nf4 && T > 768 && T <= 1280));
-            if (ok3 && !linear_launch && in_range) shape = GEMM_TILE3_64;
-        }
-        // hi + lo operands (Precision::Fp32, and the launch classes Precision::Fp16 promotes): the software-pipelined 128 x 64 kernel whenever
-        // every K is a multiple of 128 — it fetches and dequantises a weight once for both operand halves: r/k/v/g Int8 46.8 us against 76.5 on
-        // the 64x64 shape at 256 rows, 262 against 547 at 2048 (profiles/r6_exp_tile4.log).  (V7's second-stage LoRAs, K = 64..320, stay on 64x64.)
-        bool ok4 = hilo;
-        for (auto &sp : ps) ok4 = ok4 && gemm_tile4_supported(hilo, sp.W->K);
-        if (ok4) shape = GEMM_TILE4_HILO;
-        if (f_shape >= 0 && f_shape < GEMM_TILE_SHAPES) {
-            bool okf = true;
-            for (auto &sp : ps) okf = okf && gemm_tile_shape_supported(f_shape, hilo, sp.W->K);
-            if (okf) shape = f_shape;
-            else if (gemm_tile_pipelined(f_shape) && ok4) shape = GEMM_TILE4_HILO;      // a forced pipelined shape means "the pipelined kernel of this operand form"
-            else shape = 4;                                                              // (also shape 5 with hi + lo operands: its LDS image does not fit)
-        }
-        const bool wide_tile = shape == GEMM_TILE3;                                      // 128 x 128 pipelined tiles
-        const bool narrow_tile = shape == GEMM_TILE3_64 || shape == GEMM_TILE4_HILO;    // 128 x 64
-        const bool okp = ok3 || ok4;
-        // K split of a linear launch on the pipelined kernel (Wo, Fv: one `partial` problem whose output the next row kernel sums
-        // anyway): a grid of fewer than 512 tiles costs a whole round of the kernel, so the tiles are replicated over `ksb` K ranges
-        // until the rounds are full — 3 x 320 tiles (V6-3B at 2048 rows) fill 94 % of two rounds a third as long (tg3_body).
-        int ksplit = 1;
-        if (okp && kn.tile_ksplit && ps.size() == 1 && ps[0].partial && ps[0].post != POST_MIX && ps[0].act == ACT_NONE && !ps[0].bias &&
-            !ps[0].oh.hi && (f_shape < 0 || gemm_tile_pipelined(f_shape))) {
-            const long t3 = gemm_tile_blocks(GEMM_TILE3, ps[0].W->rows, T);
-            const int G = ps[0].W->K / 128;
-            double best = wide_tile ? (double)t3 / (((t3 + 511) / 512) * 512) : 0.0;
-            if (t3 >= 128 && ok3) {
-                // a copy must keep >= 2048 k: the pipeline's ramp and the fp32 slab a tile writes are fixed costs per copy — measured
-                // (V6-3B Int8, 2048 rows): Fv (K = 8960) in three copies 200 -> 173 us, Wo (K = 2560) in three copies 67 -> 86 us
-                for (int b = 2; b <= 4 && G / b >= 16; ++b) {
-                    const double fill = (double)(t3 * b) / (((t3 * b + 511) / 512) * 512);
-                    if (fill > best + 0.10 && fill >= 0.80) { best = fill; ksplit = b; }
-                }
-            }
-            if (narrow_tile) {
-                // copies over K until the launch has about one block per CU, a copy keeping >= 768 k
-                const long t11 = gemm_tile_blocks(GEMM_TILE3_64, ps[0].W->rows, T);
-                ksplit = 1;
-                for (int b = 2; b <= 4 && ps[0].W->K / b >= 768 && t11 * (b - 1) < 224; ++b) ksplit = b;
-            } else if (ksplit > 1) shape = GEMM_TILE3;
-            else if (!wide_tile) {
-                // the 64x64 shapes on a step of a few hundred rows: Wo / Fv have fewer tiles than the chip has CUs (160 at 256 rows of
-                // the 3 B model); copies over K fill it
-                const long t64 = gemm_tile_blocks(shape, ps[0].W->rows, T);
-                const int K = ps[0].W->K;
-                // (only below one tile per CU: at 320 tiles — 512 rows — the copies cost more in slabs than they fill: 49.6 -> 47.1 k tok/s)
-                if (t64 < 256) for (int b = 2; b <= 4 && K / b >= 768 && t64 * (b - 1) < 448; ++b) ksplit = b;
-            }
-        }
-        int blocks = 0;
-        for (size_t i = 0; i < ps.size(); ++i) {
-            const ProbSpec &s = ps[i];
-            GemmProb &g = Lh.p[i];
-            g.W = s.W->data; g.S = s.W->scales; g.fmt = s.W->fmt; g.rows = s.W->rows; g.K = s.W->K;
-            g.xhi = s.x.hi + (s.xoff >> 5) * 512; g.xlo = s.x.lo ? s.x.lo + (s.xoff >> 5) * 512 : nullptr; g.ldx = s.x.ld;   // column offset = whole k-tiles
-            g.spb = 16; g.nw = 8; g.ksb = ksplit; g.nblk_strip = 0;
-            g.block_begin = blocks;
-            blocks += gemm_tile_blocks(shape, s.W->rows, T) * ksplit;
-            g.act = s.act; g.post = s.post; g.bias = s.bias; g.m0 = s.m0; g.m1 = s.m1; g.ldm = s.ldm;
-            g.out_f32 = s.out; g.ldo = s.ldo; g.partial_stride = pstride;
-            g.out_hi = s.oh.hi; g.out_lo = s.oh.lo; g.ldh = s.oh.ld;
-        }
-        Lh.total_blocks = blocks;
-        Lh.xcd_map = 1;                                             // XCD-banded tile numbering (rwkv_kernels.hip tg_body)
-        // Order of the XCD bands (round 6, profiles/r6_exp_tile5_and_xcd_order.log).  Row-tile-major (1): every weight byte is fetched by ONE XCD, which walks
-        // all token tiles for it.  Token-tile-major (2): an XCD keeps its own token tiles' X rows in its L2 and streams the weights past them.  An
-        // estimate by bytes says (2) from ~640 rows on; measured, the blocks of an XCD walk K in near lock-step, so X streams through the L2 once either
-        // way: no change for plain operands (r/k/v/g Int8 at 2048 rows 144.5 / 145.8 us), worse with fp16 weights (149 -> 155), and -8 % only where
-        // the operand is doubled — hi + lo launches of 2048-row steps (258 -> 238 us).  RWKV_TILE_XCD overrides (dev).
-        if (hilo && T >= 2048 && shape == GEMM_TILE4_HILO) Lh.xcd_map = 2;
-        if (const char *e = std::getenv("RWKV_TILE_XCD")) { if (*e) Lh.xcd_map = std::atoi(e); }
-        {   // block size of the tile shape (rwkv_kernels.hip TG_SH; the pipelined kernel runs 256 threads): the profile joins on it
-            static const int waves[10] = {8, 8, 4, 4, 4, 8, 4, 4, 4, 8};
-            log_gemm(ps, T, fam, "tile", shape, blocks, ksplit, shape < 10 ? waves[shape] * 64 : 256);
-        }
-        launch(fam, [&] { launch_gemm_tile(Lh, shape, hilo, s_main); });
-        return ksplit;
-    }
-    const int np = plan_gemm(Lh, ps, T, hilo, pstride);
-    if (commit) Lh.commit = *commit;
-    log_gemm(ps, T, fam, "decode", Lh.single_shot, Lh.total_blocks + (Lh.commit.src ? 1 : 0), np, Lh.threads);
-    launch(fam, [&] { launch_gemm(Lh, hilo, s_main); });
-    return np;
+    if (ps.empty() || ps.size() > GEMM_MAXP) throw RwkvError(RWKV_ERR_INVALID, "gemm: bad problem count");
+    const int n = (int)ps.size();
+    ProbShape sh[GEMM_MAXP];
+    for (int i = 0; i < n; ++i) sh[i] = shape_of(ps[i]);
+    GemmLaunch Lh;
+    const GemmPlan pl = plan_gemm(Lh, sh, n, T, hilo, commit && commit->src, kn);
+    if (!pl.ksplit) throw RwkvError(RWKV_ERR_UNSUPPORTED, "cannot split inner dimension");
+    for (int i = 0; i < n; ++i) fill_prob(Lh.p[i], ps[i], pstride);
+    if (pl.path == GEMM_DECODE && commit) Lh.commit = *commit;
+    log_gemm(ps, T, fam, kGemmPathNames[pl.path], pl.variant, pl.grid, pl.ksplit, pl.threads);
+    if (pl.path == GEMM_SMALLK) launch(fam, [&] { launch_smallk(Lh, hilo, s_main); });
+    else if (pl.path == GEMM_TILE) launch(fam, [&] { launch_gemm_tile(Lh, pl.variant, hilo, s_main); });
+    else launch(fam, [&] { launch_gemm(Lh, hilo, s_main); });
+    return pl.ksplit;
 }
 
 // RWKV_LAUNCH_LOG (dev): what a launch of layer 0 (or the head) streams and computes, so that a profile can be priced without guessing which
@@ -2108,41 +1832,33 @@ rwkv_status rwkv_bench_gemm(int32_t rows, int32_t K, int32_t fmt, int32_t T, int
             out2 = (float *)dal((size_t)T * rows * 4);
             pbuf2 = (float *)dal((size_t)8 * T * rows * 4);
         }
+        const char *ks_env = std::getenv("RWKV_BENCH_KSPLIT");                 // (dev) K copies of a tile launch
+        const int bench_ksplit = ks_env ? std::max(1, std::min(8, std::atoi(ks_env))) : 0;
         hipStream_t run_st = st;
         auto run = [&](int n) {
             const bool second = run_st != st;
             for (int i = 0; i < n; ++i) {
-                std::vector<ProbSpec> ps(1);
-                ps[0].W = &mats[i % nmat]; ps[0].x = second ? x2 : x; ps[0].out = K > 5120 ? (second ? pbuf2 : pbuf) : (second ? out2 : out); ps[0].ldo = rows;
-                ps[0].partial = K > 5120;
+                ProbSpec ps;
+                ps.W = &mats[i % nmat]; ps.x = second ? x2 : x; ps.out = K > 5120 ? (second ? pbuf2 : pbuf) : (second ? out2 : out); ps.ldo = rows;
+                ps.partial = K > 5120;
+                const ProbShape shp = shape_of(ps);
                 GemmLaunch Lh;
-                if (T >= GEMM_TILE_MIN_T) {                      // prefill path; `spb` selects the tile shape (0..3), -1 = auto
-                    int shape = spb;
+                int shape = -1;
+                if (T >= GEMM_TILE_MIN_T) {                      // prefill path; `spb` selects the tile shape (0..12), -1 = auto
+                    shape = spb;
                     if (shape < 0 || shape >= GEMM_TILE_SHAPES) {
                         shape = GEMM_TILE3;
                         for (int sh = 0; sh < GEMM_TILE_SHAPES; ++sh) if (gemm_tile_blocks(sh, rows, T) >= 1024) { shape = sh; break; }
                     }
                     if (!gemm_tile_shape_supported(shape, hilo != 0, K)) throw RwkvError(RWKV_ERR_INVALID, "bench_gemm: the pipelined shapes need K % 128 == 0; shapes 10 / 11 take plain operands, shape 12 hi + lo");
-                    Lh = GemmLaunch{};
-                    Lh.nprob = 1; Lh.T = T;
-                    GemmProb &g = Lh.p[0];
-                    g.W = ps[0].W->data; g.S = ps[0].W->scales; g.fmt = fmt; g.rows = rows; g.K = K;
-                    g.xhi = x.hi; g.xlo = x.lo; g.ldx = K; g.ksb = 1; g.block_begin = 0;
-                    g.out_f32 = out; g.ldo = rows;
-                    if (const char *e = std::getenv("RWKV_BENCH_KSPLIT")) {      // K copies of the tile grid writing partial slabs (linear launches)
-                        g.ksb = std::max(1, std::min(8, std::atoi(e)));
-                        g.out_f32 = pbuf; g.partial_stride = (long)T * rows;
-                    }
-                    Lh.total_blocks = gemm_tile_blocks(shape, rows, T) * g.ksb;
-                    Lh.xcd_map = 1;
-                    if (const char *e = std::getenv("RWKV_TILE_XCD")) { if (*e) Lh.xcd_map = std::atoi(e); }     // 2: token-tile-major bands
-                    if (lds_kib) *lds_kib = (float)Lh.total_blocks;
-                    launch_gemm_tile(Lh, shape, hilo != 0, run_st);
-                    continue;
-                }
-                plan_gemm(Lh, ps, T, hilo != 0, (long)T * rows, spb);
+                    if (bench_ksplit) ps.out = second ? pbuf2 : pbuf;            // K copies of the tile grid writing partial slabs (linear launches)
+                    tile_geometry(Lh, &shp, 1, T, shape, std::max(1, bench_ksplit));
+                    if (knobs().tile_xcd >= 0) Lh.xcd_map = knobs().tile_xcd;    // 2: token-tile-major bands
+                } else if (!plan_decode(Lh, &shp, 1, T, hilo != 0, spb)) throw RwkvError(RWKV_ERR_UNSUPPORTED, "cannot split inner dimension");
+                fill_prob(Lh.p[0], ps, (long)T * rows);
                 if (lds_kib) *lds_kib = (float)Lh.total_blocks;
-                launch_gemm(Lh, hilo != 0, run_st);
+                if (shape >= 0) launch_gemm_tile(Lh, shape, hilo != 0, run_st);
+                else launch_gemm(Lh, hilo != 0, run_st);
             }
         };
         run(nmat);

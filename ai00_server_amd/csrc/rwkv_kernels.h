@@ -1,7 +1,15 @@
 // rwkv_kernels.h — host-visible launch descriptors for the gfx950 kernels in rwkv_kernels.hip.
 // Pure POD + launch prototypes; no HIP types except hipStream_t.
 #pragma once
+#ifdef __HIP__
 #include <hip/hip_runtime.h>
+#else                                // a plain host compiler (gemm_plan.h and its CPU test): the descriptors only carry pointers of these types
+typedef struct ihipStream_t *hipStream_t;
+#ifndef __FLT16_MANT_DIG__
+typedef unsigned short _Float16;
+#endif
+#endif
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rwkv {
@@ -19,6 +27,7 @@ struct Knobs {
     int no_tile = 0, tile_shape = -1;   // RWKV_NO_TILE: the decode GEMM for every step; RWKV_TILE_SHAPE=0..12: force a prefill tile shape (parity of every shape)
     int no_dense = 0;                // RWKV_NO_DENSE: general row metadata on dense decode steps
     int tile_ksplit = 1;             // RWKV_TILE_KSPLIT=0: no K copies of linear prefill launches (the race screen compares tile shapes BIT for bit, which needs one summation order)
+    int tile_xcd = -1;               // RWKV_TILE_XCD (dev; -1 = unset: the planner decides): order of the XCD bands of a prefill tile launch, 0 none, 1 row-tile-major, 2 token-tile-major
     int promote = -1;                // RWKV_PROMOTE (dev override; -1 = unset: the precision mode decides): bit mask of GEMM launch classes that read hi + lo
                                      // operands in the fp16 modes (1 att r/k/v(/g) + first-stage LoRAs, 2 V7 second-stage LoRAs, 4 Wo, 8 Fk / Fr, 16 Fv,
                                      // 32 head); rwkv_engine.cpp OpdClass
@@ -33,7 +42,6 @@ constexpr int TILE_ROWS = 16;        // output rows per strip (MFMA 16x16x32 M)
 constexpr int KSTEP = 32;            // K per MFMA
 constexpr int GEMM_MAX_WAVES = 10;    // 640-thread blocks: <= 168 VGPRs per lane (KSW = 8 variants)
 constexpr int GEMM_MAX_WAVES_K16 = 8; // four-tile (NT = 4) and two-tile hi + lo variants: 512-thread blocks, 2 waves per SIMD -> 256 VGPRs per lane
-int gemm_variant_max_waves(int NT, int KSW, bool hilo = false);
 constexpr int GEMM_MAXP = 8;
 constexpr int INT8_BLOCK = 128;
 constexpr int NF4_BLOCK = 64;
@@ -127,28 +135,13 @@ struct GemmLaunch {
     ShiftCommit commit;             // grid = total_blocks + 1 when commit.src is set
 };
 
-void gemm_variant(int T, bool hilo, int &NT, int &KSW);   // tile variant used for T rows
+// (which variant, tile shape and K split a launch gets, and the facts about the kernels those rules need: gemm_plan.h)
 size_t lnp_lds_bytes(int T, int C, bool hilo);                       // extra dynamic LDS of an LN-prologue launch
 void launch_gemm(const GemmLaunch &L, bool hilo, hipStream_t s);
-bool smallk_supported(const GemmLaunch &L);              // every problem: fp16, K <= 320, fp32 output, no post-op (V7's second LoRA stage)
-void launch_smallk(const GemmLaunch &L, bool hilo, hipStream_t s);   // output-stationary: one wave per (problem, strip), all rows of the step
-int gemm_max_rounds(int fmt, int NT, bool hilo);
-// prefill path (T >= GEMM_TILE_MIN_T): LDS-tiled MFMA GEMM, no K split; uses p[].block_begin and total_blocks only
-constexpr int GEMM_TILE_MIN_T = 193;                     // measured crossover (V6-3B Int8): up to 192 rows the decode kernel's 64-row passes win or tie
-constexpr int GEMM_TILE_SHAPES = 13;                      // 256x128, 128x128, 64x128, 64x64 (rows x tokens, 128-k chunks); 64x64 and 128x128 with 256-k chunks
-int gemm_tile_blocks(int shape, int rows, int T);
-constexpr int GEMM_TILE3 = 10;                            // the pipelined 128x128 kernel (non-hi/lo operands, K % 128 == 0)
-constexpr int GEMM_TILE3_64 = 11;                         // the same pipeline on 128 rows x 64 tokens (steps of a few hundred rows)
-constexpr int GEMM_TILE4_HILO = 12;                       // the software-pipelined kernel for hi + lo operands on 128 rows x 64 tokens (round 6; K % 128 == 0)
-inline bool gemm_tile_pipelined(int shape) { return shape >= GEMM_TILE3 && shape <= GEMM_TILE4_HILO; }
-bool gemm_tile3_supported(bool hilo, int K);
-bool gemm_tile4_supported(bool hilo, int K);
-inline bool gemm_tile_shape_supported(int shape, bool hilo, int K) {
-    if (shape == 5 && hilo) return false;                // 128 tokens x 256-k chunks, double-buffered, hi + lo: 256 KiB of LDS
-    return shape == GEMM_TILE4_HILO ? gemm_tile4_supported(hilo, K) : (shape >= GEMM_TILE3 ? gemm_tile3_supported(hilo, K) : true);
-}
+void launch_smallk(const GemmLaunch &L, bool hilo, hipStream_t s);   // output-stationary: one wave per (problem, strip), all rows of the step (gemm_plan.h smallk_eligible)
+// prefill path (T >= GEMM_TILE_MIN_T): LDS-tiled MFMA GEMM; uses p[].block_begin, p[].ksb, total_blocks and xcd_map only
 void launch_gemm_tile45(const GemmLaunch &L, int kind, int ntl, bool hilo, hipStream_t s);   // rwkv_kernels.hip part 5
-void launch_gemm_tile(const GemmLaunch &L, int shape, bool hilo, hipStream_t s);                             // rounds of 256 k a wave can hold at once (single-shot)
+void launch_gemm_tile(const GemmLaunch &L, int shape, bool hilo, hipStream_t s);             // shape: index into gemm_plan.h kTileShapes
 
 // V6 fused time-mix LoRA (tanh(W1 z) -> W2 -> lerp), decode-shaped steps only
 struct V6MixArgs {

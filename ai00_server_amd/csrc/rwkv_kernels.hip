@@ -12,7 +12,7 @@
 //   tile/quant       K18,K19        load-time: raw fp16 -> tiled fp16 / int8 / nf4 ; LoRA blend
 //
 // gfx950 only: wave = 64 lanes, v_mfma_f32_16x16x32_f16, no portability shims.
-#include "rwkv_kernels.h"
+#include "gemm_plan.h"
 #include <type_traits>
 #include <cstdlib>
 #include <algorithm>
@@ -490,7 +490,7 @@ Knobs Knobs::from_env() {
     k.no_ln_fuse = knob_env("RWKV_NO_LN_FUSE", 0); k.no_v6_fuse = knob_env("RWKV_NO_V6_FUSE", 0);
     k.no_tile = knob_env("RWKV_NO_TILE", 0); k.tile_shape = knob_env("RWKV_TILE_SHAPE", -1);
     k.no_dense = knob_env("RWKV_NO_DENSE", 0);
-    k.tile_ksplit = knob_env("RWKV_TILE_KSPLIT", 1);
+    k.tile_ksplit = knob_env("RWKV_TILE_KSPLIT", 1); k.tile_xcd = knob_env("RWKV_TILE_XCD", -1);
     k.promote = knob_env("RWKV_PROMOTE", -1);
     k.v6_ksp_max = knob_env("RWKV_V6_KSP_MAX", 16); k.v6_ksp_blocks = knob_env("RWKV_V6_KSP_BLOCKS", 160); k.v6_ksp_min_t = knob_env("RWKV_V6_KSP_MIN_T", 192);
     return k;
@@ -783,22 +783,6 @@ __global__ __launch_bounds__(((NT == 4 || (NT == 2 && HILO)) ? GEMM_MAX_WAVES_K1
     else gemm_body<NT, KSW, HILO, SHOT, false, W_NF4>(L, P, smem);
 }
 
-int gemm_variant_max_waves(int NT, int, bool hilo) { return (NT == 4 || (NT == 2 && hilo)) ? GEMM_MAX_WAVES_K16 : GEMM_MAX_WAVES; }
-
-void gemm_variant(int T, bool hilo, int &NT, int &KSW) {
-    // Every variant runs 256-k waves (ten per block at K = 2560): a wave's loads return in order and what a CU can pull from HBM grows with
-    // its waves, not with the loads each keeps in flight (profiles/r3_exp_stream_waves_x_loads.log: 27 MB over 256 workgroups: 5 waves
-    // 8.6-10.8 us, 10 waves 6.9-8.0, 16 waves 6.8-7.1 whatever the depth).  (The 512-k form and its LayerNorm-prologue launch lost that
-    // A/B in round 3 and were removed in round 5.)
-    KSW = 8;
-    // hi + lo operands (Precision::Fp32, or a promoted launch): 17+ rows run two token tiles per pass in 512-thread blocks (128 X registers, the
-    // register shape of the four-tile variant) — one pass over the weights for up to 32 rows instead of one per 16
-    if (hilo) NT = T <= 16 ? 1 : 2;
-    else if (T <= 16) NT = 1;
-    else if (T <= 32) NT = 2;
-    else NT = 4;                                                  // 33..64 rows in ONE pass over the weights (128 X registers)
-}
-
 void launch_gemm(const GemmLaunch &L, bool hilo, hipStream_t s) {
     int NT, KSW;
     gemm_variant(L.T, hilo, NT, KSW);
@@ -824,7 +808,6 @@ void launch_gemm(const GemmLaunch &L, bool hilo, hipStream_t s) {
 #undef GEMM_V3
 }
 
-int gemm_max_rounds(int fmt, int NT, bool hilo) { return (NT == 4 || (NT == 2 && hilo)) ? 2 : (fmt == W_F16 ? 2 : ((NT == 2 || hilo) ? 3 : 4)); }   // X registers vs the VGPR budget
 #endif  // part 0: decode GEMM
 
 
@@ -1254,7 +1237,7 @@ bool v6_mix_ln_supported(int T, int C, int Dm, bool hilo, int np) {
 // waves, so no LDS, no barrier, no reduce; the launch is a load -> MFMA -> store chain of ~10 instructions per token tile.  Replaces
 // the generic kernels on these launches (which split a K of 96 over waves sized for K = 2560: 6.4 us at 32 rows, 10.8 us at 256).
 // =====================================================================================
-constexpr int SK_KMAX = 320, SK_TG = 4;
+constexpr int SK_TG = 4;                  // (SK_KMAX: gemm_plan.h)
 template <bool HILO>
 __global__ __launch_bounds__(256) void smallk_kernel(const GemmLaunch L) {
     const int lane = threadIdx.x & 63;
@@ -1315,15 +1298,6 @@ __global__ __launch_bounds__(256) void smallk_kernel(const GemmLaunch L) {
         if (tile + 2 < tend) load_x(tile + 2, xa);
         if (tile + 1 < tend) mul_store(tile + 1, xb);
     }
-}
-// every problem: fp16 weights, K <= SK_KMAX, fp32 output only, no post-op, no K split
-bool smallk_supported(const GemmLaunch &L) {
-    if (L.nprob < 1) return false;
-    for (int i = 0; i < L.nprob; ++i) {
-        const GemmProb &g = L.p[i];
-        if (g.fmt != W_F16 || g.K > SK_KMAX || g.K % 32 || g.rows % 16 || !g.out_f32 || g.out_hi || g.post != POST_NONE || g.ksb != 1) return false;
-    }
-    return true;
 }
 // L.p[i].block_begin = first (problem, strip) item of problem i, L.total_blocks = items in all
 void launch_smallk(const GemmLaunch &L, bool hilo, hipStream_t s) {
@@ -2006,7 +1980,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tile3_kernel(const GemmLaunch L) 
     else if (P.fmt == W_INT8) tg3_body<W_INT8, NTL>(L, P, smem);
     else tg3_body<W_NF4, NTL>(L, P, smem);
 }
-bool gemm_tile3_supported(bool hilo, int K) { return !hilo && K % 128 == 0; }
 
 #endif
 #if RWKV_PART_ON(5)
@@ -2281,7 +2254,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tile4_kernel(const GemmLaunch L) 
     else if (P.fmt == W_INT8) tg4_body<W_INT8, 4, true>(L, P, smem);
     else tg4_body<W_NF4, 4, true>(L, P, smem);
 }
-bool gemm_tile4_supported(bool hilo, int K) { return hilo && K % 128 == 0; }
 
 
 // (Round 6 also built STREAM-K over this kernel and gemm_tile3: a grid of 512 resident blocks, the launch's (tile, 128-k group) units dealt evenly per
@@ -2311,26 +2283,19 @@ void launch_gemm_tile45(const GemmLaunch &L, int kind, int ntl, bool hilo, hipSt
 }
 #endif  // part 5: software-pipelined hi + lo tile kernel
 #if RWKV_PART_ON(2)
-// tile shapes, largest first: {waves, strips per wave, n-tiles, k per chunk}
-static const int kTileShapes[GEMM_TILE_SHAPES][5] = {{8, 2, 8, 128, 0}, {8, 1, 8, 128, 0}, {4, 1, 8, 128, 0}, {4, 1, 4, 128, 0}, {4, 1, 4, 256, 0}, {8, 1, 8, 256, 0},
-                                                     {4, 1, 4, 256, 1}, {4, 2, 4, 128, 1}, {4, 2, 8, 128, 1}, {8, 2, 8, 128, 1}, {4, 2, 8, 128, 2}, {4, 2, 4, 128, 2},
-                                                     {4, 2, 4, 128, 3}};
+// (the tile shapes: gemm_plan.h kTileShapes)
 // (Round 6 re-measured the 256 x 128 tile on FOUR waves — 64 rows x 128 tokens per wave, 128 accumulators in AGPRs, one block per CU, a third fewer LDS
 // and L2-port bytes per flop — in this file's plain chunked body: 537 TFLOP/s on the 7 B r/k/v/g launch against 488 for the same body on 128 x 128 and
 // 860 for the pipelined 128 x 128 kernel; round 3 had measured its pipelined form at 395-563.  profiles/r6_exp_tile_256x128_4waves.log; removed.)
 // (128 rows x 64 tokens with 8 waves, 256-k and 128-k chunks — half the operand re-reads of the 64x64 shapes on steps of a few hundred
 // rows — was built and measured in round 3: slower on every matrix but one, profiles/r3_exp_tile_128x64.log; removed.)
-int gemm_tile_blocks(int shape, int rows, int T) {
-    const int strips = kTileShapes[shape][0] * kTileShapes[shape][1], bt = kTileShapes[shape][2] * 16;
-    return ((rows / 16 + strips - 1) / strips) * ((T + bt - 1) / bt);
-}
-
 void launch_gemm_tile(const GemmLaunch &L, int shape, bool hilo, hipStream_t s) {
-    if (kTileShapes[shape][4] >= 3) {                          // part 5: software-pipelined hi + lo kernel
-        launch_gemm_tile45(L, kTileShapes[shape][4], kTileShapes[shape][2], hilo, s);
+    const TileShape &sh = kTileShapes[shape];
+    if (sh.kind >= 3) {                                        // part 5: software-pipelined hi + lo kernel
+        launch_gemm_tile45(L, sh.kind, sh.ntl, hilo, s);
         return;
     }
-    if (kTileShapes[shape][4] == 2) {                          // pipelined kernel (caller checked gemm_tile3_supported)
+    if (sh.kind == 2) {                                        // pipelined kernel (caller checked gemm_tile3_supported)
         static bool attr3[16] = {false};
         int dev3 = 0;
         (void)hipGetDevice(&dev3);
@@ -2339,29 +2304,27 @@ void launch_gemm_tile(const GemmLaunch &L, int shape, bool hilo, hipStream_t s) 
             (void)hipFuncSetAttribute((const void *)gemm_tile3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr3[dev3 & 15] = true;
         }
-        if (kTileShapes[shape][2] == 8) hipLaunchKernelGGL(gemm_tile3_kernel<8>, dim3(L.total_blocks), dim3(256), (size_t)T3_NB * 8 * 2 * 512 * 2, s, L);
-        else hipLaunchKernelGGL(gemm_tile3_kernel<4>, dim3(L.total_blocks), dim3(256), (size_t)T3_NB * 4 * 2 * 512 * 2, s, L);
+        if (sh.ntl == 8) hipLaunchKernelGGL(gemm_tile3_kernel<8>, dim3(L.total_blocks), dim3(sh.waves * 64), (size_t)T3_NB * 8 * 2 * 512 * 2, s, L);
+        else hipLaunchKernelGGL(gemm_tile3_kernel<4>, dim3(L.total_blocks), dim3(sh.waves * 64), (size_t)T3_NB * 4 * 2 * 512 * 2, s, L);
         return;
     }
-    const int bt = kTileShapes[shape][2] * 16, kc = kTileShapes[shape][3];
-    const size_t lds = (size_t)2 * (hilo ? 2 : 1) * (bt / 16) * (kc / 32) * 1024;
+    const size_t lds = (size_t)2 * (hilo ? 2 : 1) * sh.ntl * (sh.kc / 32) * 1024;
     static bool attr_done[16] = {false};
     int dev = 0;
     (void)hipGetDevice(&dev);
-#define TG_SH(X, h) X(h, 8, 2, 8, 128, false, 0) X(h, 8, 1, 8, 128, false, 1) X(h, 4, 1, 8, 128, false, 2) X(h, 4, 1, 4, 128, false, 3) X(h, 4, 1, 4, 256, false, 4) \
-                    X(h, 8, 1, 8, 256, false, 5) X(h, 4, 1, 4, 256, true, 6) X(h, 4, 2, 4, 128, true, 7) X(h, 4, 2, 8, 128, true, 8) X(h, 8, 2, 8, 128, true, 9)
-#define TG_VARIANTS(X) TG_SH(X, true) TG_SH(X, false)
-    if (!attr_done[dev & 15]) {
-#define SET_ATTR(h, w, p, n, k, g, i) (void)hipFuncSetAttribute((const void *)gemm_tile_kernel<h, w, p, n, k, g>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        TG_VARIANTS(SET_ATTR)
+    if (!attr_done[dev & 15]) {                                // one instantiation per chunked shape and operand form (kind 1: X tiles by global_load_lds)
+#define SET_ATTR(w, p, n, k, kind, i) \
+        (void)hipFuncSetAttribute((const void *)gemm_tile_kernel<true, w, p, n, k, kind == 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        (void)hipFuncSetAttribute((const void *)gemm_tile_kernel<false, w, p, n, k, kind == 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        GEMM_TILE_CHUNKED(SET_ATTR)
 #undef SET_ATTR
         attr_done[dev & 15] = true;
     }
-#define LAUNCH(h, w, p, n, k, g, i) if (hilo == h && shape == i) hipLaunchKernelGGL((gemm_tile_kernel<h, w, p, n, k, g>), dim3(L.total_blocks), dim3(w * 64), lds, s, L);
-    TG_VARIANTS(LAUNCH)
+#define LAUNCH(w, p, n, k, kind, i) \
+    if (shape == i && hilo) hipLaunchKernelGGL((gemm_tile_kernel<true, w, p, n, k, kind == 1>), dim3(L.total_blocks), dim3(w * 64), lds, s, L); \
+    if (shape == i && !hilo) hipLaunchKernelGGL((gemm_tile_kernel<false, w, p, n, k, kind == 1>), dim3(L.total_blocks), dim3(w * 64), lds, s, L);
+    GEMM_TILE_CHUNKED(LAUNCH)
 #undef LAUNCH
-#undef TG_VARIANTS
-#undef TG_SH
 }
 
 #endif  // part 2: prefill tile GEMM

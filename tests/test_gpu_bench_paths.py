@@ -132,7 +132,7 @@ def wide3b():
 def test_every_prefill_tile_shape_at_3b_width(wide3b, shape, qt):
     """gemm_tile_kernel in each of its ten shapes, the pipelined kernel on 128x128 (shape 10) and 128x64 tiles (shape 11) and the software-pipelined
     hi + lo kernel (shape 12: the promoted time-mix launch of the default Precision::Fp16; a forced pipelined shape a launch's operand form
-    cannot take falls back to the 64x64 shape) — rwkv_engine.cpp picks by grid size and operand form, the rest are reachable through
+    cannot take falls back to the 64x64 shape) — csrc/gemm_plan.h picks by grid size and operand form, the rest are reachable through
     RWKV_TILE_SHAPE — on a 548-row ragged step of 3B-wide matrices, plus `wkv_chunk_kernel<6,64>` at H = 40."""
     st, ps, ref = wide3b
     want, states = ref[qt]
