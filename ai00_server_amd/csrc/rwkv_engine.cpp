@@ -291,6 +291,26 @@ struct rwkv_engine {
     std::map<uint64_t, GraphEntry> graphs;
     std::map<int, hipGraphExec_t> greedy_graphs;               // rwkv_decode_greedy: step + arg-max feedback, keyed by slot count
     std::set<uint64_t> graph_seen;
+    // device-resident sampled generation (rwkv_gen_*): per-slot contexts, dense penalty / bias rows, the step's SampleRow array and the
+    // output ring live on the device; everything is allocated by the first rwkv_gen_arm
+    static constexpr int GEN_RING_STEPS = 1024;                  // steps one enqueue covers (longer runs are split)
+    std::vector<GenSlot> gen_host;                               // mirror of d_gen, read back after every run
+    std::vector<char> gen_armed;
+    std::vector<uint32_t> gen_held;                              // the token a running slot consumes next (its last emitted one)
+    std::vector<float *> gen_shadow;                             // per slot: sxa | sxf | wkv of the step it finished in
+    GenSlot *d_gen = nullptr;
+    float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
+    float **d_gen_shadow = nullptr;
+    SampleRow *d_gen_rows = nullptr;
+    int *d_gen_tok = nullptr, *d_gen_runstep = nullptr;
+    unsigned *d_gen_out = nullptr, *h_gen_out = nullptr;         // [2][GEN_RING_STEPS][max_batch]: tokens, then probabilities
+    std::map<std::vector<uint64_t>, GraphEntry> gen_graphs;      // one captured step per set of rows (slot mask + sampler kernels it needs)
+    std::set<std::vector<uint64_t>> gen_seen;
+    void gen_init();
+    void gen_arm(int slot, const rwkv_gen_params &p);
+    void gen_disarm_slot(int slot) { if (!gen_armed.empty()) gen_armed[(size_t)slot] = 0; }
+    void gen_step(const StepPlan &pl, bool any_nt, bool any_miro);
+    void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
     bool use_graphs = true;
     Knobs kn;                                                    // experiment switches, frozen at creation (rwkv_kernels.h)
 
@@ -319,6 +339,8 @@ struct rwkv_engine {
         if (s_copy) (void)hipStreamSynchronize(s_copy);
         for (auto &g : graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
         for (auto &g : greedy_graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
+        for (auto &g : gen_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+        if (h_gen_out) (void)hipHostFree(h_gen_out);
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
         if (slab_host) (void)hipHostFree(slab_host);
@@ -1218,6 +1240,7 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
         if (emitted) emitted[b] = 0;
         if (n_consumed) n_consumed[b] = 0;
         if (in[b].n_tokens && !in[b].tokens) throw RwkvError(RWKV_ERR_INVALID, "slot has n_tokens>0 but tokens==NULL");
+        if (in[b].n_tokens) gen_disarm_slot(b);
     }
     StepPlan pl;
     plan_step(last.data(), pl);
@@ -1296,6 +1319,7 @@ void rwkv_engine::infer(const rwkv_slot_input *in, rwkv_slot_output *out) {
         if (in[b].n_tokens && !in[b].tokens) throw RwkvError(RWKV_ERR_INVALID, "slot has n_tokens>0 but tokens==NULL");
         if (in[b].option != RWKV_OPTION_LAST && in[b].option != RWKV_OPTION_FULL && in[b].option != RWKV_OPTION_NONE)
             throw RwkvError(RWKV_ERR_INVALID, "bad RnnOption");
+        if (in[b].n_tokens) gen_disarm_slot(b);                  // the caller moves the slot's state itself: its generation context is void
     }
     StepPlan pl;
     plan_step(in, pl);
@@ -1343,6 +1367,201 @@ void rwkv_engine::infer(const rwkv_slot_input *in, rwkv_slot_output *out) {
     HIP_CHECK(hipMemcpyAsync(logits_host, logits, (size_t)pl.n_out * V * 4, hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     for (const Seg &g : segs) std::memcpy(g.dst, logits_host + g.row0 * V, g.rows * V * 4);
+}
+
+// ------------------------------------------------------------------------------------------------
+// device-resident sampled generation (rwkv_gen_arm / _run, include/rwkv_abi.h): `process` (run.rs:788-1020) with the samplers on the device
+// ------------------------------------------------------------------------------------------------
+void rwkv_engine::gen_init() {
+    if (d_gen) return;
+    const size_t B = (size_t)max_batch, V = (size_t)info.num_vocab;
+    gen_host.assign(B, GenSlot{});
+    gen_armed.assign(B, 0);
+    gen_held.assign(B, 0);
+    gen_shadow.assign(B, nullptr);
+    d_gen_pen = dalloc<float>(B * V);
+    d_gen_bias = dalloc<float>(B * V);
+    d_gen_shadow = dalloc<float *>(B);
+    d_gen_rows = dalloc<SampleRow>((size_t)chunk);
+    d_gen_tok = dalloc<int>((size_t)chunk);
+    d_gen_prob = dalloc<float>((size_t)chunk);
+    d_gen_runstep = dalloc<int>(1);
+    d_gen_out = dalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
+    HIP_CHECK(hipHostMalloc((void **)&h_gen_out, 2 * (size_t)GEN_RING_STEPS * B * 4, hipHostMallocDefault));
+    HIP_CHECK(hipMemset(d_gen_shadow, 0, B * sizeof(float *)));
+    d_gen = dalloc<GenSlot>(B);                                   // last: marks the block as complete
+    HIP_CHECK(hipMemset(d_gen, 0, B * sizeof(GenSlot)));
+}
+
+void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t V = (size_t)info.num_vocab;
+    if (V > 65536) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling needs num_vocab <= 65536");
+    if (p.allow) throw RwkvError(RWKV_ERR_UNSUPPORTED, "a formatter mask needs the host between tokens: use rwkv_infer_sample");
+    if (p.kind < RWKV_SAMPLER_NUCLEUS || p.kind > RWKV_SAMPLER_MIROSTAT) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unknown sampler kind");
+    const bool miro = p.kind == RWKV_SAMPLER_MIROSTAT;
+    if (!miro && p.top_k > 256) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling supports top_k <= 256");
+    if (p.n_stop > RWKV_GEN_MAX_STOP) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP stop tokens");
+    if (!miro && !(p.temperature > 0.f)) throw RwkvError(RWKV_ERR_INVALID, "temperature must be > 0");
+    if (p.max_tokens <= 0) throw RwkvError(RWKV_ERR_INVALID, "max_tokens must be > 0");
+    if (p.first_token >= V) throw RwkvError(RWKV_ERR_INVALID, "first_token out of range");
+    if ((p.n_penalty && (!p.penalty_tokens || !p.penalty_values)) || (p.n_bias && (!p.bias_tokens || !p.bias_values)) || (p.n_stop && !p.stop_tokens))
+        throw RwkvError(RWKV_ERR_INVALID, "null penalty / bias / stop array");
+    gen_init();
+    const size_t b = (size_t)slot;
+    if (!gen_shadow[b]) {                                          // the slot's first arm: room for its state at the step it will finish in
+        gen_shadow[b] = dalloc<float>((size_t)(2 * sx_slot_stride + wkv_slot_stride));
+        HIP_CHECK(hipMemcpy(d_gen_shadow + b, &gen_shadow[b], sizeof(float *), hipMemcpyHostToDevice));
+    }
+    GenSlot g{};
+    g.top_p = p.top_p; g.top_k = miro ? 1 : p.top_k; g.temperature = miro ? 1.0f : p.temperature; g.tau = p.tau; g.kind = p.kind;
+    g.presence = p.presence_penalty; g.frequency = p.frequency_penalty; g.decay = p.penalty_decay;
+    g.miro_target = p.miro_target; g.miro_rate = p.miro_rate;
+    g.seed = p.seed; g.stream = p.stream; g.draws = 0;
+    g.max_tokens = p.max_tokens; g.emitted = 0; g.finish = RWKV_GEN_RUNNING; g.freeze_at = -1;
+    g.n_stop = (int)p.n_stop;
+    for (size_t i = 0; i < p.n_stop; ++i) g.stop[i] = p.stop_tokens[i];
+    std::vector<unsigned> pen(V, GEN_ABSENT);                      // dense rows: 256 KiB each at the World vocabulary, once per request
+    std::vector<float> bias(V, 0.f);
+    if (!miro)
+        for (size_t i = 0; i < p.n_penalty; ++i)
+            if (p.penalty_tokens[i] < V) std::memcpy(&pen[p.penalty_tokens[i]], &p.penalty_values[i], 4);
+    for (size_t i = 0; i < p.n_bias; ++i)
+        if (p.bias_tokens[i] < V && p.bias_values[i] != 0.f) { bias[p.bias_tokens[i]] += p.bias_values[i]; g.has_bias = 1; }
+    HIP_CHECK(hipMemcpyAsync(d_gen_pen + b * V, pen.data(), V * 4, hipMemcpyHostToDevice, s_main));
+    HIP_CHECK(hipMemcpyAsync(d_gen_bias + b * V, bias.data(), V * 4, hipMemcpyHostToDevice, s_main));
+    HIP_CHECK(hipMemcpyAsync(d_gen + b, &g, sizeof(GenSlot), hipMemcpyHostToDevice, s_main));
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    gen_host[b] = g;
+    gen_held[b] = p.first_token;
+    gen_armed[b] = 1;
+}
+
+// one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, sampler state machine around nucleus_kernel
+void rwkv_engine::gen_step(const StepPlan &pl, bool any_nt, bool any_miro) {
+    run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
+    GenArgs a{};
+    a.slots = d_gen; a.row_slot = d_meta + chunk; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
+    a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
+    a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
+    a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = pl.T;
+    a.sxa = sxa; a.sxf = sxf; a.wkv = wkv; a.sx_slot_stride = sx_slot_stride; a.wkv_slot_stride = wkv_slot_stride;
+    a.shadow = d_gen_shadow;
+    launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
+    launch(FAM_SAMPLE, [&] { launch_nucleus(logits, pl.T, info.num_vocab, d_gen_rows, any_nt, any_miro, d_gen_tok, d_gen_prob, s_main); });
+    launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
+    launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
+}
+
+void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish) {
+    HIP_CHECK(hipSetDevice(device));
+    (void)hipGetLastError();                                       // the poll behind the enqueue must only see this call's errors
+    const int B = max_batch;
+    const float nan = std::nanf("");
+    std::fill(out_tokens, out_tokens + (size_t)n_steps * B, 0xFFFFFFFFu);
+    if (out_probs) std::fill(out_probs, out_probs + (size_t)n_steps * B, nan);
+    if (n_emitted) std::fill(n_emitted, n_emitted + B, 0);
+    if (finish) std::fill(finish, finish + B, (int32_t)RWKV_GEN_RUNNING);
+    for (int done = 0; done < n_steps && !gen_armed.empty();) {
+        // the rows of this enqueue: armed slots that have not finished, in slot order
+        std::vector<int> rows;
+        int n = 0;
+        bool any_nt = false, any_miro = false;
+        for (int b = 0; b < B; ++b) {
+            if (!gen_armed[(size_t)b] || gen_host[(size_t)b].finish) continue;
+            rows.push_back(b);
+            n = std::max(n, gen_host[(size_t)b].max_tokens - gen_host[(size_t)b].emitted);   // nobody runs longer than this
+            if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true;
+        }
+        if (rows.empty()) break;
+        if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
+        n = std::min({n, n_steps - done, (int)GEN_RING_STEPS});
+        // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
+        std::vector<rwkv_slot_input> in((size_t)B);
+        std::vector<uint32_t> held((size_t)B, 0);
+        std::vector<int> fb;
+        for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
+        for (int b : rows) { held[(size_t)b] = gen_held[(size_t)b]; in[(size_t)b] = rwkv_slot_input{&held[(size_t)b], 1, RWKV_OPTION_LAST, 0}; fb.push_back((int)gen_held[(size_t)b]); }
+        StepPlan pl;
+        plan_step(in.data(), pl);
+        upload_plan(pl);
+        step_max_rows = 1;
+        const size_t ring = (size_t)GEN_RING_STEPS * B;
+        HIP_CHECK(hipMemcpyAsync(d_tok_feedback, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, s_main));
+        HIP_CHECK(hipMemsetAsync(d_gen_runstep, 0xFF, 4, s_main));                          // -1: gen_pre counts up
+        HIP_CHECK(hipMemsetAsync(d_gen_out, 0xFF, (size_t)n * B * 4, s_main));              // 0xFFFFFFFF: nothing emitted
+        HIP_CHECK(hipMemsetAsync(d_gen_out + ring, 0xFF, (size_t)n * B * 4, s_main));       // ... and the same bits are a NaN
+        HIP_CHECK(hipStreamSynchronize(s_main));                                            // `fb` is pageable
+        std::vector<uint64_t> key((size_t)(B + 63) / 64 + 1, 0);
+        for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
+        key.back() = (any_nt ? 1u : 0u) | (any_miro ? 2u : 0u);
+        int s0 = 0;
+        hipGraphExec_t exec = nullptr;
+        if (use_graphs) {
+            auto it = gen_graphs.find(key);
+            if (it == gen_graphs.end()) {
+                // a set of rows runs its first step directly (like run_plan: a one-off shape never pays capture + instantiation, and the
+                // launchers' one-time attribute calls happen outside a capture); the steps after it go through the captured graph
+                if (gen_seen.insert(key).second) { gen_step(pl, any_nt, any_miro); s0 = 1; }
+                if (s0 < n) {
+                    hipGraph_t g = nullptr;
+                    HIP_CHECK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
+                    try {
+                        gen_step(pl, any_nt, any_miro);
+                    } catch (...) {
+                        (void)hipStreamEndCapture(s_main, &g);
+                        if (g) (void)hipGraphDestroy(g);
+                        throw;
+                    }
+                    HIP_CHECK(hipStreamEndCapture(s_main, &g));
+                    GraphEntry ge;
+                    HIP_CHECK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
+                    HIP_CHECK(hipGraphDestroy(g));
+                    if (gen_graphs.size() >= 64) {                     // bounded like `graphs`: the least recently used set goes
+                        auto victim = gen_graphs.begin();
+                        for (auto o = gen_graphs.begin(); o != gen_graphs.end(); ++o) if (o->second.used < victim->second.used) victim = o;
+                        (void)hipGraphExecDestroy(victim->second.exec);
+                        gen_graphs.erase(victim);
+                    }
+                    if (gen_seen.size() > 4096) gen_seen.clear();
+                    it = gen_graphs.emplace(key, ge).first;
+                }
+            }
+            if (it != gen_graphs.end()) { it->second.used = ++graph_clock; exec = it->second.exec; }
+        }
+        for (int s = s0; s < n; ++s) {
+            if (exec) HIP_CHECK(hipGraphLaunch(exec, s_main));
+            else gen_step(pl, any_nt, any_miro);
+        }
+        HIP_CHECK(hipPeekAtLastError());                               // a failed launch is this call's error, not stale tokens with RWKV_OK
+        HIP_CHECK(hipMemcpyAsync(h_gen_out, d_gen_out, (size_t)n * B * 4, hipMemcpyDeviceToHost, s_main));
+        HIP_CHECK(hipMemcpyAsync(h_gen_out + ring, d_gen_out + ring, (size_t)n * B * 4, hipMemcpyDeviceToHost, s_main));
+        std::vector<GenSlot> back((size_t)B);
+        HIP_CHECK(hipMemcpyAsync(back.data(), d_gen, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, s_main));
+        HIP_CHECK(hipStreamSynchronize(s_main));
+        std::memcpy(out_tokens + (size_t)done * B, h_gen_out, (size_t)n * B * 4);
+        if (out_probs) std::memcpy(out_probs + (size_t)done * B, h_gen_out + ring, (size_t)n * B * 4);
+        bool restored = false;
+        for (int b : rows) {
+            const size_t sb = (size_t)b;
+            const int got = back[sb].emitted - gen_host[sb].emitted;
+            gen_host[sb] = back[sb];
+            if (n_emitted) n_emitted[b] += got;
+            for (int s = n - 1; s >= 0 && got > 0; --s)
+                if (h_gen_out[(size_t)s * B + sb] != 0xFFFFFFFFu) { gen_held[sb] = h_gen_out[(size_t)s * B + sb]; break; }
+            if (back[sb].finish) {
+                // the slot rode the steps behind the one it finished in: its state goes back to what it was there (the state rule)
+                const float *sh = gen_shadow[sb];
+                HIP_CHECK(hipMemcpyAsync(sxa + b * sx_slot_stride, sh, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+                HIP_CHECK(hipMemcpyAsync(sxf + b * sx_slot_stride, sh + sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+                HIP_CHECK(hipMemcpyAsync(wkv + b * wkv_slot_stride, sh + 2 * sx_slot_stride, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+                restored = true;
+            }
+        }
+        if (restored) HIP_CHECK(hipStreamSynchronize(s_main));
+        done += n;
+    }
+    if (finish) for (int b = 0; b < B && !gen_armed.empty(); ++b) if (gen_armed[(size_t)b]) finish[b] = gen_host[(size_t)b].finish;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1547,6 +1766,7 @@ rwkv_status rwkv_state_load(rwkv_engine *e, int32_t slot, const float *src) {
         check_slot(e, slot);
         if (!src) throw RwkvError(RWKV_ERR_INVALID, "null src");
         HIP_CHECK(hipSetDevice(e->device));
+        e->gen_disarm_slot(slot);
         const size_t n = rwkv_state_len(e);
         std::memcpy(e->slab_host, src, n * 4);
         HIP_CHECK(hipMemcpyAsync(e->slab_dev, e->slab_host, n * 4, hipMemcpyHostToDevice, e->s_main));
@@ -1645,6 +1865,7 @@ rwkv_status rwkv_state_write(rwkv_engine *e, int32_t slot, const rwkv_dstate *s)
         check_slot(e, slot);
         if (!s) throw RwkvError(RWKV_ERR_INVALID, "null snap");
         HIP_CHECK(hipSetDevice(e->device));
+        e->gen_disarm_slot(slot);
         const size_t nsx = (size_t)e->sx_slot_stride * 4, nw = (size_t)e->wkv_slot_stride * 4;
         HIP_CHECK(hipMemcpyAsync(e->sxa + slot * e->sx_slot_stride, s->sxa, nsx, hipMemcpyDeviceToDevice, e->s_main));
         HIP_CHECK(hipMemcpyAsync(e->sxf + slot * e->sx_slot_stride, s->sxf, nsx, hipMemcpyDeviceToDevice, e->s_main));
@@ -1712,6 +1933,7 @@ rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *
             throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
         HIP_CHECK(hipSetDevice(e->device));
         use_knobs(e->kn);
+        for (int b = 0; b < n_slots; ++b) e->gen_disarm_slot(b);
         StepPlan pl;
         std::vector<rwkv_slot_input> in(e->max_batch);
         std::vector<uint32_t> tk(first_tokens, first_tokens + n_slots);
@@ -1765,6 +1987,35 @@ rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *
         HIP_CHECK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
         if (elapsed_ms) *elapsed_ms = ms;
         HIP_CHECK(hipMemcpy(out_tokens, e->d_hist, need * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// ---- device-resident sampled generation ------------------------------------------------------------
+rwkv_status rwkv_gen_arm(rwkv_engine *e, int32_t slot, const rwkv_gen_params *p) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!p) throw RwkvError(RWKV_ERR_INVALID, "null params");
+        use_knobs(e->kn);
+        e->gen_arm(slot, *p);
+    });
+}
+rwkv_status rwkv_gen_disarm(rwkv_engine *e, int32_t slot) {
+    return guard([&] {
+        check_slot(e, slot);
+        e->gen_disarm_slot(slot);
+    });
+}
+rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish) {
+    return guard([&] {
+        if (!e || !out_tokens || n_steps <= 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
+        use_knobs(e->kn);
+        e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish);
+    });
+}
+rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out) {
+    return guard([&] {
+        if (n && !out) throw RwkvError(RWKV_ERR_INVALID, "null out");
+        for (size_t i = 0; i < n; ++i) out[i] = gen_uniform_draw(seed, stream, first_step + (uint32_t)i);
     });
 }
 

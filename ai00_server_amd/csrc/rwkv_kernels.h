@@ -258,6 +258,52 @@ void launch_logit_adjust(float *logits, int V, const int *rows, const int *toks,
 void launch_logit_mask(float *logits, int V, const int *rows, const unsigned char *allow, int n, hipStream_t s);   // V % 4 == 0
 void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat,
                     int *out_tok, float *out_prob, hipStream_t s);
+// ---- device-resident sampled generation (rwkv_gen_*, include/rwkv_abi.h): the sampler state machine of sampler/*.rs on the device ----
+constexpr unsigned GEN_ABSENT = 0xFFFFFFFFu;   // bit pattern of "no entry" in a slot's dense penalty row (membership, not value: nucleus.rs:104-119)
+constexpr int GEN_MAX_STOP = 8;
+struct GenSlot {                    // one per slot, device-resident; the host keeps a mirror and reads it back after every run
+    float top_p; int top_k; float temperature; float tau;   // tau: Typical's tau / Mirostat's current max_surprise
+    int kind;
+    float presence, frequency, decay;                       // nucleus.rs:13-26
+    float miro_target, miro_rate;                           // mirostat.rs:85-87
+    unsigned long long seed;
+    unsigned stream, draws;                                 // draws: uniform draws since the slot was armed (the `step` of gen_uniform)
+    int max_tokens, emitted, finish;                        // finish: RWKV_GEN_*
+    int freeze_at;                                          // step of the run in which the slot finished (gen_freeze copies its state then)
+    int has_bias, n_stop;
+    unsigned stop[GEN_MAX_STOP];
+};
+struct GenArgs {
+    GenSlot *slots;                 // [max_batch]
+    const int *row_slot;            // [n_rows] slot of each row of the step
+    float *logits;                  // [n_rows][V]
+    float *penalty, *bias;          // [max_batch][V]; penalty: GEN_ABSENT bits = no entry; bias may be null when no armed slot has one
+    SampleRow *rows;                // [n_rows] this step's sampler parameters (read by nucleus_kernel)
+    const int *samp_tok;            // [n_rows] what nucleus_kernel wrote
+    const float *samp_prob;
+    int *feedback;                  // [n_rows] token each row consumes in the next step
+    unsigned *out_tok; float *out_prob;   // [steps][max_batch] output ring of this run
+    int *run_step;                  // step index inside the run; -1 before the first step
+    int max_batch, V, n_rows;
+    // gen_freeze: the state of a slot that finished in this step -> its shadow
+    float *sxa, *sxf, *wkv; long sx_slot_stride, wkv_slot_stride;
+    float *const *shadow;           // [max_batch] sxa | sxf | wkv of the slot, or null
+};
+#ifdef __HIP__
+#define RWKV_HD __host__ __device__
+#else
+#define RWKV_HD
+#endif
+RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (float)(z >> 40) * 5.9604644775390625e-8f;       // 24 bits * 2^-24: exact
+}
+void launch_gen_pre(const GenArgs &a, hipStream_t s);
+void launch_gen_post(const GenArgs &a, hipStream_t s);
+void launch_gen_freeze(const GenArgs &a, hipStream_t s);
 // two-stage arg-max; scratch_v / scratch_i hold n_rows*32 partial (value, index) pairs
 void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *scratch_v, int *scratch_i, hipStream_t s);
 

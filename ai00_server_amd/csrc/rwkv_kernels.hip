@@ -3396,6 +3396,114 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 }
 
 // =====================================================================================
+// Device-resident sampled generation (rwkv_gen_run): the sampler state machine of sampler/nucleus.rs, typical.rs and mirostat.rs
+// around `nucleus_kernel`, so that a captured step feeds itself.  Per step, after the head GEMM:
+//   gen_pre     penalty (transform, nucleus.rs:61-67) and bias (run.rs:681-683) onto the logits row from the slot's dense penalty /
+//               bias rows, and this step's SampleRow (uniform draw, Mirostat's max_surprise) for nucleus_kernel
+//   nucleus_kernel, as it is
+//   gen_post    the tail of `sample` (nucleus.rs:104-119 / mirostat.rs:85-87), the token into the feedback buffer and the output
+//               ring, stop tokens and max_tokens (run.rs:855, 905-917)
+//   gen_freeze  the state of a slot that finished IN THIS STEP into its shadow (the step keeps its shape until the run ends; the host
+//               puts the shadow back)
+// Every value is written with plain vector stores.  All arithmetic is the per-token path's, operation for operation: the host
+// mirrors (include/rwkv_sampler.hpp, harness.py) round every operation to f32, so nothing here may contract into an FMA — and
+// HIP's __fmul_rn / __fadd_rn are plain `*` / `+` that hipcc's default -ffp-contract=fast fuses after inlining (measured: the
+// penalty of a repeated token was off by one ulp after 14 draws), hence `#pragma clang fp contract(off)` in the three helpers.
+// =====================================================================================
+__device__ __forceinline__ float gen_adjust(float x, unsigned pbits, float b) {
+#pragma clang fp contract(off)
+    if (pbits != GEN_ABSENT) {
+        const float np = -__uint_as_float(pbits);
+        return b != 0.f ? x + (np + b) : x + np;                   // x + ((-p) + b): NucleusSampler::adjustments()
+    }
+    return b != 0.f ? x + b : x;
+}
+__global__ __launch_bounds__(256) void gen_pre_kernel(GenArgs a) {
+    const int row = blockIdx.y, tid = threadIdx.x;
+    if (blockIdx.x == 0 && row == 0 && tid == 0) *a.run_step += 1;   // nothing in this launch reads it; gen_post / gen_freeze of the step do
+    const int slot = a.row_slot[row];
+    const GenSlot &g = a.slots[slot];
+    if (g.finish) return;                                          // rides along until the run ends: its rows are thrown away
+    if (blockIdx.x == 0 && tid == 0)
+        a.rows[row] = SampleRow{g.top_p, g.top_k, g.temperature, gen_uniform_draw(g.seed, g.stream, g.draws), g.kind, g.tau};
+    const bool pen = g.kind != 2;                                  // Mirostat's transform is a no-op (mirostat.rs:40)
+    if (!pen && !g.has_bias) return;
+    const int V = a.V;
+    float *x = a.logits + (long)row * V;
+    const float *pr = a.penalty + (long)slot * V, *br = g.has_bias ? a.bias + (long)slot * V : nullptr;
+    for (int i = (blockIdx.x * 256 + tid) * 4; i < V; i += gridDim.x * 1024) {     // V % 16 == 0 (validate_info)
+        float4 v = *(const float4 *)(x + i);
+        const uint4 p = pen ? *(const uint4 *)(pr + i) : make_uint4(GEN_ABSENT, GEN_ABSENT, GEN_ABSENT, GEN_ABSENT);
+        const float4 b = br ? *(const float4 *)(br + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v.x = gen_adjust(v.x, p.x, b.x); v.y = gen_adjust(v.y, p.y, b.y); v.z = gen_adjust(v.z, p.z, b.z); v.w = gen_adjust(v.w, p.w, b.w);
+        *(float4 *)(x + i) = v;
+    }
+}
+__device__ __forceinline__ unsigned gen_decay(unsigned pbits, int i, int tok, float decay, float freq, float pres) {
+#pragma clang fp contract(off)
+    float p = __uint_as_float(pbits);
+    const bool present = pbits != GEN_ABSENT;
+    if (present) p = p * decay;                                    // nucleus.rs:104-108
+    if (i == tok) p = present ? p + freq : pres;                   // nucleus.rs:110-119
+    return (present || i == tok) ? __float_as_uint(p) : GEN_ABSENT;
+}
+__device__ __forceinline__ float gen_mirostat(float max_surprise, float surprise, float target, float rate) {   // mirostat.rs:85-87
+#pragma clang fp contract(off)
+    const float error = surprise - target;
+    const float step = rate * error;
+    return fminf(max_surprise - step, 4.0f * target);
+}
+__global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
+    const int row = blockIdx.y, tid = threadIdx.x;
+    const int slot = a.row_slot[row];
+    GenSlot &g = a.slots[slot];
+    const int tok = a.samp_tok[row];
+    // The penalty pass does not look at `finish` (thread 0 of block 0 writes it in this launch): a finished slot's row is dead data
+    // until the slot is armed again, which rebuilds it.
+    if (g.kind != 2) {
+        const int V = a.V;
+        float *pr = a.penalty + (long)slot * V;
+        const float decay = g.decay, freq = g.frequency, pres = g.presence;
+        for (int i = (blockIdx.x * 256 + tid) * 4; i < V; i += gridDim.x * 1024) {
+            uint4 p = *(const uint4 *)(pr + i);
+            p.x = gen_decay(p.x, i, tok, decay, freq, pres); p.y = gen_decay(p.y, i + 1, tok, decay, freq, pres);
+            p.z = gen_decay(p.z, i + 2, tok, decay, freq, pres); p.w = gen_decay(p.w, i + 3, tok, decay, freq, pres);
+            *(uint4 *)(pr + i) = p;
+        }
+    }
+    if (blockIdx.x != 0 || tid != 0 || g.finish) return;
+    const float prob = a.samp_prob[row];
+    const int k = *a.run_step;
+    a.out_tok[(long)k * a.max_batch + slot] = (unsigned)tok;
+    a.out_prob[(long)k * a.max_batch + slot] = prob;
+    a.feedback[row] = tok;
+    g.draws += 1;
+    g.emitted += 1;
+    if (g.kind == 2) g.tau = gen_mirostat(g.tau, prob, g.miro_target, g.miro_rate);   // `prob` is the token surprise
+    bool stop = tok == 0;                                          // run.rs:855
+    for (int j = 0; j < g.n_stop; ++j) stop |= g.stop[j] == (unsigned)tok;
+    const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
+    if (fin) { g.freeze_at = k; g.finish = fin; }
+}
+__global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
+    const int slot = a.row_slot[blockIdx.y];
+    const GenSlot &g = a.slots[slot];
+    if (!g.finish || g.freeze_at != *a.run_step) return;           // the common case: one load per block and out
+    float *sh = a.shadow[slot];
+    if (!sh) return;
+    const long nsx = a.sx_slot_stride, nw = a.wkv_slot_stride;      // multiples of 64 floats
+    const float *src[3] = {a.sxa + slot * nsx, a.sxf + slot * nsx, a.wkv + slot * nw};
+    float *dst[3] = {sh, sh + nsx, sh + 2 * nsx};
+    const long len[3] = {nsx, nsx, nw};
+    for (int part = 0; part < 3; ++part)
+        for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < len[part]; i += (long)gridDim.x * 1024)
+            *(float4 *)(dst[part] + i) = *(const float4 *)(src[part] + i);
+}
+void launch_gen_pre(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_pre_kernel, dim3(16, a.n_rows), dim3(256), 0, s, a); }
+void launch_gen_post(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_post_kernel, dim3(16, a.n_rows), dim3(256), 0, s, a); }
+void launch_gen_freeze(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_freeze_kernel, dim3(64, a.n_rows), dim3(256), 0, s, a); }
+
+// =====================================================================================
 // Load-time layout kernels
 // =====================================================================================
 // fp16 tile: out uint4 index ((strip*KT + kt)*64 + lane) <- W[strip*16 + (lane&15)][kt*32 + (lane>>4)*8 .. +8]

@@ -59,6 +59,16 @@ class _SampleC(C.Structure):
                 ("kind", C.c_int32), ("tau", C.c_float), ("allow", C.POINTER(C.c_uint8))]
 
 
+class _GenParamsC(C.Structure):
+    _fields_ = [("first_token", C.c_uint32), ("max_tokens", C.c_int32), ("kind", C.c_int32), ("top_p", C.c_float),
+                ("top_k", C.c_int32), ("temperature", C.c_float), ("tau", C.c_float), ("presence_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("penalty_decay", C.c_float), ("miro_target", C.c_float), ("miro_rate", C.c_float),
+                ("penalty_tokens", C.POINTER(C.c_uint32)), ("penalty_values", C.POINTER(C.c_float)), ("n_penalty", C.c_size_t),
+                ("bias_tokens", C.POINTER(C.c_uint32)), ("bias_values", C.POINTER(C.c_float)), ("n_bias", C.c_size_t),
+                ("stop_tokens", C.POINTER(C.c_uint32)), ("n_stop", C.c_size_t), ("allow", C.POINTER(C.c_uint8)),
+                ("seed", C.c_uint64), ("stream", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _SlotOutC(C.Structure):
     _fields_ = [("logits", C.POINTER(C.c_float)), ("logits_capacity_rows", C.c_size_t), ("n_rows", C.c_size_t),
                 ("n_consumed", C.c_size_t)]
@@ -84,6 +94,11 @@ ABI_SYMBOLS = {
     "rwkv_host_free": (None, [C.c_void_p]),
     "rwkv_infer_sample": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(_SampleC), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]),
+    "rwkv_gen_arm": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenParamsC)]),
+    "rwkv_gen_disarm": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "rwkv_gen_run": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32)]),
+    "rwkv_gen_uniform": (C.c_int32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_float)]),
     "rwkv_plan_chunk": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "rwkv_state_len": (C.c_size_t, [C.c_void_p]),
     "rwkv_state_shape": (None, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -204,6 +219,20 @@ def plan_chunk(n_tokens: list[int], token_chunk_size: int) -> list[int]:
     out = (C.c_int32 * n)()
     _check(lib().rwkv_plan_chunk(n, token_chunk_size, a, out))
     return list(out)
+
+
+def gen_uniform(seed: int, stream: int, step: int, n: int | None = None):
+    """The uniform draw of (seed, stream, step) that a slot armed with `gen_arm` makes (rwkv_gen_uniform; host only, needs no GPU):
+    one float, or with `n` the float32 array of the draws step .. step + n - 1."""
+    out = np.empty(1 if n is None else int(n), np.float32)
+    _check(lib().rwkv_gen_uniform(int(seed), int(stream), int(step), out.size, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return float(out[0]) if n is None else out
+
+
+class GenFinish(enum.IntEnum):   # RWKV_GEN_*: FinishReason::{Stop, Length} run.rs:905-917
+    Running = 0
+    Stop = 1
+    Length = 2
 
 
 def list_adapters() -> list[str]:
@@ -500,6 +529,53 @@ class Runtime:
             ib.tokens = list(ib.tokens[consumed[b]:])
             out.append((int(toks_o[b]), float(probs_o[b])) if emitted[b] else None)
         return inp, out
+
+    # ---- device-resident sampled generation (rwkv_gen_arm / _run / _disarm): the sampler state lives on the device
+    def gen_arm(self, slot: int, first_token: int, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
+                stop_tokens=(), bias: dict | None = None, allow=None):
+        """Arm `slot` with the settings AND the current state of a host-side sampler (`harness.NucleusSampler` / `TypicalSampler` /
+        `MirostatSampler`, after its `init(prompt)`): the penalty map it holds is handed over, `sampler.bias` (or `bias`) rides along.
+        `first_token` is the token the first step consumes; draw `i` of the slot is `gen_uniform(seed, stream, i)` (stream defaults
+        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`)."""
+        kind = int(getattr(sampler, "kind", 0))
+        pen = {} if kind == 2 else dict(getattr(sampler, "penalties", {}))
+        bias = dict(bias if bias is not None else getattr(sampler, "bias", {}) or {})
+        pt = np.fromiter(pen.keys(), dtype=np.uint32, count=len(pen))
+        pv = np.fromiter(pen.values(), dtype=np.float32, count=len(pen))
+        bt = np.fromiter(bias.keys(), dtype=np.uint32, count=len(bias))
+        bv = np.fromiter(bias.values(), dtype=np.float32, count=len(bias))
+        st = np.asarray(list(stop_tokens), dtype=np.uint32)
+        u32p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, dtype=np.uint8)
+        p = _GenParamsC(int(first_token), int(max_tokens), kind, float(getattr(sampler, "top_p", 0.0)), int(sampler.top_k),
+                        float(sampler.temperature), float(getattr(sampler, "tau", 0.0)),
+                        float(getattr(sampler, "ap", 0.0)), float(getattr(sampler, "af", 0.0)), float(getattr(sampler, "ad", 1.0)),
+                        float(getattr(sampler, "target", 0.0)), float(getattr(sampler, "rate", 0.0)),
+                        pt.ctypes.data_as(u32p) if pt.size else None, pv.ctypes.data_as(f32p) if pv.size else None, pt.size,
+                        bt.ctypes.data_as(u32p) if bt.size else None, bv.ctypes.data_as(f32p) if bv.size else None, bt.size,
+                        st.ctypes.data_as(u32p) if st.size else None, st.size,
+                        allow.ctypes.data_as(C.POINTER(C.c_uint8)) if allow is not None else None,
+                        int(seed), int(slot if stream is None else stream), 0)
+        _check(lib().rwkv_gen_arm(self._h, int(slot), C.byref(p)))
+
+    def gen_disarm(self, slot: int):
+        _check(lib().rwkv_gen_disarm(self._h, int(slot)))
+
+    def gen_run(self, n_steps: int):
+        """Up to `n_steps` decode steps of every armed, unfinished slot without a host turn-around.  Returns (tokens uint32
+        [n_steps, max_batch] with 0xFFFFFFFF where a slot emitted nothing, probs float32 of the same shape with NaN there,
+        n_emitted [max_batch] of this call, finish [max_batch] of `GenFinish`)."""
+        B = self.max_batch
+        toks = np.empty((n_steps, B), np.uint32)
+        probs = np.empty((n_steps, B), np.float32)
+        n_emitted, finish = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _check(lib().rwkv_gen_run(self._h, int(n_steps), toks.ctypes.data_as(C.POINTER(C.c_uint32)), probs.ctypes.data_as(C.POINTER(C.c_float)),
+                                  n_emitted.ctypes.data_as(i32p), finish.ctypes.data_as(i32p)))
+        return toks, probs, n_emitted, finish
+
+    gen_uniform = staticmethod(gen_uniform)
 
     # ---- measurement loops (bench.py): the same ABI calls with every per-step Python object hoisted out, so that the rate is
     # the library's, not the interpreter's

@@ -5,6 +5,11 @@
 // With RWKV_DECODE_SAMPLER=nucleus|typical|mirostat the same loop samples on the device instead (rwkv_infer_sample) with the
 // host-side sampler state of include/rwkv_sampler.hpp: init(prompt), then per token adjustments -> infer_sample -> update; the
 // uniform draw of (step, slot) is frac(0.137 + 0.618034 (step + 1) + 0.31 slot) so that a test can replay it.
+// With RWKV_DECODE_SEED=<seed> the draws are the counter function of the device-resident loop instead (rwkv_gen_uniform): the draw on
+// the prompt's row is (seed, 0x80000000 | slot, 0), the draw of step s >= 1 is (seed, slot, s - 1).  RWKV_DECODE_RESIDENT=<steps per
+// run> then generates with the same draws through rwkv_gen_arm / rwkv_gen_run: the first token is sampled per token from the prompt's
+// row as above, the slot is armed with gen_params_for() of its sampler and the device carries on (a slot stops at token 0, run.rs:855).
+// Same output format.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +44,11 @@ int main(int argc, char **argv) {
         }
         const char *mode_env = std::getenv("RWKV_DECODE_SAMPLER");
         const std::string mode = mode_env ? mode_env : "";
+        const char *seed_env = std::getenv("RWKV_DECODE_SEED"), *res_env = std::getenv("RWKV_DECODE_RESIDENT");
+        const bool seeded = seed_env || res_env;
+        const uint64_t seed = seed_env ? std::strtoull(seed_env, nullptr, 10) : 0;
+        const int resident = res_env ? std::atoi(res_env) : 0;
+        if (res_env && (resident <= 0 || mode.empty())) { std::fprintf(stderr, "RWKV_DECODE_RESIDENT needs a step count > 0 and RWKV_DECODE_SAMPLER\n"); return 2; }
         if (!mode.empty()) {
             std::vector<rwkv::NucleusSampler> nuc((size_t)B);
             std::vector<rwkv::TypicalSampler> typ((size_t)B);
@@ -50,7 +60,8 @@ int main(int argc, char **argv) {
                 std::vector<rwkv::SamplerAdjust> adj((size_t)B);
                 std::vector<rwkv_sample_params> sp((size_t)B);
                 for (int b = 0; b < B; ++b) {
-                    const float u = std::fmod(0.137f + 0.618034f * (float)(step + 1) + 0.31f * (float)b, 1.0f);
+                    float u = std::fmod(0.137f + 0.618034f * (float)(step + 1) + 0.31f * (float)b, 1.0f);
+                    if (seeded) rwkv::check(rwkv_gen_uniform(seed, step == 0 ? 0x80000000u | (uint32_t)b : (uint32_t)b, step == 0 ? 0u : (uint32_t)(step - 1), 1, &u));
                     if (live[b]) input.batches[(size_t)b].tokens = pending[b];
                     if (mode == "typical") { adj[(size_t)b] = typ[(size_t)b].adjustments(); sp[(size_t)b] = typ[(size_t)b].params_for(u, adj[(size_t)b]); }
                     else if (mode == "mirostat") sp[(size_t)b] = mir[(size_t)b].params_for(u, adj[(size_t)b]);
@@ -70,6 +81,26 @@ int main(int argc, char **argv) {
                     gen[b].push_back(tok);
                     pending[b] = {tok};
                 }
+                if (resident && n_new > 1) {                             // the prompt's token is out: the device generates the rest
+                    rwkv::GenArrays keep;
+                    for (int b = 0; b < B; ++b) {
+                        if (!live[b]) continue;
+                        const uint32_t first = pending[b][0];
+                        rt.gen_arm(b, mode == "typical" ? typ[(size_t)b].gen_params_for(first, n_new - 1, seed, (uint32_t)b, keep)
+                                      : mode == "mirostat" ? mir[(size_t)b].gen_params_for(first, n_new - 1, seed, (uint32_t)b, keep)
+                                                           : nuc[(size_t)b].gen_params_for(first, n_new - 1, seed, (uint32_t)b, keep));
+                    }
+                    for (bool running = true; running;) {
+                        const auto g = rt.gen_run(resident);
+                        running = false;
+                        for (int s = 0; s < resident; ++s)
+                            for (int b = 0; b < B; ++b)
+                                if (live[b] && g.tokens[(size_t)s * (size_t)B + (size_t)b] != 0xFFFFFFFFu) gen[b].push_back(g.tokens[(size_t)s * (size_t)B + (size_t)b]);
+                        for (int b = 0; b < B; ++b) if (live[b] && g.finish[(size_t)b] == RWKV_GEN_RUNNING) running = true;
+                    }
+                    break;
+                }
+                if (resident) break;
             }
             for (size_t s = 0; s < prompts.size() && (int)s < B; ++s) {
                 for (auto t : gen[s]) std::printf("%u ", t);

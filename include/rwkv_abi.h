@@ -24,14 +24,15 @@
 extern "C" {
 #endif
 
-#define RWKV_ABI_VERSION 7   /* 2: rwkv_sample_params gained kind/tau; rwkv_engine_save_prefab
+#define RWKV_ABI_VERSION 8   /* 2: rwkv_sample_params gained kind/tau; rwkv_engine_save_prefab
                               * 3: rwkv_sample_params gained allow (formatter mask); rwkv_host_alloc/free; RWKV_OPTION_NONE
                               * 4: rwkv_engine_token_chunk_size
                               * 5: rwkv_state_back_layer_async / rwkv_state_sync
                               * 6: no new symbol — rwkv_infer no longer waits for a step that emits no row; rwkv_state_back_layer_async checks
                               *    that the rows end inside the pinned block that holds `dst`
                               * 7: rwkv_load_desc.precision: RWKV_PRECISION_FP16 now holds 1e-3 at depth (the launches that carry a model's f16 operand
-                              *    rounding read hi + lo operands); the old all-f16 behaviour is RWKV_PRECISION_FP16_RAW */
+                              *    rounding read hi + lo operands); the old all-f16 behaviour is RWKV_PRECISION_FP16_RAW
+                              * 8: device-resident sampled generation: rwkv_gen_params, rwkv_gen_arm / _disarm / _run, rwkv_gen_uniform */
 
 typedef int32_t rwkv_status;
 enum {
@@ -218,6 +219,77 @@ enum { RWKV_SAMPLER_NUCLEUS = 0, RWKV_SAMPLER_TYPICAL = 1, RWKV_SAMPLER_MIROSTAT
  * logits row; only 8 bytes per slot cross PCIe.  n_consumed[b] as in rwkv_slot_output.  num_vocab <= 65536. */
 rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const rwkv_sample_params *sp,
                               uint32_t *out_tokens, float *out_probs, uint8_t *emitted, size_t *n_consumed);
+
+/* ---- device-resident sampled generation (completed): the decode loop of `process` (run.rs:788-1020) with `sample()`
+ * (run.rs:664-697) and the whole `Sampler` state machine (sampler/nucleus.rs, typical.rs, mirostat.rs) kept on the device.  A slot is
+ * ARMED with its sampler settings; rwkv_gen_run then generates up to n_steps tokens per armed slot with one captured graph launch per
+ * step and no host turn-around between tokens; only token ids and probabilities cross PCIe.
+ *
+ *  - Sampler arithmetic is that of the per-token path (rwkv_infer_sample fed by include/rwkv_sampler.hpp), bit for bit: a token with
+ *    penalty p and bias b gets  x + ((-p) + b)  (transform nucleus.rs:61-67, then the bias loop run.rs:681-683, merged in that order),
+ *    then the same sampling kernel runs.  After the draw every PRESENT penalty is multiplied by penalty_decay and the drawn token's entry
+ *    becomes presence_penalty if it was absent, else entry + frequency_penalty (nucleus.rs:104-119).  Absent is membership, not value:
+ *    with presence_penalty = 0 the entry exists after the first draw.  Mirostat: max_surprise = fmin(max_surprise - rate * (surprise -
+ *    target), 4 * target) (mirostat.rs:85-87), each operation rounded to f32 on its own (no fused multiply-add).
+ *  - The uniform draw `fastrand::f32()` would make (nucleus.rs:93) is a counter function, so that a host can restate any step:
+ *        z = seed + 0x9E3779B97F4A7C15 * (((uint64)stream << 32 | step) + 1)        (mod 2^64)
+ *        z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31
+ *        u = (float)(z >> 40) * 2^-24                                               exact in f32, in [0, 1)
+ *    `step` counts the draws of the slot since rwkv_gen_arm and carries over from one rwkv_gen_run to the next.
+ *  - STATE RULE: when rwkv_gen_run returns, a slot's state has consumed `first_token` and every token emitted so far EXCEPT THE LAST ONE
+ *    EMITTED — whether the slot is still running (the last token is held on the device; the next run continues from it), hit a stop
+ *    token, or reached max_tokens.  That is the state the reference backs up at a stop (run.rs:990-1005).  A stop token is emitted as the
+ *    slot's last token.  Token 0 always stops (run.rs:855).
+ *  - A slot that finishes inside a run keeps riding the remaining steps of that run (the captured step does not change shape); its rows
+ *    are computed and thrown away and its state is put back as the rule says before the call returns.  It takes no part in later runs.
+ *  - Stop STRINGS stay with the caller: one that needs the exact state at a stop string runs with n_steps = 1; otherwise a slot
+ *    overshoots the string by at most n_steps - 1 tokens.
+ *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a formatter mask (`allow` must be NULL: a grammar needs the
+ *    host between two tokens, run.rs:676-679 — keep using rwkv_infer_sample), top_k > 256 (Nucleus / Typical), more than
+ *    RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
+ *  - rwkv_infer on OTHER slots between two runs is allowed (continuous batching: prefill a new request, arm it, carry on).  rwkv_infer /
+ *    rwkv_infer_sample with tokens for an armed slot, rwkv_state_load and rwkv_state_write on it disarm it.
+ *  Same thread contract as rwkv_infer (the `infer` task). */
+#define RWKV_GEN_MAX_STOP 8
+typedef struct rwkv_gen_params rwkv_gen_params;
+struct rwkv_gen_params {
+    uint32_t first_token;          /* the token the first step consumes: the one the caller sampled from the prompt's row (run.rs:809-832)  */
+    int32_t max_tokens;            /* emit at most this many, > 0 (`max_tokens`, run.rs:905-917)                                            */
+    int32_t kind;                  /* RWKV_SAMPLER_*                                                                                       */
+    float top_p;                   /* as in rwkv_sample_params: nucleus.rs:13-26, typical.rs:11-24                                         */
+    int32_t top_k;
+    float temperature;
+    float tau;                     /* Typical: tau.  Mirostat: the initial max_surprise (2 * target, mirostat.rs:30-36)                     */
+    float presence_penalty;        /* nucleus.rs:13-26 / typical.rs:11-24; unused by Mirostat                                               */
+    float frequency_penalty;
+    float penalty_decay;
+    float miro_target;             /* mirostat.rs:85-87: `tau` and `rate` of MirostatParams                                                 */
+    float miro_rate;
+    const uint32_t *penalty_tokens; /* the penalty map `init` left over the prompt (nucleus.rs:49-59); may be NULL when n_penalty == 0      */
+    const float *penalty_values;
+    size_t n_penalty;
+    const uint32_t *bias_tokens;   /* GenerateRequest::bias (run.rs:681-683); may be NULL when n_bias == 0                                  */
+    const float *bias_values;
+    size_t n_bias;
+    const uint32_t *stop_tokens;   /* extra stop tokens, n_stop <= RWKV_GEN_MAX_STOP; token 0 always stops (run.rs:855)                     */
+    size_t n_stop;
+    const uint8_t *allow;          /* must be NULL (see above)                                                                              */
+    uint64_t seed;                 /* rwkv_gen_uniform(seed, stream, step)                                                                  */
+    uint32_t stream;
+    uint32_t reserved;
+};
+enum { RWKV_GEN_RUNNING = 0, RWKV_GEN_STOP = 1, RWKV_GEN_LENGTH = 2 };   /* FinishReason::{Stop, Length} run.rs:905-917; 0 = not finished */
+/* arm `slot` (its state is what the prompt left, run.rs:788-832); re-arming replaces the context.  The arrays are copied. */
+rwkv_status rwkv_gen_arm(rwkv_engine *e, int32_t slot, const rwkv_gen_params *p);
+rwkv_status rwkv_gen_disarm(rwkv_engine *e, int32_t slot);      /* drop the context (`finish`, run.rs:1007-1020); the state stays as the rule says */
+/* Up to n_steps decode steps (run.rs:788-1020, one `infer` + `sample` each) for every armed, unfinished slot.  out_tokens / out_probs:
+ * [n_steps][max_batch], step-major, 0xFFFFFFFF / NaN where a slot emitted nothing in that step (out_probs may be NULL; it carries what
+ * rwkv_infer_sample's does: the token's probability, or its surprise for Mirostat); pinned or pageable.  n_emitted / finish: [max_batch],
+ * tokens the slot emitted IN THIS CALL and RWKV_GEN_* (both may be NULL).  With nothing armed: RWKV_OK, nothing emitted.  A launch error is
+ * returned by this call, never stale tokens. */
+rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
+/* the draws `first_step .. first_step + n - 1` of (seed, stream): pure host function, no device needed */
+rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out);
 
 /* ---- `Tokenizer` lib.rs:375; run.rs:157-168,856; sampler/bnf.rs:14-27 ---------------------- */
 typedef struct rwkv_tokenizer rwkv_tokenizer;

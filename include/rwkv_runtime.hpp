@@ -145,6 +145,25 @@ class Runtime {
         }
         return out;
     }
+    // Device-resident sampled generation (rwkv_gen_arm / _run / _disarm): arm a slot with `sampler.gen_params_for(...)`
+    // (include/rwkv_sampler.hpp), then every gen_run generates up to n_steps tokens per armed slot without a host turn-around.
+    void gen_arm(int slot, const rwkv_gen_params &p) { check(rwkv_gen_arm(e_.get(), slot, &p)); }
+    void gen_disarm(int slot) { check(rwkv_gen_disarm(e_.get(), slot)); }
+    struct Generated {
+        std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing
+        std::vector<float> probs;                    // same shape, NaN there
+        std::vector<int32_t> n_emitted, finish;      // [max_batch]: tokens of this call, RWKV_GEN_*
+    };
+    Generated gen_run(int n_steps) {
+        if (n_steps <= 0) throw std::invalid_argument("gen_run: n_steps must be > 0");
+        Generated g;
+        g.tokens.resize((size_t)n_steps * (size_t)max_batch);
+        g.probs.resize(g.tokens.size());
+        g.n_emitted.resize((size_t)max_batch);
+        g.finish.resize((size_t)max_batch);
+        check(rwkv_gen_run(e_.get(), n_steps, g.tokens.data(), g.probs.data(), g.n_emitted.data(), g.finish.data()));
+        return g;
+    }
     rwkv_engine *raw() const { return e_.get(); }
     ModelInfo info{};
     int max_batch = 0;

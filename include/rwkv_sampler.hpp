@@ -7,7 +7,10 @@
 //   MirostatSampler  mirostat.rs:11-90    max_surprise, updated from the token surprise the device returns (:85-87)
 // `params_for()` fills the rwkv_sample_params of one slot: `-penalty` (transform) and `bias` (run.rs:681-683) merged into one
 // sparse adjustment list, plus the uniform draw `fastrand::f32()` would make.  All arithmetic is f32, as in the reference.
-// Header-only; needs rwkv_abi.h only for the struct.
+// `gen_params_for()` hands the same state to the DEVICE instead (rwkv_gen_arm, ABI 8): after `init()` over the prompt it fills a
+// rwkv_gen_params with the sampler's settings, the penalty map as it stands (positive values: the device negates them like `transform`)
+// and the bias, so that the slot is armed with the map the host would have had.
+// Header-only; needs rwkv_abi.h only for the structs.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -21,6 +24,11 @@ namespace rwkv {
 struct SamplerAdjust {                 // keeps the arrays rwkv_sample_params points into alive until the call returns
     std::vector<uint32_t> tokens;
     std::vector<float> values;
+};
+
+struct GenArrays {                     // keeps the arrays rwkv_gen_params points into alive until rwkv_gen_arm returns (it copies them)
+    std::vector<uint32_t> penalty_tokens, bias_tokens, stop_tokens;
+    std::vector<float> penalty_values, bias_values;
 };
 
 class NucleusSampler {
@@ -61,6 +69,28 @@ class NucleusSampler {
         return rwkv_sample_params{top_p, top_k, temperature, uniform, adj.tokens.empty() ? nullptr : adj.tokens.data(),
                                   adj.values.empty() ? nullptr : adj.values.data(), adj.tokens.size(), RWKV_SAMPLER_NUCLEUS, 0.f, allow};
     }
+    // the slot's generation context for rwkv_gen_arm: this sampler's settings and its penalty map / bias as they stand now
+    virtual rwkv_gen_params gen_params_for(uint32_t first_token, int32_t max_tokens, uint64_t seed, uint32_t stream, GenArrays &keep,
+                                           const std::vector<uint32_t> &stop_tokens = {}) const {
+        keep = GenArrays{};
+        for (auto &kv : penalties) { keep.penalty_tokens.push_back(kv.first); keep.penalty_values.push_back(kv.second); }
+        for (auto &kv : bias) { keep.bias_tokens.push_back(kv.first); keep.bias_values.push_back(kv.second); }
+        keep.stop_tokens = stop_tokens;
+        rwkv_gen_params p{};
+        p.first_token = first_token; p.max_tokens = max_tokens; p.kind = RWKV_SAMPLER_NUCLEUS;
+        p.top_p = top_p; p.top_k = top_k; p.temperature = temperature;
+        p.presence_penalty = presence_penalty; p.frequency_penalty = frequency_penalty; p.penalty_decay = penalty_decay;
+        p.penalty_tokens = keep.penalty_tokens.empty() ? nullptr : keep.penalty_tokens.data();
+        p.penalty_values = keep.penalty_values.empty() ? nullptr : keep.penalty_values.data();
+        p.n_penalty = keep.penalty_tokens.size();
+        p.bias_tokens = keep.bias_tokens.empty() ? nullptr : keep.bias_tokens.data();
+        p.bias_values = keep.bias_values.empty() ? nullptr : keep.bias_values.data();
+        p.n_bias = keep.bias_tokens.size();
+        p.stop_tokens = keep.stop_tokens.empty() ? nullptr : keep.stop_tokens.data();
+        p.n_stop = keep.stop_tokens.size();
+        p.seed = seed; p.stream = stream;
+        return p;
+    }
 };
 
 class TypicalSampler : public NucleusSampler {       // typical.rs: TypicalParams defaults tau 0.5, top_k 128, temperature 1.0
@@ -68,6 +98,14 @@ class TypicalSampler : public NucleusSampler {       // typical.rs: TypicalParam
     float tau = 0.5f;
     rwkv_sample_params params_for(float uniform, const SamplerAdjust &adj, const uint8_t *allow = nullptr) const override {
         rwkv_sample_params p = NucleusSampler::params_for(uniform, adj, allow);
+        p.top_p = 0.f;
+        p.kind = RWKV_SAMPLER_TYPICAL;
+        p.tau = tau;
+        return p;
+    }
+    rwkv_gen_params gen_params_for(uint32_t first_token, int32_t max_tokens, uint64_t seed, uint32_t stream, GenArrays &keep,
+                                   const std::vector<uint32_t> &stop_tokens = {}) const override {
+        rwkv_gen_params p = NucleusSampler::gen_params_for(first_token, max_tokens, seed, stream, keep, stop_tokens);
         p.top_p = 0.f;
         p.kind = RWKV_SAMPLER_TYPICAL;
         p.tau = tau;
@@ -88,6 +126,19 @@ class MirostatSampler {                              // mirostat.rs:11-36: tau (
     }
     rwkv_sample_params params_for(float uniform, const SamplerAdjust &, const uint8_t *allow = nullptr) const {
         return rwkv_sample_params{0.f, 1, 1.0f, uniform, nullptr, nullptr, 0, RWKV_SAMPLER_MIROSTAT, max_surprise, allow};
+    }
+    // the device carries max_surprise on from its current value (mirostat.rs:85-87 run there)
+    rwkv_gen_params gen_params_for(uint32_t first_token, int32_t max_tokens, uint64_t seed, uint32_t stream, GenArrays &keep,
+                                   const std::vector<uint32_t> &stop_tokens = {}) const {
+        keep = GenArrays{};
+        keep.stop_tokens = stop_tokens;
+        rwkv_gen_params p{};
+        p.first_token = first_token; p.max_tokens = max_tokens; p.kind = RWKV_SAMPLER_MIROSTAT;
+        p.top_k = 1; p.temperature = 1.0f; p.tau = max_surprise; p.miro_target = target; p.miro_rate = rate;
+        p.stop_tokens = keep.stop_tokens.empty() ? nullptr : keep.stop_tokens.data();
+        p.n_stop = keep.stop_tokens.size();
+        p.seed = seed; p.stream = stream;
+        return p;
     }
 };
 

@@ -1,9 +1,9 @@
-//! Raw bindings of `include/rwkv_abi.h` (ABI version 7), one `pub fn` per export, in the header's order.
+//! Raw bindings of `include/rwkv_abi.h` (ABI version 8), one `pub fn` per export, in the header's order.
 //! tests/test_abi_cpu.py diffs this file against the header (names and argument counts) and against the built library.
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_float, c_void};
 
-pub const RWKV_ABI_VERSION: i32 = 7;
+pub const RWKV_ABI_VERSION: i32 = 8;
 
 pub type rwkv_status = i32;
 pub const RWKV_OK: rwkv_status = 0;
@@ -28,6 +28,10 @@ pub const RWKV_OPTION_NONE: i32 = 2;
 pub const RWKV_SAMPLER_NUCLEUS: i32 = 0;
 pub const RWKV_SAMPLER_TYPICAL: i32 = 1;
 pub const RWKV_SAMPLER_MIROSTAT: i32 = 2;
+pub const RWKV_GEN_MAX_STOP: usize = 8;
+pub const RWKV_GEN_RUNNING: i32 = 0;
+pub const RWKV_GEN_STOP: i32 = 1;
+pub const RWKV_GEN_LENGTH: i32 = 2;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 
 #[repr(C)] pub struct rwkv_engine { _p: [u8; 0] }
@@ -52,6 +56,14 @@ pub struct rwkv_slot_output { pub logits: *mut f32, pub logits_capacity_rows: us
 pub struct rwkv_sample_params { pub top_p: c_float, pub top_k: i32, pub temperature: c_float, pub uniform: c_float,
                                 pub adj_tokens: *const u32, pub adj_values: *const c_float, pub n_adj: usize,
                                 pub kind: i32, pub tau: c_float, pub allow: *const u8 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rwkv_gen_params { pub first_token: u32, pub max_tokens: i32, pub kind: i32, pub top_p: c_float, pub top_k: i32,
+                             pub temperature: c_float, pub tau: c_float, pub presence_penalty: c_float, pub frequency_penalty: c_float,
+                             pub penalty_decay: c_float, pub miro_target: c_float, pub miro_rate: c_float,
+                             pub penalty_tokens: *const u32, pub penalty_values: *const c_float, pub n_penalty: usize,
+                             pub bias_tokens: *const u32, pub bias_values: *const c_float, pub n_bias: usize,
+                             pub stop_tokens: *const u32, pub n_stop: usize, pub allow: *const u8,
+                             pub seed: u64, pub stream: u32, pub reserved: u32 }
 
 extern "C" {
     // errors / version / adapters  (lib.rs:339-349)
@@ -92,6 +104,12 @@ extern "C" {
     // on-device sampling front-end (run.rs:664-697 + sampler/*.rs)
     pub fn rwkv_infer_sample(e: *mut rwkv_engine, inp: *const rwkv_slot_input, sp: *const rwkv_sample_params, out_tokens: *mut u32,
                              out_probs: *mut c_float, emitted: *mut u8, n_consumed: *mut usize) -> rwkv_status;
+    // device-resident sampled generation: the decode loop of `process` with the samplers on the device (run.rs:788-1020, sampler/*.rs)
+    pub fn rwkv_gen_arm(e: *mut rwkv_engine, slot: i32, p: *const rwkv_gen_params) -> rwkv_status;
+    pub fn rwkv_gen_disarm(e: *mut rwkv_engine, slot: i32) -> rwkv_status;
+    pub fn rwkv_gen_run(e: *mut rwkv_engine, n_steps: i32, out_tokens: *mut u32, out_probs: *mut c_float, n_emitted: *mut i32,
+                        finish: *mut i32) -> rwkv_status;
+    pub fn rwkv_gen_uniform(seed: u64, stream: u32, first_step: u32, n: usize, out: *mut c_float) -> rwkv_status;
     // Tokenizer  (lib.rs:375, run.rs:157, 856, bnf.rs:15)
     pub fn rwkv_tokenizer_create(vocab_json: *const c_char, len: usize, out: *mut *mut rwkv_tokenizer) -> rwkv_status;
     pub fn rwkv_tokenizer_destroy(t: *mut rwkv_tokenizer);

@@ -211,6 +211,52 @@ impl Engine {
         let out: Vec<*mut f32> = rows.iter_mut().map(|r| r.as_mut_ptr()).collect();
         check(unsafe { sys::rwkv_softmax(self.raw, inp.as_ptr(), out.as_ptr(), rows.len()) })
     }
+    /// Arm `slot` for device-resident sampled generation (rwkv_gen_arm): the decode loop of `process` (run.rs:788-1020) with `sample()`
+    /// (run.rs:664-697) and the sampler state machine (sampler/*.rs) on the device.  The slot's state is what the prompt left.
+    pub fn gen_arm(&self, slot: usize, p: &GenParams) -> Result<()> {
+        let (pt, pv): (Vec<u32>, Vec<f32>) = p.penalties.iter().copied().unzip();
+        let (bt, bv): (Vec<u32>, Vec<f32>) = p.bias.iter().copied().unzip();
+        let raw = sys::rwkv_gen_params {
+            first_token: p.first_token, max_tokens: p.max_tokens as i32, kind: p.kind as i32, top_p: p.top_p, top_k: p.top_k as i32,
+            temperature: p.temperature, tau: p.tau, presence_penalty: p.presence_penalty, frequency_penalty: p.frequency_penalty,
+            penalty_decay: p.penalty_decay, miro_target: p.miro_target, miro_rate: p.miro_rate,
+            penalty_tokens: pt.as_ptr(), penalty_values: pv.as_ptr(), n_penalty: pt.len(),
+            bias_tokens: bt.as_ptr(), bias_values: bv.as_ptr(), n_bias: bt.len(),
+            stop_tokens: p.stop_tokens.as_ptr(), n_stop: p.stop_tokens.len(), allow: ptr::null(),
+            seed: p.seed, stream: p.stream, reserved: 0,
+        };
+        check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) })
+    }
+    pub fn gen_disarm(&self, slot: usize) -> Result<()> { check(unsafe { sys::rwkv_gen_disarm(self.raw, slot as i32) }) }
+    /// Up to `n_steps` tokens for every armed, unfinished slot with no host turn-around (rwkv_gen_run).  When it returns a slot's
+    /// state has consumed everything it emitted except the last token (what run.rs:990-1005 backs up at a stop).
+    pub fn gen_run(&self, n_steps: usize) -> Result<Generated> {
+        let mut g = Generated { tokens: vec![u32::MAX; n_steps * self.max_batch], probs: vec![f32::NAN; n_steps * self.max_batch],
+                                n_emitted: vec![0; self.max_batch], finish: vec![0; self.max_batch] };
+        check(unsafe { sys::rwkv_gen_run(self.raw, n_steps as i32, g.tokens.as_mut_ptr(), g.probs.as_mut_ptr(), g.n_emitted.as_mut_ptr(), g.finish.as_mut_ptr()) })?;
+        Ok(g)
+    }
+}
+
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum SamplerKind { #[default] Nucleus = 0, Typical = 1, Mirostat = 2 }
+/// `rwkv_gen_params`: sampler settings (nucleus.rs:13-26, typical.rs:11-24, mirostat.rs:11-36), the penalty map `init` left over the
+/// prompt (nucleus.rs:49-59), `GenerateRequest::bias` (run.rs:681-683), stop tokens (token 0 always stops, run.rs:855) and the
+/// (seed, stream) of the counter-based uniform draw (`gen_uniform`).
+#[derive(Clone, Debug, Default)]
+pub struct GenParams {
+    pub first_token: u32, pub max_tokens: usize, pub kind: SamplerKind, pub top_p: f32, pub top_k: usize, pub temperature: f32, pub tau: f32,
+    pub presence_penalty: f32, pub frequency_penalty: f32, pub penalty_decay: f32, pub miro_target: f32, pub miro_rate: f32,
+    pub penalties: Vec<(u32, f32)>, pub bias: Vec<(u32, f32)>, pub stop_tokens: Vec<u32>, pub seed: u64, pub stream: u32,
+}
+/// what `Engine::gen_run` returns: `tokens` / `probs` are [n_steps][max_batch] (u32::MAX / NaN where a slot emitted nothing),
+/// `n_emitted` counts this call's tokens per slot, `finish` is RWKV_GEN_RUNNING / _STOP / _LENGTH
+#[derive(Clone, Debug)]
+pub struct Generated { pub tokens: Vec<u32>, pub probs: Vec<f32>, pub n_emitted: Vec<i32>, pub finish: Vec<i32> }
+/// draw `step` of (seed, stream): pure host function (rwkv_gen_uniform)
+pub fn gen_uniform(seed: u64, stream: u32, step: u32) -> f32 {
+    let mut u = 0f32;
+    unsafe { sys::rwkv_gen_uniform(seed, stream, step, 1, &mut u) };
+    u
 }
 
 /// Read-backs in flight into one pinned block (`Engine::state_back_layer_async`).  Holds the block's mutable borrow until the copy

@@ -1,0 +1,121 @@
+"""Three decode loops on one engine in one process: device-resident greedy (rwkv_decode_greedy), the per-token sampled loop
+(rwkv_infer_sample, one call per token) and device-resident sampled generation (rwkv_gen_arm / rwkv_gen_run).
+
+    python scripts/gen_resident_bench.py [--out profiles/r7_gen_resident.json] [--tokens 256] [--steps-per-run 32] [--regions 5]
+
+Workload: synthetic RWKV-V6-3B, Int8 on every layer, default precision, 32 slots and 1 slot, Nucleus with the reference defaults
+(sampler/nucleus.rs:13-26), `--tokens` tokens per slot per timed region.  Every loop is warmed with one untimed region (graphs
+captured, code objects loaded); the `--regions` timed regions of the loops alternate, so that drift of the machine hits all of them
+alike; each region is a host clock around work that ends in a device synchronise; the median is reported with the spread.
+
+The per-token loop is timed twice: `sample_bare` is Runtime.serve_loop_sample — no penalty map at all, every per-step Python object
+hoisted out: the LEAST the per-token path can cost and the yardstick the resident loop is held to — and `sample_host_samplers` is
+the same call driven by harness.NucleusSampler objects (penalty maps on the host, adjustment lists per token), which includes the
+Python interpreter's share and is reported for orientation only.  The resident loop always carries the penalty state machine.
+Token 0 stops a resident slot (run.rs:855), so its rate counts the tokens really emitted."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ai00_server_amd import harness as H  # noqa: E402
+from ai00_server_amd import runtime as rt  # noqa: E402
+from oracle import rwkv_ref as R  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--workload", default="v6-3b")
+    ap.add_argument("--tokens", type=int, default=256)
+    ap.add_argument("--steps-per-run", type=int, default=32)
+    ap.add_argument("--regions", type=int, default=5)
+    ap.add_argument("--batches", default="32,1")
+    a = ap.parse_args()
+    batches = [int(x) for x in a.batches.split(",")]
+    B = max(batches)
+    st, tensors = R.synth_st(a.workload, fast=True)
+    info = R.model_info(tensors)
+    del tensors
+    t0 = time.time()
+    eng = rt.ModelBuilder(st).quant(info.num_layer, rt.Quant.Int8).build(max_batch=B, token_chunk_size=max(128, B), precision=rt.Precision.Fp16)
+    load_s = time.time() - t0
+    V = info.num_vocab
+    first = [t % V for t in R.synth_prompt(900, B)]
+    n, spr = a.tokens, a.steps_per_run
+
+    def greedy(nb):
+        t = time.perf_counter()
+        eng.decode_greedy(first[:nb], n)
+        return time.perf_counter() - t, nb * n
+
+    def sample_bare(nb):
+        return eng.serve_loop_sample(first[:nb], n), nb * n
+
+    def sample_host(nb):
+        smp = [H.NucleusSampler() if b < nb else None for b in range(B)]
+        cur = list(first)
+        t = time.perf_counter()
+        for s in range(n):
+            inp = rt.RnnInput([rt.RnnInputBatch([cur[b]] if b < nb else []) for b in range(B)])
+            us = rt.gen_uniform(1, 0, s * B, B)
+            _, res = eng.infer_sample(inp, smp, [float(u) for u in us])
+            for b in range(nb):
+                cur[b] = res[b][0]
+                smp[b].update(cur[b])
+        return time.perf_counter() - t, nb * n
+
+    arm_s = {}
+
+    def resident(nb):
+        t = time.perf_counter()
+        for b in range(nb):
+            eng.gen_arm(b, first[b], n, H.NucleusSampler(), seed=1)
+        arm_s.setdefault(nb, []).append(time.perf_counter() - t)
+        emitted = 0
+        t = time.perf_counter()
+        for _ in range(-(-n // spr)):
+            _, _, ne, fin = eng.gen_run(spr)
+            emitted += int(ne.sum())
+        return time.perf_counter() - t, emitted
+
+    loops = {"greedy": greedy, "sample_bare": sample_bare, "sample_host_samplers": sample_host, "resident": resident}
+    out = {"workload": f"RWKV-{a.workload} int8, default precision, synthetic weights", "tokens_per_slot_per_region": n, "steps_per_gen_run": spr,
+           "regions": a.regions, "load_s": load_s, "sampler": "Nucleus top_p 0.5 top_k 128 temperature 1.0 penalties 0.3 / 0.3 / 0.99654026",
+           "batches": {}}
+    for nb in batches:
+        times = {k: [] for k in loops}
+        for rep in range(a.regions + 1):                       # region 0 warms every loop and is dropped
+            for k, f in loops.items():
+                dt, tokens = f(nb)
+                if rep:
+                    times[k].append((dt, tokens))
+        res = {}
+        for k, v in times.items():
+            rates = [tok / dt for dt, tok in v]
+            steps = [dt / n * 1e3 for dt, _ in v]
+            res[k] = {"tokens_per_s": statistics.median(rates), "ms_per_step": statistics.median(steps),
+                      "tokens_per_s_min": min(rates), "tokens_per_s_max": max(rates),
+                      "spread_pct": 100.0 * (max(rates) - min(rates)) / statistics.median(rates), "tokens_per_region": [tok for _, tok in v]}
+        res["resident"]["arm_ms_per_slot"] = 1e3 * statistics.median(arm_s[nb]) / nb
+        res["resident_vs_sample_bare"] = res["resident"]["tokens_per_s"] / res["sample_bare"]["tokens_per_s"]
+        res["resident_vs_greedy"] = res["resident"]["tokens_per_s"] / res["greedy"]["tokens_per_s"]
+        out["batches"][str(nb)] = res
+    eng.close()
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
