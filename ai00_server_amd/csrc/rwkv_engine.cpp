@@ -296,20 +296,31 @@ struct rwkv_engine {
     static constexpr int GEN_RING_STEPS = 1024;                  // steps one enqueue covers (longer runs are split)
     std::vector<GenSlot> gen_host;                               // mirror of d_gen, read back after every run
     std::vector<char> gen_armed;
-    std::vector<uint32_t> gen_held;                              // the token a running slot consumes next (its last emitted one)
+    std::vector<std::vector<uint32_t>> gen_prompt;               // rwkv_gen_arm_prompt: the slot's prompt tail, and how much of it the steps
+    std::vector<size_t> gen_ppos;                                //   so far have consumed (each mixed step's slice rides in its plan upload)
     std::vector<float *> gen_shadow;                             // per slot: sxa | sxf | wkv of the step it finished in
     GenSlot *d_gen = nullptr;
     float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
     float **d_gen_shadow = nullptr;
     SampleRow *d_gen_rows = nullptr;
     int *d_gen_tok = nullptr, *d_gen_runstep = nullptr;
+    int *d_gen_held = nullptr;                                   // [max_batch] the token a running slot consumes next (its last emitted one)
     unsigned *d_gen_out = nullptr, *h_gen_out = nullptr;         // [2][GEN_RING_STEPS][max_batch]: tokens, then probabilities
     std::map<std::vector<uint64_t>, GraphEntry> gen_graphs;      // one captured step per set of rows (slot mask + sampler kernels it needs)
     std::set<std::vector<uint64_t>> gen_seen;
     void gen_init();
-    void gen_arm(int slot, const rwkv_gen_params &p);
-    void gen_disarm_slot(int slot) { if (!gen_armed.empty()) gen_armed[(size_t)slot] = 0; }
+    void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt);
+    void gen_disarm_slot(int slot) {
+        if (gen_armed.empty()) return;
+        gen_armed[(size_t)slot] = 0;
+        gen_prompt[(size_t)slot].clear();
+        gen_ppos[(size_t)slot] = 0;
+    }
+    size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
+    GenArgs gen_args(int n_rows) const;
     void gen_step(const StepPlan &pl, bool any_nt, bool any_miro);
+    void gen_decode_steps(const std::vector<int> &rows, int n);
+    void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
     bool use_graphs = true;
     Knobs kn;                                                    // experiment switches, frozen at creation (rwkv_kernels.h)
@@ -1377,12 +1388,16 @@ void rwkv_engine::gen_init() {
     const size_t B = (size_t)max_batch, V = (size_t)info.num_vocab;
     gen_host.assign(B, GenSlot{});
     gen_armed.assign(B, 0);
-    gen_held.assign(B, 0);
+    gen_prompt.assign(B, {});
+    gen_ppos.assign(B, 0);
+    d_gen_held = dalloc<int>(B);
+    HIP_CHECK(hipMemset(d_gen_held, 0, B * sizeof(int)));
     gen_shadow.assign(B, nullptr);
     d_gen_pen = dalloc<float>(B * V);
     d_gen_bias = dalloc<float>(B * V);
     d_gen_shadow = dalloc<float *>(B);
     d_gen_rows = dalloc<SampleRow>((size_t)chunk);
+    HIP_CHECK(hipMemset(d_gen_rows, 0, (size_t)chunk * sizeof(SampleRow)));   // a rider's row may be one no step has written yet: top_k 0 is inert
     d_gen_tok = dalloc<int>((size_t)chunk);
     d_gen_prob = dalloc<float>((size_t)chunk);
     d_gen_runstep = dalloc<int>(1);
@@ -1393,7 +1408,7 @@ void rwkv_engine::gen_init() {
     HIP_CHECK(hipMemset(d_gen, 0, B * sizeof(GenSlot)));
 }
 
-void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p) {
+void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt) {
     HIP_CHECK(hipSetDevice(device));
     const size_t V = (size_t)info.num_vocab;
     if (V > 65536) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling needs num_vocab <= 65536");
@@ -1404,7 +1419,8 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p) {
     if (p.n_stop > RWKV_GEN_MAX_STOP) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP stop tokens");
     if (!miro && !(p.temperature > 0.f)) throw RwkvError(RWKV_ERR_INVALID, "temperature must be > 0");
     if (p.max_tokens <= 0) throw RwkvError(RWKV_ERR_INVALID, "max_tokens must be > 0");
-    if (p.first_token >= V) throw RwkvError(RWKV_ERR_INVALID, "first_token out of range");
+    if (!prompt && p.first_token >= V) throw RwkvError(RWKV_ERR_INVALID, "first_token out of range");
+    for (size_t i = 0; i < n_prompt; ++i) if (prompt[i] >= V) throw RwkvError(RWKV_ERR_INVALID, "prompt token out of range");
     if ((p.n_penalty && (!p.penalty_tokens || !p.penalty_values)) || (p.n_bias && (!p.bias_tokens || !p.bias_values)) || (p.n_stop && !p.stop_tokens))
         throw RwkvError(RWKV_ERR_INVALID, "null penalty / bias / stop array");
     gen_init();
@@ -1431,26 +1447,137 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p) {
     HIP_CHECK(hipMemcpyAsync(d_gen_pen + b * V, pen.data(), V * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemcpyAsync(d_gen_bias + b * V, bias.data(), V * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemcpyAsync(d_gen + b, &g, sizeof(GenSlot), hipMemcpyHostToDevice, s_main));
+    const int first = prompt ? 0 : (int)p.first_token;             // with a prompt the slot's first draw fills it
+    HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     gen_host[b] = g;
-    gen_held[b] = p.first_token;
+    gen_prompt[b].assign(prompt, prompt + n_prompt);
+    gen_ppos[b] = 0;
     gen_armed[b] = 1;
+}
+
+GenArgs rwkv_engine::gen_args(int n_rows) const {
+    GenArgs a{};
+    a.slots = d_gen; a.row_slot = d_meta + chunk; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
+    a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
+    a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
+    a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = n_rows;
+    a.sxa = sxa; a.sxf = sxf; a.wkv = wkv; a.sx_slot_stride = sx_slot_stride; a.wkv_slot_stride = wkv_slot_stride;
+    a.shadow = d_gen_shadow;
+    return a;
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, sampler state machine around nucleus_kernel
 void rwkv_engine::gen_step(const StepPlan &pl, bool any_nt, bool any_miro) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    GenArgs a{};
-    a.slots = d_gen; a.row_slot = d_meta + chunk; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
-    a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
-    a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
-    a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = pl.T;
-    a.sxa = sxa; a.sxf = sxf; a.wkv = wkv; a.sx_slot_stride = sx_slot_stride; a.wkv_slot_stride = wkv_slot_stride;
-    a.shadow = d_gen_shadow;
+    const GenArgs a = gen_args(pl.T);
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
     launch(FAM_SAMPLE, [&] { launch_nucleus(logits, pl.T, info.num_vocab, d_gen_rows, any_nt, any_miro, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
+}
+
+// `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
+void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
+    const int B = max_batch;
+    if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
+    bool any_nt = false, any_miro = false;
+    for (int b : rows) { if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true; }
+    // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
+    std::vector<rwkv_slot_input> in((size_t)B);
+    const uint32_t none = 0;
+    for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
+    for (int b : rows) in[(size_t)b] = rwkv_slot_input{&none, 1, RWKV_OPTION_LAST, 0};
+    StepPlan pl;
+    plan_step(in.data(), pl);
+    upload_plan(pl);
+    step_max_rows = 1;
+    launch_gen_handover(d_tok_feedback, d_gen_held, d_meta + chunk, pl.T, false, s_main);
+    std::vector<uint64_t> key((size_t)(B + 63) / 64 + 1, 0);
+    for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
+    key.back() = (any_nt ? 1u : 0u) | (any_miro ? 2u : 0u);
+    int s0 = 0;
+    hipGraphExec_t exec = nullptr;
+    if (use_graphs) {
+        auto it = gen_graphs.find(key);
+        if (it == gen_graphs.end()) {
+            // a set of rows runs its first step directly (like run_plan: a one-off shape never pays capture + instantiation, and the
+            // launchers' one-time attribute calls happen outside a capture); the steps after it go through the captured graph
+            if (gen_seen.insert(key).second) { gen_step(pl, any_nt, any_miro); s0 = 1; }
+            if (s0 < n) {
+                hipGraph_t g = nullptr;
+                HIP_CHECK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
+                try {
+                    gen_step(pl, any_nt, any_miro);
+                } catch (...) {
+                    (void)hipStreamEndCapture(s_main, &g);
+                    if (g) (void)hipGraphDestroy(g);
+                    throw;
+                }
+                HIP_CHECK(hipStreamEndCapture(s_main, &g));
+                GraphEntry ge;
+                HIP_CHECK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
+                HIP_CHECK(hipGraphDestroy(g));
+                if (gen_graphs.size() >= 64) {                     // bounded like `graphs`: the least recently used set goes
+                    auto victim = gen_graphs.begin();
+                    for (auto o = gen_graphs.begin(); o != gen_graphs.end(); ++o) if (o->second.used < victim->second.used) victim = o;
+                    (void)hipGraphExecDestroy(victim->second.exec);
+                    gen_graphs.erase(victim);
+                }
+                if (gen_seen.size() > 4096) gen_seen.clear();
+                it = gen_graphs.emplace(key, ge).first;
+            }
+        }
+        if (it != gen_graphs.end()) { it->second.used = ++graph_clock; exec = it->second.exec; }
+    }
+    for (int s = s0; s < n; ++s) {
+        if (exec) HIP_CHECK(hipGraphLaunch(exec, s_main));
+        else gen_step(pl, any_nt, any_miro);
+    }
+    launch_gen_handover(d_tok_feedback, d_gen_held, d_meta + chunk, pl.T, true, s_main);
+}
+
+// One MIXED step (rwkv_gen_arm_prompt): every slot of `dec` contributes its one feedback row, every slot of `pro` a share of what is
+// left of the chunk (plan_step's water-filling: a pending count of 1 is always served first, so decode rows are never starved).  The
+// logits block holds the decode rows and the last row of every prompt that ends here; the <true> kernels sample exactly those.  Runs
+// uncaptured through the plan path, like the first step of a new row set: its shape is a one-off.
+void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain) {
+    const int B = max_batch;
+    // dec.size() < chunk: gen_run checked, before its first step, that all live slots together fit one chunk
+    std::vector<rwkv_slot_input> in((size_t)B);
+    std::vector<char> is_dec((size_t)B, 0);
+    const uint32_t none = 0;
+    for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
+    for (int b : dec) { in[(size_t)b] = rwkv_slot_input{&none, 1, RWKV_OPTION_LAST, 0}; is_dec[(size_t)b] = 1; }
+    for (int b : pro) in[(size_t)b] = rwkv_slot_input{gen_prompt[(size_t)b].data() + gen_ppos[(size_t)b], gen_prompt_left(b), RWKV_OPTION_LAST, 0};
+    StepPlan pl;
+    plan_step(in.data(), pl);
+    for (int i = 0; i < pl.n_seq; ++i) if (is_dec[(size_t)pl.seq_slot[i]]) pl.token[(size_t)pl.seq_begin[i]] = -1;   // gen_tokens_kernel: held[slot]
+    bool any_nt = false, any_miro = false;
+    for (int b = 0; b < B; ++b) {
+        if (!pl.slot_out_rows[(size_t)b]) continue;
+        if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true;
+    }
+    upload_plan(pl);
+    uploaded_id = 0;                                               // the uploaded token row is not the plan's: nobody may skip an upload on it
+    launch(FAM_ROW, [&] { launch_gen_tokens(d_meta, d_meta + chunk, d_gen_held, d_gen_runstep, pl.T, s_main); });
+    step_max_rows = 0;
+    for (int n : pl.seq_len) step_max_rows = std::max(step_max_rows, n);
+    run_layers(pl.T, pl.n_seq, pl.n_out, d_meta, pl.dense);
+    if (pl.n_out > 0) {
+        GenArgs a = gen_args(pl.n_out);
+        a.out_rows = d_meta + 4 * chunk;
+        a.held = d_gen_held;
+        launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
+        launch(FAM_SAMPLE, [&] { launch_nucleus(logits, pl.n_out, info.num_vocab, d_gen_rows, any_nt, any_miro, d_gen_tok, d_gen_prob, s_main); });
+        launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
+        launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
+    }
+    for (int b : dec) remain[(size_t)b] -= 1;
+    for (int b : pro) {
+        gen_ppos[(size_t)b] += (size_t)pl.slot_consumed[(size_t)b];
+        if (pl.slot_out_rows[(size_t)b]) remain[(size_t)b] -= 1;      // the prompt ended: its last row was the slot's first draw
+    }
 }
 
 void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish) {
@@ -1462,93 +1589,62 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
     if (out_probs) std::fill(out_probs, out_probs + (size_t)n_steps * B, nan);
     if (n_emitted) std::fill(n_emitted, n_emitted + B, 0);
     if (finish) std::fill(finish, finish + B, (int32_t)RWKV_GEN_RUNNING);
+    const size_t ring = (size_t)GEN_RING_STEPS * B;
     for (int done = 0; done < n_steps && !gen_armed.empty();) {
-        // the rows of this enqueue: armed slots that have not finished, in slot order
-        std::vector<int> rows;
-        int n = 0;
-        bool any_nt = false, any_miro = false;
+        // One enqueue: up to a ring of steps with no wait in between.  The host knows which slots are in their prompt and when each
+        // prompt ends (the plan says so); what it cannot know is who finished on the device, so a slot rides until the enqueue ends or
+        // until it can emit nothing more (`remain`: max_tokens less what it has emitted for certain).
+        const int nb = std::min(n_steps - done, (int)GEN_RING_STEPS);
+        std::vector<int> live, remain((size_t)B, 0);
         for (int b = 0; b < B; ++b) {
             if (!gen_armed[(size_t)b] || gen_host[(size_t)b].finish) continue;
-            rows.push_back(b);
-            n = std::max(n, gen_host[(size_t)b].max_tokens - gen_host[(size_t)b].emitted);   // nobody runs longer than this
-            if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true;
+            live.push_back(b);
+            remain[(size_t)b] = gen_host[(size_t)b].max_tokens - gen_host[(size_t)b].emitted;
         }
-        if (rows.empty()) break;
-        if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
-        n = std::min({n, n_steps - done, (int)GEN_RING_STEPS});
-        // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
-        std::vector<rwkv_slot_input> in((size_t)B);
-        std::vector<uint32_t> held((size_t)B, 0);
-        std::vector<int> fb;
-        for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
-        for (int b : rows) { held[(size_t)b] = gen_held[(size_t)b]; in[(size_t)b] = rwkv_slot_input{&held[(size_t)b], 1, RWKV_OPTION_LAST, 0}; fb.push_back((int)gen_held[(size_t)b]); }
-        StepPlan pl;
-        plan_step(in.data(), pl);
-        upload_plan(pl);
-        step_max_rows = 1;
-        const size_t ring = (size_t)GEN_RING_STEPS * B;
-        HIP_CHECK(hipMemcpyAsync(d_tok_feedback, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, s_main));
-        HIP_CHECK(hipMemsetAsync(d_gen_runstep, 0xFF, 4, s_main));                          // -1: gen_pre counts up
-        HIP_CHECK(hipMemsetAsync(d_gen_out, 0xFF, (size_t)n * B * 4, s_main));              // 0xFFFFFFFF: nothing emitted
-        HIP_CHECK(hipMemsetAsync(d_gen_out + ring, 0xFF, (size_t)n * B * 4, s_main));       // ... and the same bits are a NaN
-        HIP_CHECK(hipStreamSynchronize(s_main));                                            // `fb` is pageable
-        std::vector<uint64_t> key((size_t)(B + 63) / 64 + 1, 0);
-        for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-        key.back() = (any_nt ? 1u : 0u) | (any_miro ? 2u : 0u);
-        int s0 = 0;
-        hipGraphExec_t exec = nullptr;
-        if (use_graphs) {
-            auto it = gen_graphs.find(key);
-            if (it == gen_graphs.end()) {
-                // a set of rows runs its first step directly (like run_plan: a one-off shape never pays capture + instantiation, and the
-                // launchers' one-time attribute calls happen outside a capture); the steps after it go through the captured graph
-                if (gen_seen.insert(key).second) { gen_step(pl, any_nt, any_miro); s0 = 1; }
-                if (s0 < n) {
-                    hipGraph_t g = nullptr;
-                    HIP_CHECK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
-                    try {
-                        gen_step(pl, any_nt, any_miro);
-                    } catch (...) {
-                        (void)hipStreamEndCapture(s_main, &g);
-                        if (g) (void)hipGraphDestroy(g);
-                        throw;
-                    }
-                    HIP_CHECK(hipStreamEndCapture(s_main, &g));
-                    GraphEntry ge;
-                    HIP_CHECK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
-                    HIP_CHECK(hipGraphDestroy(g));
-                    if (gen_graphs.size() >= 64) {                     // bounded like `graphs`: the least recently used set goes
-                        auto victim = gen_graphs.begin();
-                        for (auto o = gen_graphs.begin(); o != gen_graphs.end(); ++o) if (o->second.used < victim->second.used) victim = o;
-                        (void)hipGraphExecDestroy(victim->second.exec);
-                        gen_graphs.erase(victim);
-                    }
-                    if (gen_seen.size() > 4096) gen_seen.clear();
-                    it = gen_graphs.emplace(key, ge).first;
-                }
+        if (live.empty()) break;
+        // refused before anything is enqueued (a throw from the middle of an enqueue would lose the steps already run): every live slot
+        // may become a decode row while a prompt is still pending, and a prompt needs a row of its own next to them
+        if ((int)live.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
+        HIP_CHECK(hipMemsetAsync(d_gen_runstep, 0xFF, 4, s_main));                          // -1: the first kernel of a step counts up
+        HIP_CHECK(hipMemsetAsync(d_gen_out, 0xFF, (size_t)nb * B * 4, s_main));             // 0xFFFFFFFF: nothing emitted
+        HIP_CHECK(hipMemsetAsync(d_gen_out + ring, 0xFF, (size_t)nb * B * 4, s_main));      // ... and the same bits are a NaN
+        int k = 0;
+        while (k < nb) {
+            std::vector<int> dec, pro;                             // ascending slot order
+            for (int b : live) {
+                if (gen_prompt_left(b)) pro.push_back(b);
+                else if (remain[(size_t)b] > 0) dec.push_back(b);
             }
-            if (it != gen_graphs.end()) { it->second.used = ++graph_clock; exec = it->second.exec; }
-        }
-        for (int s = s0; s < n; ++s) {
-            if (exec) HIP_CHECK(hipGraphLaunch(exec, s_main));
-            else gen_step(pl, any_nt, any_miro);
+            if (!pro.empty()) {
+                gen_mixed_step(dec, pro, remain);
+                k += 1;
+                continue;
+            }
+            if (dec.empty()) break;
+            int n = 0;
+            for (int b : dec) n = std::max(n, remain[(size_t)b]);  // nobody runs longer than this
+            n = std::min(n, nb - k);
+            gen_decode_steps(dec, n);
+            for (int b : dec) remain[(size_t)b] = std::max(0, remain[(size_t)b] - n);
+            k += n;
         }
         HIP_CHECK(hipPeekAtLastError());                               // a failed launch is this call's error, not stale tokens with RWKV_OK
-        HIP_CHECK(hipMemcpyAsync(h_gen_out, d_gen_out, (size_t)n * B * 4, hipMemcpyDeviceToHost, s_main));
-        HIP_CHECK(hipMemcpyAsync(h_gen_out + ring, d_gen_out + ring, (size_t)n * B * 4, hipMemcpyDeviceToHost, s_main));
+        if (k > 0) {
+            HIP_CHECK(hipMemcpyAsync(h_gen_out, d_gen_out, (size_t)k * B * 4, hipMemcpyDeviceToHost, s_main));
+            HIP_CHECK(hipMemcpyAsync(h_gen_out + ring, d_gen_out + ring, (size_t)k * B * 4, hipMemcpyDeviceToHost, s_main));
+        }
         std::vector<GenSlot> back((size_t)B);
         HIP_CHECK(hipMemcpyAsync(back.data(), d_gen, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, s_main));
         HIP_CHECK(hipStreamSynchronize(s_main));
-        std::memcpy(out_tokens + (size_t)done * B, h_gen_out, (size_t)n * B * 4);
-        if (out_probs) std::memcpy(out_probs + (size_t)done * B, h_gen_out + ring, (size_t)n * B * 4);
+        if (k == 0) break;
+        std::memcpy(out_tokens + (size_t)done * B, h_gen_out, (size_t)k * B * 4);
+        if (out_probs) std::memcpy(out_probs + (size_t)done * B, h_gen_out + ring, (size_t)k * B * 4);
         bool restored = false;
-        for (int b : rows) {
+        for (int b : live) {
             const size_t sb = (size_t)b;
             const int got = back[sb].emitted - gen_host[sb].emitted;
             gen_host[sb] = back[sb];
             if (n_emitted) n_emitted[b] += got;
-            for (int s = n - 1; s >= 0 && got > 0; --s)
-                if (h_gen_out[(size_t)s * B + sb] != 0xFFFFFFFFu) { gen_held[sb] = h_gen_out[(size_t)s * B + sb]; break; }
             if (back[sb].finish) {
                 // the slot rode the steps behind the one it finished in: its state goes back to what it was there (the state rule)
                 const float *sh = gen_shadow[sb];
@@ -1559,7 +1655,7 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
             }
         }
         if (restored) HIP_CHECK(hipStreamSynchronize(s_main));
-        done += n;
+        done += k;
     }
     if (finish) for (int b = 0; b < B && !gen_armed.empty(); ++b) if (gen_armed[(size_t)b]) finish[b] = gen_host[(size_t)b].finish;
 }
@@ -1996,7 +2092,23 @@ rwkv_status rwkv_gen_arm(rwkv_engine *e, int32_t slot, const rwkv_gen_params *p)
         check_slot(e, slot);
         if (!p) throw RwkvError(RWKV_ERR_INVALID, "null params");
         use_knobs(e->kn);
-        e->gen_arm(slot, *p);
+        e->gen_arm(slot, *p, nullptr, 0);
+    });
+}
+rwkv_status rwkv_gen_arm_prompt(rwkv_engine *e, int32_t slot, const uint32_t *tokens, size_t n_tokens, const rwkv_gen_params *p) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!p) throw RwkvError(RWKV_ERR_INVALID, "null params");
+        if (!tokens || n_tokens == 0) throw RwkvError(RWKV_ERR_INVALID, "a prompt needs at least one token");
+        use_knobs(e->kn);
+        e->gen_arm(slot, *p, tokens, n_tokens);
+    });
+}
+rwkv_status rwkv_gen_prompt_left(const rwkv_engine *e, int32_t slot, size_t *left) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!left) throw RwkvError(RWKV_ERR_INVALID, "null left");
+        *left = e->gen_prompt_left(slot);
     });
 }
 rwkv_status rwkv_gen_disarm(rwkv_engine *e, int32_t slot) {

@@ -275,13 +275,15 @@ struct GenSlot {                    // one per slot, device-resident; the host k
 };
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
-    const int *row_slot;            // [n_rows] slot of each row of the step
+    const int *row_slot;            // slot of each row of the step
+    const int *out_rows;            // null: decode-only step, logits row == step row.  Mixed step: [n_rows] step row of each logits row
+    int *held;                      // [max_batch] mixed step: the token a slot drew last (next step's input row of the slot)
     float *logits;                  // [n_rows][V]
     float *penalty, *bias;          // [max_batch][V]; penalty: GEN_ABSENT bits = no entry; bias may be null when no armed slot has one
     SampleRow *rows;                // [n_rows] this step's sampler parameters (read by nucleus_kernel)
     const int *samp_tok;            // [n_rows] what nucleus_kernel wrote
     const float *samp_prob;
-    int *feedback;                  // [n_rows] token each row consumes in the next step
+    int *feedback;                  // [n_rows] decode-only step: token each row consumes in the next step
     unsigned *out_tok; float *out_prob;   // [steps][max_batch] output ring of this run
     int *run_step;                  // step index inside the run; -1 before the first step
     int max_batch, V, n_rows;
@@ -304,6 +306,8 @@ RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, 
 void launch_gen_pre(const GenArgs &a, hipStream_t s);
 void launch_gen_post(const GenArgs &a, hipStream_t s);
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);
+void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T > 0
+void launch_gen_handover(int *feedback, int *held, const int *row_slot, int T, bool to_held, hipStream_t s);         // T > 0
 // two-stage arg-max; scratch_v / scratch_i hold n_rows*32 partial (value, index) pairs
 void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *scratch_v, int *scratch_i, hipStream_t s);
 

@@ -3409,6 +3409,13 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 // mirrors (include/rwkv_sampler.hpp, harness.py) round every operation to f32, so nothing here may contract into an FMA — and
 // HIP's __fmul_rn / __fadd_rn are plain `*` / `+` that hipcc's default -ffp-contract=fast fuses after inlining (measured: the
 // penalty of a repeated token was off by one ulp after 14 draws), hence `#pragma clang fp contract(off)` in the three helpers.
+//
+// Two instantiations of the three kernels.  <false> is the decode-only step: logits row == step row, the token goes to feedback[row].
+// <true> is a MIXED step (rwkv_gen_arm_prompt): the step also carries prompt rows, the logits block holds only the rows the plan emits
+// (decode slots and slots whose prompt ends in this step: out_rows, ascending slot order), so logits row r belongs to slot
+// row_slot[out_rows[r]] — being in the block IS the "emits this step" predicate, a slot in mid-prefill has no row and is neither
+// sampled, penalised, counted nor frozen — and the token goes to held[slot], from where gen_tokens_kernel puts it into the next
+// step's token array.  A slot whose prompt just ended has draws == 0: its first draw is draw 0 of (seed, stream).
 // =====================================================================================
 __device__ __forceinline__ float gen_adjust(float x, unsigned pbits, float b) {
 #pragma clang fp contract(off)
@@ -3418,12 +3425,22 @@ __device__ __forceinline__ float gen_adjust(float x, unsigned pbits, float b) {
     }
     return b != 0.f ? x + b : x;
 }
+template <bool MIXED>
+__device__ __forceinline__ int gen_slot_of(const GenArgs &a, int row) { return MIXED ? a.row_slot[a.out_rows[row]] : a.row_slot[row]; }
+template <bool MIXED>
 __global__ __launch_bounds__(256) void gen_pre_kernel(GenArgs a) {
     const int row = blockIdx.y, tid = threadIdx.x;
-    if (blockIdx.x == 0 && row == 0 && tid == 0) *a.run_step += 1;   // nothing in this launch reads it; gen_post / gen_freeze of the step do
-    const int slot = a.row_slot[row];
+    // nothing in this launch reads it; gen_post / gen_freeze of the step do (a mixed step counts in gen_tokens_kernel: it may emit no row)
+    if (!MIXED && blockIdx.x == 0 && row == 0 && tid == 0) *a.run_step += 1;
+    const int slot = gen_slot_of<MIXED>(a, row);
     const GenSlot &g = a.slots[slot];
-    if (g.finish) return;                                          // rides along until the run ends: its rows are thrown away
+    if (g.finish) {                                                // rides along until the run ends: its rows are thrown away
+        // between mixed steps a rider's logits row moves: park inert parameters there (top_k 0 returns at once) instead of a neighbour's.
+        // (A decode-only step behind a mixed one leaves a rider's rows[row] as it finds it — this slot's, another slot's or the inert
+        // row, always valid parameters — and whatever nucleus_kernel makes of them is dead data: gen_post drops a finished slot's row.)
+        if (MIXED && blockIdx.x == 0 && tid == 0) a.rows[row] = SampleRow{0.f, 0, 1.f, 0.f, 0, 0.f};
+        return;
+    }
     if (blockIdx.x == 0 && tid == 0)
         a.rows[row] = SampleRow{g.top_p, g.top_k, g.temperature, gen_uniform_draw(g.seed, g.stream, g.draws), g.kind, g.tau};
     const bool pen = g.kind != 2;                                  // Mirostat's transform is a no-op (mirostat.rs:40)
@@ -3453,9 +3470,10 @@ __device__ __forceinline__ float gen_mirostat(float max_surprise, float surprise
     const float step = rate * error;
     return fminf(max_surprise - step, 4.0f * target);
 }
+template <bool MIXED>
 __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int row = blockIdx.y, tid = threadIdx.x;
-    const int slot = a.row_slot[row];
+    const int slot = gen_slot_of<MIXED>(a, row);
     GenSlot &g = a.slots[slot];
     const int tok = a.samp_tok[row];
     // The penalty pass does not look at `finish` (thread 0 of block 0 writes it in this launch): a finished slot's row is dead data
@@ -3476,7 +3494,7 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int k = *a.run_step;
     a.out_tok[(long)k * a.max_batch + slot] = (unsigned)tok;
     a.out_prob[(long)k * a.max_batch + slot] = prob;
-    a.feedback[row] = tok;
+    if (MIXED) a.held[slot] = tok; else a.feedback[row] = tok;
     g.draws += 1;
     g.emitted += 1;
     if (g.kind == 2) g.tau = gen_mirostat(g.tau, prob, g.miro_target, g.miro_rate);   // `prob` is the token surprise
@@ -3485,8 +3503,9 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
     if (fin) { g.freeze_at = k; g.finish = fin; }
 }
+template <bool MIXED>
 __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
-    const int slot = a.row_slot[blockIdx.y];
+    const int slot = gen_slot_of<MIXED>(a, blockIdx.y);
     const GenSlot &g = a.slots[slot];
     if (!g.finish || g.freeze_at != *a.run_step) return;           // the common case: one load per block and out
     float *sh = a.shadow[slot];
@@ -3499,9 +3518,39 @@ __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
         for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < len[part]; i += (long)gridDim.x * 1024)
             *(float4 *)(dst[part] + i) = *(const float4 *)(src[part] + i);
 }
-void launch_gen_pre(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_pre_kernel, dim3(16, a.n_rows), dim3(256), 0, s, a); }
-void launch_gen_post(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_post_kernel, dim3(16, a.n_rows), dim3(256), 0, s, a); }
-void launch_gen_freeze(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_freeze_kernel, dim3(64, a.n_rows), dim3(256), 0, s, a); }
+// a.n_rows: rows of the logits block (> 0); a.out_rows != null selects the mixed-step instantiation
+void launch_gen_pre(const GenArgs &a, hipStream_t s) {
+    if (a.out_rows) hipLaunchKernelGGL(gen_pre_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_pre_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+}
+void launch_gen_post(const GenArgs &a, hipStream_t s) {
+    if (a.out_rows) hipLaunchKernelGGL(gen_post_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_post_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+}
+void launch_gen_freeze(const GenArgs &a, hipStream_t s) {
+    if (a.out_rows) hipLaunchKernelGGL(gen_freeze_kernel<true>, dim3(64, a.n_rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_freeze_kernel<false>, dim3(64, a.n_rows), dim3(256), 0, s, a);
+}
+// The token ids of a mixed step: the plan carries the prompt rows' ids and -1 in the row of every slot that feeds itself; that row
+// takes the token its slot drew last (held[slot]).  Also counts the run's step: a mixed step may emit no row at all.
+__global__ __launch_bounds__(256) void gen_tokens_kernel(int *token, const int *row_slot, const int *held, int *run_step, int T) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) *run_step += 1;
+    if (r < T && token[r] < 0) token[r] = held[row_slot[r]];
+}
+// hand-over between the per-slot held tokens and the per-row feedback buffer of a run of decode-only steps (whose rows are `row_slot`)
+__global__ __launch_bounds__(256) void gen_handover_kernel(int *feedback, int *held, const int *row_slot, int T, int to_held) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= T) return;
+    if (to_held) held[row_slot[r]] = feedback[r];
+    else feedback[r] = held[row_slot[r]];
+}
+void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s) {
+    hipLaunchKernelGGL(gen_tokens_kernel, dim3((T + 255) / 256), dim3(256), 0, s, token, row_slot, held, run_step, T);
+}
+void launch_gen_handover(int *feedback, int *held, const int *row_slot, int T, bool to_held, hipStream_t s) {
+    hipLaunchKernelGGL(gen_handover_kernel, dim3((T + 255) / 256), dim3(256), 0, s, feedback, held, row_slot, T, to_held ? 1 : 0);
+}
 
 // =====================================================================================
 // Load-time layout kernels

@@ -95,6 +95,8 @@ ABI_SYMBOLS = {
     "rwkv_infer_sample": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(_SampleC), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]),
     "rwkv_gen_arm": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenParamsC)]),
+    "rwkv_gen_arm_prompt": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(_GenParamsC)]),
+    "rwkv_gen_prompt_left": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "rwkv_gen_disarm": (C.c_int32, [C.c_void_p, C.c_int32]),
     "rwkv_gen_run": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -531,12 +533,8 @@ class Runtime:
         return inp, out
 
     # ---- device-resident sampled generation (rwkv_gen_arm / _run / _disarm): the sampler state lives on the device
-    def gen_arm(self, slot: int, first_token: int, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
-                stop_tokens=(), bias: dict | None = None, allow=None):
-        """Arm `slot` with the settings AND the current state of a host-side sampler (`harness.NucleusSampler` / `TypicalSampler` /
-        `MirostatSampler`, after its `init(prompt)`): the penalty map it holds is handed over, `sampler.bias` (or `bias`) rides along.
-        `first_token` is the token the first step consumes; draw `i` of the slot is `gen_uniform(seed, stream, i)` (stream defaults
-        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`)."""
+    def _gen_params(self, slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow):
+        """rwkv_gen_params from the settings AND the current state of a host-side sampler; returns (struct, arrays to keep alive)"""
         kind = int(getattr(sampler, "kind", 0))
         pen = {} if kind == 2 else dict(getattr(sampler, "penalties", {}))
         bias = dict(bias if bias is not None else getattr(sampler, "bias", {}) or {})
@@ -557,7 +555,35 @@ class Runtime:
                         st.ctypes.data_as(u32p) if st.size else None, st.size,
                         allow.ctypes.data_as(C.POINTER(C.c_uint8)) if allow is not None else None,
                         int(seed), int(slot if stream is None else stream), 0)
+        return p, (pt, pv, bt, bv, st, allow)
+
+    def gen_arm(self, slot: int, first_token: int, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
+                stop_tokens=(), bias: dict | None = None, allow=None):
+        """Arm `slot` with the settings AND the current state of a host-side sampler (`harness.NucleusSampler` / `TypicalSampler` /
+        `MirostatSampler`, after its `init(prompt)`): the penalty map it holds is handed over, `sampler.bias` (or `bias`) rides along.
+        `first_token` is the token the first step consumes; draw `i` of the slot is `gen_uniform(seed, stream, i)` (stream defaults
+        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`)."""
+        p, keep = self._gen_params(slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow)
         _check(lib().rwkv_gen_arm(self._h, int(slot), C.byref(p)))
+        del keep
+
+    def gen_arm_prompt(self, slot: int, tokens, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
+                       stop_tokens=(), bias: dict | None = None, allow=None):
+        """Admission (rwkv_gen_arm_prompt): arm `slot` with the not-yet-consumed tail of its PROMPT instead of a first token.  The
+        following `gen_run` steps prefill it next to the decode rows of the slots that are running and draw its first token on the
+        device (draw 0 of (seed, stream)) from the prompt's last row.  `sampler` is the host sampler right after `init(prompt)`,
+        before any `update`: its penalty map is handed over as in `gen_arm`."""
+        p, keep = self._gen_params(slot, 0, max_tokens, sampler, seed, stream, stop_tokens, bias, allow)
+        toks = np.ascontiguousarray(list(tokens), dtype=np.uint32).reshape(-1)
+        _check(lib().rwkv_gen_arm_prompt(self._h, int(slot), toks.ctypes.data_as(C.POINTER(C.c_uint32)) if toks.size else None, toks.size,
+                                         C.byref(p)))
+        del keep
+
+    def gen_prompt_left(self, slot: int) -> int:
+        """Prompt tokens of `slot` the resident steps have not consumed yet (0 once it is decoding, or when it is not armed)."""
+        left = C.c_size_t(0)
+        _check(lib().rwkv_gen_prompt_left(self._h, int(slot), C.byref(left)))
+        return int(left.value)
 
     def gen_disarm(self, slot: int):
         _check(lib().rwkv_gen_disarm(self._h, int(slot)))

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define RWKV_ABI_VERSION 8   /* 2: rwkv_sample_params gained kind/tau; rwkv_engine_save_prefab
+#define RWKV_ABI_VERSION 9   /* 2: rwkv_sample_params gained kind/tau; rwkv_engine_save_prefab
                               * 3: rwkv_sample_params gained allow (formatter mask); rwkv_host_alloc/free; RWKV_OPTION_NONE
                               * 4: rwkv_engine_token_chunk_size
                               * 5: rwkv_state_back_layer_async / rwkv_state_sync
@@ -32,7 +32,9 @@ extern "C" {
                               *    that the rows end inside the pinned block that holds `dst`
                               * 7: rwkv_load_desc.precision: RWKV_PRECISION_FP16 now holds 1e-3 at depth (the launches that carry a model's f16 operand
                               *    rounding read hi + lo operands); the old all-f16 behaviour is RWKV_PRECISION_FP16_RAW
-                              * 8: device-resident sampled generation: rwkv_gen_params, rwkv_gen_arm / _disarm / _run, rwkv_gen_uniform */
+                              * 8: device-resident sampled generation: rwkv_gen_params, rwkv_gen_arm / _disarm / _run, rwkv_gen_uniform
+                              * 9: resident generation admits prompts: rwkv_gen_arm_prompt (prefill rides in the resident steps, the first token is drawn
+                              *    on the device), rwkv_gen_prompt_left */
 
 typedef int32_t rwkv_status;
 enum {
@@ -281,6 +283,32 @@ struct rwkv_gen_params {
 enum { RWKV_GEN_RUNNING = 0, RWKV_GEN_STOP = 1, RWKV_GEN_LENGTH = 2 };   /* FinishReason::{Stop, Length} run.rs:905-917; 0 = not finished */
 /* arm `slot` (its state is what the prompt left, run.rs:788-832); re-arming replaces the context.  The arrays are copied. */
 rwkv_status rwkv_gen_arm(rwkv_engine *e, int32_t slot, const rwkv_gen_params *p);
+/* Arm `slot` with a PROMPT instead of a first token (ADMISSION: the engine may be generating on other slots, nobody stands still).
+ * `p->first_token` is ignored.  The penalty arrays are the map `Sampler::init` left over the prompt (nucleus.rs:49-59), i.e. BEFORE any
+ * draw; the caller still computes it on the host (rwkv_sampler.hpp).  The slot's state is whatever it holds (zero, an InitState, a
+ * prefix-cache hit); `tokens` are the not-yet-consumed tail of the prompt, n_tokens >= 1 (else RWKV_ERR_INVALID), copied on return.
+ *  - A STEP of rwkv_gen_run then carries one feedback row per running slot plus, for every slot still in its prompt, a share of what is
+ *    left of token_chunk_size after those rows — the split rwkv_plan_chunk gives with n_tokens = 1 for a running slot; decode rows come
+ *    first and are never starved (there must be fewer running slots than token_chunk_size).  A prompt slot emits nothing (0xFFFFFFFF /
+ *    NaN in its column) until its prompt is exhausted.
+ *  - In the step that exhausts the prompt its last row is sampled on the device with draw counter step = 0 of (seed, stream), by the same
+ *    arithmetic as every later draw; penalty / Mirostat update, stop-token and max_tokens tests follow as after any draw.  That token is
+ *    the slot's first emitted token and counts towards max_tokens; the slot carries on as an armed slot.
+ *  - STATE RULE, base case: a slot that finishes on its first draw has consumed exactly the prompt.
+ *  - The refusals of rwkv_gen_arm apply.  What disarms a slot drops its pending prompt too.  A prompt may straddle rwkv_gen_run calls.
+ *  - When every running slot has finished and only prompt slots remain, the run goes on until n_steps.
+ *  - WHAT A JOINER DOES TO THE OTHERS: a step is bit-exact for a given number of rows whatever the neighbouring rows hold, but only
+ *    2e-5 across step shapes (a one-token-per-slot step fuses LayerNorm and token shift into its GEMMs, a step that carries prompt rows
+ *    does not).  While a prompt is being consumed the running slots' rows are in steps of another shape, so their logits move in the
+ *    last bits (seen: 109 units in the last place of a probability, ids equal) and a draw that sits on a boundary of the cumulative
+ *    distribution can pick another token: a request's output depends, at that level, on who else arrives.  It is exactly what the
+ *    per-token calls give when issued with the same rows per step.
+ *  - All armed, unfinished slots together must fit token_chunk_size, else rwkv_gen_run returns RWKV_ERR_INVALID before any step runs.
+ *  - The host runs at most four prompt-carrying steps ahead of the device (the metadata staging ring); nothing else is waited for
+ *    between the steps of a run. */
+rwkv_status rwkv_gen_arm_prompt(rwkv_engine *e, int32_t slot, const uint32_t *tokens, size_t n_tokens, const rwkv_gen_params *p);
+/* prompt tokens of `slot` not yet consumed (0 once it is decoding, or when it is not armed); host-side bookkeeping, no device wait */
+rwkv_status rwkv_gen_prompt_left(const rwkv_engine *e, int32_t slot, size_t *left);
 rwkv_status rwkv_gen_disarm(rwkv_engine *e, int32_t slot);      /* drop the context (`finish`, run.rs:1007-1020); the state stays as the rule says */
 /* Up to n_steps decode steps (run.rs:788-1020, one `infer` + `sample` each) for every armed, unfinished slot.  out_tokens / out_probs:
  * [n_steps][max_batch], step-major, 0xFFFFFFFF / NaN where a slot emitted nothing in that step (out_probs may be NULL; it carries what

@@ -148,6 +148,16 @@ class Runtime {
     // Device-resident sampled generation (rwkv_gen_arm / _run / _disarm): arm a slot with `sampler.gen_params_for(...)`
     // (include/rwkv_sampler.hpp), then every gen_run generates up to n_steps tokens per armed slot without a host turn-around.
     void gen_arm(int slot, const rwkv_gen_params &p) { check(rwkv_gen_arm(e_.get(), slot, &p)); }
+    // Admission (rwkv_gen_arm_prompt): `p` from `sampler.gen_params_for_prompt(...)`, i.e. after init(prompt) and before any update;
+    // the prompt's tail rides in the resident steps and its first token is drawn on the device.
+    void gen_arm_prompt(int slot, const std::vector<uint32_t> &tokens, const rwkv_gen_params &p) {
+        check(rwkv_gen_arm_prompt(e_.get(), slot, tokens.data(), tokens.size(), &p));
+    }
+    size_t gen_prompt_left(int slot) const {
+        size_t left = 0;
+        check(rwkv_gen_prompt_left(e_.get(), slot, &left));
+        return left;
+    }
     void gen_disarm(int slot) { check(rwkv_gen_disarm(e_.get(), slot)); }
     struct Generated {
         std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing

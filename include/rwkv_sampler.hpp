@@ -10,6 +10,8 @@
 // `gen_params_for()` hands the same state to the DEVICE instead (rwkv_gen_arm, ABI 8): after `init()` over the prompt it fills a
 // rwkv_gen_params with the sampler's settings, the penalty map as it stands (positive values: the device negates them like `transform`)
 // and the bias, so that the slot is armed with the map the host would have had.
+// `gen_params_for_prompt()` is the same hand-over for rwkv_gen_arm_prompt (ABI 9): call it right after `init()`, BEFORE the first
+// `update()` — the device draws the first token itself and runs that update there.
 // Header-only; needs rwkv_abi.h only for the structs.
 #pragma once
 #include <cmath>
@@ -91,6 +93,11 @@ class NucleusSampler {
         p.seed = seed; p.stream = stream;
         return p;
     }
+    // for rwkv_gen_arm_prompt: the map as `init` left it, no first token (the device draws it)
+    rwkv_gen_params gen_params_for_prompt(int32_t max_tokens, uint64_t seed, uint32_t stream, GenArrays &keep,
+                                          const std::vector<uint32_t> &stop_tokens = {}) const {
+        return gen_params_for(0, max_tokens, seed, stream, keep, stop_tokens);
+    }
 };
 
 class TypicalSampler : public NucleusSampler {       // typical.rs: TypicalParams defaults tau 0.5, top_k 128, temperature 1.0
@@ -139,6 +146,10 @@ class MirostatSampler {                              // mirostat.rs:11-36: tau (
         p.n_stop = keep.stop_tokens.size();
         p.seed = seed; p.stream = stream;
         return p;
+    }
+    rwkv_gen_params gen_params_for_prompt(int32_t max_tokens, uint64_t seed, uint32_t stream, GenArrays &keep,
+                                          const std::vector<uint32_t> &stop_tokens = {}) const {
+        return gen_params_for(0, max_tokens, seed, stream, keep, stop_tokens);
     }
 };
 

@@ -1,9 +1,9 @@
-//! Raw bindings of `include/rwkv_abi.h` (ABI version 8), one `pub fn` per export, in the header's order.
+//! Raw bindings of `include/rwkv_abi.h` (ABI version 9), one `pub fn` per export, in the header's order.
 //! tests/test_abi_cpu.py diffs this file against the header (names and argument counts) and against the built library.
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_float, c_void};
 
-pub const RWKV_ABI_VERSION: i32 = 8;
+pub const RWKV_ABI_VERSION: i32 = 9;
 
 pub type rwkv_status = i32;
 pub const RWKV_OK: rwkv_status = 0;
@@ -106,6 +106,8 @@ extern "C" {
                              out_probs: *mut c_float, emitted: *mut u8, n_consumed: *mut usize) -> rwkv_status;
     // device-resident sampled generation: the decode loop of `process` with the samplers on the device (run.rs:788-1020, sampler/*.rs)
     pub fn rwkv_gen_arm(e: *mut rwkv_engine, slot: i32, p: *const rwkv_gen_params) -> rwkv_status;
+    pub fn rwkv_gen_arm_prompt(e: *mut rwkv_engine, slot: i32, tokens: *const u32, n_tokens: usize, p: *const rwkv_gen_params) -> rwkv_status;
+    pub fn rwkv_gen_prompt_left(e: *const rwkv_engine, slot: i32, left: *mut usize) -> rwkv_status;
     pub fn rwkv_gen_disarm(e: *mut rwkv_engine, slot: i32) -> rwkv_status;
     pub fn rwkv_gen_run(e: *mut rwkv_engine, n_steps: i32, out_tokens: *mut u32, out_probs: *mut c_float, n_emitted: *mut i32,
                         finish: *mut i32) -> rwkv_status;

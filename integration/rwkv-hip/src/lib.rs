@@ -213,7 +213,17 @@ impl Engine {
     }
     /// Arm `slot` for device-resident sampled generation (rwkv_gen_arm): the decode loop of `process` (run.rs:788-1020) with `sample()`
     /// (run.rs:664-697) and the sampler state machine (sampler/*.rs) on the device.  The slot's state is what the prompt left.
-    pub fn gen_arm(&self, slot: usize, p: &GenParams) -> Result<()> {
+    pub fn gen_arm(&self, slot: usize, p: &GenParams) -> Result<()> { self.gen_arm_with(slot, p, None) }
+    /// Admission (rwkv_gen_arm_prompt, run.rs:788-832 without leaving the loop): arm `slot` with the not-yet-consumed tail of its
+    /// prompt.  `p.penalties` is the map `Sampler::init` left (before any draw), `p.first_token` is ignored: the following `gen_run`
+    /// steps prefill next to the running slots' decode rows and draw the first token on the device (draw 0 of (seed, stream)).
+    pub fn gen_arm_prompt(&self, slot: usize, tokens: &[u32], p: &GenParams) -> Result<()> { self.gen_arm_with(slot, p, Some(tokens)) }
+    /// prompt tokens of `slot` the resident steps have not consumed yet (rwkv_gen_prompt_left)
+    pub fn gen_prompt_left(&self, slot: usize) -> Result<usize> {
+        let mut left = 0usize;
+        check(unsafe { sys::rwkv_gen_prompt_left(self.raw, slot as i32, &mut left) })?; Ok(left)
+    }
+    fn gen_arm_with(&self, slot: usize, p: &GenParams, prompt: Option<&[u32]>) -> Result<()> {
         let (pt, pv): (Vec<u32>, Vec<f32>) = p.penalties.iter().copied().unzip();
         let (bt, bv): (Vec<u32>, Vec<f32>) = p.bias.iter().copied().unzip();
         let raw = sys::rwkv_gen_params {
@@ -225,7 +235,10 @@ impl Engine {
             stop_tokens: p.stop_tokens.as_ptr(), n_stop: p.stop_tokens.len(), allow: ptr::null(),
             seed: p.seed, stream: p.stream, reserved: 0,
         };
-        check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) })
+        match prompt {
+            None => check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) }),
+            Some(t) => check(unsafe { sys::rwkv_gen_arm_prompt(self.raw, slot as i32, t.as_ptr(), t.len(), &raw) }),
+        }
     }
     pub fn gen_disarm(&self, slot: usize) -> Result<()> { check(unsafe { sys::rwkv_gen_disarm(self.raw, slot as i32) }) }
     /// Up to `n_steps` tokens for every armed, unfinished slot with no host turn-around (rwkv_gen_run).  When it returns a slot's

@@ -12,7 +12,16 @@ The per-token loop is timed twice: `sample_bare` is Runtime.serve_loop_sample â€
 hoisted out: the LEAST the per-token path can cost and the yardstick the resident loop is held to â€” and `sample_host_samplers` is
 the same call driven by harness.NucleusSampler objects (penalty maps on the host, adjustment lists per token), which includes the
 Python interpreter's share and is reported for orientation only.  The resident loop always carries the penalty state machine.
-Token 0 stops a resident slot (run.rs:855), so its rate counts the tokens really emitted."""
+Token 0 stops a resident slot (run.rs:855), so its rate counts the tokens really emitted.
+
+`--loops resident` times the resident loop alone (the decode-only regression guard: run it on two builds, alternating, with
+RWKV_HIP_LIB-less checkouts side by side).  `--admission` adds the admission scenario: 24 slots generate, every 16 steps one of the
+other 8 slots receives a 256-token prompt and then generates; (a) `leave_and_prefill` is the sequence of ABI 8 (leave the run,
+rwkv_infer_sample prefill, host sampler update, rwkv_gen_arm, re-enter), (b) `arm_prompt` is rwkv_gen_arm_prompt (ABI 9).  Reported for
+both, by the host clock: tokens/s over the region; the time from the admission to the joiner's first token being in the host's hands;
+and the longest gap between two tokens of a running slot: for (a) the time between the two runs around an admission plus one step, for
+(b) the longest single-step run while a prompt is being consumed (rwkv_gen_run(1) per step during an admission, so that every step
+is timed on its own)."""
 import argparse
 import json
 import os
@@ -38,6 +47,8 @@ def main():
     ap.add_argument("--steps-per-run", type=int, default=32)
     ap.add_argument("--regions", type=int, default=5)
     ap.add_argument("--batches", default="32,1")
+    ap.add_argument("--loops", default="greedy,sample_bare,sample_host_samplers,resident")
+    ap.add_argument("--admission", action="store_true")
     a = ap.parse_args()
     batches = [int(x) for x in a.batches.split(",")]
     B = max(batches)
@@ -87,6 +98,65 @@ def main():
         return time.perf_counter() - t, emitted
 
     loops = {"greedy": greedy, "sample_bare": sample_bare, "sample_host_samplers": sample_host, "resident": resident}
+    loops = {k: f for k, f in loops.items() if k in a.loops.split(",")}
+
+    def admission(mode, running=24, joiners=8, every=16, plen=256, tail=4):
+        """One region.  Both modes call gen_run(every) while nobody is being admitted.  `leave_and_prefill` admits between two runs with
+        existing calls; the running slots' gap there is the host time between the two runs plus one step.  `arm_prompt` arms the prompt
+        and then calls gen_run(1) until the joiner's first token is out, each call timed: a running slot emits one token per call, so
+        the longest such call IS its longest gap (it includes the per-call read-back a longer run would not pay).
+        Returns (seconds, tokens emitted, [first-token latency per joiner], longest running-slot gap, mixed steps per admission)."""
+        for b in range(running):
+            eng.gen_arm(b, first[b], 1 << 20, H.NucleusSampler(), seed=1)
+        prompts = [[t % V for t in R.synth_prompt(950 + j, plen)] for j in range(joiners)]
+        emitted, lat, plain, gaps, mixed = 0, [], [], [], []
+        t_region = time.perf_counter()
+        for r in range(joiners + tail):
+            t0 = time.perf_counter()
+            _, _, ne, _ = eng.gen_run(every)
+            t1 = time.perf_counter()
+            emitted += int(ne.sum())
+            plain.append((t1 - t0) / every)
+            if r >= joiners:
+                continue
+            slot, q = running + r, prompts[r]
+            smp = H.NucleusSampler()
+            smp.init(q)
+            ta = time.perf_counter()
+            if mode == "arm_prompt":
+                eng.gen_arm_prompt(slot, q, 1 << 20, smp, seed=1)
+                n = 0
+                while True:
+                    tg = time.perf_counter()
+                    toks, _, ne, _ = eng.gen_run(1)
+                    te = time.perf_counter()
+                    emitted += int(ne.sum())
+                    gaps.append(te - tg)
+                    n += 1
+                    if toks[0, slot] != 0xFFFFFFFF:
+                        break
+                lat.append(te - ta)
+                mixed.append(n)
+            else:
+                inp = rt.RnnInput([rt.RnnInputBatch(list(q) if b == slot else []) for b in range(B)])
+                sm = [smp if b == slot else None for b in range(B)]
+                us = [rt.gen_uniform(1, slot, 0) if b == slot else 0.0 for b in range(B)]
+                res, n = None, 0
+                while inp.num_token() > 0:
+                    inp, out_ = eng.infer_sample(inp, sm, us)
+                    res = out_[slot] or res
+                    n += 1
+                lat.append(time.perf_counter() - ta)
+                emitted += 1
+                smp.update(res[0])
+                eng.gen_arm(slot, res[0], 1 << 20, smp, seed=1)
+                gaps.append(time.perf_counter() - t1 + statistics.median(plain))
+                mixed.append(n)
+        dt = time.perf_counter() - t_region
+        for b in range(B):
+            eng.gen_disarm(b)
+        return dt, emitted, lat, max(gaps), max(mixed)
+
     out = {"workload": f"RWKV-{a.workload} int8, default precision, synthetic weights", "tokens_per_slot_per_region": n, "steps_per_gen_run": spr,
            "regions": a.regions, "load_s": load_s, "sampler": "Nucleus top_p 0.5 top_k 128 temperature 1.0 penalties 0.3 / 0.3 / 0.99654026",
            "batches": {}}
@@ -104,10 +174,33 @@ def main():
             res[k] = {"tokens_per_s": statistics.median(rates), "ms_per_step": statistics.median(steps),
                       "tokens_per_s_min": min(rates), "tokens_per_s_max": max(rates),
                       "spread_pct": 100.0 * (max(rates) - min(rates)) / statistics.median(rates), "tokens_per_region": [tok for _, tok in v]}
-        res["resident"]["arm_ms_per_slot"] = 1e3 * statistics.median(arm_s[nb]) / nb
-        res["resident_vs_sample_bare"] = res["resident"]["tokens_per_s"] / res["sample_bare"]["tokens_per_s"]
-        res["resident_vs_greedy"] = res["resident"]["tokens_per_s"] / res["greedy"]["tokens_per_s"]
+        if "resident" in res:
+            res["resident"]["arm_ms_per_slot"] = 1e3 * statistics.median(arm_s[nb]) / nb
+            for other in ("sample_bare", "greedy"):
+                if other in res:
+                    res["resident_vs_" + other] = res["resident"]["tokens_per_s"] / res[other]["tokens_per_s"]
         out["batches"][str(nb)] = res
+    if a.admission:
+        adm = {}
+        modes = ("leave_and_prefill", "arm_prompt")
+        runs = {m: [] for m in modes}
+        for rep_ in range(a.regions + 1):                          # region 0 warms both and is dropped; the two alternate
+            for m in modes:
+                r = admission(m)
+                if rep_:
+                    runs[m].append(r)
+        for m in modes:
+            rates = [tok / dt for dt, tok, _, _, _ in runs[m]]
+            lats = [statistics.median(l) * 1e3 for _, _, l, _, _ in runs[m]]
+            gaps = [g * 1e3 for _, _, _, g, _ in runs[m]]
+            sp = lambda v: 100.0 * (max(v) - min(v)) / statistics.median(v)
+            adm[m] = {"tokens_per_s": statistics.median(rates), "tokens_per_s_spread_pct": sp(rates),
+                      "first_token_ms": statistics.median(lats), "first_token_ms_spread_pct": sp(lats),
+                      "longest_running_gap_ms": statistics.median(gaps), "longest_running_gap_ms_spread_pct": sp(gaps),
+                      "steps_per_admission": runs[m][0][4]}
+        adm["scenario"] = ("24 slots generating, every 16 steps one of 8 more slots gets a 256-token prompt; gen_run(16) per call, "
+                           "gen_run(1) per step while arm_prompt consumes a prompt; token_chunk_size %d" % eng.token_chunk_size)
+        out["admission"] = adm
     eng.close()
     line = json.dumps(out)
     print(line)
