@@ -756,10 +756,19 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
             Dm = dm_l;
             w.W1 = load_mat(p + "att.time_mix_w1", W_F16, -1, "", 5 * Dm, C);
             for (int c = 0; c < 5; ++c) w.W2[c] = load_mat(p + "att.time_mix_w2", W_F16, c, p + "att.time_mix_w2#" + std::to_string(c), C, Dm);
+            // the decay LoRA rank as the FILE states it (load_mat pads rows to whole strips): the WKV kernels read [T][Dd] / [C][Dd] rows in four
+            // parts of whole 8-element vectors (rwkv_kernels.hip wkv_kernel), so the rank must be a multiple of 32, and ftd holds 128 columns
+            if (!pf) {
+                const StTensor &d1 = st.get(p + "att.time_decay_w1");
+                const long dd = d1.shape.size() == 2 ? (long)d1.shape[0] : -1;
+                if (dd < 0) throw RwkvError(RWKV_ERR_FORMAT, p + "att.time_decay_w1: expected a matrix");
+                if (dd < 32 || dd > 128 || dd % 32)
+                    throw RwkvError(RWKV_ERR_UNSUPPORTED, "time_decay LoRA dim must be 32, 64, 96 or 128 (" + p + "att.time_decay_w1 has " + std::to_string(dd) + ")");
+            }
             w.D1 = load_mat(p + "att.time_decay_w1", W_F16, -1, "", 0, C);
             if (l > 0 && w.D1->rows != Dd) throw RwkvError(RWKV_ERR_FORMAT, "time_decay LoRA dim differs between layers");
             Dd = w.D1->rows;
-            if (Dd > 128 || Dd % 4) throw RwkvError(RWKV_ERR_UNSUPPORTED, "time_decay LoRA dim must be <=128");
+            if (Dd > 128 || Dd % 32) throw RwkvError(RWKV_ERR_UNSUPPORTED, "time_decay LoRA dim must be 32, 64, 96 or 128");
             w.D2 = load_raw16(p + "att.time_decay_w2", true, (size_t)C * Dd);
         } else {
             const char *n7[] = {"r", "w", "k", "v", "a", "g"};

@@ -3003,7 +3003,7 @@ __global__ __launch_bounds__(256, CH == 8 ? 5 : (VER == 7 ? 2 : 3)) void wkv_chu
 }
 void launch_wkv(const WkvArgs &a, bool multi_row, hipStream_t s) {
     // every sequence of the step has <= 8 rows: the five-blocks-per-CU form.  V6's decay LoRA is compiled for Dd = 64 and 128 only (the KS of
-    // its MFMA stage): any other Dd the loader accepts (multiples of 4 up to 128) falls through to the generic per-token kernel below,
+    // its MFMA stage): any other Dd the loader accepts (32 and 96: multiples of 32 up to 128, whole 8-element vectors per quarter row) falls through to the generic per-token kernel below,
     // like the long form does (a <6, 128, 8> instance would read D2 / td rows with the wrong extent).
     if (multi_row && a.max_rows > 0 && a.max_rows <= 8 && (a.version != 6 || a.Dd == 64 || a.Dd == 128)) {
         if (a.version == 5) hipLaunchKernelGGL((wkv_chunk_kernel<5, 64, 8>), dim3(a.n_seq, a.H), dim3(256), 0, s, a);

@@ -48,7 +48,8 @@ static void master_leave(void);
 #define LN_EPS 1e-5f
 #define GN_EPS 64e-5f   /* GroupNorm eps of the reference models: 1e-5 * head_size_divisor^2 (8^2), as in rwkv_ref.GN_EPS */
 
-/* Y[b][r] = sum_k W[r][k] X[b][k];  W fp16 row-major [rows][K], K % 8 == 0;  slots in groups of 8 so the accumulators stay in registers */
+/* Y[b][r] = sum_k W[r][k] X[b][k];  W fp16 row-major [rows][K], any K >= 1 (a K that is no multiple of 8 — a V6 decay LoRA of rank 4, 36, 100 —
+ * ends in one masked vector: weights padded with zeros, X read through a mask, never past its row);  slots in groups of 8 so the accumulators stay in registers */
 /* Called by EVERY thread of the step's team (orphaned worksharing loop, implicit barrier at its end): one persistent team per step
  * instead of a fork per GEMM.  The static schedule over rows is the one rwkv_cpu_place used to first-touch W, so a thread reads the
  * rows that live on its own NUMA node. */
@@ -84,6 +85,7 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
     }
     const int rnd = ((g_f16_mask >> cls) & 1) | ((cls >= CLS_ATT_R && cls <= CLS_ATT_W) ? (g_f16_mask & 1) : 0);
     const long npair = (rows + 1) / 2;
+    static const int32_t tail_mask[16] = {-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma omp for schedule(static)
     for (long p = 0; p < npair; ++p) {
         const long r0 = 2 * p;
@@ -91,10 +93,13 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
         float wf[2][GEMM_KP] __attribute__((aligned(32)));
         __m256 accb[2][64];                                            /* lane-wise partial sums of (row, slot), carried across the K panels; B <= 64 */
         for (long k0 = 0; k0 < K; k0 += GEMM_KP) {
-            const long kn = K - k0 < GEMM_KP ? K - k0 : GEMM_KP;
-            for (int i = 0; i < nr; ++i)
-                for (long k = 0; k < kn; k += 8)
+            const long kn = K - k0 < GEMM_KP ? K - k0 : GEMM_KP, kn8 = kn & ~7L;   /* kn8 < kn only in the last panel of a K % 8 != 0 */
+            const __m256i tmask = _mm256_loadu_si256((const __m256i *)(tail_mask + 8 - (kn - kn8)));
+            for (int i = 0; i < nr; ++i) {
+                for (long k = 0; k < kn8; k += 8)
                     _mm256_store_ps(&wf[i][k], _mm256_cvtph_ps(_mm_loadu_si128((const __m128i *)(W + (r0 + i) * K + k0 + k))));
+                for (long k = kn8; k < kn8 + 8 && kn8 < kn; ++k) wf[i][k] = k < kn ? _cvtsh_ss(W[(r0 + i) * K + k0 + k]) : 0.f;
+            }
             if (nr == 1) for (long k = 0; k < kn; k += 8) _mm256_store_ps(&wf[1][k], _mm256_setzero_ps());
             for (int b0 = 0; b0 < B; b0 += 4) {
                 const int nb = B - b0 < 4 ? B - b0 : 4;
@@ -105,20 +110,28 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
                 const float *x0 = X + (long)b0 * ldx + k0, *x1 = X + (long)(b0 + (nb > 1 ? 1 : 0)) * ldx + k0;      /* (slots past B re-read a valid one; their sums are dropped) */
                 const float *x2 = X + (long)(b0 + (nb > 2 ? 2 : 0)) * ldx + k0, *x3 = X + (long)(b0 + (nb > 3 ? 3 : 0)) * ldx + k0;
                 if (!rnd) {
-                    for (long k = 0; k < kn; k += 8) {
+                    for (long k = 0; k < kn8; k += 8) {
                         const __m256 w0 = _mm256_load_ps(&wf[0][k]), w1 = _mm256_load_ps(&wf[1][k]);
                         const __m256 v0 = _mm256_loadu_ps(x0 + k), v1 = _mm256_loadu_ps(x1 + k), v2 = _mm256_loadu_ps(x2 + k), v3 = _mm256_loadu_ps(x3 + k);
                         a00 = _mm256_fmadd_ps(w0, v0, a00); a01 = _mm256_fmadd_ps(w0, v1, a01); a02 = _mm256_fmadd_ps(w0, v2, a02); a03 = _mm256_fmadd_ps(w0, v3, a03);
                         a10 = _mm256_fmadd_ps(w1, v0, a10); a11 = _mm256_fmadd_ps(w1, v1, a11); a12 = _mm256_fmadd_ps(w1, v2, a12); a13 = _mm256_fmadd_ps(w1, v3, a13);
                     }
                 } else {
-                    for (long k = 0; k < kn; k += 8) {
+                    for (long k = 0; k < kn8; k += 8) {
                         const __m256 w0 = _mm256_load_ps(&wf[0][k]), w1 = _mm256_load_ps(&wf[1][k]);
                         const __m256 v0 = round_f16(_mm256_loadu_ps(x0 + k)), v1 = round_f16(_mm256_loadu_ps(x1 + k));
                         const __m256 v2 = round_f16(_mm256_loadu_ps(x2 + k)), v3 = round_f16(_mm256_loadu_ps(x3 + k));
                         a00 = _mm256_fmadd_ps(w0, v0, a00); a01 = _mm256_fmadd_ps(w0, v1, a01); a02 = _mm256_fmadd_ps(w0, v2, a02); a03 = _mm256_fmadd_ps(w0, v3, a03);
                         a10 = _mm256_fmadd_ps(w1, v0, a10); a11 = _mm256_fmadd_ps(w1, v1, a11); a12 = _mm256_fmadd_ps(w1, v2, a12); a13 = _mm256_fmadd_ps(w1, v3, a13);
                     }
+                }
+                if (kn8 < kn) {
+                    const __m256 w0 = _mm256_load_ps(&wf[0][kn8]), w1 = _mm256_load_ps(&wf[1][kn8]);
+                    __m256 v0 = _mm256_maskload_ps(x0 + kn8, tmask), v1 = _mm256_maskload_ps(x1 + kn8, tmask);
+                    __m256 v2 = _mm256_maskload_ps(x2 + kn8, tmask), v3 = _mm256_maskload_ps(x3 + kn8, tmask);
+                    if (rnd) { v0 = round_f16(v0); v1 = round_f16(v1); v2 = round_f16(v2); v3 = round_f16(v3); }
+                    a00 = _mm256_fmadd_ps(w0, v0, a00); a01 = _mm256_fmadd_ps(w0, v1, a01); a02 = _mm256_fmadd_ps(w0, v2, a02); a03 = _mm256_fmadd_ps(w0, v3, a03);
+                    a10 = _mm256_fmadd_ps(w1, v0, a10); a11 = _mm256_fmadd_ps(w1, v1, a11); a12 = _mm256_fmadd_ps(w1, v2, a12); a13 = _mm256_fmadd_ps(w1, v3, a13);
                 }
                 if (k0 + kn < K) {
                     accb[0][b0] = a00; accb[0][b0 + 1] = a01; accb[0][b0 + 2] = a02; accb[0][b0 + 3] = a03;

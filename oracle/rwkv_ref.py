@@ -683,9 +683,11 @@ CONFIGS = {
 
 
 def synth_checkpoint(version: int, L: int, C: int, F: int, V: int, seed: int = 20251024,
-                     fast: bool = False, alloc=None, shapes_only: bool = False) -> dict[str, np.ndarray]:
+                     fast: bool = False, alloc=None, shapes_only: bool = False, lora_dims=None) -> dict[str, np.ndarray]:
     """Seeded synthetic fp16 tensors in the converted `.st` layout (App. A.1 of SURVEY.md;
     names/transposes follow convert_safetensors.py:96-101 literally).
+    `lora_dims`: the LoRA ranks, V6 `(Dm, Dd)` (token-shift mix, decay), V7 `(Dw, Da, Dv, Dg)`; None = the ranks of the published
+    models of that width (below) — the draw order does not depend on it, so None gives the tensors it always gave.
     `fast=True` fills the big matrices by tiling a 16M-sample random block (bench-only; same statistics).
     `alloc(name, shape)` may supply the destination arrays (e.g. views into a file buffer);
     `shapes_only=True` returns {name: shape} without generating anything."""
@@ -751,7 +753,7 @@ def synth_checkpoint(version: int, L: int, C: int, F: int, V: int, seed: int = 2
             uni(a + "time_decay", (H, N), -6, -0.5)
             vec(a + "time_first", (H, N), 0.0, 0.3)
         elif version == 6:
-            Dm, Dd = (64, 128) if C >= 4096 else (32, 64)
+            Dm, Dd = ((64, 128) if C >= 4096 else (32, 64)) if lora_dims is None else lora_dims
             for n in "xwkvrg":
                 uni(a + f"time_mix_{n}", (1, 1, C), 0, 1)
             vec(a + "time_mix_w1", (5 * Dm, C))          # orig [C,5Dm] transposed
@@ -764,6 +766,8 @@ def synth_checkpoint(version: int, L: int, C: int, F: int, V: int, seed: int = 2
             Dw, Da, Dv, Dg = (96, 96, 64, 320) if C >= 2560 else (64, 64, 32, 128)
             if C < 1024:
                 Dw, Da, Dv, Dg = 32, 32, 32, 64
+            if lora_dims is not None:
+                Dw, Da, Dv, Dg = lora_dims
             for n in "rwkvag":
                 uni(a + f"x_{n}", (1, 1, C), 0, 1)
             uni(a + "w0", (1, 1, C), -7, -1)

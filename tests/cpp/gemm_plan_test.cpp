@@ -1,11 +1,16 @@
 // CPU driver of ai00_server_amd/csrc/gemm_plan.h for tests/test_gemm_plan_cpp.py: plans the launches it reads, prints what the engine would log.
 //   stdin, one launch per line:  T hilo commit no_tile tile_shape tile_ksplit tile_xcd nprob {rows K fmt partial kcopies smallk}...
 //   stdout, one line per launch: kind variant grid threads ksplit
+//   with the argument "geometry" the line goes on with what the kernels of that launch index by:
+//     total_blocks strips_per_tile_block tokens_per_tile_block nprob {Kb ksb nslice nblk_strip spb nw block_begin tile_blocks}...
+//   (tile_blocks: gemm_tile_blocks of the problem on the planned shape, 0 on the other paths; the two per-block figures are 0 there too)
 // Compiled with a plain host compiler: no HIP, no library of the project.
 #include "../../ai00_server_amd/csrc/gemm_plan.h"
 #include <cstdio>
+#include <cstring>
 
-int main() {
+int main(int argc, char **argv) {
+    const bool geometry = argc > 1 && !std::strcmp(argv[1], "geometry");
     using namespace rwkv;
     int T, hilo, commit, n;
     Knobs kn;
@@ -19,7 +24,18 @@ int main() {
         }
         GemmLaunch Lh;
         const GemmPlan pl = plan_gemm(Lh, ps, n, T, hilo != 0, commit != 0, kn);
-        std::printf("%s %d %d %d %d\n", kGemmPathNames[pl.path], pl.variant, pl.grid, pl.threads, pl.ksplit);
+        std::printf("%s %d %d %d %d", kGemmPathNames[pl.path], pl.variant, pl.grid, pl.threads, pl.ksplit);
+        if (geometry) {
+            const bool tile = pl.path == GEMM_TILE;
+            const TileShape ts = kTileShapes[tile ? pl.variant : 0];
+            std::printf(" %d %d %d %d", Lh.total_blocks, tile ? ts.waves * ts.spw : 0, tile ? ts.ntl * 16 : 0, n);
+            for (int i = 0; i < n; ++i) {
+                const GemmProb &g = Lh.p[i];
+                std::printf(" %d %d %d %d %d %d %d %d", g.Kb, g.ksb, g.nslice, g.nblk_strip, g.spb, g.nw, g.block_begin,
+                            tile ? gemm_tile_blocks(pl.variant, ps[i].rows, T) : 0);
+            }
+        }
+        std::printf("\n");
     }
     return 0;
 }
