@@ -81,7 +81,9 @@ enum { RWKV_QUANT_NONE = 0, RWKV_QUANT_INT8 = 1, RWKV_QUANT_NF4 = 2 };   /* `Qua
  *        second-stage LoRAs and the output projection) — logits, state and embeddings within 1e-3 of an fp32 evaluation at 32 layers;
  *   FP32: every launch reads hi + lo operands (fp32-class: <= 2e-5);
  *   FP16_RAW: f16 operands everywhere — the fastest mode; relative error ~1e-3 of the row's magnitude, NOT within 1e-3 absolute at 32 layers
- *        (V7-2.9B NF4 measures 4.7e-3).  For callers that accept that. */
+ *        (V7-2.9B NF4 measures 4.7e-3).  For callers that accept that.
+ * Saturation, in every mode: an activation outside f16's range enters a matrix product as +-65504 (operands saturate); no operand
+ * becomes inf or NaN.  This is about activations; a quantised weight is whatever its format dequantises to. */
 enum { RWKV_PRECISION_FP16 = 0, RWKV_PRECISION_FP32 = 1, RWKV_PRECISION_FP16_RAW = 2 };
 enum { RWKV_ADAPTER_AUTO = -1, RWKV_ADAPTER_ECONOMICAL = -2 };           /* reload.rs AdapterOption; >=0 = Manual(n) */
 

@@ -71,6 +71,12 @@ static inline __m256 round_f16(__m256 x) {
  * every group of 8 slots re-read and re-converted the row, one load per FMA: 27 GB/s of weights at 32 slots on 16 cores.)  The arithmetic of
  * one (row, slot) dot product is unchanged — eight lane-wise partial sums over k in k order, then the same horizontal sum — so every result
  * is bit-identical to the old loop nest (tests/test_oracle.py holds the backend against the numpy restatement either way). */
+/* Saturation switch (tests/test_values_cpu.py; off = 0 everywhere else): every GEMM's X operand is clamped to +-65504 on the way in and not
+ * rounded — `RwkvRef(clip_operands=True)`, the engine's contract for out-of-range operands.  Off, nothing changes. */
+static int g_clip = 0;
+void rwkv_cpu_set_operand_clip(int on) { g_clip = on; }
+static inline __m256 clamp_f16_range(__m256 x) { return _mm256_min_ps(_mm256_max_ps(x, _mm256_set1_ps(-65504.0f)), _mm256_set1_ps(65504.0f)); }
+static inline __m256 operand(__m256 x, int rnd) { return rnd == 1 ? round_f16(x) : clamp_f16_range(x); }
 #define GEMM_KP 1024
 static inline float hsum8(__m256 v) {
     __m128 s = _mm_add_ps(_mm256_castps256_ps128(v), _mm256_extractf128_ps(v, 1));
@@ -83,7 +89,8 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
         for (int b = 0; b < B; b += 64) gemm_f16(W, rows, K, X + (long)b * ldx, ldx, Y + (long)b * ldy, ldy, B - b < 64 ? B - b : 64, cls);
         return;
     }
-    const int rnd = ((g_f16_mask >> cls) & 1) | ((cls >= CLS_ATT_R && cls <= CLS_ATT_W) ? (g_f16_mask & 1) : 0);
+    const int rnd1 = ((g_f16_mask >> cls) & 1) | ((cls >= CLS_ATT_R && cls <= CLS_ATT_W) ? (g_f16_mask & 1) : 0);
+    const int rnd = rnd1 ? 1 : g_clip ? 2 : 0;                        /* 0: as is; 1: rounded to f16 (saturating); 2: saturated only */
     const long npair = (rows + 1) / 2;
     static const int32_t tail_mask[16] = {-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma omp for schedule(static)
@@ -119,8 +126,8 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
                 } else {
                     for (long k = 0; k < kn8; k += 8) {
                         const __m256 w0 = _mm256_load_ps(&wf[0][k]), w1 = _mm256_load_ps(&wf[1][k]);
-                        const __m256 v0 = round_f16(_mm256_loadu_ps(x0 + k)), v1 = round_f16(_mm256_loadu_ps(x1 + k));
-                        const __m256 v2 = round_f16(_mm256_loadu_ps(x2 + k)), v3 = round_f16(_mm256_loadu_ps(x3 + k));
+                        const __m256 v0 = operand(_mm256_loadu_ps(x0 + k), rnd), v1 = operand(_mm256_loadu_ps(x1 + k), rnd);
+                        const __m256 v2 = operand(_mm256_loadu_ps(x2 + k), rnd), v3 = operand(_mm256_loadu_ps(x3 + k), rnd);
                         a00 = _mm256_fmadd_ps(w0, v0, a00); a01 = _mm256_fmadd_ps(w0, v1, a01); a02 = _mm256_fmadd_ps(w0, v2, a02); a03 = _mm256_fmadd_ps(w0, v3, a03);
                         a10 = _mm256_fmadd_ps(w1, v0, a10); a11 = _mm256_fmadd_ps(w1, v1, a11); a12 = _mm256_fmadd_ps(w1, v2, a12); a13 = _mm256_fmadd_ps(w1, v3, a13);
                     }
@@ -129,7 +136,7 @@ static void gemm_f16(const uint16_t *W, long rows, long K, const float *X, long 
                     const __m256 w0 = _mm256_load_ps(&wf[0][kn8]), w1 = _mm256_load_ps(&wf[1][kn8]);
                     __m256 v0 = _mm256_maskload_ps(x0 + kn8, tmask), v1 = _mm256_maskload_ps(x1 + kn8, tmask);
                     __m256 v2 = _mm256_maskload_ps(x2 + kn8, tmask), v3 = _mm256_maskload_ps(x3 + kn8, tmask);
-                    if (rnd) { v0 = round_f16(v0); v1 = round_f16(v1); v2 = round_f16(v2); v3 = round_f16(v3); }
+                    if (rnd) { v0 = operand(v0, rnd); v1 = operand(v1, rnd); v2 = operand(v2, rnd); v3 = operand(v3, rnd); }
                     a00 = _mm256_fmadd_ps(w0, v0, a00); a01 = _mm256_fmadd_ps(w0, v1, a01); a02 = _mm256_fmadd_ps(w0, v2, a02); a03 = _mm256_fmadd_ps(w0, v3, a03);
                     a10 = _mm256_fmadd_ps(w1, v0, a10); a11 = _mm256_fmadd_ps(w1, v1, a11); a12 = _mm256_fmadd_ps(w1, v2, a12); a13 = _mm256_fmadd_ps(w1, v3, a13);
                 }

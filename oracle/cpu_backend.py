@@ -208,6 +208,12 @@ class CpuBackend:
         self.lib.rwkv_cpu_set_operand_rounding.argtypes = [C.c_int]
         self.lib.rwkv_cpu_set_operand_rounding(int(mask))
 
+    def set_operand_clip(self, on: bool) -> None:
+        """`RwkvRef(clip_operands=True)` for this restatement: every GEMM's activation operand is clamped to +-65504 on the way in.  A switch
+        of the library, like the rounding mask: a test that turns it on turns it off again."""
+        self.lib.rwkv_cpu_set_operand_clip.argtypes = [C.c_int]
+        self.lib.rwkv_cpu_set_operand_clip(int(bool(on)))
+
     def init_states(self, B: int) -> np.ndarray:
         i = self.info
         return np.zeros((B, i.num_layer, i.head_size + 2, i.num_emb), dtype=np.float32)

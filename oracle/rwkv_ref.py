@@ -246,15 +246,23 @@ class RwkvRef:
     run.rs:1121-1130, so a batch is just this applied per slot)."""
 
     def __init__(self, tensors: dict[str, np.ndarray], quant_layers: int = 0,
-                 quant_type: int = QUANT_NONE, lora: list | None = None):
+                 quant_type: int = QUANT_NONE, lora: list | None = None, clip_operands: bool = False):
         """`lora`: [(lora_tensors, alpha), ...] blended at load like `ModelBuilder::lora(Lora { data, blend: LoraBlend::full(alpha) })`
         (lib.rs:466-482).  As published in web-rwkv's loader (runtime/loader.rs, 0.10.x; not vendored in the reference tree —
         restated, UNPINNED): `full(alpha)` is the one pattern `blocks\.([0-9]+)\.([0-9a-zA-Z\.\_]+)` — per-block tensors only; a matrix
         `X.weight` with `X.lora.0` [in, r] / `X.lora.1` [out, r] in the file gets W += alpha * B A^T (factor [alpha, 1]); any other
         tensor the file holds under the model's own name is blended whole, v = alpha * l + (1 - alpha) * v (factor [alpha, 1 - alpha]:
         alpha = 1 replaces a fine-tuned vector).  Matrices are blended on the fp16 values in fp32 and rounded back once (then
-        quantised, if their layer is); vectors stay fp32."""
+        quantised, if their layer is); vectors stay fp32.
+        `clip_operands=True`: every activation a matrix is multiplied with is clamped to +-65504 first — the engine's saturation contract
+        (GEMM operands are f16 pairs, out-of-range values saturate, nothing becomes inf or NaN).  Off, the default, is the
+        arithmetic this oracle always had.  Operands a tanh or a sigmoid produced cannot leave the range and are not touched.
+        `self.probe`, when set to a callable `(name, layer, array)`, is shown intermediates a test wants to reason about (decays, the
+        WKV output before its GroupNorm, V7's kappa sum of squares, the relu^2 operand, the embedding row); it changes no arithmetic."""
         self.info = model_info(tensors)
+        self.clip_operands = clip_operands
+        self.probe = None
+        self._l = 0
         self.quant_layers = quant_layers
         self.quant_type = quant_type
         qn = set()
@@ -282,6 +290,14 @@ class RwkvRef:
             dst[...] = v16 if vec32 is None else vec32
             self.w[k] = dst
 
+    def _op(self, x):
+        """A GEMM's activation operand (see `clip_operands`)."""
+        return np.clip(x, np.float32(-65504.0), np.float32(65504.0)) if self.clip_operands else x
+
+    def _see(self, name, arr):
+        if self.probe is not None:
+            self.probe(name, self._l, arr)
+
     # ---- state slab: [L][N+2][C] fp32 == shape [C, N+2, L, 1] fastest-dim-first (run.rs:987)
     def state_shape(self):
         i = self.info
@@ -307,10 +323,12 @@ class RwkvRef:
     def _token(self, token: int, state: np.ndarray, want_logits: bool):
         i, w = self.info, self.w
         H, N, C = i.num_head, i.head_size, i.num_emb
+        self._see("emb_row", w["emb.weight"][token])
         x = _ln(w["emb.weight"][token], w["blocks.0.ln0.weight"], w["blocks.0.ln0.bias"])
         v_first = None
         for l in range(i.num_layer):
             p = f"blocks.{l}."
+            self._l = l
             xx = _ln(x, w[p + "ln1.weight"], w[p + "ln1.bias"])
             sx = state[l, 0].copy()
             S = state[l, 1:1 + N].reshape(N, H, N).transpose(1, 0, 2).copy()  # [H, i, j]
@@ -330,7 +348,7 @@ class RwkvRef:
         if not want_logits:
             return None
         xo = _ln(x, w["ln_out.weight"], w["ln_out.bias"])
-        return w["head.weight"] @ xo
+        return w["head.weight"] @ self._op(xo)
 
     def _wkv56(self, p, r, k, v, wdec, u, S):
         H, N = self.info.num_head, self.info.head_size
@@ -343,30 +361,32 @@ class RwkvRef:
 
     def _att5(self, p, xx, sx, S):
         w = self.w
-        mix = lambda n: xx * w[p + f"att.time_mix_{n}"].reshape(-1) + sx * (1 - w[p + f"att.time_mix_{n}"].reshape(-1))
+        mix = lambda n: self._op(xx * w[p + f"att.time_mix_{n}"].reshape(-1) + sx * (1 - w[p + f"att.time_mix_{n}"].reshape(-1)))
         r = w[p + "att.receptance.weight"] @ mix("r")
         k = w[p + "att.key.weight"] @ mix("k")
         v = w[p + "att.value.weight"] @ mix("v")
         g = w[p + "att.gate.weight"] @ mix("g")
         g = g * _sigmoid(g)
         wdec = np.exp(-np.exp(w[p + "att.time_decay"].reshape(-1)))
+        self._see("wdec", wdec)
         out, S = self._wkv56(p, r, k, v, wdec, w[p + "att.time_first"].reshape(-1), S)
+        self._see("wkv_out", out)
         y = _gn(out, self.info.num_head, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"]) * g
-        return w[p + "att.output.weight"] @ y, S
+        return w[p + "att.output.weight"] @ self._op(y), S
 
     def _att6(self, p, xx, sx, S):
         w = self.w
         C = self.info.num_emb
         dx = sx - xx
         z = xx + dx * w[p + "att.time_mix_x"].reshape(-1)
-        m = np.tanh(w[p + "att.time_mix_w1"] @ z)               # [5*Dm]  (stored [5*Dm, C])
+        m = np.tanh(w[p + "att.time_mix_w1"] @ self._op(z))      # [5*Dm]  (stored [5*Dm, C])
         w2 = w[p + "att.time_mix_w2"]                            # [5, C, Dm]
         Dm = w2.shape[2]
         m = m.reshape(5, Dm)
         xs = {}
         for c, n in enumerate("wkvrg"):                          # BlinkDL order: mw, mk, mv, mr, mg
             mc = w2[c] @ m[c]
-            xs[n] = xx + dx * (w[p + f"att.time_mix_{n}"].reshape(-1) + mc)
+            xs[n] = self._op(xx + dx * (w[p + f"att.time_mix_{n}"].reshape(-1) + mc))
         r = w[p + "att.receptance.weight"] @ xs["r"]
         k = w[p + "att.key.weight"] @ xs["k"]
         v = w[p + "att.value.weight"] @ xs["v"]
@@ -375,9 +395,11 @@ class RwkvRef:
         td = np.tanh(w[p + "att.time_decay_w1"] @ xs["w"])       # [Dd]  (stored [Dd, C])
         d = w[p + "att.time_decay"].reshape(-1) + w[p + "att.time_decay_w2"] @ td  # w2 stored [C, Dd]
         wdec = np.exp(-np.exp(d.astype(np.float32)))
+        self._see("wdec", wdec)
         out, S = self._wkv56(p, r, k, v, wdec, w[p + "att.time_first"].reshape(-1), S)
+        self._see("wkv_out", out)
         y = _gn(out, self.info.num_head, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"]) * g
-        return w[p + "att.output.weight"] @ y, S
+        return w[p + "att.output.weight"] @ self._op(y), S
 
     def _ffn56(self, p, xx, sx):
         w = self.w
@@ -389,46 +411,52 @@ class RwkvRef:
             dx = sx - xx
             xk = xx + dx * w[p + "ffn.time_mix_k"].reshape(-1)
             xr = xx + dx * w[p + "ffn.time_mix_r"].reshape(-1)
-        r = _sigmoid(w[p + "ffn.receptance.weight"] @ xr)
-        k = np.maximum(w[p + "ffn.key.weight"] @ xk, 0) ** 2
-        return r * (w[p + "ffn.value.weight"] @ k)
+        r = _sigmoid(w[p + "ffn.receptance.weight"] @ self._op(xr))
+        k = np.maximum(w[p + "ffn.key.weight"] @ self._op(xk), 0) ** 2
+        self._see("relu2", k)
+        return r * (w[p + "ffn.value.weight"] @ self._op(k))
 
     def _att7(self, p, l, xx, sx, S, v_first):
         w = self.w
         H, N = self.info.num_head, self.info.head_size
         dx = sx - xx
-        xm = {n: xx + dx * w[p + f"att.x_{n}"].reshape(-1) for n in "rwkvag"}
+        xm = {n: self._op(xx + dx * w[p + f"att.x_{n}"].reshape(-1)) for n in "rwkvag"}
         r = w[p + "att.receptance.weight"] @ xm["r"]
         k = w[p + "att.key.weight"] @ xm["k"]
         v = w[p + "att.value.weight"] @ xm["v"]
         wd = w[p + "att.w2"] @ np.tanh(w[p + "att.w1"] @ xm["w"])
-        a = _sigmoid(w[p + "att.a0"].reshape(-1) + w[p + "att.a2"] @ (w[p + "att.a1"] @ xm["a"]))
+        a = _sigmoid(w[p + "att.a0"].reshape(-1) + w[p + "att.a2"] @ self._op(w[p + "att.a1"] @ xm["a"]))
         g = w[p + "att.g2"] @ _sigmoid(w[p + "att.g1"] @ xm["g"])
         kk = (k * w[p + "att.k_k"].reshape(-1)).reshape(H, N)
-        kk = kk / np.maximum(np.sqrt((kk * kk).sum(axis=1, keepdims=True)), np.float32(1e-12))
+        ss = (kk * kk).sum(axis=1, keepdims=True)
+        self._see("kappa_ss", ss)
+        kk = kk / np.maximum(np.sqrt(ss), np.float32(1e-12))
         kk = kk.reshape(-1)
         k = k * (1 + (a - 1) * w[p + "att.k_a"].reshape(-1))
         if l == 0:
             v_first = v
         else:
-            v = v + (v_first - v) * _sigmoid(w[p + "att.v0"].reshape(-1) + w[p + "att.v2"] @ (w[p + "att.v1"] @ xm["v"]))
+            v = v + (v_first - v) * _sigmoid(w[p + "att.v0"].reshape(-1) + w[p + "att.v2"] @ self._op(w[p + "att.v1"] @ xm["v"]))
         wdec = np.exp(np.float32(-0.606531) * _sigmoid((w[p + "att.w0"].reshape(-1) + wd).astype(np.float32)))
+        self._see("wdec", wdec)
         # S[h, i(value), j(key)]
         rh, kh, vh, kkh, ah, wh = (t.reshape(H, N) for t in (r, k, v, kk, a, wdec))
         sa = np.einsum("hij,hj->hi", S, -kkh)
         S = S * wh[:, None, :] + sa[:, :, None] * (kkh * ah)[:, None, :] + vh[:, :, None] * kh[:, None, :]
         S = S.astype(np.float32)
         out = np.einsum("hij,hj->hi", S, rh).reshape(-1)
+        self._see("wkv_out", out)
         y = _gn(out, H, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"])
         bonus = (rh * kh * w[p + "att.r_k"].reshape(H, N)).sum(axis=1, keepdims=True) * vh
         y = y + bonus.reshape(-1)
-        return w[p + "att.output.weight"] @ (y * g), S, v_first
+        return w[p + "att.output.weight"] @ self._op(y * g), S, v_first
 
     def _ffn7(self, p, xx, sx):
         w = self.w
         xk = xx + (sx - xx) * w[p + "ffn.x_k"].reshape(-1)
-        k = np.maximum(w[p + "ffn.key.weight"] @ xk, 0) ** 2
-        return w[p + "ffn.value.weight"] @ k
+        k = np.maximum(w[p + "ffn.key.weight"] @ self._op(xk), 0) ** 2
+        self._see("relu2", k)
+        return w[p + "ffn.value.weight"] @ self._op(k)
 
     # ---- public: mirrors `runtime.infer` for ONE slot ---------------------------------
     def forward(self, tokens, state: np.ndarray, full: bool = False):
@@ -475,10 +503,12 @@ class RwkvRefBatch(RwkvRef):
     def step(self, tokens, states: np.ndarray, want_logits: bool = True):
         i, w = self.info, self.w
         H, N, C, B = i.num_head, i.head_size, i.num_emb, len(tokens)
+        self._see("emb_row", w["emb.weight"][np.asarray(tokens, dtype=np.int64)])
         x = _ln_rows(w["emb.weight"][np.asarray(tokens, dtype=np.int64)], w["blocks.0.ln0.weight"], w["blocks.0.ln0.bias"])
         v_first = None
         for l in range(i.num_layer):
             p = f"blocks.{l}."
+            self._l = l
             xx = _ln_rows(x, w[p + "ln1.weight"], w[p + "ln1.bias"])
             sx = states[:, l, 0].copy()
             S = states[:, l, 1:1 + N].reshape(B, N, H, N).transpose(0, 2, 1, 3).copy()      # [B, H, i, j]
@@ -498,7 +528,7 @@ class RwkvRefBatch(RwkvRef):
         if not want_logits:
             return None
         xo = _ln_rows(x, w["ln_out.weight"], w["ln_out.bias"])
-        return (xo @ w["head.weight"].T).astype(np.float32)
+        return (self._op(xo) @ w["head.weight"].T).astype(np.float32)
 
     def _bgn(self, x, wt, b):                                    # GroupNorm over each head, x [B, C]
         B = x.shape[0]
@@ -520,7 +550,7 @@ class RwkvRefBatch(RwkvRef):
 
     def _batt5(self, p, xx, sx, S):
         w = self.w
-        mix = lambda n: xx * w[p + f"att.time_mix_{n}"].reshape(-1) + sx * (1 - w[p + f"att.time_mix_{n}"].reshape(-1))
+        mix = lambda n: self._op(xx * w[p + f"att.time_mix_{n}"].reshape(-1) + sx * (1 - w[p + f"att.time_mix_{n}"].reshape(-1)))
         r = mix("r") @ w[p + "att.receptance.weight"].T
         k = mix("k") @ w[p + "att.key.weight"].T
         v = mix("v") @ w[p + "att.value.weight"].T
@@ -528,23 +558,25 @@ class RwkvRefBatch(RwkvRef):
         g = g * _sigmoid(g)
         wdec = np.exp(-np.exp(w[p + "att.time_decay"].reshape(-1)))
         wdec = np.broadcast_to(wdec, r.shape)
+        self._see("wdec", wdec)
         out, S = self._bwkv56(r, k, v, wdec, w[p + "att.time_first"].reshape(-1), S)
+        self._see("wkv_out", out)
         y = self._bgn(out, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"]) * g
-        return y @ w[p + "att.output.weight"].T, S
+        return self._op(y) @ w[p + "att.output.weight"].T, S
 
     def _batt6(self, p, xx, sx, S):
         w = self.w
         B = xx.shape[0]
         dx = sx - xx
         z = xx + dx * w[p + "att.time_mix_x"].reshape(-1)
-        m = np.tanh(z @ w[p + "att.time_mix_w1"].T)
+        m = np.tanh(self._op(z) @ w[p + "att.time_mix_w1"].T)
         w2 = w[p + "att.time_mix_w2"]
         Dm = w2.shape[2]
         m = m.reshape(B, 5, Dm)
         xs = {}
         for c, n in enumerate("wkvrg"):
             mc = m[:, c] @ w2[c].T
-            xs[n] = xx + dx * (w[p + f"att.time_mix_{n}"].reshape(-1) + mc)
+            xs[n] = self._op(xx + dx * (w[p + f"att.time_mix_{n}"].reshape(-1) + mc))
         r = xs["r"] @ w[p + "att.receptance.weight"].T
         k = xs["k"] @ w[p + "att.key.weight"].T
         v = xs["v"] @ w[p + "att.value.weight"].T
@@ -553,9 +585,11 @@ class RwkvRefBatch(RwkvRef):
         td = np.tanh(xs["w"] @ w[p + "att.time_decay_w1"].T)
         d = w[p + "att.time_decay"].reshape(-1) + td @ w[p + "att.time_decay_w2"].T
         wdec = np.exp(-np.exp(d.astype(np.float32)))
+        self._see("wdec", wdec)
         out, S = self._bwkv56(r, k, v, wdec, w[p + "att.time_first"].reshape(-1), S)
+        self._see("wkv_out", out)
         y = self._bgn(out, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"]) * g
-        return y @ w[p + "att.output.weight"].T, S
+        return self._op(y) @ w[p + "att.output.weight"].T, S
 
     def _bffn56(self, p, xx, sx):
         w = self.w
@@ -567,46 +601,52 @@ class RwkvRefBatch(RwkvRef):
             dx = sx - xx
             xk = xx + dx * w[p + "ffn.time_mix_k"].reshape(-1)
             xr = xx + dx * w[p + "ffn.time_mix_r"].reshape(-1)
-        r = _sigmoid(xr @ w[p + "ffn.receptance.weight"].T)
-        k = np.maximum(xk @ w[p + "ffn.key.weight"].T, 0) ** 2
-        return r * (k @ w[p + "ffn.value.weight"].T)
+        r = _sigmoid(self._op(xr) @ w[p + "ffn.receptance.weight"].T)
+        k = np.maximum(self._op(xk) @ w[p + "ffn.key.weight"].T, 0) ** 2
+        self._see("relu2", k)
+        return r * (self._op(k) @ w[p + "ffn.value.weight"].T)
 
     def _batt7(self, p, l, xx, sx, S, v_first):
         w = self.w
         B = xx.shape[0]
         H, N = self.info.num_head, self.info.head_size
         dx = sx - xx
-        xm = {n: xx + dx * w[p + f"att.x_{n}"].reshape(-1) for n in "rwkvag"}
+        xm = {n: self._op(xx + dx * w[p + f"att.x_{n}"].reshape(-1)) for n in "rwkvag"}
         r = xm["r"] @ w[p + "att.receptance.weight"].T
         k = xm["k"] @ w[p + "att.key.weight"].T
         v = xm["v"] @ w[p + "att.value.weight"].T
         wd = np.tanh(xm["w"] @ w[p + "att.w1"].T) @ w[p + "att.w2"].T
-        a = _sigmoid(w[p + "att.a0"].reshape(-1) + (xm["a"] @ w[p + "att.a1"].T) @ w[p + "att.a2"].T)
+        a = _sigmoid(w[p + "att.a0"].reshape(-1) + self._op(xm["a"] @ w[p + "att.a1"].T) @ w[p + "att.a2"].T)
         g = _sigmoid(xm["g"] @ w[p + "att.g1"].T) @ w[p + "att.g2"].T
         kk = (k * w[p + "att.k_k"].reshape(-1)).reshape(B, H, N)
-        kk = kk / np.maximum(np.sqrt((kk * kk).sum(axis=2, keepdims=True)), np.float32(1e-12))
+        ss = (kk * kk).sum(axis=2, keepdims=True)
+        self._see("kappa_ss", ss)
+        kk = kk / np.maximum(np.sqrt(ss), np.float32(1e-12))
         kk = kk.reshape(B, -1)
         k = k * (1 + (a - 1) * w[p + "att.k_a"].reshape(-1))
         if l == 0:
             v_first = v
         else:
-            v = v + (v_first - v) * _sigmoid(w[p + "att.v0"].reshape(-1) + (xm["v"] @ w[p + "att.v1"].T) @ w[p + "att.v2"].T)
+            v = v + (v_first - v) * _sigmoid(w[p + "att.v0"].reshape(-1) + self._op(xm["v"] @ w[p + "att.v1"].T) @ w[p + "att.v2"].T)
         wdec = np.exp(np.float32(-0.606531) * _sigmoid((w[p + "att.w0"].reshape(-1) + wd).astype(np.float32)))
+        self._see("wdec", wdec)
         rh, kh, vh, kkh, ah, wh = (t.reshape(B, H, N) for t in (r, k, v, kk, a, wdec))
         sa = np.einsum("bhij,bhj->bhi", S, -kkh)
         S = S * wh[:, :, None, :] + sa[:, :, :, None] * (kkh * ah)[:, :, None, :] + vh[:, :, :, None] * kh[:, :, None, :]
         S = S.astype(np.float32)
         out = np.einsum("bhij,bhj->bhi", S, rh).reshape(B, -1)
+        self._see("wkv_out", out)
         y = self._bgn(out, w[p + "att.ln_x.weight"], w[p + "att.ln_x.bias"])
         bonus = (rh * kh * w[p + "att.r_k"].reshape(1, H, N)).sum(axis=2, keepdims=True) * vh
         y = y + bonus.reshape(B, -1)
-        return (y * g) @ w[p + "att.output.weight"].T, S, v_first
+        return self._op(y * g) @ w[p + "att.output.weight"].T, S, v_first
 
     def _bffn7(self, p, xx, sx):
         w = self.w
         xk = xx + (sx - xx) * w[p + "ffn.x_k"].reshape(-1)
-        k = np.maximum(xk @ w[p + "ffn.key.weight"].T, 0) ** 2
-        return k @ w[p + "ffn.value.weight"].T
+        k = np.maximum(self._op(xk) @ w[p + "ffn.key.weight"].T, 0) ** 2
+        self._see("relu2", k)
+        return self._op(k) @ w[p + "ffn.value.weight"].T
 
     def init_states(self, B: int) -> np.ndarray:
         i = self.info
