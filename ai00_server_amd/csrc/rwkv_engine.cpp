@@ -13,15 +13,17 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <set>
 #include <memory>
 #include <mutex>
+#include <numeric>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/rwkv_abi.h"
 #include "gemm_plan.h"
+#include "graph_cache.h"
 #include "safetensors.hpp"
 
 using namespace rwkv;
@@ -58,6 +60,30 @@ static rwkv_status guard(F &&f) {
         return std::strncmp(e.what(), "safetensors:", 12) == 0 ? RWKV_ERR_FORMAT : RWKV_ERR_INVALID;
     }
 }
+
+// The one place a stream is put into capture mode: what `enqueue` puts on `st` becomes an executable graph.  If `enqueue` throws, the capture is
+// ended and the half-built graph destroyed before the exception goes on, so the stream is never left capturing.
+template <class F>
+static hipGraphExec_t capture(hipStream_t st, F &&enqueue) {
+    hipGraph_t g = nullptr;
+    HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    try {
+        enqueue();
+    } catch (...) {
+        (void)hipStreamEndCapture(st, &g);
+        if (g) (void)hipGraphDestroy(g);
+        throw;
+    }
+    HIP_CHECK(hipStreamEndCapture(st, &g));
+    hipGraphExec_t exec = nullptr;
+    const hipError_t err = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    HIP_CHECK(err);
+    return exec;
+}
+struct GraphExecDeleter { void operator()(hipGraphExec_t x) const { if (x) (void)hipGraphExecDestroy(x); } };
+template <class Key>
+using GraphCacheOf = GraphCache<Key, hipGraphExec_t, GraphExecDeleter>;
 
 // ------------------------------------------------------------------------------------------------
 // model info (Loader::info, lib.rs:587)
@@ -202,7 +228,26 @@ struct StepPlan {
     std::vector<int> token, slot, prev, last, seq_slot, seq_begin, seq_len, out_rows;
     std::vector<int> slot_consumed, slot_out_begin, slot_out_rows;   // per slot
     uint64_t id = 0;                // plans with the same id have identical metadata apart from the token ids
+    int max_rows() const { return seq_len.empty() ? 0 : *std::max_element(seq_len.begin(), seq_len.end()); }   // most rows any sequence has
 };
+
+// Row metadata of a step: the one description of d_meta, and of each pinned staging buffer that is copied over it whole.
+struct MetaView {
+    int *token, *slot, *prev, *last, *out_rows;                 // [chunk] each: per row (out_rows: the rows that reach the head)
+    int *seq_slot, *seq_begin, *seq_len;                        // [max_batch] each: per sequence of the step
+    static size_t words(int chunk, int B) { return (size_t)chunk * 5 + (size_t)B * 3 + 16; }
+    MetaView(int *base = nullptr, int chunk = 0, int B = 0)
+        : token(base), slot(token + chunk), prev(slot + chunk), last(prev + chunk), out_rows(last + chunk),
+          seq_slot(out_rows + chunk), seq_begin(seq_slot + B), seq_len(seq_begin + B) {}
+};
+
+// rwkv_infer_sample's pinned block: per-row parameters in [chunk], sparse logit adjustments in [ADJ_CAP] x 3, 8 bytes per row out [chunk] x 2
+// (the kernels read the rows and write the outputs in place, through the block's device-visible alias: dv_*)
+struct SampStage { SampleRow *rows; int *adj_row, *adj_tok; float *adj_val; int *out_tok; float *out_prob; const SampleRow *dv_rows; int *dv_out_tok; float *dv_out_prob; };
+
+// which sampler kernels a set of rows needs, as bits (also the last word of a generation graph's key)
+enum : unsigned { NEEDS_NT = 1, NEEDS_MIRO = 2 };               // nucleus / typical, mirostat
+static unsigned sampler_need(int kind) { return kind == RWKV_SAMPLER_MIROSTAT ? NEEDS_MIRO : NEEDS_NT; }
 
 struct rwkv_dstate {
     int device = 0;
@@ -229,7 +274,7 @@ struct rwkv_engine {
     hipStream_t s_copy = nullptr;                              // rwkv_state_back_layer_async: pack + device-to-host copy beside the compute stream
     hipEvent_t ev_copy_a = nullptr, ev_copy_b = nullptr;
     float *emb_stage = nullptr;                                // [max_batch][64 * C]: one packed layer slice per slot
-    std::vector<void *> allocs;
+    std::vector<void *> allocs, host_allocs;                   // dalloc / hostalloc
     std::map<std::string, DMat> mats;
     std::map<std::string, float *> vecs;
     std::map<std::string, _Float16 *> raws;
@@ -259,6 +304,7 @@ struct rwkv_engine {
     long pstride = 0;
     // row meta (device + pinned host)
     int *d_meta = nullptr, *h_meta = nullptr;                  // h_meta: a ring of META_RING pinned staging buffers (state-only steps are not waited for)
+    MetaView dm;                                               // the sections of d_meta
     static constexpr int META_RING = 4;
     hipEvent_t meta_ev[META_RING] = {nullptr, nullptr, nullptr, nullptr};
     int meta_next = 0;
@@ -274,7 +320,7 @@ struct rwkv_engine {
     float *d_adj_val = nullptr;
     unsigned char *d_allow = nullptr, *h_allow = nullptr;   // formatter masks of the rows that carry one: [n][V] bytes, pinned mirror
     int *d_allow_row = nullptr;
-    unsigned char *h_samp = nullptr;
+    SampStage samp{};
     static constexpr size_t ADJ_CAP = 1 << 16;
     float *d_amax_v = nullptr;
     size_t hist_cap = 0;
@@ -285,12 +331,9 @@ struct rwkv_engine {
     int prof_n[RWKV_PROFILE_FAMILIES] = {0};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
-    // graph cache for decode-shaped steps
-    struct GraphEntry { hipGraphExec_t exec = nullptr; uint64_t used = 0; };
-    uint64_t graph_clock = 0;
-    std::map<uint64_t, GraphEntry> graphs;
-    std::map<int, hipGraphExec_t> greedy_graphs;               // rwkv_decode_greedy: step + arg-max feedback, keyed by slot count
-    std::set<uint64_t> graph_seen;
+    // captured steps (graph_cache.h holds the policy: captured on second sight, least recently used evicted)
+    GraphCacheOf<uint64_t> graphs{64, {}};                     // run_plan: keyed by step shape
+    std::optional<GraphCacheOf<int>> greedy_graphs;            // rwkv_decode_greedy: step + arg-max feedback, keyed by slot count; room for every count
     // device-resident sampled generation (rwkv_gen_*): per-slot contexts, dense penalty / bias rows, the step's SampleRow array and the
     // output ring live on the device; everything is allocated by the first rwkv_gen_arm
     static constexpr int GEN_RING_STEPS = 1024;                  // steps one enqueue covers (longer runs are split)
@@ -306,8 +349,7 @@ struct rwkv_engine {
     int *d_gen_tok = nullptr, *d_gen_runstep = nullptr;
     int *d_gen_held = nullptr;                                   // [max_batch] the token a running slot consumes next (its last emitted one)
     unsigned *d_gen_out = nullptr, *h_gen_out = nullptr;         // [2][GEN_RING_STEPS][max_batch]: tokens, then probabilities
-    std::map<std::vector<uint64_t>, GraphEntry> gen_graphs;      // one captured step per set of rows (slot mask + sampler kernels it needs)
-    std::set<std::vector<uint64_t>> gen_seen;
+    GraphCacheOf<std::vector<uint64_t>> gen_graphs{64, {}};      // one captured step per set of rows (slot mask + sampler kernels it needs)
     void gen_init();
     void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt);
     void gen_disarm_slot(int slot) {
@@ -318,11 +360,12 @@ struct rwkv_engine {
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
     GenArgs gen_args(int n_rows) const;
-    void gen_step(const StepPlan &pl, bool any_nt, bool any_miro);
+    unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind); return k; }
+    void gen_sample(const GenArgs &a, unsigned needs);
+    void gen_step(const StepPlan &pl, unsigned needs);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
-    bool use_graphs = true;
     Knobs kn;                                                    // experiment switches, frozen at creation (rwkv_kernels.h)
 
     template <class T>
@@ -330,6 +373,13 @@ struct rwkv_engine {
         void *p = nullptr;
         HIP_CHECK(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 16)));
         allocs.push_back(p);
+        return (T *)p;
+    }
+    template <class T>
+    T *hostalloc(size_t n, unsigned flags = hipHostMallocDefault) {   // pinned; freed by the destructor like dalloc's
+        void *p = nullptr;
+        HIP_CHECK(hipHostMalloc(&p, n * sizeof(T), flags));
+        host_allocs.push_back(p);
         return (T *)p;
     }
     Opd alloc_opd(int ld) {
@@ -348,20 +398,11 @@ struct rwkv_engine {
         if (s_main) (void)hipStreamSynchronize(s_main);
         if (s_soft) (void)hipStreamSynchronize(s_soft);
         if (s_copy) (void)hipStreamSynchronize(s_copy);
-        for (auto &g : graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-        for (auto &g : greedy_graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
-        for (auto &g : gen_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-        if (h_gen_out) (void)hipHostFree(h_gen_out);
+        graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
-        if (slab_host) (void)hipHostFree(slab_host);
-        if (logits_host) (void)hipHostFree(logits_host);
-        if (soft_host) (void)hipHostFree(soft_host);
-        if (h_meta) (void)hipHostFree(h_meta);
+        for (void *p : host_allocs) (void)hipHostFree(p);
         for (auto ev : meta_ev) if (ev) (void)hipEventDestroy(ev);
-        if (h_tok) (void)hipHostFree(h_tok);
-        if (h_samp) (void)hipHostFree(h_samp);
-        if (h_allow) (void)hipHostFree(h_allow);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (s_main) (void)hipStreamDestroy(s_main);
@@ -421,8 +462,14 @@ struct rwkv_engine {
     void run_plan(const StepPlan &pl);
     void infer_sample(const rwkv_slot_input *in, const rwkv_sample_params *sp, uint32_t *out_tokens, float *out_probs,
                       uint8_t *emitted, size_t *n_consumed);
-    RowMeta meta_ptrs(int T) const;
-    const int *d_seq_slot, *d_seq_begin, *d_seq_len, *d_out_rows;
+    // the input of a step in which each of `slots` feeds one token and asks for its row (`Last`); tokens[i] belongs to slots[i], and steps whose
+    // ids come from the device (the feedback buffer, held tokens) pass nullptr: the plan then carries a zero nobody reads
+    std::vector<rwkv_slot_input> one_token_each(const std::vector<int> &slots, const uint32_t *tokens) const {
+        static const uint32_t none = 0;
+        std::vector<rwkv_slot_input> in((size_t)max_batch, rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0});
+        for (size_t i = 0; i < slots.size(); ++i) in[(size_t)slots[i]] = rwkv_slot_input{tokens ? tokens + i : &none, 1, RWKV_OPTION_LAST, 0};
+        return in;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -804,7 +851,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     HIP_CHECK(hipMemset(wkv, 0, (size_t)max_batch * wkv_slot_stride * 4));
     const size_t slab = (size_t)L * 66 * C;
     slab_dev = dalloc<float>(slab);
-    HIP_CHECK(hipHostMalloc((void **)&slab_host, slab * 4, hipHostMallocDefault));
+    slab_host = hostalloc<float>(slab);
 
     const size_t TC = (size_t)chunk * C;
     pstride = (long)TC;
@@ -823,22 +870,31 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     opM = alloc_opd(std::max(16, info.version == 6 ? 5 * Dm : 16));
     for (auto &o : opL) o = alloc_opd(std::max(16, Dl));
     logits = dalloc<float>((size_t)chunk * V);
-    HIP_CHECK(hipHostMalloc((void **)&logits_host, (size_t)chunk * V * 4, hipHostMallocDefault));
-    meta_cap = (size_t)chunk * 5 + (size_t)max_batch * 3 + 16;
+    logits_host = hostalloc<float>((size_t)chunk * V);
+    meta_cap = MetaView::words(chunk, max_batch);
     d_meta = dalloc<int>(meta_cap);
-    HIP_CHECK(hipHostMalloc((void **)&h_meta, meta_cap * 4 * META_RING, hipHostMallocDefault));
+    dm = MetaView(d_meta, chunk, max_batch);
+    h_meta = hostalloc<int>(meta_cap * META_RING);
     for (auto &ev : meta_ev) HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIP_CHECK(hipHostMalloc((void **)&h_tok, (size_t)max_batch * 4, hipHostMallocMapped | hipHostMallocCoherent));   // uncached on the device: always the host's latest store
+    h_tok = hostalloc<int>((size_t)max_batch, hipHostMallocMapped | hipHostMallocCoherent);   // uncached on the device: always the host's latest store
     HIP_CHECK(hipHostGetDevicePointer((void **)&dv_tok, h_tok, 0));
     d_tok_feedback = dalloc<int>(chunk);
     soft_rows_cap = (size_t)std::max(1, max_batch);
     soft_in = dalloc<float>(soft_rows_cap * V);
     soft_out = dalloc<float>(soft_rows_cap * V);
-    HIP_CHECK(hipHostMalloc((void **)&soft_host, soft_rows_cap * V * 4, hipHostMallocDefault));
+    soft_host = hostalloc<float>(soft_rows_cap * V);
     d_adj_row = dalloc<int>(ADJ_CAP); d_adj_tok = dalloc<int>(ADJ_CAP); d_adj_val = dalloc<float>(ADJ_CAP);
     d_allow = dalloc<unsigned char>((size_t)max_batch * V); d_allow_row = dalloc<int>(max_batch);
-    HIP_CHECK(hipHostMalloc((void **)&h_allow, (size_t)max_batch * V + (size_t)max_batch * 4 + 16, hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void **)&h_samp, (size_t)chunk * (sizeof(SampleRow) + 8) + ADJ_CAP * 12, hipHostMallocDefault));
+    h_allow = hostalloc<unsigned char>((size_t)max_batch * V + (size_t)max_batch * 4 + 16);
+    // the sampling block: the offsets that place its sections also size it (the last section's end)
+    const size_t o_adj = (size_t)chunk * sizeof(SampleRow), o_out = o_adj + ADJ_CAP * 12, samp_bytes = o_out + (size_t)chunk * 8;
+    unsigned char *h_samp = hostalloc<unsigned char>(samp_bytes);
+    unsigned char *dv_samp = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer((void **)&dv_samp, h_samp, 0));
+    int *adj = (int *)(h_samp + o_adj), *out = (int *)(h_samp + o_out), *dv_out = (int *)(dv_samp + o_out);
+    samp = SampStage{(SampleRow *)h_samp, adj, adj + ADJ_CAP, (float *)(adj + 2 * ADJ_CAP), out, (float *)(out + chunk),
+                     (const SampleRow *)dv_samp, dv_out, (float *)(dv_out + chunk)};
+    greedy_graphs.emplace((size_t)max_batch, GraphExecDeleter{});
     d_amax_v = dalloc<float>((size_t)chunk * 32);
     d_amax_i = dalloc<int>((size_t)chunk * 32);
     HIP_CHECK(hipDeviceSynchronize());
@@ -967,33 +1023,22 @@ void rwkv_engine::plan_step(const rwkv_slot_input *in, StepPlan &pl) {
     for (int b = 0; b < B; ++b) { last_ntok[b] = in[b].n_tokens; last_opt[b] = in[b].option; }
 }
 
-// meta layout in d_meta: token[chunk] slot[chunk] prev[chunk] last[chunk] out_rows[chunk] seq_slot[B] seq_begin[B] seq_len[B]
-RowMeta rwkv_engine::meta_ptrs(int) const {
-    RowMeta rm;
-    rm.dense = 0;
-    rm.token = d_meta;
-    rm.slot = d_meta + chunk;
-    rm.prev = d_meta + 2 * chunk;
-    rm.last = d_meta + 3 * chunk;
-    return rm;
-}
-
 void rwkv_engine::upload_plan(const StepPlan &pl) {
     // a staging buffer is free again when the copy that read it has run (a step that emits nothing returns without waiting for the device,
     // so the previous copies may still be queued: four buffers, each guarded by the event recorded behind its copy)
     const int slot = meta_next;
     meta_next = (meta_next + 1) % META_RING;
     HIP_CHECK(hipEventSynchronize(meta_ev[slot]));
-    int *h = h_meta + (size_t)slot * meta_cap;
-    std::memcpy(h, pl.token.data(), pl.T * 4);
-    std::memcpy(h + chunk, pl.slot.data(), pl.T * 4);
-    std::memcpy(h + 2 * chunk, pl.prev.data(), pl.T * 4);
-    std::memcpy(h + 3 * chunk, pl.last.data(), pl.T * 4);
-    std::memcpy(h + 4 * chunk, pl.out_rows.data(), pl.n_out * 4);
-    std::memcpy(h + 5 * chunk, pl.seq_slot.data(), pl.n_seq * 4);
-    std::memcpy(h + 5 * chunk + max_batch, pl.seq_begin.data(), pl.n_seq * 4);
-    std::memcpy(h + 5 * chunk + 2 * max_batch, pl.seq_len.data(), pl.n_seq * 4);
-    HIP_CHECK(hipMemcpyAsync(d_meta, h, meta_cap * 4, hipMemcpyHostToDevice, s_main));
+    const MetaView h(h_meta + (size_t)slot * meta_cap, chunk, max_batch);
+    std::memcpy(h.token, pl.token.data(), pl.T * 4);
+    std::memcpy(h.slot, pl.slot.data(), pl.T * 4);
+    std::memcpy(h.prev, pl.prev.data(), pl.T * 4);
+    std::memcpy(h.last, pl.last.data(), pl.T * 4);
+    std::memcpy(h.out_rows, pl.out_rows.data(), pl.n_out * 4);
+    std::memcpy(h.seq_slot, pl.seq_slot.data(), pl.n_seq * 4);
+    std::memcpy(h.seq_begin, pl.seq_begin.data(), pl.n_seq * 4);
+    std::memcpy(h.seq_len, pl.seq_len.data(), pl.n_seq * 4);
+    HIP_CHECK(hipMemcpyAsync(d_meta, h.token, meta_cap * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipEventRecord(meta_ev[slot], s_main));
     uploaded_id = pl.id;
 }
@@ -1003,11 +1048,7 @@ void rwkv_engine::upload_plan(const StepPlan &pl) {
 // ------------------------------------------------------------------------------------------------
 void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bool dense) {
     const int C = info.num_emb, V = info.num_vocab, H = info.num_head, L = info.num_layer;
-    RowMeta rm = meta_ptrs(T);
-    rm.token = d_token;
-    rm.dense = dense ? 1 : 0;
-    const int *seq_slot = d_meta + 5 * chunk, *seq_begin = seq_slot + max_batch, *seq_len = seq_begin + max_batch;
-    const int *out_rows = d_meta + 4 * chunk;
+    const RowMeta rm{d_token, dm.slot, dm.prev, dm.last, dense ? 1 : 0};
 
     float *cur = xA, *oth = xB;
     int np = 0;
@@ -1135,7 +1176,7 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
         {
             WkvArgs k{};
             k.version = info.version; k.H = H; k.C = C; k.n_seq = n_seq;
-            k.seq_slot = seq_slot; k.seq_begin = seq_begin; k.seq_len = seq_len; k.dense = dense ? 1 : 0;
+            k.seq_slot = dm.seq_slot; k.seq_begin = dm.seq_begin; k.seq_len = dm.seq_len; k.dense = dense ? 1 : 0;
             k.state = wkv + (long)l * H * 4096; k.slot_stride = wkv_slot_stride;
             k.r = fr; k.k = fk; k.v = fv; k.g = fg;
             k.wdec_or_decay = w.wdec; k.u = w.u; k.td = ftd; k.D2 = w.D2; k.Dd = Dd;
@@ -1185,7 +1226,7 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
     if (n_out > 0) {
         Opd aO = opO;
         if (!wide(CLS_HEAD)) aO.lo = nullptr;
-        LnOutArgs o{cur, P, np, pstride, lnow, lnob, dense ? nullptr : out_rows, aO.hi, aO.lo, C, C};
+        LnOutArgs o{cur, P, np, pstride, lnow, lnob, dense ? nullptr : dm.out_rows, aO.hi, aO.lo, C, C};
         launch(FAM_ROW, [&] { launch_ln_out(o, n_out, s_main); });
         std::vector<ProbSpec> ps(1);
         ps[0].W = head; ps[0].x = aO; ps[0].out = logits; ps[0].ldo = V;
@@ -1200,54 +1241,21 @@ void rwkv_engine::run_plan(const StepPlan &pl) {
     // Dense steps read their token ids from pinned host memory through its device-visible alias (one uncached read per row in
     // the embedding kernel) and nothing else changes between two steps of the same plan, so a repeated dense plan needs no
     // host-to-device copy at all; everything else uploads its metadata.
-    const int *tok_ptr = d_meta;
-    if (pl.dense) {
-        std::memcpy(h_tok, pl.token.data(), (size_t)pl.T * 4);
-        tok_ptr = dv_tok;
-        if (pl.id != uploaded_id) upload_plan(pl);
-    } else {
-        upload_plan(pl);
-    }
-    step_max_rows = 0;
-    for (int n : pl.seq_len) step_max_rows = std::max(step_max_rows, n);
+    if (pl.dense) std::memcpy(h_tok, pl.token.data(), (size_t)pl.T * 4);
+    if (!pl.dense || pl.id != uploaded_id) upload_plan(pl);
+    const int *tok_ptr = pl.dense ? dv_tok : dm.token;
+    step_max_rows = pl.max_rows();
     const bool short_rows = step_max_rows <= 8;                  // picks the WKV form: part of the graph's identity
     const uint64_t key = ((uint64_t)pl.dense << 63) | ((uint64_t)short_rows << 62) | ((uint64_t)pl.T << 40) | ((uint64_t)pl.n_seq << 20) | (uint64_t)pl.n_out;
-    if (use_graphs && !profiling) {
-        auto it = graphs.find(key);
-        // a shape is captured the SECOND time it shows up: decode-shaped steps repeat at once, while the one-off shapes of
-        // prefill tails would pay capture + instantiation (milliseconds) for a single replay and churn the cache
-        if (it == graphs.end() && graph_seen.insert(key).second) {
-            if (graph_seen.size() > 4096) graph_seen.clear();
-            run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense);
-            return;
-        }
-        if (it == graphs.end()) {
-            hipGraph_t g = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
-            try {
-                run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense);
-            } catch (...) {
-                (void)hipStreamEndCapture(s_main, &g);
-                if (g) (void)hipGraphDestroy(g);
-                throw;
-            }
-            HIP_CHECK(hipStreamEndCapture(s_main, &g));
-            GraphEntry ge;
-            HIP_CHECK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            if (graphs.size() >= 64) {                             // full: the least recently replayed shape goes, the rest stay warm
-                auto victim = graphs.begin();
-                for (auto o = graphs.begin(); o != graphs.end(); ++o) if (o->second.used < victim->second.used) victim = o;
-                (void)hipGraphExecDestroy(victim->second.exec);
-                graphs.erase(victim);
-            }
-            it = graphs.emplace(key, ge).first;
-        }
-        it->second.used = ++graph_clock;
-        HIP_CHECK(hipGraphLaunch(it->second.exec, s_main));
-    } else {
-        run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense);
+    auto enqueue = [&] { run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense); };
+    if (profiling) return enqueue();                            // timed launch by launch: event pairs, no graph
+    hipGraphExec_t *exec = graphs.find(key);
+    if (!exec) {
+        // a shape's first step runs directly (graph_cache.h says why; the launchers' one-time attribute calls also happen here, outside a capture)
+        if (!graphs.should_capture(key)) return enqueue();
+        exec = &graphs.insert(key, capture(s_main, enqueue));
     }
+    HIP_CHECK(hipGraphLaunch(*exec, s_main));
 }
 
 void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_params *sp, uint32_t *out_tokens, float *out_probs,
@@ -1266,12 +1274,8 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
     plan_step(last.data(), pl);
     if (pl.T == 0) return;
     // pack per-row sampler params + sparse adjustments (rows are in out_rows order == ascending slot order)
-    SampleRow *hs = (SampleRow *)h_samp;
-    int *h_row = (int *)(h_samp + (size_t)chunk * sizeof(SampleRow));
-    int *h_tok = h_row + ADJ_CAP;
-    float *h_val = (float *)(h_tok + ADJ_CAP);
     size_t nadj = 0;
-    bool any_nt = false, any_miro = false;
+    unsigned needs = 0;
     int n_allow = 0;
     int *h_allow_row = (int *)(h_allow + (size_t)max_batch * info.num_vocab);
     for (int b = 0; b < max_batch; ++b) {
@@ -1283,30 +1287,22 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
         if (p.n_adj && (!p.adj_tokens || !p.adj_values)) throw RwkvError(RWKV_ERR_INVALID, "null adjustment arrays");
         if (nadj + p.n_adj > ADJ_CAP) throw RwkvError(RWKV_ERR_INVALID, "too many logit adjustments");
         if (p.kind < RWKV_SAMPLER_NUCLEUS || p.kind > RWKV_SAMPLER_MIROSTAT) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unknown sampler kind");
-        if (p.kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true;
-        hs[r] = SampleRow{p.top_p, p.top_k, p.temperature, p.uniform, p.kind, p.tau};
+        needs |= sampler_need(p.kind);
+        samp.rows[r] = SampleRow{p.top_p, p.top_k, p.temperature, p.uniform, p.kind, p.tau};
         if (p.allow) {                                             // formatter mask: staged row by row, one H2D copy for all
             std::memcpy(h_allow + (size_t)n_allow * info.num_vocab, p.allow, (size_t)info.num_vocab);
             h_allow_row[n_allow++] = r;
         }
-        for (size_t i = 0; i < p.n_adj; ++i, ++nadj) { h_row[nadj] = r; h_tok[nadj] = (int)p.adj_tokens[i]; h_val[nadj] = p.adj_values[i]; }
+        for (size_t i = 0; i < p.n_adj; ++i, ++nadj) { samp.adj_row[nadj] = r; samp.adj_tok[nadj] = (int)p.adj_tokens[i]; samp.adj_val[nadj] = p.adj_values[i]; }
     }
-    // The sampler kernel reads its per-row parameters from, and writes its 8 bytes per row to, pinned host memory directly
-    // (device-visible mapping of h_samp): no copy operation sits in front of the step or between it and the host seeing its
-    // tokens.  (Measured against an H2D copy of the parameters ahead of the step: no difference beyond run-to-run noise.)
-    const SampleRow *rows_ptr = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer((void **)&rows_ptr, hs, 0));
+    // The sampler kernel reads its per-row parameters from, and writes its 8 bytes per row to, pinned host memory directly (samp.dv_*): no copy sits
+    // in front of the step or between it and the host seeing its tokens.  (Measured against an H2D copy of the parameters: no difference beyond noise.)
     run_plan(pl);
     if (pl.n_out > 0) {
-        int *ht = (int *)(h_samp + (size_t)chunk * sizeof(SampleRow) + (size_t)ADJ_CAP * 12);
-        float *hp = (float *)(ht + chunk);
-        int *dv_out_tok = nullptr;
-        HIP_CHECK(hipHostGetDevicePointer((void **)&dv_out_tok, ht, 0));
-        float *dv_prob = (float *)(dv_out_tok + chunk);
         if (nadj) {
-            HIP_CHECK(hipMemcpyAsync(d_adj_row, h_row, nadj * 4, hipMemcpyHostToDevice, s_main));
-            HIP_CHECK(hipMemcpyAsync(d_adj_tok, h_tok, nadj * 4, hipMemcpyHostToDevice, s_main));
-            HIP_CHECK(hipMemcpyAsync(d_adj_val, h_val, nadj * 4, hipMemcpyHostToDevice, s_main));
+            HIP_CHECK(hipMemcpyAsync(d_adj_row, samp.adj_row, nadj * 4, hipMemcpyHostToDevice, s_main));
+            HIP_CHECK(hipMemcpyAsync(d_adj_tok, samp.adj_tok, nadj * 4, hipMemcpyHostToDevice, s_main));
+            HIP_CHECK(hipMemcpyAsync(d_adj_val, samp.adj_val, nadj * 4, hipMemcpyHostToDevice, s_main));
             launch_logit_adjust(logits, info.num_vocab, d_adj_row, d_adj_tok, d_adj_val, (int)nadj, s_main);
         }
         if (n_allow) {                                             // after the adjustments: -inf + bias stays -inf (run.rs:676-683)
@@ -1314,13 +1310,13 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
             HIP_CHECK(hipMemcpyAsync(d_allow_row, h_allow_row, (size_t)n_allow * 4, hipMemcpyHostToDevice, s_main));
             launch_logit_mask(logits, info.num_vocab, d_allow_row, d_allow, n_allow, s_main);
         }
-        launch_nucleus(logits, pl.n_out, info.num_vocab, rows_ptr, any_nt, any_miro, dv_out_tok, dv_prob, s_main);
+        launch_nucleus(logits, pl.n_out, info.num_vocab, samp.dv_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, samp.dv_out_tok, samp.dv_out_prob, s_main);
         HIP_CHECK(hipStreamSynchronize(s_main));
         for (int b = 0; b < max_batch; ++b) {
             if (pl.slot_out_rows[b] == 0) continue;
             const int r = pl.slot_out_begin[b];
-            if (out_tokens) out_tokens[b] = (uint32_t)ht[r];
-            if (out_probs) out_probs[b] = hp[r];
+            if (out_tokens) out_tokens[b] = (uint32_t)samp.out_tok[r];
+            if (out_probs) out_probs[b] = samp.out_prob[r];
             if (emitted) emitted[b] = 1;
         }
     } else {
@@ -1411,7 +1407,7 @@ void rwkv_engine::gen_init() {
     d_gen_prob = dalloc<float>((size_t)chunk);
     d_gen_runstep = dalloc<int>(1);
     d_gen_out = dalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
-    HIP_CHECK(hipHostMalloc((void **)&h_gen_out, 2 * (size_t)GEN_RING_STEPS * B * 4, hipHostMallocDefault));
+    h_gen_out = hostalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
     HIP_CHECK(hipMemset(d_gen_shadow, 0, B * sizeof(float *)));
     d_gen = dalloc<GenSlot>(B);                                   // last: marks the block as complete
     HIP_CHECK(hipMemset(d_gen, 0, B * sizeof(GenSlot)));
@@ -1467,7 +1463,7 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
 
 GenArgs rwkv_engine::gen_args(int n_rows) const {
     GenArgs a{};
-    a.slots = d_gen; a.row_slot = d_meta + chunk; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
+    a.slots = d_gen; a.row_slot = dm.slot; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
     a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
     a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
     a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = n_rows;
@@ -1476,74 +1472,42 @@ GenArgs rwkv_engine::gen_args(int n_rows) const {
     return a;
 }
 
-// one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, sampler state machine around nucleus_kernel
-void rwkv_engine::gen_step(const StepPlan &pl, bool any_nt, bool any_miro) {
-    run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    const GenArgs a = gen_args(pl.T);
+// the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
+void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
-    launch(FAM_SAMPLE, [&] { launch_nucleus(logits, pl.T, info.num_vocab, d_gen_rows, any_nt, any_miro, d_gen_tok, d_gen_prob, s_main); });
+    launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
 }
 
+// one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs) {
+    run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
+    gen_sample(gen_args(pl.T), needs);
+}
+
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
 void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
-    const int B = max_batch;
     if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
-    bool any_nt = false, any_miro = false;
-    for (int b : rows) { if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true; }
+    const unsigned needs = gen_needs(rows);
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
-    std::vector<rwkv_slot_input> in((size_t)B);
-    const uint32_t none = 0;
-    for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
-    for (int b : rows) in[(size_t)b] = rwkv_slot_input{&none, 1, RWKV_OPTION_LAST, 0};
     StepPlan pl;
-    plan_step(in.data(), pl);
+    plan_step(one_token_each(rows, nullptr).data(), pl);
     upload_plan(pl);
     step_max_rows = 1;
-    launch_gen_handover(d_tok_feedback, d_gen_held, d_meta + chunk, pl.T, false, s_main);
-    std::vector<uint64_t> key((size_t)(B + 63) / 64 + 1, 0);
+    launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
+    std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = (any_nt ? 1u : 0u) | (any_miro ? 2u : 0u);
+    key.back() = needs;
     int s0 = 0;
-    hipGraphExec_t exec = nullptr;
-    if (use_graphs) {
-        auto it = gen_graphs.find(key);
-        if (it == gen_graphs.end()) {
-            // a set of rows runs its first step directly (like run_plan: a one-off shape never pays capture + instantiation, and the
-            // launchers' one-time attribute calls happen outside a capture); the steps after it go through the captured graph
-            if (gen_seen.insert(key).second) { gen_step(pl, any_nt, any_miro); s0 = 1; }
-            if (s0 < n) {
-                hipGraph_t g = nullptr;
-                HIP_CHECK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
-                try {
-                    gen_step(pl, any_nt, any_miro);
-                } catch (...) {
-                    (void)hipStreamEndCapture(s_main, &g);
-                    if (g) (void)hipGraphDestroy(g);
-                    throw;
-                }
-                HIP_CHECK(hipStreamEndCapture(s_main, &g));
-                GraphEntry ge;
-                HIP_CHECK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
-                HIP_CHECK(hipGraphDestroy(g));
-                if (gen_graphs.size() >= 64) {                     // bounded like `graphs`: the least recently used set goes
-                    auto victim = gen_graphs.begin();
-                    for (auto o = gen_graphs.begin(); o != gen_graphs.end(); ++o) if (o->second.used < victim->second.used) victim = o;
-                    (void)hipGraphExecDestroy(victim->second.exec);
-                    gen_graphs.erase(victim);
-                }
-                if (gen_seen.size() > 4096) gen_seen.clear();
-                it = gen_graphs.emplace(key, ge).first;
-            }
-        }
-        if (it != gen_graphs.end()) { it->second.used = ++graph_clock; exec = it->second.exec; }
+    hipGraphExec_t *exec = gen_graphs.find(key);
+    if (!exec) {
+        // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs); }));
     }
-    for (int s = s0; s < n; ++s) {
-        if (exec) HIP_CHECK(hipGraphLaunch(exec, s_main));
-        else gen_step(pl, any_nt, any_miro);
-    }
-    launch_gen_handover(d_tok_feedback, d_gen_held, d_meta + chunk, pl.T, true, s_main);
+    for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
+    launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
 }
 
 // One MIXED step (rwkv_gen_arm_prompt): every slot of `dec` contributes its one feedback row, every slot of `pro` a share of what is
@@ -1553,34 +1517,23 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
 void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain) {
     const int B = max_batch;
     // dec.size() < chunk: gen_run checked, before its first step, that all live slots together fit one chunk
-    std::vector<rwkv_slot_input> in((size_t)B);
-    std::vector<char> is_dec((size_t)B, 0);
-    const uint32_t none = 0;
-    for (int b = 0; b < B; ++b) in[(size_t)b] = rwkv_slot_input{nullptr, 0, RWKV_OPTION_LAST, 0};
-    for (int b : dec) { in[(size_t)b] = rwkv_slot_input{&none, 1, RWKV_OPTION_LAST, 0}; is_dec[(size_t)b] = 1; }
+    std::vector<rwkv_slot_input> in = one_token_each(dec, nullptr);
     for (int b : pro) in[(size_t)b] = rwkv_slot_input{gen_prompt[(size_t)b].data() + gen_ppos[(size_t)b], gen_prompt_left(b), RWKV_OPTION_LAST, 0};
     StepPlan pl;
     plan_step(in.data(), pl);
-    for (int i = 0; i < pl.n_seq; ++i) if (is_dec[(size_t)pl.seq_slot[i]]) pl.token[(size_t)pl.seq_begin[i]] = -1;   // gen_tokens_kernel: held[slot]
-    bool any_nt = false, any_miro = false;
-    for (int b = 0; b < B; ++b) {
-        if (!pl.slot_out_rows[(size_t)b]) continue;
-        if (gen_host[(size_t)b].kind == RWKV_SAMPLER_MIROSTAT) any_miro = true; else any_nt = true;
-    }
+    for (int i = 0; i < pl.n_seq; ++i) if (!gen_prompt_left(pl.seq_slot[i])) pl.token[(size_t)pl.seq_begin[i]] = -1;   // a decode row; gen_tokens_kernel: held[slot]
+    std::vector<int> drawn;                                        // the slots that sample here: every decode row, every prompt that ends
+    for (int b = 0; b < B; ++b) if (pl.slot_out_rows[(size_t)b]) drawn.push_back(b);
     upload_plan(pl);
     uploaded_id = 0;                                               // the uploaded token row is not the plan's: nobody may skip an upload on it
-    launch(FAM_ROW, [&] { launch_gen_tokens(d_meta, d_meta + chunk, d_gen_held, d_gen_runstep, pl.T, s_main); });
-    step_max_rows = 0;
-    for (int n : pl.seq_len) step_max_rows = std::max(step_max_rows, n);
-    run_layers(pl.T, pl.n_seq, pl.n_out, d_meta, pl.dense);
+    launch(FAM_ROW, [&] { launch_gen_tokens(dm.token, dm.slot, d_gen_held, d_gen_runstep, pl.T, s_main); });
+    step_max_rows = pl.max_rows();
+    run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (pl.n_out > 0) {
         GenArgs a = gen_args(pl.n_out);
-        a.out_rows = d_meta + 4 * chunk;
+        a.out_rows = dm.out_rows;
         a.held = d_gen_held;
-        launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
-        launch(FAM_SAMPLE, [&] { launch_nucleus(logits, pl.n_out, info.num_vocab, d_gen_rows, any_nt, any_miro, d_gen_tok, d_gen_prob, s_main); });
-        launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
-        launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
+        gen_sample(a, gen_needs(drawn));
     }
     for (int b : dec) remain[(size_t)b] -= 1;
     for (int b : pro) {
@@ -2040,12 +1993,9 @@ rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *
         use_knobs(e->kn);
         for (int b = 0; b < n_slots; ++b) e->gen_disarm_slot(b);
         StepPlan pl;
-        std::vector<rwkv_slot_input> in(e->max_batch);
-        std::vector<uint32_t> tk(first_tokens, first_tokens + n_slots);
-        for (int b = 0; b < e->max_batch; ++b) {
-            in[b] = rwkv_slot_input{b < n_slots ? &tk[b] : nullptr, (size_t)(b < n_slots ? 1 : 0), RWKV_OPTION_LAST, 0};
-        }
-        e->plan_step(in.data(), pl);
+        std::vector<int> slots((size_t)n_slots);
+        std::iota(slots.begin(), slots.end(), 0);
+        e->plan_step(e->one_token_each(slots, first_tokens).data(), pl);
         e->upload_plan(pl);
         const size_t need = (size_t)n_steps * n_slots;
         if (need > e->hist_cap) {                                  // grow: the old buffer goes back (dalloc only frees at destroy)
@@ -2056,34 +2006,20 @@ rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *
             e->d_hist = e->dalloc<int>(need);
             e->hist_cap = need;
         }
-        HIP_CHECK(hipMemcpyAsync(e->d_tok_feedback, tk.data(), n_slots * 4, hipMemcpyHostToDevice, e->s_main));
+        HIP_CHECK(hipMemcpyAsync(e->d_tok_feedback, first_tokens, n_slots * 4, hipMemcpyHostToDevice, e->s_main));
         HIP_CHECK(hipStreamSynchronize(e->s_main));
         // one graph = one decode step + arg-max feeding the next step's token ids on the device; kept per slot count (the plan of
         // "slots 0..n-1, one token each" is always the same and every buffer it names lives as long as the engine), so a
         // serving loop that calls this repeatedly pays capture + instantiation (~0.7 ms for 260 nodes) once
-        hipGraphExec_t exec = nullptr;
-        auto cached = e->greedy_graphs.find(n_slots);
-        if (cached != e->greedy_graphs.end()) {
-            exec = cached->second;
-        } else {
-            hipGraph_t g = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(e->s_main, hipStreamCaptureModeThreadLocal));
-            try {
+        hipGraphExec_t *exec = e->greedy_graphs->find(n_slots);
+        if (!exec)
+            exec = &e->greedy_graphs->insert(n_slots, capture(e->s_main, [&] {
                 e->run_layers(pl.T, pl.n_seq, pl.n_out, e->d_tok_feedback, pl.dense);
                 launch_argmax(e->logits, n_slots, e->info.num_vocab, e->d_tok_feedback, e->d_amax_v, e->d_amax_i, e->s_main);
-            } catch (...) {
-                (void)hipStreamEndCapture(e->s_main, &g);
-                if (g) (void)hipGraphDestroy(g);
-                throw;
-            }
-            HIP_CHECK(hipStreamEndCapture(e->s_main, &g));
-            HIP_CHECK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            e->greedy_graphs.emplace(n_slots, exec);
-        }
+            }));
         HIP_CHECK(hipEventRecord(e->ev0, e->s_main));
         for (int s = 0; s < n_steps; ++s) {
-            HIP_CHECK(hipGraphLaunch(exec, e->s_main));
+            HIP_CHECK(hipGraphLaunch(*exec, e->s_main));
             HIP_CHECK(hipMemcpyAsync(e->d_hist + (size_t)s * n_slots, e->d_tok_feedback, n_slots * 4, hipMemcpyDeviceToDevice, e->s_main));
         }
         HIP_CHECK(hipEventRecord(e->ev1, e->s_main));
@@ -2237,19 +2173,16 @@ rwkv_status rwkv_bench_gemm(int32_t rows, int32_t K, int32_t fmt, int32_t T, int
         HIP_CHECK(hipStreamSynchronize(st));
         hipEvent_t ev_fork = nullptr, ev_join = nullptr;
         if (dual) { HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming)); }
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        if (dual) {
-            HIP_CHECK(hipEventRecord(ev_fork, st));
-            HIP_CHECK(hipStreamWaitEvent(st2, ev_fork, 0));
-            run_st = st2; run(iters); run_st = st;
-            HIP_CHECK(hipEventRecord(ev_join, st2));
-        }
-        run(iters);
-        if (dual) HIP_CHECK(hipStreamWaitEvent(st, ev_join, 0));
-        HIP_CHECK(hipStreamEndCapture(st, &g));
-        HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+        const hipGraphExec_t ge = capture(st, [&] {
+            if (dual) {
+                HIP_CHECK(hipEventRecord(ev_fork, st));
+                HIP_CHECK(hipStreamWaitEvent(st2, ev_fork, 0));
+                run_st = st2; run(iters); run_st = st;
+                HIP_CHECK(hipEventRecord(ev_join, st2));
+            }
+            run(iters);
+            if (dual) HIP_CHECK(hipStreamWaitEvent(st, ev_join, 0));
+        });
         HIP_CHECK(hipGraphLaunch(ge, st));
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipEventRecord(e0, st));
@@ -2258,7 +2191,7 @@ rwkv_status rwkv_bench_gemm(int32_t rows, int32_t K, int32_t fmt, int32_t T, int
         HIP_CHECK(hipEventSynchronize(e1));
         float ms = 0;
         HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
+        (void)hipGraphExecDestroy(ge);
         if (us_per_launch) *us_per_launch = ms * 1e3f / iters;
         for (void *p : bufs) (void)hipFree(p);
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(st);
