@@ -300,6 +300,9 @@ struct rwkv_engine {
     float *logits = nullptr, *logits_host = nullptr;
     float *soft_in = nullptr, *soft_out = nullptr, *soft_host = nullptr;
     size_t soft_rows_cap = 0;
+    // scoring (rwkv_infer_score on s_main, rwkv_score_rows on s_soft): one target in and one ln-probability out per logits row; pinned mirrors
+    unsigned *d_score_tgt = nullptr, *h_score_tgt = nullptr, *d_soft_tgt = nullptr, *h_soft_tgt = nullptr;
+    float *d_score_out = nullptr, *h_score_out = nullptr, *d_soft_score = nullptr, *h_soft_score = nullptr;
     Opd opA[6], opM, opY, opK, opO, opL[4];
     long pstride = 0;
     // row meta (device + pinned host)
@@ -462,6 +465,7 @@ struct rwkv_engine {
     void run_plan(const StepPlan &pl);
     void infer_sample(const rwkv_slot_input *in, const rwkv_sample_params *sp, uint32_t *out_tokens, float *out_probs,
                       uint8_t *emitted, size_t *n_consumed);
+    void infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
     // the input of a step in which each of `slots` feeds one token and asks for its row (`Last`); tokens[i] belongs to slots[i], and steps whose
     // ids come from the device (the feedback buffer, held tokens) pass nullptr: the plan then carries a zero nobody reads
     std::vector<rwkv_slot_input> one_token_each(const std::vector<int> &slots, const uint32_t *tokens) const {
@@ -883,6 +887,10 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     soft_in = dalloc<float>(soft_rows_cap * V);
     soft_out = dalloc<float>(soft_rows_cap * V);
     soft_host = hostalloc<float>(soft_rows_cap * V);
+    d_score_tgt = dalloc<unsigned>(chunk); d_score_out = dalloc<float>(chunk);
+    h_score_tgt = hostalloc<unsigned>(chunk); h_score_out = hostalloc<float>(chunk);
+    d_soft_tgt = dalloc<unsigned>(soft_rows_cap); d_soft_score = dalloc<float>(soft_rows_cap);
+    h_soft_tgt = hostalloc<unsigned>(soft_rows_cap); h_soft_score = hostalloc<float>(soft_rows_cap);
     d_adj_row = dalloc<int>(ADJ_CAP); d_adj_tok = dalloc<int>(ADJ_CAP); d_adj_val = dalloc<float>(ADJ_CAP);
     d_allow = dalloc<unsigned char>((size_t)max_batch * V); d_allow_row = dalloc<int>(max_batch);
     h_allow = hostalloc<unsigned char>((size_t)max_batch * V + (size_t)max_batch * 4 + 16);
@@ -1385,6 +1393,49 @@ void rwkv_engine::infer(const rwkv_slot_input *in, rwkv_slot_output *out) {
     for (const Seg &g : segs) std::memcpy(g.dst, logits_host + g.row0 * V, g.rows * V * 4);
 }
 
+// rwkv_infer_score: the step rwkv_infer would run with RWKV_OPTION_FULL on the scored slots (same plan, same step shape, same captured graph),
+// then score_rows_kernel over the n_out rows of `logits`; 4 bytes per row come back instead of the row (perplexity run.rs:699-755, Choose 936-982)
+void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed) {
+    HIP_CHECK(hipSetDevice(device));
+    (void)hipGetLastError();                                   // as in infer(): the poll below must only see THIS call's errors
+    const uint32_t V = (uint32_t)info.num_vocab;
+    std::vector<rwkv_slot_input> full(in, in + max_batch);
+    for (int b = 0; b < max_batch; ++b) {                      // every refusal comes before anything is launched or disarmed
+        n_consumed[b] = 0;
+        if (in[b].n_tokens && !in[b].tokens) throw RwkvError(RWKV_ERR_INVALID, "slot has n_tokens>0 but tokens==NULL");
+        if (!targets[b]) {
+            if (in[b].n_tokens && in[b].option != RWKV_OPTION_NONE)
+                throw RwkvError(RWKV_ERR_INVALID, "a slot without targets must be state-only (RWKV_OPTION_NONE) in rwkv_infer_score");
+            continue;
+        }
+        full[b].option = RWKV_OPTION_FULL;
+        if (!in[b].n_tokens) continue;
+        if (!out_logp || !out_logp[b]) throw RwkvError(RWKV_ERR_INVALID, "scored slot " + std::to_string(b) + " has no out_logp buffer");
+        for (size_t i = 0; i < in[b].n_tokens; ++i)
+            if (targets[b][i] >= V && targets[b][i] != RWKV_SCORE_SKIP)
+                throw RwkvError(RWKV_ERR_INVALID, "target " + std::to_string(targets[b][i]) + " of slot " + std::to_string(b) + " is not a token of this vocabulary");
+    }
+    for (int b = 0; b < max_batch; ++b) if (in[b].n_tokens) gen_disarm_slot(b);
+    StepPlan pl;
+    plan_step(full.data(), pl);
+    if (pl.T == 0) return;
+    for (int b = 0; b < max_batch; ++b)                        // a Full slot emits one row per consumed token: rows and targets line up
+        if (targets[b]) std::memcpy(h_score_tgt + pl.slot_out_begin[b], targets[b], (size_t)pl.slot_out_rows[b] * 4);
+    run_plan(pl);
+    for (int b = 0; b < max_batch; ++b) n_consumed[b] = (size_t)pl.slot_consumed[b];
+    if (pl.n_out == 0) {                                       // only state-only slots rode: not waited for, like a row-less rwkv_infer
+        HIP_CHECK(hipPeekAtLastError());
+        return;
+    }
+    HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+    launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+    HIP_CHECK(hipMemcpyAsync(h_score_out, d_score_out, (size_t)pl.n_out * 4, hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipPeekAtLastError());
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    for (int b = 0; b < max_batch; ++b)
+        if (targets[b] && pl.slot_out_rows[b]) std::memcpy(out_logp[b], h_score_out + pl.slot_out_begin[b], (size_t)pl.slot_out_rows[b] * 4);
+}
+
 // ------------------------------------------------------------------------------------------------
 // device-resident sampled generation (rwkv_gen_arm / _run, include/rwkv_abi.h): `process` (run.rs:788-1020) with the samplers on the device
 // ------------------------------------------------------------------------------------------------
@@ -1761,6 +1812,15 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
     });
 }
 
+rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp,
+                             size_t *n_consumed) {
+    return guard([&] {
+        if (!e || !in || !targets || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        use_knobs(e->kn);
+        e->infer_score(in, targets, out_logp, n_consumed);
+    });
+}
+
 rwkv_status rwkv_plan_chunk(int32_t max_batch, int32_t token_chunk_size, const size_t *n_tokens, int32_t *consumed) {
     return guard([&] {
         if (max_batch <= 0 || token_chunk_size <= 0 || !n_tokens || !consumed) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
@@ -1958,14 +2018,14 @@ rwkv_status rwkv_read_init_state(const rwkv_engine *e, const uint8_t *st_bytes, 
 }
 
 // ---- softmax (second caller thread, own stream) ---------------------------------------------------
+static std::mutex g_soft_mu;                                   // one softmax task per engine by contract; guard the staging rwkv_softmax and rwkv_score_rows share
 rwkv_status rwkv_softmax(rwkv_engine *e, const float *const *in, float *const *out, size_t n_rows) {
     return guard([&] {
         if (!e || (n_rows && (!in || !out))) throw RwkvError(RWKV_ERR_INVALID, "null argument");
         if (!n_rows) return;
         HIP_CHECK(hipSetDevice(e->device));
         const size_t V = (size_t)e->info.num_vocab;
-        static std::mutex mu;                                  // one softmax task per engine by contract; guard the staging
-        std::lock_guard<std::mutex> lk(mu);
+        std::lock_guard<std::mutex> lk(g_soft_mu);
         // staging for max_batch rows is allocated at load (never from this thread: the allocator belongs to the infer
         // thread); larger requests are processed in groups
         for (size_t r0 = 0; r0 < n_rows; r0 += e->soft_rows_cap) {
@@ -1979,6 +2039,34 @@ rwkv_status rwkv_softmax(rwkv_engine *e, const float *const *in, float *const *o
             HIP_CHECK(hipMemcpyAsync(e->soft_host, e->soft_out, n * V * 4, hipMemcpyDeviceToHost, e->s_soft));
             HIP_CHECK(hipStreamSynchronize(e->s_soft));
             for (size_t r = 0; r < n; ++r) std::memcpy(out[r0 + r], e->soft_host + r * V, V * 4);
+        }
+    });
+}
+
+// ln softmax(row)[target] of host rows (the `head` term of Choose, run.rs:971-972): rwkv_softmax's staging, stream and thread rule; one float per
+// row comes back instead of the row
+rwkv_status rwkv_score_rows(rwkv_engine *e, const float *const *in, const uint32_t *targets, float *out_logp, size_t n_rows) {
+    return guard([&] {
+        if (!e || (n_rows && (!in || !targets || !out_logp))) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        if (!n_rows) return;
+        const size_t V = (size_t)e->info.num_vocab;
+        for (size_t r = 0; r < n_rows; ++r) {                  // before anything is written or launched
+            if (!in[r]) throw RwkvError(RWKV_ERR_INVALID, "null row");
+            if (targets[r] >= V && targets[r] != RWKV_SCORE_SKIP) throw RwkvError(RWKV_ERR_INVALID, "target " + std::to_string(targets[r]) + " is not a token of this vocabulary");
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        std::lock_guard<std::mutex> lk(g_soft_mu);
+        for (size_t r0 = 0; r0 < n_rows; r0 += e->soft_rows_cap) {
+            const size_t n = std::min(e->soft_rows_cap, n_rows - r0);
+            for (size_t r = 0; r < n; ++r) std::memcpy(e->soft_host + r * V, in[r0 + r], V * 4);
+            std::memcpy(e->h_soft_tgt, targets + r0, n * 4);
+            HIP_CHECK(hipMemcpyAsync(e->soft_in, e->soft_host, n * V * 4, hipMemcpyHostToDevice, e->s_soft));
+            HIP_CHECK(hipMemcpyAsync(e->d_soft_tgt, e->h_soft_tgt, n * 4, hipMemcpyHostToDevice, e->s_soft));
+            launch_score_rows(e->soft_in, e->d_soft_tgt, e->d_soft_score, (int)n, (int)V, e->s_soft);
+            HIP_CHECK(hipMemcpyAsync(e->h_soft_score, e->d_soft_score, n * 4, hipMemcpyDeviceToHost, e->s_soft));
+            HIP_CHECK(hipPeekAtLastError());
+            HIP_CHECK(hipStreamSynchronize(e->s_soft));
+            std::memcpy(out_logp + r0, e->h_soft_score, n * 4);
         }
     });
 }

@@ -252,6 +252,8 @@ struct StatePackArgs {
 void launch_state_pack(const StatePackArgs &a, hipStream_t s);
 
 void launch_softmax(const float *in, float *out, int n_rows, int V, hipStream_t s);
+// out[r] = ln softmax(logits[r])[targets[r]], one pass over each row (n_rows > 0, V % 16 == 0); targets[r] >= V: not scored, out[r] = NaN
+void launch_score_rows(const float *logits, const unsigned *targets, float *out, int n_rows, int V, hipStream_t s);
 // on-device sampling front-end (f-1): V <= 65536, top_k <= 256
 struct SampleRow { float top_p; int top_k; float temperature; float uniform; int kind; float tau; };   // kind 0 nucleus, 1 typical, 2 mirostat (tau = max_surprise)
 void launch_logit_adjust(float *logits, int V, const int *rows, const int *toks, const float *vals, int n, hipStream_t s);

@@ -3074,6 +3074,83 @@ void launch_softmax(const float *in, float *out, int n_rows, int V, hipStream_t 
     hipLaunchKernelGGL(softmax_kernel, dim3(n_rows), dim3(256), 0, s, in, out, V);
 }
 
+// =====================================================================================
+// score_rows: ln softmax(x)[target] of every row (perplexity / Choose, run.rs:699-755, 936-982) — one fp32 out per row.
+// One 256-thread block per row, ONE pass: every lane reads 16 bytes at a time and keeps four online (m, s) pairs (s = sum of exp(x - m) over
+// what the pair has seen; when a larger x arrives s is rescaled by exp(m_old - x)), so a partial is a chain of at most V / 1024 additions.
+// Pairs are merged in a fixed order (the lane's four, xor butterfly over the wave, the four waves through LDS): the result is a function of the
+// row's bits, the target and V alone.  -inf entries (masked tokens) count as zero; a row holding +inf or NaN gives NaN.
+// =====================================================================================
+constexpr int SCORE_THREADS = 256;
+struct ScorePair { float m, s; };
+// one more element into a pair: exactly one exp (of -|x - m|); x = -inf adds nothing, the first finite x after -inf starts the sum at 1
+__device__ __forceinline__ void score_push(ScorePair &p, float x) {
+    const float hi = fmaxf(p.m, x), lo = fminf(p.m, x);
+    const float t = lo == -INFINITY ? 0.f : expf(lo - hi);
+    p.s = x > p.m ? p.s * t + 1.f : p.s + t;
+    p.m = hi;
+}
+// symmetric in (a, b) bit for bit: the pair with the larger m keeps its sum, the other one is rescaled (equal m: a plain commutative add)
+__device__ __forceinline__ ScorePair score_merge(ScorePair a, ScorePair b) {
+    const bool a_hi = a.m >= b.m;
+    const float mh = a_hi ? a.m : b.m, ml = a_hi ? b.m : a.m, sh = a_hi ? a.s : b.s, sl = a_hi ? b.s : a.s;
+    const float t = ml == -INFINITY ? 0.f : expf(ml - mh);
+    return ScorePair{mh, a.m == b.m ? a.s + b.s : sh + sl * t};
+}
+__global__ __launch_bounds__(SCORE_THREADS) void score_rows_kernel(const float *logits, const unsigned *targets, float *out, int V) {
+    __shared__ ScorePair red[SCORE_THREADS / 64];
+    __shared__ float red_xt[SCORE_THREADS / 64];
+    const int row = blockIdx.x;
+    const unsigned tgt = targets[row];
+    if (tgt >= (unsigned)V) {                                  // RWKV_SCORE_SKIP (the host refuses every other value >= V): not scored
+        if (threadIdx.x == 0) out[row] = __builtin_nanf("");
+        return;
+    }
+    const float4 *x4 = (const float4 *)(logits + (long)row * V);   // V % 16 == 0: every row starts 64-byte aligned
+    const int n4 = V >> 2, t4 = (int)(tgt >> 2), tc = (int)(tgt & 3);
+    ScorePair p[4] = {{-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}};
+    float xt = -INFINITY;                                      // the target's logit: kept by the lane that reads it (no second read of the row)
+    bool bad = false;                                          // +inf or NaN seen
+    for (int base = 0; base < n4; base += 4 * SCORE_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                          // four 16-byte loads in flight; past the row's end: -inf, which adds nothing
+            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
+            v[u] = i < n4 ? x4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
+            const float e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            if (i == t4) xt = tc == 0 ? e[0] : tc == 1 ? e[1] : tc == 2 ? e[2] : e[3];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                bad |= !(e[c] < INFINITY);
+                score_push(p[c], e[c]);
+            }
+        }
+    }
+    ScorePair a = score_merge(score_merge(p[0], p[1]), score_merge(p[2], p[3]));
+    if (bad) a.s = __builtin_nanf("");                         // rides the merges: NaN * t and NaN + s stay NaN
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const ScorePair o{__shfl_xor(a.m, k, 64), __shfl_xor(a.s, k, 64)};
+        a = score_merge(a, o);
+        xt = fmaxf(xt, __shfl_xor(xt, k, 64));                 // one lane of the block holds the value, all others -inf
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red_xt[threadIdx.x >> 6] = xt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = score_merge(score_merge(red[0], red[1]), score_merge(red[2], red[3]));
+        xt = fmaxf(fmaxf(red_xt[0], red_xt[1]), fmaxf(red_xt[2], red_xt[3]));
+        // a masked target is -inf whatever the rest of the row holds (a row of nothing but -inf included), unless the row is poisoned
+        out[row] = a.s != a.s ? a.s : xt == -INFINITY ? -INFINITY : (xt - a.m) - logf(a.s);
+    }
+}
+void launch_score_rows(const float *logits, const unsigned *targets, float *out, int n_rows, int V, hipStream_t s) {
+    hipLaunchKernelGGL(score_rows_kernel, dim3(n_rows), dim3(SCORE_THREADS), 0, s, logits, targets, out, V);
+}
+
 constexpr int ARGMAX_SEG = 32;                                  // segments per row in stage 1
 __device__ __forceinline__ void argmax_block(float &best, int &idx, float *bv, int *bi) {
 #pragma unroll

@@ -5,6 +5,7 @@
     greedy_process            `process` decode loop   run.rs:788-1020   with the arg-max sampler (Nucleus top_k=1,
                                                        sampler/nucleus.rs:77-89) and token 0 = stop (run.rs:855)
     perplexity                `perplexity`            run.rs:699-755    (RnnOption::Full consumer)
+    perplexity_scored         the same request with the realised tokens scored on the device (`Runtime.infer_score`)
     ReplicaRouter             SURVEY 8(e)             request-level sharding over N independent engines (no collective)
 
 Works against anything that has `.max_batch`, `.infer(RnnInput)` and `.state` like `runtime.Runtime`.
@@ -17,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .runtime import RnnInput, RnnInputBatch, RnnOption
+from .runtime import SCORE_SKIP, RnnInput, RnnInputBatch, RnnOption
 
 
 @dataclass
@@ -96,6 +97,27 @@ def perplexity(loop: InferLoop, batch: int, tokens, head: float | None = None) -
                 p.append(float(e[toks[index]] / e.sum(dtype=np.float32)))
             index += 1
     return float(-sum(math.log(x) for x in p) / len(toks))
+
+
+def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = None) -> float:
+    """`perplexity` with the realised tokens scored on the device (`Runtime.infer_score`, rwkv_infer_score): tokens' = [0] + tokens, or
+    tokens when `head` (the probability of tokens[0]) is given; every row's target is the next token, the last row is `SCORE_SKIP`;
+    ppl = -(sum ln p [+ ln head]) / len(tokens').  4 bytes per token come back instead of a logits row.  Takes an `InferLoop` (whose
+    queues must be drained) or a runtime.  Unlike `perplexity` — and run.rs:737-740 — the device subtracts the row maximum before it
+    exponentiates, so logits beyond ~88 still score finitely; where `perplexity` is finite the two agree to fp32."""
+    rt = getattr(loop_or_runtime, "rt", loop_or_runtime)
+    toks = list(tokens) if head is not None else [0] + list(tokens)
+    targets = [None] * rt.max_batch
+    targets[batch] = toks[1:] + [SCORE_SKIP]
+    inp = RnnInput([RnnInputBatch(toks if b == batch else [], RnnOption.Full) for b in range(rt.max_batch)])
+    acc = math.log(head) if head is not None else 0.0
+    while inp.num_token() > 0:
+        inp, targets, scores = rt.infer_score(inp, targets)
+        lp = np.asarray(scores[batch], dtype=np.float64)
+        if not len(inp.batches[batch].tokens):                    # the request's last row is the skipped one
+            lp = lp[:-1]
+        acc += float(lp.sum())
+    return float(-acc / len(toks))
 
 
 class NucleusSampler:

@@ -94,6 +94,9 @@ ABI_SYMBOLS = {
     "rwkv_host_free": (None, [C.c_void_p]),
     "rwkv_infer_sample": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(_SampleC), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]),
+    "rwkv_score_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
+    "rwkv_infer_score": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
+                                     C.POINTER(C.c_size_t)]),
     "rwkv_gen_arm": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenParamsC)]),
     "rwkv_gen_arm_prompt": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(_GenParamsC)]),
     "rwkv_gen_prompt_left": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
@@ -129,6 +132,7 @@ ABI_SYMBOLS = {
     "rwkv_bench_gemm": (C.c_int32, [C.c_int32] * 8 + [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 PROFILE_FAMILIES = 8
+SCORE_SKIP = 0xFFFFFFFF          # RWKV_SCORE_SKIP: a row that is not scored (its output is NaN)
 
 _lib = None
 
@@ -531,6 +535,57 @@ class Runtime:
             ib.tokens = list(ib.tokens[consumed[b]:])
             out.append((int(toks_o[b]), float(probs_o[b])) if emitted[b] else None)
         return inp, out
+
+    def infer_score(self, inp: RnnInput, targets: list):
+        """Like `infer`, for slots that are scored instead of read (rwkv_infer_score).  `targets[b]` is None (the slot has no tokens, or
+        rides state-only with `RnnOption.NoOutput`) or one target per pending token of slot b: `targets[b][i]` (a token id, or `SCORE_SKIP`) is
+        scored on the row that consuming `tokens[b][i]` produces.  Returns (inp, targets, scores): tokens and targets drained by what the call
+        consumed, `scores[b]` the float32 ln-probabilities of the rows it consumed (NaN where skipped; empty for a slot that is not scored)."""
+        B = self.max_batch
+        if len(inp.batches) != B or len(targets) != B:
+            raise RwkvError(-1, f"infer_score needs max_batch={B} entries")
+        ins = (_SlotInC * B)()
+        tp, op = (C.POINTER(C.c_uint32) * B)(), (C.POINTER(C.c_float) * B)()
+        keep, scores = [], []
+        for b, ib in enumerate(inp.batches):
+            toks = np.ascontiguousarray(ib.tokens, dtype=np.uint32).reshape(-1)
+            keep.append(toks)
+            ins[b] = _SlotInC(toks.ctypes.data_as(C.POINTER(C.c_uint32)) if toks.size else None, toks.size, int(ib.option), 0)
+            out = np.empty(0, np.float32)
+            if targets[b] is not None:
+                tg = np.ascontiguousarray(targets[b], dtype=np.uint32).reshape(-1)
+                if tg.size != toks.size:
+                    raise RwkvError(-1, f"slot {b}: {tg.size} targets for {toks.size} tokens")
+                out = np.full(min(toks.size, self.token_chunk_size), np.nan, np.float32)
+                keep.append(tg)
+                if tg.size:
+                    tp[b] = tg.ctypes.data_as(C.POINTER(C.c_uint32))
+                    op[b] = out.ctypes.data_as(C.POINTER(C.c_float))
+            scores.append(out)
+        consumed = (C.c_size_t * B)()
+        _check(lib().rwkv_infer_score(self._h, ins, tp, op, consumed))
+        del keep
+        rest = []
+        for b, ib in enumerate(inp.batches):
+            n = int(consumed[b])
+            ib.tokens = ib.tokens[n:] if isinstance(ib.tokens, np.ndarray) else list(ib.tokens[n:])
+            rest.append(None if targets[b] is None else targets[b][n:])
+            scores[b] = scores[b][:n] if targets[b] is not None else scores[b]
+        return inp, rest, scores
+
+    def score_rows(self, rows, targets) -> np.ndarray:
+        """ln softmax(rows[i])[targets[i]] on the device (rwkv_score_rows; the softmax task's stream and thread): `rows` are host rows of
+        num_vocab floats, `targets` token ids or `SCORE_SKIP` (-> NaN).  One float32 per row comes back."""
+        ins = [np.ascontiguousarray(r, np.float32).reshape(-1) for r in rows]
+        tg = np.ascontiguousarray(targets, dtype=np.uint32).reshape(-1)
+        if tg.size != len(ins) or any(r.size != self.info.num_vocab for r in ins):
+            raise RwkvError(-1, "score_rows: one target per row, num_vocab values per row")
+        out = np.full(len(ins), np.nan, np.float32)
+        if not ins:
+            return out
+        pi = (C.c_void_p * len(ins))(*[r.ctypes.data for r in ins])
+        _check(lib().rwkv_score_rows(self._h, pi, tg.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(C.POINTER(C.c_float)), len(ins)))
+        return out
 
     # ---- device-resident sampled generation (rwkv_gen_arm / _run / _disarm): the sampler state lives on the device
     def _gen_params(self, slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow):

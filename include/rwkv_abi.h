@@ -34,7 +34,9 @@ extern "C" {
                               *    rounding read hi + lo operands); the old all-f16 behaviour is RWKV_PRECISION_FP16_RAW
                               * 8: device-resident sampled generation: rwkv_gen_params, rwkv_gen_arm / _disarm / _run, rwkv_gen_uniform
                               * 9: resident generation admits prompts: rwkv_gen_arm_prompt (prefill rides in the resident steps, the first token is drawn
-                              *    on the device), rwkv_gen_prompt_left */
+                              *    on the device), rwkv_gen_prompt_left
+                              *    additive under 9 (no existing symbol or struct changed): rwkv_infer_score, rwkv_score_rows, RWKV_SCORE_SKIP: target tokens
+                              *    are scored on the device, 4 bytes per token come back instead of a logits row */
 
 typedef int32_t rwkv_status;
 enum {
@@ -191,6 +193,30 @@ rwkv_status rwkv_read_init_state(const rwkv_engine *e, const uint8_t *st_bytes, 
  * n rows of num_vocab floats each, host pointers in / out (may alias).  Own stream: may run
  * concurrently with rwkv_infer from the second caller thread. */
 rwkv_status rwkv_softmax(rwkv_engine *e, const float *const *in, float *const *out, size_t n_rows);
+
+/* ---- scoring on the device: what `perplexity` (run.rs:699-755) and GenerateKind::Choose (run.rs:936-982) need of a logits row is ONE
+ * number, the probability the model gave to the token that actually followed.  Both calls return its natural logarithm
+ *      logp = (x[t] - m) - ln sum_i exp(x[i] - m),   m = max_i x[i]
+ * computed on the device in one pass over the row (fp32, a fixed reduction order: a row's result depends on its bits, its target and num_vocab only,
+ * not on how many rows ride along), within 2e-5 * max(1, |logp|) of a float64 evaluation.
+ *  - DEVIATION from the reference, on purpose: run.rs:737-740 exponentiates WITHOUT subtracting the maximum, so it yields inf / NaN once a logit
+ *    passes about 88; this form stays finite there.  Wherever the reference is finite the two agree to the bound above.
+ *  - target RWKV_SCORE_SKIP: the row is not scored, the output is a quiet NaN (the last row of a perplexity request has no next token).
+ *  - x[t] == -inf (a masked token) gives -inf, not NaN; a row holding +inf or NaN gives NaN.
+ *  - any other target >= num_vocab: RWKV_ERR_INVALID before anything is launched or written. */
+#define RWKV_SCORE_SKIP 4294967295u   /* 0xFFFFFFFF */
+/* like rwkv_softmax: n_rows host rows of num_vocab floats in, one ln-probability per row out; own (softmax) stream and the softmax task's thread.
+ * This is Choose's `head` term (the probability of choice[0] on the prompt's last row, run.rs:971-972) when the caller holds the row. */
+rwkv_status rwkv_score_rows(rwkv_engine *e, const float *const *in, const uint32_t *targets, float *out_logp, size_t n_rows);
+/* like rwkv_infer, for slots that are scored instead of read.  All arrays have max_batch entries.  A slot with targets[b] != NULL is SCORED: it
+ * is planned as RWKV_OPTION_FULL (in[b].option is ignored; the rwkv_plan_chunk split and the step shapes are those of rwkv_infer, so the rows that are
+ * scored are the very rows a Full call with the same occupancy would have returned), targets[b] has in[b].n_tokens entries, targets[b][i] is scored
+ * on the row produced by consuming tokens[b][i], and out_logp[b][0 .. n_consumed[b]) is written by this call; the caller advances tokens, targets
+ * and out_logp together by n_consumed[b].  A slot with targets[b] == NULL must have n_tokens == 0 or option == RWKV_OPTION_NONE (a state-only
+ * prefill riding along), else RWKV_ERR_INVALID.  No logits row crosses PCIe: 4 bytes per row do.  The call returns when the scores are in place (a
+ * call in which only state-only slots ride returns when the step is queued, as rwkv_infer does); errors as for a row-emitting rwkv_infer.  Thread
+ * contract of rwkv_infer; tokens for an armed generation slot disarm it. */
+rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
 
 /* ---- on-device sampling front-end: what `sample()` run.rs:664-697 + NucleusSampler::sample
  * (sampler/nucleus.rs:69-101) do with three PCIe hops and a 65,536-element CPU sort, done on the device.

@@ -7,6 +7,7 @@
 //   Tokenizer::{encode,decode}      run.rs:157,856
 // Errors surface as rwkv::Error (std::runtime_error) carrying the rwkv_status — the analogue of `anyhow ?`.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -143,6 +144,47 @@ class Runtime {
             t.erase(t.begin(), t.begin() + (long)consumed[(size_t)b]);
             out[(size_t)b] = Sampled{emitted[(size_t)b] != 0, tok[(size_t)b], prob[(size_t)b]};
         }
+        return out;
+    }
+    // rwkv_infer_score: one step like infer(), for slots that are scored instead of read (perplexity run.rs:699-755, Choose run.rs:936-982).
+    // Slot b is scored when `targets[b]` holds one target per pending token (targets[b][i] — a token id or RWKV_SCORE_SKIP — is scored on
+    // the row that consuming tokens[b][i] produces); a slot with no targets must have no tokens or RnnOption::None.  `input` and `targets`
+    // are consumed in place; returns per slot the ln-probabilities of the rows this call consumed (NaN where skipped).  No row crosses PCIe.
+    std::vector<std::vector<float>> infer_score(RnnInput &input, std::vector<std::vector<uint32_t>> &targets) {
+        if ((int)input.batches.size() != max_batch || (int)targets.size() != max_batch) throw std::invalid_argument("infer_score: need max_batch entries");
+        std::vector<rwkv_slot_input> in((size_t)max_batch);
+        std::vector<const uint32_t *> tp((size_t)max_batch, nullptr);
+        std::vector<float *> op((size_t)max_batch, nullptr);
+        std::vector<std::vector<float>> out((size_t)max_batch);
+        std::vector<size_t> consumed((size_t)max_batch);
+        for (size_t b = 0; b < (size_t)max_batch; ++b) {
+            auto &ib = input.batches[b];
+            in[b] = rwkv_slot_input{ib.tokens.data(), ib.tokens.size(), (int32_t)ib.option, 0};
+            if (targets[b].empty()) continue;
+            if (targets[b].size() != ib.tokens.size()) throw std::invalid_argument("infer_score: a scored slot needs one target per pending token");
+            out[b].resize(std::min(ib.tokens.size(), (size_t)token_chunk_size));
+            tp[b] = targets[b].data();
+            op[b] = out[b].data();
+        }
+        check(rwkv_infer_score(e_.get(), in.data(), tp.data(), op.data(), consumed.data()));
+        for (size_t b = 0; b < (size_t)max_batch; ++b) {
+            auto &t = input.batches[b].tokens;
+            t.erase(t.begin(), t.begin() + (long)consumed[b]);
+            if (!tp[b]) continue;
+            targets[b].erase(targets[b].begin(), targets[b].begin() + (long)consumed[b]);
+            out[b].resize(consumed[b]);
+        }
+        return out;
+    }
+    // rwkv_score_rows: ln softmax(rows[i])[targets[i]] of host rows on the device (RWKV_SCORE_SKIP -> NaN) — Choose's `head` term (run.rs:971-972).
+    // The softmax task's stream and thread, like softmax() below.
+    std::vector<float> score_rows(const std::vector<std::vector<float>> &rows, const std::vector<uint32_t> &targets) {
+        if (rows.size() != targets.size()) throw std::invalid_argument("score_rows: one target per row");
+        for (const auto &r : rows) if (r.size() != (size_t)info.num_vocab) throw std::invalid_argument("score_rows: every row must hold num_vocab values");
+        std::vector<const float *> pi(rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) pi[i] = rows[i].data();
+        std::vector<float> out(rows.size());
+        check(rwkv_score_rows(e_.get(), pi.data(), targets.data(), out.data(), rows.size()));
         return out;
     }
     // Device-resident sampled generation (rwkv_gen_arm / _run / _disarm): arm a slot with `sampler.gen_params_for(...)`

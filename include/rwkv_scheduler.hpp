@@ -8,6 +8,8 @@
 //   Scheduler::finish          run.rs:629-662   busy slot -> Idle(content), state + output cached under the content
 //   Scheduler::perplexity      run.rs:699-755   Full rows of a token list -> -mean ln p of the realised tokens
 //   Scheduler::choose / state  run.rs:936-989   GenerateKind::Choose (perplexity per choice, optional calibration) / ::State
+//   Scheduler::perplexity_scored / choose_scored   the same two requests with the target tokens scored ON THE DEVICE (Engine::infer_score /
+//                                              score_rows = rwkv_infer_score / rwkv_score_rows): 4 bytes per token cross PCIe, not a row
 //
 // Differences from the reference, on purpose: (1) synchronous — the caller owns the thread (the reference spreads this over
 // tokio tasks and channels; the decisions are the same); (2) `step()` re-collects the pending tokens of all busy slots on
@@ -17,6 +19,7 @@
 //
 // Header-only, no HIP: `Engine` needs  int max_batch;  ModelInfo info;  State state (init/load/back);
 //                                       std::vector<RnnOutputBatch> infer(RnnInput &)  (consumes tokens in place).
+// The *_scored members need, in addition, the two scoring calls of rwkv::Runtime: infer_score(RnnInput &, targets &) and score_rows(rows, targets).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -371,6 +374,52 @@ class Scheduler {
         return ppl;
     }
 
+    // `perplexity` with the realised tokens scored on the device: tokens' ride Engine::infer_score on slot `batch`, every row but the last
+    // has its next token as target (the last row is RWKV_SCORE_SKIP), result = -(sum ln p [+ ln head]) / len(tokens').  Same contract as
+    // perplexity(): the slot's state advances by tokens'.  Busy slots with state-only requests pending (RnnOption::None) ride the same steps;
+    // requests that want rows wait for the next step() (infer_score hands out no rows).
+    // DEVIATION from the reference, on purpose: the device subtracts the row maximum before exponentiating (rwkv_abi.h), so a logit beyond
+    // ~88, where run.rs:737-740 and perplexity() overflow to inf / NaN, still scores finitely; wherever those are finite the two agree to fp32.
+    float perplexity_scored(int batch, const Tokens &tokens, const float *head) {
+        return scored_ppl(batch, tokens, head != nullptr, head ? std::log((double)*head) : 0.0);
+    }
+
+    // `choose` on top of perplexity_scored: the same snapshot, per-choice load / write and optional calibration.  `head` of a choice is
+    // probs[choice[0]] when the caller hands `probs` in; otherwise ln softmax(last logits)[choice[0]] comes from Engine::score_rows on the request's last row.
+    std::vector<float> choose_scored(int batch, const std::vector<Tokens> &choices, bool calibrate, const std::vector<float> &probs = {}) {
+        need_busy(batch);
+        Request &r = reqs_[(size_t)batch];
+        if (!r.suffix.empty() || r.output.empty()) throw std::logic_error("choose_scored(): the prompt has not been read in yet");
+        std::vector<double> head(choices.size(), 0.0);
+        if (probs.empty()) {
+            std::vector<std::vector<float>> rows;
+            std::vector<uint32_t> first;
+            for (const Tokens &c : choices) if (!c.empty()) { rows.push_back(r.output); first.push_back(c[0]); }
+            const std::vector<float> lp = rows.empty() ? std::vector<float>() : e_.score_rows(rows, first);
+            for (size_t i = 0, k = 0; i < choices.size(); ++i) if (!choices[i].empty()) head[i] = lp.at(k++);
+        } else {
+            for (size_t i = 0; i < choices.size(); ++i) if (!choices[i].empty()) head[i] = std::log((double)probs.at(choices[i][0]));
+        }
+        auto backed = snapshot(e_.state, batch, 0);
+        std::vector<float> ppl(choices.size(), std::numeric_limits<float>::infinity());
+        if (calibrate) {
+            const std::vector<float> init = r.state_id != 0 ? init_states_.at(r.state_id) : e_.state.init();
+            for (size_t i = 0; i < choices.size(); ++i) {
+                if (choices[i].empty()) continue;
+                e_.state.load(init, batch);
+                ppl[i] = -scored_ppl(batch, choices[i], false, 0.0);
+            }
+            restore(e_.state, backed, batch, 0);
+        }
+        for (size_t i = 0; i < choices.size(); ++i) {
+            if (choices[i].empty()) continue;
+            const float p = scored_ppl(batch, choices[i], true, head[i]);
+            ppl[i] = calibrate ? ppl[i] + p : p;
+            restore(e_.state, backed, batch, 0);
+        }
+        return ppl;
+    }
+
     // GenerateKind::State (run.rs:980-985): the slot's state slab as it stands (`Token::Embed(embed, shape)`).
     std::vector<float> state(int batch) { need_busy(batch); return e_.state.back(batch); }
 
@@ -465,6 +514,42 @@ class Scheduler {
         std::vector<float> p;
         size_t index = 1, want = 0;
     };
+    float scored_ppl(int batch, const Tokens &tokens, bool has_head, double head_logp) {
+        need_busy(batch);
+        if (!reqs_[(size_t)batch].suffix.empty()) throw std::logic_error("perplexity_scored(): the slot still has tokens pending");
+        Tokens all;
+        if (!has_head) all.push_back(0);
+        all.insert(all.end(), tokens.begin(), tokens.end());
+        const size_t n = all.size();
+        RnnInput in;
+        in.batches.resize(slots_.size());
+        std::vector<Tokens> targets(slots_.size());
+        Tokens &tg = targets[(size_t)batch];
+        tg.assign(all.begin() + (n ? 1 : 0), all.end());            // row j predicts tokens'[j + 1] ...
+        if (n) tg.push_back(RWKV_SCORE_SKIP);                        // ... and the last row has nothing to predict
+        in.batches[(size_t)batch].tokens = all;
+        in.batches[(size_t)batch].option = RnnOption::Full;
+        double acc = has_head ? head_logp : 0.0;
+        size_t row = 0;
+        while (!in.batches[(size_t)batch].tokens.empty()) {
+            for (size_t b = 0; b < slots_.size(); ++b) {            // state-only requests ride along
+                if ((int)b == batch) continue;
+                const bool rides = slots_[b].kind == SlotKind::Busy && !reqs_[b].suffix.empty() && reqs_[b].option == RnnOption::None;
+                in.batches[b].tokens = rides ? reqs_[b].suffix : Tokens();
+                in.batches[b].option = RnnOption::None;
+            }
+            const std::vector<std::vector<float>> out = e_.infer_score(in, targets);
+            for (float lp : out[(size_t)batch]) if (++row < n) acc += (double)lp;   // rows 1 .. n - 1 are scored, row n is the skipped one
+            for (size_t b = 0; b < slots_.size(); ++b) {
+                if ((int)b == batch || slots_[b].kind != SlotKind::Busy || reqs_[b].option != RnnOption::None) continue;
+                Request &r = reqs_[b];
+                const size_t consumed = r.suffix.size() - in.batches[b].tokens.size();
+                r.prefix.insert(r.prefix.end(), r.suffix.begin(), r.suffix.begin() + (long)consumed);
+                r.suffix.erase(r.suffix.begin(), r.suffix.begin() + (long)consumed);
+            }
+        }
+        return (float)(-acc / (double)n);
+    }
     int step_impl(Probe *probe) {
         RnnInput in;
         in.batches.resize(slots_.size());

@@ -33,6 +33,7 @@ pub const RWKV_GEN_RUNNING: i32 = 0;
 pub const RWKV_GEN_STOP: i32 = 1;
 pub const RWKV_GEN_LENGTH: i32 = 2;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
+pub const RWKV_SCORE_SKIP: u32 = 4294967295;
 
 #[repr(C)] pub struct rwkv_engine { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_dstate { _p: [u8; 0] }
@@ -101,6 +102,10 @@ extern "C" {
     pub fn rwkv_read_init_state(e: *const rwkv_engine, st_bytes: *const u8, st_len: usize, dst: *mut f32) -> rwkv_status;
     // softmax task  (run.rs:1178-1183)
     pub fn rwkv_softmax(e: *mut rwkv_engine, inp: *const *const f32, out: *const *mut f32, n_rows: usize) -> rwkv_status;
+    // scoring on the device: perplexity / Choose (run.rs:699-755, 936-982)
+    pub fn rwkv_score_rows(e: *mut rwkv_engine, inp: *const *const f32, targets: *const u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
+    pub fn rwkv_infer_score(e: *mut rwkv_engine, inp: *const rwkv_slot_input, targets: *const *const u32, out_logp: *const *mut c_float,
+                            n_consumed: *mut usize) -> rwkv_status;
     // on-device sampling front-end (run.rs:664-697 + sampler/*.rs)
     pub fn rwkv_infer_sample(e: *mut rwkv_engine, inp: *const rwkv_slot_input, sp: *const rwkv_sample_params, out_tokens: *mut u32,
                              out_probs: *mut c_float, emitted: *mut u8, n_consumed: *mut usize) -> rwkv_status;

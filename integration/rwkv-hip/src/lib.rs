@@ -211,6 +211,42 @@ impl Engine {
         let out: Vec<*mut f32> = rows.iter_mut().map(|r| r.as_mut_ptr()).collect();
         check(unsafe { sys::rwkv_softmax(self.raw, inp.as_ptr(), out.as_ptr(), rows.len()) })
     }
+    /// `rwkv_score_rows`: ln softmax(rows[i])[targets[i]] on the device (`sys::RWKV_SCORE_SKIP` -> NaN), one float per row back — the `head`
+    /// term of Choose (run.rs:971-972).  Call from the softmax task's thread.
+    pub fn score_rows(&self, rows: &[Vec<f32>], targets: &[u32]) -> Result<Vec<f32>> {
+        let v = self.info.num_vocab as usize;
+        if rows.len() != targets.len() || rows.iter().any(|r| r.len() != v) {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "score_rows: one target per row, num_vocab values per row".into() });
+        }
+        let inp: Vec<*const f32> = rows.iter().map(|r| r.as_ptr()).collect();
+        let mut out = vec![f32::NAN; rows.len()];
+        check(unsafe { sys::rwkv_score_rows(self.raw, inp.as_ptr(), targets.as_ptr(), out.as_mut_ptr(), rows.len()) })?;
+        Ok(out)
+    }
+    /// `rwkv_infer_score`: one step like `infer`, for slots that are scored instead of read (perplexity run.rs:699-755, Choose run.rs:936-982).
+    /// `targets[b]` is `None` (slot b has no tokens, or rides state-only with `OutputOption::None`) or one target per pending token of
+    /// slot b: `targets[b][i]` (a token id or `sys::RWKV_SCORE_SKIP`) is scored on the row that consuming `tokens[b][i]` produces.  Tokens
+    /// and targets are drained by what the call consumed; returns per slot the ln-probabilities of the consumed rows (NaN where skipped).
+    pub fn infer_score(&self, input: &mut [SlotInput], targets: &mut [Option<Vec<u32>>]) -> Result<Vec<Vec<f32>>> {
+        if input.len() != self.max_batch || targets.len() != self.max_batch {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: format!("infer_score: {} slot inputs, {} target lists for max_batch {}", input.len(), targets.len(), self.max_batch) });
+        }
+        if input.iter().zip(targets.iter()).any(|(s, t)| t.as_ref().map_or(false, |t| t.len() != s.tokens.len())) {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "infer_score: a scored slot needs one target per pending token".into() });
+        }
+        let inp: Vec<_> = input.iter().map(|s| sys::rwkv_slot_input {
+            tokens: if s.tokens.is_empty() { ptr::null() } else { s.tokens.as_ptr() }, n_tokens: s.tokens.len(), option: s.option as i32, reserved: 0 }).collect();
+        let mut out: Vec<Vec<f32>> = targets.iter().map(|t| vec![f32::NAN; t.as_ref().map_or(0, |t| t.len().min(self.token_chunk_size))]).collect();
+        let tp: Vec<*const u32> = targets.iter().map(|t| match t { Some(t) if !t.is_empty() => t.as_ptr(), _ => ptr::null() }).collect();
+        let op: Vec<*mut f32> = out.iter_mut().map(|o| if o.is_empty() { ptr::null_mut() } else { o.as_mut_ptr() }).collect();
+        let mut consumed = vec![0usize; self.max_batch];
+        check(unsafe { sys::rwkv_infer_score(self.raw, inp.as_ptr(), tp.as_ptr(), op.as_ptr(), consumed.as_mut_ptr()) })?;
+        for (((s, t), o), &n) in input.iter_mut().zip(targets.iter_mut()).zip(out.iter_mut()).zip(&consumed) {
+            s.tokens.drain(..n);
+            if let Some(t) = t { t.drain(..n); o.truncate(n); }
+        }
+        Ok(out)
+    }
     /// Arm `slot` for device-resident sampled generation (rwkv_gen_arm): the decode loop of `process` (run.rs:788-1020) with `sample()`
     /// (run.rs:664-697) and the sampler state machine (sampler/*.rs) on the device.  The slot's state is what the prompt left.
     pub fn gen_arm(&self, slot: usize, p: &GenParams) -> Result<()> { self.gen_arm_with(slot, p, None) }
