@@ -346,6 +346,16 @@ struct rwkv_engine {
     std::vector<size_t> gen_ppos;                                //   so far have consumed (each mixed step's slice rides in its plan upload)
     std::vector<float *> gen_shadow;                             // per slot: sxa | sxf | wkv of the step it finished in
     GenSlot *d_gen = nullptr;
+    // stop STRINGS (rwkv_gen_set_token_bytes / _set_stops): the engine's token-bytes table and, beside d_gen, one GenStop per slot
+    GenStop *d_gen_stop = nullptr;
+    std::vector<char> gen_has_stops;                             // per slot: it carries stop strings (host knowledge: selects the kernels of a step)
+    unsigned *d_tok_off = nullptr;                               // [n_tok + 1]; not in `allocs`: a new table replaces it
+    unsigned char *d_tok_bytes = nullptr;
+    int n_tok = 0;
+    void gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens, size_t n);
+    void gen_set_stops(int slot, const rwkv_gen_stops &s);
+    size_t gen_stop_tail(int slot, uint8_t *out, size_t cap);
+    bool gen_any_stops(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_stops[(size_t)b]) return true; return false; }
     float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
     float **d_gen_shadow = nullptr;
     SampleRow *d_gen_rows = nullptr;
@@ -358,14 +368,15 @@ struct rwkv_engine {
     void gen_disarm_slot(int slot) {
         if (gen_armed.empty()) return;
         gen_armed[(size_t)slot] = 0;
+        gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
         gen_prompt[(size_t)slot].clear();
         gen_ppos[(size_t)slot] = 0;
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows) const;
+    GenArgs gen_args(int n_rows, bool stops) const;
     unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs);
+    void gen_step(const StepPlan &pl, unsigned needs, bool stops);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
@@ -404,6 +415,8 @@ struct rwkv_engine {
         graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
+        if (d_tok_off) (void)hipFree(d_tok_off);
+        if (d_tok_bytes) (void)hipFree(d_tok_bytes);
         for (void *p : host_allocs) (void)hipHostFree(p);
         for (auto ev : meta_ev) if (ev) (void)hipEventDestroy(ev);
         if (ev0) (void)hipEventDestroy(ev0);
@@ -1439,11 +1452,17 @@ void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *
 // ------------------------------------------------------------------------------------------------
 // device-resident sampled generation (rwkv_gen_arm / _run, include/rwkv_abi.h): `process` (run.rs:788-1020) with the samplers on the device
 // ------------------------------------------------------------------------------------------------
+static_assert(RWKV_GEN_MAX_STOP_STR == GEN_MAX_STOP_STR && RWKV_GEN_STOP_LEN == GEN_STOP_LEN && RWKV_GEN_STOP_BUF == GEN_STOP_BUF &&
+              RWKV_GEN_TOKEN_LEN == GEN_TOKEN_LEN && RWKV_GEN_HANDBACK == GEN_FIN_HANDBACK && RWKV_GEN_STOP == GEN_FIN_STOP &&
+              RWKV_GEN_LENGTH == GEN_FIN_LENGTH, "include/rwkv_abi.h and csrc/gen_stop.h spell the same limits");
 void rwkv_engine::gen_init() {
     if (d_gen) return;
     const size_t B = (size_t)max_batch, V = (size_t)info.num_vocab;
     gen_host.assign(B, GenSlot{});
     gen_armed.assign(B, 0);
+    gen_has_stops.assign(B, 0);
+    d_gen_stop = dalloc<GenStop>(B);
+    HIP_CHECK(hipMemset(d_gen_stop, 0, B * sizeof(GenStop)));
     gen_prompt.assign(B, {});
     gen_ppos.assign(B, 0);
     d_gen_held = dalloc<int>(B);
@@ -1503,17 +1522,92 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     HIP_CHECK(hipMemcpyAsync(d_gen_pen + b * V, pen.data(), V * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemcpyAsync(d_gen_bias + b * V, bias.data(), V * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemcpyAsync(d_gen + b, &g, sizeof(GenSlot), hipMemcpyHostToDevice, s_main));
+    HIP_CHECK(hipMemsetAsync(&d_gen_stop[b].n_str, 0, 2 * sizeof(int), s_main));   // re-arming clears the stop strings and their buffer
     const int first = prompt ? 0 : (int)p.first_token;             // with a prompt the slot's first draw fills it
     HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     gen_host[b] = g;
+    gen_has_stops[b] = 0;
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
     gen_armed[b] = 1;
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows) const {
+// The token-bytes table of the stop-string matcher: what `tokenizer.decode(&[token])` (run.rs:856) yields per id.  Captured steps hold the
+// table's pointers, so a new table drops them; it is refused while a slot still matches against the old one.
+void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens, size_t n) {
+    HIP_CHECK(hipSetDevice(device));
+    if (!lens || n == 0 || n >= 0x7fffffffu) throw RwkvError(RWKV_ERR_INVALID, "token table: null lens or no tokens");
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (lens[i] < -1) throw RwkvError(RWKV_ERR_INVALID, "token table: negative length");
+        if (lens[i] > RWKV_GEN_TOKEN_LEN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "token table: a token is longer than RWKV_GEN_TOKEN_LEN");
+        if (lens[i] > 0) total += (size_t)lens[i];
+    }
+    if (total && !bytes) throw RwkvError(RWKV_ERR_INVALID, "token table: null bytes");
+    if (total >= GEN_TOK_UNKNOWN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "token table: more than 2 GiB of bytes");
+    for (char h : gen_has_stops) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has stop strings set");
+    std::vector<unsigned> off(n + 1);
+    size_t pos = 0;
+    for (size_t i = 0; i < n; ++i) {
+        off[i] = (unsigned)pos | (lens[i] < 0 ? GEN_TOK_UNKNOWN : 0u);
+        if (lens[i] > 0) pos += (size_t)lens[i];
+    }
+    off[n] = (unsigned)pos;
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    gen_graphs.clear();
+    if (d_tok_off) { (void)hipFree(d_tok_off); d_tok_off = nullptr; }
+    if (d_tok_bytes) { (void)hipFree(d_tok_bytes); d_tok_bytes = nullptr; }
+    n_tok = 0;
+    HIP_CHECK(hipMalloc((void **)&d_tok_off, (n + 1) * sizeof(unsigned)));
+    HIP_CHECK(hipMalloc((void **)&d_tok_bytes, std::max<size_t>(total, 16)));
+    HIP_CHECK(hipMemcpy(d_tok_off, off.data(), (n + 1) * sizeof(unsigned), hipMemcpyHostToDevice));
+    if (total) HIP_CHECK(hipMemcpy(d_tok_bytes, bytes, total, hipMemcpyHostToDevice));
+    n_tok = (int)n;
+}
+
+// `GenerateRequest::stop` (run.rs:899-932) of an armed, unfinished slot, and the bytes the caller's matcher holds after the tokens it handled itself
+void rwkv_engine::gen_set_stops(int slot, const rwkv_gen_stops &s) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "stop strings need an armed, unfinished slot");
+    if ((s.n && (!s.strs || !s.lens)) || (s.n_tail && !s.tail)) throw RwkvError(RWKV_ERR_INVALID, "null stop-string array");
+    if (s.n > RWKV_GEN_MAX_STOP_STR) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP_STR stop strings");
+    if (s.n_tail > RWKV_GEN_STOP_BUF) throw RwkvError(RWKV_ERR_UNSUPPORTED, "the tail is longer than RWKV_GEN_STOP_BUF");
+    for (size_t i = 0; i < s.n; ++i) {
+        if (s.lens[i] > RWKV_GEN_STOP_LEN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "a stop string is longer than RWKV_GEN_STOP_LEN");
+        if (s.lens[i] && !s.strs[i]) throw RwkvError(RWKV_ERR_INVALID, "null stop string");
+    }
+    if (s.n && !d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "stop strings need the token table: rwkv_gen_set_token_bytes");
+    std::vector<GenStop> h(1);
+    std::memset(h.data(), 0, sizeof(GenStop));
+    for (size_t i = 0; i < s.n; ++i) {
+        h[0].len[i] = (unsigned short)s.lens[i];
+        if (s.lens[i]) std::memcpy(h[0].str[i], s.strs[i], s.lens[i]);
+    }
+    h[0].n_str = (int)s.n;
+    h[0].buf_len = (int)s.n_tail;
+    if (s.n_tail) std::memcpy(h[0].buf, s.tail, s.n_tail);
+    HIP_CHECK(hipMemcpyAsync(d_gen_stop + b, h.data(), sizeof(GenStop), hipMemcpyHostToDevice, s_main));
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    gen_has_stops[b] = s.n ? 1 : 0;
+}
+
+size_t rwkv_engine::gen_stop_tail(int slot, uint8_t *out, size_t cap) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    std::vector<GenStop> h(1);
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_gen_stop + b, sizeof(GenStop), hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    const size_t len = (size_t)std::min(std::max(h[0].buf_len, 0), (int)GEN_STOP_BUF);
+    if (out && cap) std::memcpy(out, h[0].buf, std::min(len, cap));
+    return len;
+}
+
+GenArgs rwkv_engine::gen_args(int n_rows, bool stops) const {
     GenArgs a{};
+    if (stops) { a.stops = d_gen_stop; a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
     a.slots = d_gen; a.row_slot = dm.slot; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
     a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
     a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
@@ -1532,15 +1626,16 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T), needs);
+    gen_sample(gen_args(pl.T, stops), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
 void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
     const unsigned needs = gen_needs(rows);
+    const bool stops = gen_any_stops(rows);                        // a slot of this row set has stop strings: gen_post_kernel<., true>
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
@@ -1549,13 +1644,13 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs;
+    key.back() = needs | (stops ? 1ull << 32 : 0);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -1581,7 +1676,7 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     step_max_rows = pl.max_rows();
     run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (pl.n_out > 0) {
-        GenArgs a = gen_args(pl.n_out);
+        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn));
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         gen_sample(a, gen_needs(drawn));
@@ -2155,6 +2250,26 @@ rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, 
         if (!e || !out_tokens || n_steps <= 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
         use_knobs(e->kn);
         e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish);
+    });
+}
+rwkv_status rwkv_gen_set_token_bytes(rwkv_engine *e, const uint8_t *bytes, const int32_t *lens, size_t n_tokens) {
+    return guard([&] {
+        if (!e) throw RwkvError(RWKV_ERR_INVALID, "null engine");
+        e->gen_set_token_bytes(bytes, lens, n_tokens);
+    });
+}
+rwkv_status rwkv_gen_set_stops(rwkv_engine *e, int32_t slot, const rwkv_gen_stops *s) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!s) throw RwkvError(RWKV_ERR_INVALID, "null stops");
+        e->gen_set_stops(slot, *s);
+    });
+}
+rwkv_status rwkv_gen_stop_tail(rwkv_engine *e, int32_t slot, uint8_t *out, size_t cap, size_t *len) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!len || (cap && !out)) throw RwkvError(RWKV_ERR_INVALID, "null out / len");
+        *len = e->gen_stop_tail(slot, out, cap);
     });
 }
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out) {

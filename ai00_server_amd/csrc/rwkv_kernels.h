@@ -12,6 +12,8 @@ typedef unsigned short _Float16;
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gen_stop.h"                // RWKV_HD, the stop-string matcher and its limits
+
 namespace rwkv {
 
 enum WFmt : int { W_F16 = 0, W_INT8 = 1, W_NF4 = 2 };
@@ -275,8 +277,18 @@ struct GenSlot {                    // one per slot, device-resident; the host k
     int has_bias, n_stop;
     unsigned stop[GEN_MAX_STOP];
 };
+struct alignas(16) GenStop {        // one per slot, beside GenSlot (whose size stays): the slot's stop STRINGS and the bytes its matcher still holds
+    unsigned char str[GEN_MAX_STOP_STR][GEN_STOP_LEN];      // 16-byte aligned: staged into LDS with uint4 loads
+    unsigned char buf[GEN_STOP_BUF];                        // `context.buffer` (run.rs:869): written by the device only while the slot goes on
+    unsigned short len[GEN_MAX_STOP_STR];
+    int n_str, buf_len;                                     // n_str == 0: no strings, the slot takes the token-stop path
+};
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
+    GenStop *stops;                 // [max_batch], or null: no slot of this step has stop strings (selects gen_post_kernel<., false>)
+    const unsigned *tok_off;        // token table: bytes of id i are tok_bytes[off(i) .. off(i + 1)), off = tok_off[] & ~GEN_TOK_UNKNOWN;
+    const unsigned char *tok_bytes; //   tok_off[i] & GEN_TOK_UNKNOWN: id i is not in the vocabulary; ids >= n_tok are not either
+    int n_tok;
     const int *row_slot;            // slot of each row of the step
     const int *out_rows;            // null: decode-only step, logits row == step row.  Mixed step: [n_rows] step row of each logits row
     int *held;                      // [max_batch] mixed step: the token a slot drew last (next step's input row of the slot)
@@ -293,11 +305,6 @@ struct GenArgs {
     float *sxa, *sxf, *wkv; long sx_slot_stride, wkv_slot_stride;
     float *const *shadow;           // [max_batch] sxa | sxf | wkv of the slot, or null
 };
-#ifdef __HIP__
-#define RWKV_HD __host__ __device__
-#else
-#define RWKV_HD
-#endif
 RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

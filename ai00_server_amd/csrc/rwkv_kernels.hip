@@ -3479,7 +3479,7 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 //               bias rows, and this step's SampleRow (uniform draw, Mirostat's max_surprise) for nucleus_kernel
 //   nucleus_kernel, as it is
 //   gen_post    the tail of `sample` (nucleus.rs:104-119 / mirostat.rs:85-87), the token into the feedback buffer and the output
-//               ring, stop tokens and max_tokens (run.rs:855, 905-917)
+//               ring, stop tokens and max_tokens (run.rs:855, 905-917); with STOPS, the slot's stop STRINGS over the decoded bytes (run.rs:899-932, gen_stop.h)
 //   gen_freeze  the state of a slot that finished IN THIS STEP into its shadow (the step keeps its shape until the run ends; the host
 //               puts the shadow back)
 // Every value is written with plain vector stores.  All arithmetic is the per-token path's, operation for operation: the host
@@ -3547,7 +3547,40 @@ __device__ __forceinline__ float gen_mirostat(float max_surprise, float surprise
     const float step = rate * error;
     return fminf(max_surprise - step, 4.0f * target);
 }
+// What thread 0 did for a drawn token before stop strings existed, up to the finish decision: the token into the output ring and the
+// feedback path, the counters, Mirostat's update.  Returns the token-stop predicate (token 0, run.rs:855, or a listed stop token).
 template <bool MIXED>
+__device__ __forceinline__ bool gen_emit(const GenArgs &a, GenSlot &g, int row, int slot, int tok, int k) {
+    const float prob = a.samp_prob[row];
+    a.out_tok[(long)k * a.max_batch + slot] = (unsigned)tok;
+    a.out_prob[(long)k * a.max_batch + slot] = prob;
+    if (MIXED) a.held[slot] = tok; else a.feedback[row] = tok;
+    g.draws += 1;
+    g.emitted += 1;
+    if (g.kind == 2) g.tau = gen_mirostat(g.tau, prob, g.miro_target, g.miro_rate);   // `prob` is the token surprise
+    bool stop = tok == 0;                                          // run.rs:855
+    for (int j = 0; j < g.n_stop; ++j) stop |= g.stop[j] == (unsigned)tok;
+    return stop;
+}
+struct alignas(16) GenStopLds { unsigned char str[GEN_MAX_STOP_STR][GEN_STOP_LEN]; unsigned char buf[GEN_STOP_BUF]; };
+// LDS written by some lanes of ONE wave and read by others of the same wave: the wave's LDS operations execute in order, the fences
+// keep the compiler from moving them across (and wait for the counter); no other wave of the block touches the array.
+__device__ __forceinline__ void gen_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+template <int CTRL>
+__device__ __forceinline__ GenStopScan gen_scan_dpp(GenStopScan r) {
+    return GenStopScan{__builtin_amdgcn_update_dpp(0, r.safe, CTRL, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, r.matched, CTRL, 0xf, 0xf, true)};
+}
+// <., STOPS = false> is the step as it was: thread 0 of block (0, row) does the bookkeeping and the token stops.  <., true> is launched when
+// a slot of the step has stop STRINGS (run.rs:899-932, 990-1011; gen_stop.h): wave 0 of block (0, row) stages the slot's buffer, the drawn
+// token's bytes and the strings in LDS, lane j walks string j (gen_stop_scan), a DPP reduction over the 8 lanes is the `min_by`
+// (gen_stop_merge), lane 0 decides (gen_stop_decide) and validates the head (gen_stop_keep_from), and the wave moves the tail to the front
+// of the slot's buffer.  A slot that finishes leaves its buffer as it was before this token.  A slot of such a step without strings of
+// its own takes the <., false> path.
+template <bool MIXED, bool STOPS>
 __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int row = blockIdx.y, tid = threadIdx.x;
     const int slot = gen_slot_of<MIXED>(a, row);
@@ -3566,19 +3599,53 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
             *(uint4 *)(pr + i) = p;
         }
     }
-    if (blockIdx.x != 0 || tid != 0 || g.finish) return;
-    const float prob = a.samp_prob[row];
+    if (blockIdx.x != 0 || tid >= (STOPS ? 64 : 1) || g.finish) return;
     const int k = *a.run_step;
-    a.out_tok[(long)k * a.max_batch + slot] = (unsigned)tok;
-    a.out_prob[(long)k * a.max_batch + slot] = prob;
-    if (MIXED) a.held[slot] = tok; else a.feedback[row] = tok;
-    g.draws += 1;
-    g.emitted += 1;
-    if (g.kind == 2) g.tau = gen_mirostat(g.tau, prob, g.miro_target, g.miro_rate);   // `prob` is the token surprise
-    bool stop = tok == 0;                                          // run.rs:855
-    for (int j = 0; j < g.n_stop; ++j) stop |= g.stop[j] == (unsigned)tok;
-    const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
-    if (fin) { g.freeze_at = k; g.finish = fin; }
+    const int nstr = STOPS ? a.stops[slot].n_str : 0;
+    if (nstr <= 0) {
+        if (tid != 0) return;
+        const bool stop = gen_emit<MIXED>(a, g, row, slot, tok, k);
+        const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
+        if (fin) { g.freeze_at = k; g.finish = fin; }
+        return;
+    }
+    if constexpr (STOPS) {                                         // wave 0, all 64 lanes, uniform control flow down to the reduction
+        __shared__ GenStopLds lds;
+        GenStop &st = a.stops[slot];
+        const int blen = min(max(st.buf_len, 0), GEN_STOP_BUF);
+        unsigned o0 = GEN_TOK_UNKNOWN, o1 = 0;
+        if ((unsigned)tok < (unsigned)a.n_tok) { o0 = a.tok_off[tok]; o1 = a.tok_off[tok + 1]; }
+        const bool unknown = (o0 & GEN_TOK_UNKNOWN) != 0;          // `tokenizer.decode` failed: empty word, stop (run.rs:858-862)
+        const unsigned wbeg = o0 & ~GEN_TOK_UNKNOWN;
+        const int wlen = unknown ? 0 : min((int)((o1 & ~GEN_TOK_UNKNOWN) - wbeg), GEN_TOKEN_LEN);
+        const bool fits = blen + wlen <= GEN_STOP_BUF;
+        const int n = fits ? blen + wlen : blen;
+        ((uint4 *)lds.str)[tid] = ((const uint4 *)st.str)[tid];    // 8 x 128 bytes = 64 lanes x 16
+        if (tid < GEN_STOP_BUF / 16) ((uint4 *)lds.buf)[tid] = ((const uint4 *)st.buf)[tid];
+        gen_wave_lds_sync();
+        if (fits) for (int i = tid; i < wlen; i += 64) lds.buf[blen + i] = a.tok_bytes[wbeg + i];   // `buffer.append(word)`, run.rs:869
+        gen_wave_lds_sync();
+        GenStopScan r = GEN_STOP_NONE;
+        if (tid < nstr && tid < GEN_MAX_STOP_STR) r = gen_stop_scan(lds.buf, n, lds.str[tid], min((int)st.len[tid], GEN_STOP_LEN));
+        GenStopScan o = gen_scan_dpp<0xB1>(r);                     // quad_perm [1,0,3,2]: the neighbour; the lower lane holds the earlier string
+        r = (tid & 1) ? gen_stop_merge(o, r) : gen_stop_merge(r, o);
+        o = gen_scan_dpp<0x4E>(r);                                 // quad_perm [2,3,0,1]
+        r = (tid & 2) ? gen_stop_merge(o, r) : gen_stop_merge(r, o);
+        o = gen_scan_dpp<0x141>(r);                                // row_half_mirror: lane i <-> 7 - i, every lane of a quad holds the quad's result
+        r = (tid & 4) ? gen_stop_merge(o, r) : gen_stop_merge(r, o);
+        int keep_from = -1;                                        // >= 0: the slot goes on and its buffer becomes lds.buf[keep_from .. n)
+        if (tid == 0) {
+            const bool stop = gen_emit<MIXED>(a, g, row, slot, tok, k) || unknown;
+            const int fin = gen_stop_decide(stop, fits, r.matched != 0, g.emitted >= g.max_tokens);
+            if (fin) { g.freeze_at = k; g.finish = fin; }
+            else keep_from = gen_stop_keep_from(lds.buf, r.safe);  // run.rs:1008-1010: the head leaves only as valid UTF-8
+        }
+        keep_from = __builtin_amdgcn_readfirstlane(keep_from);
+        if (keep_from < 0) return;
+        const int left = n - keep_from;
+        for (int i = tid; i < left; i += 64) st.buf[i] = lds.buf[keep_from + i];
+        if (tid == 0) st.buf_len = left;
+    }
 }
 template <bool MIXED>
 __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
@@ -3600,9 +3667,13 @@ void launch_gen_pre(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_pre_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_pre_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
 }
+// a.stops != null selects the stop-string instantiation
 void launch_gen_post(const GenArgs &a, hipStream_t s) {
-    if (a.out_rows) hipLaunchKernelGGL(gen_post_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(gen_post_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+    if (a.stops) {
+        if (a.out_rows) hipLaunchKernelGGL((gen_post_kernel<true, true>), dim3(16, a.n_rows), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gen_post_kernel<false, true>), dim3(16, a.n_rows), dim3(256), 0, s, a);
+    } else if (a.out_rows) hipLaunchKernelGGL((gen_post_kernel<true, false>), dim3(16, a.n_rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gen_post_kernel<false, false>), dim3(16, a.n_rows), dim3(256), 0, s, a);
 }
 void launch_gen_freeze(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_freeze_kernel<true>, dim3(64, a.n_rows), dim3(256), 0, s, a);

@@ -186,6 +186,87 @@ class MirostatSampler:
         self.max_surprise = np.float32(min(np.float32(self.max_surprise - self.rate * err), np.float32(4.0) * self.target))
 
 
+class StopMatcher:
+    """The stop-STRING state machine of `process` (run.rs:855-869, 899-932, 990-1011), per token — the reference the device matcher
+    (rwkv_gen_set_stops) is held to, and what a caller runs over the tokens it samples itself.
+
+    Per token: the token's bytes join the buffer; every stop string walks the WHOLE buffer (on a mismatch `index_safe` moves behind the
+    mismatching byte, which is not retried as a new start: "ab" over "aab" does not match); `min_by` picks a matched string before an
+    unmatched one, then the smallest index, the first of equals; buffer = head | tail there.  A request that goes on sends the head and
+    keeps the tail only if the head is valid UTF-8, else it keeps the whole buffer.  `cap` (the device's RWKV_GEN_STOP_BUF; None = no
+    limit) bounds the buffer as the device's is bounded: a token that does not fit is not taken in and finishes with Handback."""
+    RUNNING, STOP, LENGTH, HANDBACK = 0, 1, 2, 3                      # runtime.GenFinish
+
+    def __init__(self, stops, tail: bytes = b"", cap: int | None = None):
+        self.stops = [bytes(s) for s in stops]
+        self.buffer = bytes(tail)
+        self.cap = cap
+
+    @staticmethod
+    def scan(buffer: bytes, stop: bytes):                             # run.rs:905-924
+        index_safe = index_unsafe = 0
+        while index_unsafe < len(buffer):
+            index_stop = index_unsafe - index_safe
+            if index_stop >= len(stop):
+                return index_safe, True
+            differ = buffer[index_unsafe] != stop[index_stop]
+            index_unsafe += 1
+            if differ:
+                index_safe = index_unsafe
+        return index_safe, index_unsafe - index_safe >= len(stop)
+
+    def split(self, buffer: bytes):
+        """(mid, matched) of run.rs:900-932: `min` keeps the first minimum like Iterator::min_by; no stops: everything is head"""
+        if not self.stops:
+            return len(buffer), False
+        return min((self.scan(buffer, s) for s in self.stops), key=lambda r: (not r[1], r[0]))
+
+    def advance(self, word, stop_token: bool = False, at_max: bool = False):
+        """One drawn token in the device's order (csrc/gen_stop.h gen_stop_decide).  `word` is the token's bytes, None for an id the
+        tokenizer does not know (decode error: empty word and stop); `stop_token`: the token is 0 or a listed stop token; `at_max`: the
+        request has `max_tokens` tokens with this one.  Returns (finish, content): the `Token::Content` bytes this token releases (on a stop
+        the reference sends them through from_utf8_lossy).  A token that finishes leaves `tail()` as it was before it."""
+        stop_token = stop_token or word is None
+        grown = self.buffer + (word or b"")
+        mid, matched = self.split(grown)
+        if stop_token:
+            return self.STOP, grown[:mid]
+        if self.cap is not None and len(grown) > self.cap:
+            return self.HANDBACK, b""
+        if matched:
+            return self.STOP, grown[:mid]
+        if at_max:
+            return self.LENGTH, b""
+        try:
+            grown[:mid].decode("utf-8")                               # String::from_utf8, run.rs:1008
+        except UnicodeDecodeError:
+            self.buffer = grown
+            return self.RUNNING, b""
+        self.buffer = grown[mid:]
+        return self.RUNNING, grown[:mid]
+
+    def push(self, word):
+        """`word` (bytes, or None for a decode error) -> (stop_matched, content bytes to emit)"""
+        fin, content = self.advance(word)
+        self.handback = fin == self.HANDBACK
+        return fin == self.STOP, content
+
+    def tail(self) -> bytes:
+        """what rwkv_gen_set_stops takes as `tail`: the bytes held back so far"""
+        return self.buffer
+
+    def replay(self, words):
+        """The `Token::Content` pieces of a run's tokens (their bytes, None = unknown id), for a caller that got the tokens back from
+        `gen_run`; stops behind the token that stops.  Returns (pieces, finish)."""
+        pieces = []
+        for w in words:
+            fin, content = self.advance(w)
+            pieces.append(content)
+            if fin:
+                return pieces, fin
+        return pieces, self.RUNNING
+
+
 class StateJob:
     """`GenerateKind::State` requests as a batch job with SLOT TURNOVER — the documented `/embeddings` route (docs/doc-api/openai.md:
     376-437; `GenerateKind::State` run.rs:980-989; `api/oai/state.rs:29-40`) fed a list of documents.  The scheduling is the reference's

@@ -69,6 +69,11 @@ class _GenParamsC(C.Structure):
                 ("seed", C.c_uint64), ("stream", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _GenStopsC(C.Structure):
+    _fields_ = [("strs", C.POINTER(C.POINTER(C.c_uint8))), ("lens", C.POINTER(C.c_size_t)), ("n", C.c_size_t),
+                ("tail", C.POINTER(C.c_uint8)), ("n_tail", C.c_size_t)]
+
+
 class _SlotOutC(C.Structure):
     _fields_ = [("logits", C.POINTER(C.c_float)), ("logits_capacity_rows", C.c_size_t), ("n_rows", C.c_size_t),
                 ("n_consumed", C.c_size_t)]
@@ -103,6 +108,9 @@ ABI_SYMBOLS = {
     "rwkv_gen_disarm": (C.c_int32, [C.c_void_p, C.c_int32]),
     "rwkv_gen_run": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
+    "rwkv_gen_set_token_bytes": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t]),
+    "rwkv_gen_set_stops": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenStopsC)]),
+    "rwkv_gen_stop_tail": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "rwkv_gen_uniform": (C.c_int32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_float)]),
     "rwkv_plan_chunk": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "rwkv_state_len": (C.c_size_t, [C.c_void_p]),
@@ -239,6 +247,10 @@ class GenFinish(enum.IntEnum):   # RWKV_GEN_*: FinishReason::{Stop, Length} run.
     Running = 0
     Stop = 1
     Length = 2
+    Handback = 3                 # the slot's stop-string buffer is full: the caller replays its own matcher and goes on per token
+
+
+GEN_MAX_STOP_STR, GEN_STOP_LEN, GEN_STOP_BUF, GEN_TOKEN_LEN = 8, 128, 512, 256      # RWKV_GEN_* limits of the device's stop-string matcher
 
 
 def list_adapters() -> list[str]:
@@ -642,6 +654,35 @@ class Runtime:
 
     def gen_disarm(self, slot: int):
         _check(lib().rwkv_gen_disarm(self._h, int(slot)))
+
+    def gen_set_token_bytes(self, table):
+        """What `tokenizer.decode([token])` yields per id (rwkv_gen_set_token_bytes; run.rs:856): `table[i]` is the bytes of id i, or None
+        for an id that is not in the vocabulary (the decode error of run.rs:858-862: empty word, stop).  `Tokenizer.token_index_to_bytes()`
+        with its empty entries turned into None is such a table.  The device matches stop strings over these bytes."""
+        lens = np.array([-1 if b is None else len(b) for b in table], np.int32)
+        data = np.frombuffer(b"".join(b for b in table if b is not None) or b"\0", np.uint8)
+        _check(lib().rwkv_gen_set_token_bytes(self._h, data.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None, lens.size))
+
+    def gen_set_stops(self, slot: int, stops, tail: bytes = b""):
+        """`GenerateRequest::stop` of an armed, unfinished slot (rwkv_gen_set_stops; run.rs:899-932): matched on the device, inside the
+        step, by the reference's own walk.  `tail` is the buffer the caller's matcher (`harness.StopMatcher.tail()`) holds after the tokens
+        it handled itself.  Replaces strings and buffer; an empty list clears them."""
+        stops = [bytes(s) for s in stops]
+        keep = [np.frombuffer(s or b"\0", np.uint8) for s in stops]
+        strs = (C.POINTER(C.c_uint8) * max(1, len(stops)))(*[k.ctypes.data_as(C.POINTER(C.c_uint8)) for k in keep])
+        lens = (C.c_size_t * max(1, len(stops)))(*[len(s) for s in stops])
+        t = np.frombuffer(bytes(tail) or b"\0", np.uint8)
+        s = _GenStopsC(strs, lens, len(stops), t.ctypes.data_as(C.POINTER(C.c_uint8)), len(tail))
+        _check(lib().rwkv_gen_set_stops(self._h, int(slot), C.byref(s)))
+        del keep
+
+    def gen_stop_tail(self, slot: int) -> bytes:
+        """The slot's matcher buffer as it stands (rwkv_gen_stop_tail): what a caller that resumes per token hands its own matcher."""
+        out = (C.c_uint8 * GEN_STOP_BUF)()
+        n = C.c_size_t(0)
+        _check(lib().rwkv_gen_stop_tail(self._h, int(slot), out, GEN_STOP_BUF, C.byref(n)))
+        return bytes(out[:min(int(n.value), GEN_STOP_BUF)])
 
     def gen_run(self, n_steps: int):
         """Up to `n_steps` decode steps of every armed, unfinished slot without a host turn-around.  Returns (tokens uint32

@@ -36,7 +36,9 @@ extern "C" {
                               * 9: resident generation admits prompts: rwkv_gen_arm_prompt (prefill rides in the resident steps, the first token is drawn
                               *    on the device), rwkv_gen_prompt_left
                               *    additive under 9 (no existing symbol or struct changed): rwkv_infer_score, rwkv_score_rows, RWKV_SCORE_SKIP: target tokens
-                              *    are scored on the device, 4 bytes per token come back instead of a logits row */
+                              *    are scored on the device, 4 bytes per token come back instead of a logits row
+                              *    additive under 9: rwkv_gen_set_token_bytes, rwkv_gen_set_stops, rwkv_gen_stop_tail, RWKV_GEN_HANDBACK: stop STRINGS are
+                              *    matched on the device inside the resident step */
 
 typedef int32_t rwkv_status;
 enum {
@@ -272,8 +274,17 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
  *    slot's last token.  Token 0 always stops (run.rs:855).
  *  - A slot that finishes inside a run keeps riding the remaining steps of that run (the captured step does not change shape); its rows
  *    are computed and thrown away and its state is put back as the rule says before the call returns.  It takes no part in later runs.
- *  - Stop STRINGS stay with the caller: one that needs the exact state at a stop string runs with n_steps = 1; otherwise a slot
- *    overshoots the string by at most n_steps - 1 tokens.
+ *  - Stop STRINGS (`GenerateRequest::stop`, run.rs:899-932) are matched on the device, inside the step, over the decoded bytes of the
+ *    output: rwkv_gen_set_token_bytes hands the engine what `tokenizer.decode(&[token])` yields per id, rwkv_gen_set_stops hands an armed
+ *    slot its strings.  The matcher is the reference's, byte for byte — per drawn token the whole buffer is walked once per string, the
+ *    mismatching byte is not retried as a new start ("ab" over "aab" does not match), `min_by` picks a matched string before an unmatched
+ *    one and then the smallest index, and the part in front of that index leaves the buffer only when it is valid UTF-8 (run.rs:1008-1010)
+ *    — so a slot finishes with RWKV_GEN_STOP at the token the reference stops at, with the state the rule above prescribes, whatever
+ *    n_steps is.  An id that is not in the table is the reference's decode error: empty word, stop (run.rs:856-862).  A slot without
+ *    strings runs what it ran before.  When a token's bytes do not fit the slot's RWKV_GEN_STOP_BUF bytes of buffer (a head that never
+ *    becomes valid UTF-8 keeps growing) the slot finishes with RWKV_GEN_HANDBACK: the token is emitted and the state rule holds as for any
+ *    finish; the caller, who has every token, replays its own matcher (include/rwkv_scheduler.hpp StopMatcher) and goes on per token.
+ *    A slot that finishes — whatever the reason — leaves its buffer as it was before its last token.
  *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a formatter mask (`allow` must be NULL: a grammar needs the
  *    host between two tokens, run.rs:676-679 — keep using rwkv_infer_sample), top_k > 256 (Nucleus / Typical), more than
  *    RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
@@ -281,6 +292,10 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
  *    rwkv_infer_sample with tokens for an armed slot, rwkv_state_load and rwkv_state_write on it disarm it.
  *  Same thread contract as rwkv_infer (the `infer` task). */
 #define RWKV_GEN_MAX_STOP 8
+#define RWKV_GEN_MAX_STOP_STR 8   /* stop strings per slot                                  */
+#define RWKV_GEN_STOP_LEN 128     /* bytes per stop string                                  */
+#define RWKV_GEN_STOP_BUF 512     /* bytes of matcher buffer per slot (`context.buffer`)    */
+#define RWKV_GEN_TOKEN_LEN 256    /* bytes per token of the token table                     */
 typedef struct rwkv_gen_params rwkv_gen_params;
 struct rwkv_gen_params {
     uint32_t first_token;          /* the token the first step consumes: the one the caller sampled from the prompt's row (run.rs:809-832)  */
@@ -308,7 +323,8 @@ struct rwkv_gen_params {
     uint32_t stream;
     uint32_t reserved;
 };
-enum { RWKV_GEN_RUNNING = 0, RWKV_GEN_STOP = 1, RWKV_GEN_LENGTH = 2 };   /* FinishReason::{Stop, Length} run.rs:905-917; 0 = not finished */
+enum { RWKV_GEN_RUNNING = 0, RWKV_GEN_STOP = 1, RWKV_GEN_LENGTH = 2,     /* FinishReason::{Stop, Length} run.rs:905-917; 0 = not finished */
+       RWKV_GEN_HANDBACK = 3 };   /* the slot's stop-string buffer is full: the device cannot decide this token, the caller goes on (see above) */
 /* arm `slot` (its state is what the prompt left, run.rs:788-832); re-arming replaces the context.  The arrays are copied. */
 rwkv_status rwkv_gen_arm(rwkv_engine *e, int32_t slot, const rwkv_gen_params *p);
 /* Arm `slot` with a PROMPT instead of a first token (ADMISSION: the engine may be generating on other slots, nobody stands still).
@@ -341,9 +357,29 @@ rwkv_status rwkv_gen_disarm(rwkv_engine *e, int32_t slot);      /* drop the cont
 /* Up to n_steps decode steps (run.rs:788-1020, one `infer` + `sample` each) for every armed, unfinished slot.  out_tokens / out_probs:
  * [n_steps][max_batch], step-major, 0xFFFFFFFF / NaN where a slot emitted nothing in that step (out_probs may be NULL; it carries what
  * rwkv_infer_sample's does: the token's probability, or its surprise for Mirostat); pinned or pageable.  n_emitted / finish: [max_batch],
- * tokens the slot emitted IN THIS CALL and RWKV_GEN_* (both may be NULL).  With nothing armed: RWKV_OK, nothing emitted.  A launch error is
+ * tokens the slot emitted IN THIS CALL and RWKV_GEN_* (both may be NULL; RWKV_GEN_HANDBACK only for a slot with stop strings).  With nothing armed: RWKV_OK, nothing emitted.  A launch error is
  * returned by this call, never stale tokens. */
 rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
+/* `tokenizer.decode(&[token])` for every id (run.rs:856): `bytes` is the concatenation of the tokens' bytes in id order, lens[i] the length
+ * of id i, or -1 for an id that is not in the vocabulary (ids >= n_tokens are not either): such an id is the reference's decode error, an
+ * empty word and a stop (run.rs:858-862).  A token longer than RWKV_GEN_TOKEN_LEN: RWKV_ERR_UNSUPPORTED.  Copied.  May be called again; that
+ * disarms nothing, but is refused (RWKV_ERR_INVALID) while any slot has stop strings set. */
+rwkv_status rwkv_gen_set_token_bytes(rwkv_engine *e, const uint8_t *bytes, const int32_t *lens, size_t n_tokens);
+typedef struct rwkv_gen_stops rwkv_gen_stops;
+struct rwkv_gen_stops {
+    const uint8_t *const *strs;    /* `GenerateRequest::stop` as bytes (run.rs:905), n <= RWKV_GEN_MAX_STOP_STR strings of <= RWKV_GEN_STOP_LEN bytes */
+    const size_t *lens;
+    size_t n;
+    const uint8_t *tail;           /* `context.buffer` (run.rs:869, 1010) as the caller's own matcher holds it after the tokens it handled itself:  */
+    size_t n_tail;                 /*   non-empty after rwkv_gen_arm (whose first_token the caller sampled and matched), normally empty after       */
+};                                 /*   rwkv_gen_arm_prompt; n_tail <= RWKV_GEN_STOP_BUF                                                           */
+/* The stop strings of an armed, unfinished slot (run.rs:899-932), set between runs; replaces strings and buffer, n = 0 clears them.  Copied.
+ * RWKV_ERR_INVALID: the slot is not armed (or has finished), no token table, a NULL array.  RWKV_ERR_UNSUPPORTED: one of the limits above.
+ * Re-arming a slot and everything that disarms it clear its strings. */
+rwkv_status rwkv_gen_set_stops(rwkv_engine *e, int32_t slot, const rwkv_gen_stops *s);
+/* The slot's buffer as it stands (`context.buffer` after `buffer = tail`, run.rs:1010): *len bytes, of which min(*len, cap) are copied to
+ * `out` (may be NULL with cap = 0).  Waits for the device.  For a caller that resumes per token after RWKV_GEN_HANDBACK or between runs. */
+rwkv_status rwkv_gen_stop_tail(rwkv_engine *e, int32_t slot, uint8_t *out, size_t cap, size_t *len);
 /* the draws `first_step .. first_step + n - 1` of (seed, stream): pure host function, no device needed */
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out);
 

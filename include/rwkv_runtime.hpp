@@ -201,10 +201,37 @@ class Runtime {
         return left;
     }
     void gen_disarm(int slot) { check(rwkv_gen_disarm(e_.get(), slot)); }
+    // Stop strings on the device (rwkv_gen_set_token_bytes / _set_stops / _stop_tail; run.rs:855-869, 899-932, 990-1011).  `table[i]` is what
+    // `tokenizer.decode(&[i])` yields; `known[i] == 0` marks an id that is not in the vocabulary (decode error: empty word and stop).
+    void gen_set_token_bytes(const std::vector<std::string> &table, const std::vector<uint8_t> &known = {}) {
+        std::vector<int32_t> lens(table.size());
+        std::string bytes;
+        for (size_t i = 0; i < table.size(); ++i) {
+            const bool ok = known.empty() || known[i];
+            lens[i] = ok ? (int32_t)table[i].size() : -1;
+            if (ok) bytes += table[i];
+        }
+        check(rwkv_gen_set_token_bytes(e_.get(), (const uint8_t *)bytes.data(), lens.data(), lens.size()));
+    }
+    // the strings of an armed, unfinished slot; `tail` is StopMatcher::tail() of the caller's own matcher (include/rwkv_scheduler.hpp)
+    void gen_set_stops(int slot, const std::vector<std::string> &stops, const std::vector<uint8_t> &tail = {}) {
+        std::vector<const uint8_t *> strs(stops.size());
+        std::vector<size_t> lens(stops.size());
+        for (size_t i = 0; i < stops.size(); ++i) { strs[i] = (const uint8_t *)stops[i].data(); lens[i] = stops[i].size(); }
+        const rwkv_gen_stops s{strs.data(), lens.data(), stops.size(), tail.data(), tail.size()};
+        check(rwkv_gen_set_stops(e_.get(), slot, &s));
+    }
+    std::vector<uint8_t> gen_stop_tail(int slot) {
+        std::vector<uint8_t> out(RWKV_GEN_STOP_BUF);
+        size_t len = 0;
+        check(rwkv_gen_stop_tail(e_.get(), slot, out.data(), out.size(), &len));
+        out.resize(std::min(len, out.size()));
+        return out;
+    }
     struct Generated {
         std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing
         std::vector<float> probs;                    // same shape, NaN there
-        std::vector<int32_t> n_emitted, finish;      // [max_batch]: tokens of this call, RWKV_GEN_*
+        std::vector<int32_t> n_emitted, finish;      // [max_batch]: tokens of this call, RWKV_GEN_* (RWKV_GEN_HANDBACK: replay StopMatcher, go on per token)
     };
     Generated gen_run(int n_steps) {
         if (n_steps <= 0) throw std::invalid_argument("gen_run: n_steps must be > 0");

@@ -30,6 +30,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rwkv_runtime.hpp"
@@ -214,6 +215,75 @@ inline StopScan scan_stops(const std::vector<uint8_t> &buffer, const std::vector
     return best;
 }
 
+// The whole stop-string state machine of `process` per token (run.rs:855-869, 899-932, 990-1011) on top of scan_stops: the per-token
+// reference the device matcher (rwkv_gen_set_stops) is held to, what a caller runs over tokens it samples itself, and what it replays
+// over the tokens a resident run handed back.  `cap` (RWKV_GEN_STOP_BUF on the device; 0 = unbounded) bounds the buffer as the device's
+// is bounded.  (Python twin: harness.StopMatcher.)
+class StopMatcher {
+   public:
+    using Bytes = std::vector<uint8_t>;
+    struct Step { int finish; Bytes content; };                       // finish: RWKV_GEN_*; content: the `Token::Content` bytes this token releases
+    explicit StopMatcher(std::vector<std::string> stops, Bytes tail = {}, size_t cap = 0) : stops_(std::move(stops)), buffer_(std::move(tail)), cap_(cap) {}
+    // String::from_utf8 (run.rs:1008): well-formed UTF-8 only — no overlong form, no surrogate, nothing above U+10FFFF, nothing cut short
+    static bool utf8_valid(const uint8_t *p, size_t n) {
+        for (size_t i = 0; i < n;) {
+            const uint8_t c = p[i];
+            if (c < 0x80) { ++i; continue; }
+            size_t more;
+            uint8_t lo = 0x80, hi = 0xBF;
+            if (c >= 0xC2 && c <= 0xDF) more = 1;
+            else if (c >= 0xE0 && c <= 0xEF) { more = 2; if (c == 0xE0) lo = 0xA0; if (c == 0xED) hi = 0x9F; }
+            else if (c >= 0xF0 && c <= 0xF4) { more = 3; if (c == 0xF0) lo = 0x90; if (c == 0xF4) hi = 0x8F; }
+            else return false;
+            if (n - i <= more || p[i + 1] < lo || p[i + 1] > hi) return false;
+            for (size_t k = 2; k <= more; ++k) if ((p[i + k] & 0xC0) != 0x80) return false;
+            i += more + 1;
+        }
+        return true;
+    }
+    // One drawn token, decided in the device's order.  `word`: the token's bytes, nullptr for an id the tokenizer does not know (decode
+    // error, run.rs:858-862: empty word and stop); `stop_token`: token 0 or a listed stop token; `at_max`: the request has max_tokens
+    // tokens with this one.  A token that finishes leaves tail() as it was before it.
+    Step advance(const Bytes *word, bool stop_token = false, bool at_max = false) {
+        stop_token = stop_token || !word;
+        Bytes grown = buffer_;
+        if (word) grown.insert(grown.end(), word->begin(), word->end());
+        const StopScan sc = scan_stops(grown, stops_);
+        const Bytes head(grown.begin(), grown.begin() + (long)sc.head);
+        if (stop_token) return Step{RWKV_GEN_STOP, head};
+        if (cap_ && grown.size() > cap_) return Step{RWKV_GEN_HANDBACK, {}};
+        if (sc.matched) return Step{RWKV_GEN_STOP, head};
+        if (at_max) return Step{RWKV_GEN_LENGTH, {}};
+        if (!utf8_valid(head.data(), head.size())) { buffer_ = std::move(grown); return Step{RWKV_GEN_RUNNING, {}}; }
+        buffer_.assign(grown.begin() + (long)sc.head, grown.end());  // `context.buffer = tail.to_vec()`, run.rs:1010
+        return Step{RWKV_GEN_RUNNING, head};
+    }
+    // `word` (nullptr: decode error) -> (stop_matched, content bytes to emit)
+    std::pair<bool, Bytes> push(const Bytes *word) {
+        Step st = advance(word);
+        handback = st.finish == RWKV_GEN_HANDBACK;
+        return {st.finish == RWKV_GEN_STOP, std::move(st.content)};
+    }
+    const Bytes &tail() const { return buffer_; }                     // what rwkv_gen_set_stops takes as `tail`
+    // the `Token::Content` pieces of a run's tokens (`known[i] == 0`: unknown id), stopping behind the token that stops; *finish gets RWKV_GEN_*
+    std::vector<Bytes> replay(const std::vector<Bytes> &words, const std::vector<uint8_t> &known = {}, int *finish = nullptr) {
+        std::vector<Bytes> pieces;
+        if (finish) *finish = RWKV_GEN_RUNNING;
+        for (size_t i = 0; i < words.size(); ++i) {
+            Step st = advance(known.empty() || known[i] ? &words[i] : nullptr);
+            pieces.push_back(std::move(st.content));
+            if (st.finish) { if (finish) *finish = st.finish; break; }
+        }
+        return pieces;
+    }
+    bool handback = false;                                            // the last push did not fit `cap`
+
+   private:
+    std::vector<std::string> stops_;
+    Bytes buffer_;
+    size_t cap_;
+};
+
 enum class SlotResult { Success, Fault, Failure };   // run.rs: Success(batch) / Fault(batch) (had to back a slot) / Failure (all busy)
 
 template <class Engine>
@@ -303,6 +373,16 @@ class Scheduler {
         slots_[batch].kind = SlotKind::Busy;
         slots_[batch].content.clear();
         return back ? SlotResult::Fault : SlotResult::Success;
+    }
+
+    // Hand a busy slot whose prompt has been read in to the resident loop WITH its stop strings (run.rs:899-932 on the device): arm it with
+    // `p` (its first_token is the token the caller sampled from the prompt's row and has already pushed through `matcher`), then set the
+    // strings and the bytes the matcher still holds.  Needs an engine with gen_arm / gen_set_stops (rwkv::Runtime) whose token table is set.
+    void arm_with_stops(int batch, const rwkv_gen_params &p, const std::vector<std::string> &stops, const StopMatcher &matcher) {
+        need_busy(batch);
+        if (!reqs_[(size_t)batch].suffix.empty()) throw std::logic_error("arm_with_stops(): the prompt has not been read in yet");
+        e_.gen_arm(batch, p);
+        e_.gen_set_stops(batch, stops, matcher.tail());
     }
 
     // feed more tokens to a busy slot (the decode loop appends the sampled token: run.rs:1004-1010)

@@ -32,6 +32,11 @@ pub const RWKV_GEN_MAX_STOP: usize = 8;
 pub const RWKV_GEN_RUNNING: i32 = 0;
 pub const RWKV_GEN_STOP: i32 = 1;
 pub const RWKV_GEN_LENGTH: i32 = 2;
+pub const RWKV_GEN_HANDBACK: i32 = 3;
+pub const RWKV_GEN_MAX_STOP_STR: usize = 8;
+pub const RWKV_GEN_STOP_LEN: usize = 128;
+pub const RWKV_GEN_STOP_BUF: usize = 512;
+pub const RWKV_GEN_TOKEN_LEN: usize = 256;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 pub const RWKV_SCORE_SKIP: u32 = 4294967295;
 
@@ -65,6 +70,8 @@ pub struct rwkv_gen_params { pub first_token: u32, pub max_tokens: i32, pub kind
                              pub bias_tokens: *const u32, pub bias_values: *const c_float, pub n_bias: usize,
                              pub stop_tokens: *const u32, pub n_stop: usize, pub allow: *const u8,
                              pub seed: u64, pub stream: u32, pub reserved: u32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rwkv_gen_stops { pub strs: *const *const u8, pub lens: *const usize, pub n: usize, pub tail: *const u8, pub n_tail: usize }
 
 extern "C" {
     // errors / version / adapters  (lib.rs:339-349)
@@ -116,6 +123,10 @@ extern "C" {
     pub fn rwkv_gen_disarm(e: *mut rwkv_engine, slot: i32) -> rwkv_status;
     pub fn rwkv_gen_run(e: *mut rwkv_engine, n_steps: i32, out_tokens: *mut u32, out_probs: *mut c_float, n_emitted: *mut i32,
                         finish: *mut i32) -> rwkv_status;
+    // stop strings matched on the device (run.rs:855-869, 899-932, 990-1011)
+    pub fn rwkv_gen_set_token_bytes(e: *mut rwkv_engine, bytes: *const u8, lens: *const i32, n_tokens: usize) -> rwkv_status;
+    pub fn rwkv_gen_set_stops(e: *mut rwkv_engine, slot: i32, s: *const rwkv_gen_stops) -> rwkv_status;
+    pub fn rwkv_gen_stop_tail(e: *mut rwkv_engine, slot: i32, out: *mut u8, cap: usize, len: *mut usize) -> rwkv_status;
     pub fn rwkv_gen_uniform(seed: u64, stream: u32, first_step: u32, n: usize, out: *mut c_float) -> rwkv_status;
     // Tokenizer  (lib.rs:375, run.rs:157, 856, bnf.rs:15)
     pub fn rwkv_tokenizer_create(vocab_json: *const c_char, len: usize, out: *mut *mut rwkv_tokenizer) -> rwkv_status;

@@ -277,6 +277,29 @@ impl Engine {
         }
     }
     pub fn gen_disarm(&self, slot: usize) -> Result<()> { check(unsafe { sys::rwkv_gen_disarm(self.raw, slot as i32) }) }
+    /// `tokenizer.decode(&[token])` for every id (rwkv_gen_set_token_bytes, run.rs:856): `None` is an id that is not in the vocabulary —
+    /// the decode error of run.rs:858-862, an empty word and a stop.  What the device matches stop strings over.
+    pub fn gen_set_token_bytes(&self, tokens: &[Option<&[u8]>]) -> Result<()> {
+        let lens: Vec<i32> = tokens.iter().map(|t| t.map_or(-1, |b| b.len() as i32)).collect();
+        let bytes: Vec<u8> = tokens.iter().flat_map(|t| t.unwrap_or(&[]).iter().copied()).collect();
+        check(unsafe { sys::rwkv_gen_set_token_bytes(self.raw, bytes.as_ptr(), lens.as_ptr(), lens.len()) })
+    }
+    /// `GenerateRequest::stop` of an armed, unfinished slot (rwkv_gen_set_stops, run.rs:899-932), matched on the device inside the step;
+    /// `tail` is `context.buffer` as the caller's own matcher holds it after the tokens it handled itself.  An empty list clears them.
+    pub fn gen_set_stops(&self, slot: usize, stops: &[&[u8]], tail: &[u8]) -> Result<()> {
+        let strs: Vec<*const u8> = stops.iter().map(|s| s.as_ptr()).collect();
+        let lens: Vec<usize> = stops.iter().map(|s| s.len()).collect();
+        let raw = sys::rwkv_gen_stops { strs: strs.as_ptr(), lens: lens.as_ptr(), n: stops.len(), tail: tail.as_ptr(), n_tail: tail.len() };
+        check(unsafe { sys::rwkv_gen_set_stops(self.raw, slot as i32, &raw) })
+    }
+    /// the slot's matcher buffer as it stands (rwkv_gen_stop_tail; `buffer = tail`, run.rs:1010): what a caller that resumes per token starts from
+    pub fn gen_stop_tail(&self, slot: usize) -> Result<Vec<u8>> {
+        let mut out = vec![0u8; sys::RWKV_GEN_STOP_BUF];
+        let mut len = 0usize;
+        check(unsafe { sys::rwkv_gen_stop_tail(self.raw, slot as i32, out.as_mut_ptr(), out.len(), &mut len) })?;
+        out.truncate(len);
+        Ok(out)
+    }
     /// Up to `n_steps` tokens for every armed, unfinished slot with no host turn-around (rwkv_gen_run).  When it returns a slot's
     /// state has consumed everything it emitted except the last token (what run.rs:990-1005 backs up at a stop).
     pub fn gen_run(&self, n_steps: usize) -> Result<Generated> {
@@ -298,7 +321,7 @@ pub struct GenParams {
     pub penalties: Vec<(u32, f32)>, pub bias: Vec<(u32, f32)>, pub stop_tokens: Vec<u32>, pub seed: u64, pub stream: u32,
 }
 /// what `Engine::gen_run` returns: `tokens` / `probs` are [n_steps][max_batch] (u32::MAX / NaN where a slot emitted nothing),
-/// `n_emitted` counts this call's tokens per slot, `finish` is RWKV_GEN_RUNNING / _STOP / _LENGTH
+/// `n_emitted` counts this call's tokens per slot, `finish` is RWKV_GEN_RUNNING / _STOP / _LENGTH / _HANDBACK
 #[derive(Clone, Debug)]
 pub struct Generated { pub tokens: Vec<u32>, pub probs: Vec<f32>, pub n_emitted: Vec<i32>, pub finish: Vec<i32> }
 /// draw `step` of (seed, stream): pure host function (rwkv_gen_uniform)

@@ -21,7 +21,11 @@ rwkv_infer_sample prefill, host sampler update, rwkv_gen_arm, re-enter), (b) `ar
 both, by the host clock: tokens/s over the region; the time from the admission to the joiner's first token being in the host's hands;
 and the longest gap between two tokens of a running slot: for (a) the time between the two runs around an admission plus one step, for
 (b) the longest single-step run while a prompt is being consumed (rwkv_gen_run(1) per step during an admission, so that every step
-is timed on its own)."""
+is timed on its own).
+
+`--stops N,LEN` gives every slot of the resident loop N stop strings of LEN bytes that never match, over a synthetic token table (ids map
+to 1-4 letters): the price of matching stop strings on the device (rwkv_gen_set_stops).  `--loops resident_1` is what a caller with stop
+strings had to do before: rwkv_gen_run(1) per token and `harness.StopMatcher` over every slot's token on the host."""
 import argparse
 import json
 import os
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--batches", default="32,1")
     ap.add_argument("--loops", default="greedy,sample_bare,sample_host_samplers,resident")
     ap.add_argument("--admission", action="store_true")
+    ap.add_argument("--stops", default=None, help="N,LEN: every resident slot carries N never-matching stop strings of LEN bytes")
     a = ap.parse_args()
     batches = [int(x) for x in a.batches.split(",")]
     B = max(batches)
@@ -61,6 +66,12 @@ def main():
     V = info.num_vocab
     first = [t % V for t in R.synth_prompt(900, B)]
     n, spr = a.tokens, a.steps_per_run
+    n_stops, stop_len = (int(x) for x in a.stops.split(",")) if a.stops else (0, 0)
+    stops = [bytes([122]) * (stop_len - 1) + bytes([48 + i]) for i in range(n_stops)]      # "zzz…0": the table below has no z
+    trng = np.random.default_rng(3)
+    tab = [bytes(trng.integers(97, 103, int(trng.integers(1, 5))).tolist()) for _ in range(V)]
+    if n_stops or "resident_1" in a.loops.split(","):
+        eng.gen_set_token_bytes(tab)
 
     def greedy(nb):
         t = time.perf_counter()
@@ -90,14 +101,35 @@ def main():
         for b in range(nb):
             eng.gen_arm(b, first[b], n, H.NucleusSampler(), seed=1)
         arm_s.setdefault(nb, []).append(time.perf_counter() - t)
+        for b in range(nb if n_stops else 0):
+            eng.gen_set_stops(b, stops)
         emitted = 0
         t = time.perf_counter()
         for _ in range(-(-n // spr)):
             _, _, ne, fin = eng.gen_run(spr)
             emitted += int(ne.sum())
+        dt = time.perf_counter() - t
+        for b in range(nb if n_stops else 0):
+            eng.gen_disarm(b)                                       # the next loop's slots carry no strings
+        return dt, emitted
+
+    def resident_1(nb):
+        """the only exact form without device stop strings: one rwkv_gen_run(1) per token, the host matcher over every slot's token"""
+        hs = stops or [b"zzzzzzzzzzzzzzz0"]
+        for b in range(nb):
+            eng.gen_arm(b, first[b], n, H.NucleusSampler(), seed=1)
+        ms = [H.StopMatcher(hs) for _ in range(nb)]
+        emitted = 0
+        t = time.perf_counter()
+        for _ in range(n):
+            toks, _, ne, fin = eng.gen_run(1)
+            emitted += int(ne.sum())
+            for b in range(nb):
+                if toks[0, b] != 0xFFFFFFFF:
+                    ms[b].push(tab[int(toks[0, b])])
         return time.perf_counter() - t, emitted
 
-    loops = {"greedy": greedy, "sample_bare": sample_bare, "sample_host_samplers": sample_host, "resident": resident}
+    loops = {"greedy": greedy, "sample_bare": sample_bare, "sample_host_samplers": sample_host, "resident": resident, "resident_1": resident_1}
     loops = {k: f for k, f in loops.items() if k in a.loops.split(",")}
 
     def admission(mode, running=24, joiners=8, every=16, plen=256, tail=4):
@@ -158,7 +190,7 @@ def main():
         return dt, emitted, lat, max(gaps), max(mixed)
 
     out = {"workload": f"RWKV-{a.workload} int8, default precision, synthetic weights", "tokens_per_slot_per_region": n, "steps_per_gen_run": spr,
-           "regions": a.regions, "load_s": load_s, "sampler": "Nucleus top_p 0.5 top_k 128 temperature 1.0 penalties 0.3 / 0.3 / 0.99654026",
+           "regions": a.regions, "load_s": load_s, "stop_strings_per_slot": n_stops, "stop_string_bytes": stop_len, "sampler": "Nucleus top_p 0.5 top_k 128 temperature 1.0 penalties 0.3 / 0.3 / 0.99654026",
            "batches": {}}
     for nb in batches:
         times = {k: [] for k in loops}
