@@ -106,6 +106,43 @@ def build_harness(verbose: bool = True) -> str:
     return HARNESS_BIN
 
 
+PROBE_DIR = os.path.join(HERE, "..", "tests", "cpp")
+PROBE_SRC = os.path.join(PROBE_DIR, "gemm_probe.hip")
+PROBE_BIN = os.path.join(PROBE_DIR, "gemm_probe")
+PROBE_STAMP = os.path.join(PROBE_DIR, ".gemm_probe_stamp")
+
+
+def compile_gemm_probe(obj: str) -> str:
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", PROBE_SRC, "-o", obj])
+    return obj
+
+
+def build_gemm_probe(verbose: bool = True) -> str:
+    """tests/cpp/gemm_probe.hip (the stand-alone GEMM probe of tests/test_gpu_gemm_exact.py) linked against the kernel objects of the
+    library build: they are self-contained (Knobs, use_knobs and every launch_* live in them).  The probe is compiled to an object first
+    (object files on the line of a .hip source would be read as HIP source).  Content-stamped like the library.  Built by the test that
+    runs it, not by build(): the library build depends on nothing under tests/."""
+    import hashlib
+    build(verbose=verbose)
+    h = hashlib.sha256(_sources_digest().encode())
+    for src in (PROBE_SRC, os.path.join(PROBE_DIR, "gemm_probe_plan.h")):
+        with open(src, "rb") as f:
+            h.update(f.read())
+    if os.path.exists(PROBE_BIN) and os.path.exists(PROBE_STAMP) and open(PROBE_STAMP).read().strip() == h.hexdigest():
+        return PROBE_BIN
+    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+    if not all(os.path.exists(p) for p in parts):
+        build(force=True, verbose=verbose)
+    obj = compile_gemm_probe(os.path.join(PROBE_DIR, "gemm_probe.o"))
+    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", PROBE_BIN]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    with open(PROBE_STAMP, "w") as f:
+        f.write(h.hexdigest())
+    return PROBE_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)

@@ -4,14 +4,33 @@
 //   with the argument "geometry" the line goes on with what the kernels of that launch index by:
 //     total_blocks strips_per_tile_block tokens_per_tile_block nprob {Kb ksb nslice nblk_strip spb nw block_begin tile_blocks}...
 //   (tile_blocks: gemm_tile_blocks of the problem on the planned shape, 0 on the other paths; the two per-block figures are 0 there too)
+//   with the argument "probe" it reads the launches of tests/gemm_cases.py instead and prints the plan line tests/cpp/gemm_probe.hip prints for
+//   them on the GPU (gemm_probe_plan.h: NT, tail and the per-problem geometry too):
+//     T hilo mode force_spb tile_shape ksplit xcd_map nslab nprob {rows K fmt partial kcopies smallk}...
 // Compiled with a plain host compiler: no HIP, no library of the project.
-#include "../../ai00_server_amd/csrc/gemm_plan.h"
+#include "gemm_probe_plan.h"
 #include <cstdio>
 #include <cstring>
 
 int main(int argc, char **argv) {
     const bool geometry = argc > 1 && !std::strcmp(argv[1], "geometry");
     using namespace rwkv;
+    if (argc > 1 && !std::strcmp(argv[1], "probe")) {
+        ProbeReq q;
+        for (int ci = 0; std::scanf("%d %d %d %d %d %d %d %d %d", &q.T, &q.hilo, &q.mode, &q.force_spb, &q.tile_shape, &q.ksplit, &q.xcd_map, &q.nslab, &q.nprob) == 9; ++ci) {
+            if (q.nprob < 1 || q.nprob > GEMM_MAXP) return 2;
+            ProbShape ps[GEMM_MAXP];
+            for (int i = 0; i < q.nprob; ++i) {
+                int partial, kcopies, smallk;
+                if (std::scanf("%d %d %d %d %d %d", &ps[i].rows, &ps[i].K, &ps[i].fmt, &partial, &kcopies, &smallk) != 6) return 2;
+                ps[i].partial = partial != 0; ps[i].kcopies = kcopies != 0; ps[i].smallk = smallk != 0;
+            }
+            ProbePlan r;
+            probe_plan(q, ps, r);
+            probe_print(stdout, ci, q, r);
+        }
+        return 0;
+    }
     int T, hilo, commit, n;
     Knobs kn;
     while (std::scanf("%d %d %d %d %d %d %d %d", &T, &hilo, &commit, &kn.no_tile, &kn.tile_shape, &kn.tile_ksplit, &kn.tile_xcd, &n) == 8) {
