@@ -246,8 +246,11 @@ struct MetaView {
 struct SampStage { SampleRow *rows; int *adj_row, *adj_tok; float *adj_val; int *out_tok; float *out_prob; const SampleRow *dv_rows; int *dv_out_tok; float *dv_out_prob; };
 
 // which sampler kernels a set of rows needs, as bits (also the last word of a generation graph's key)
-enum : unsigned { NEEDS_NT = 1, NEEDS_MIRO = 2 };               // nucleus / typical, mirostat
-static unsigned sampler_need(int kind) { return kind == RWKV_SAMPLER_MIROSTAT ? NEEDS_MIRO : NEEDS_NT; }
+enum : unsigned { NEEDS_NT = 1, NEEDS_MIRO = 2, NEEDS_WIDE = 4 };   // nucleus / typical, mirostat, rows of sample_wide_kernel (any kind)
+static unsigned sampler_need(int kind, bool wide = false) { return wide ? NEEDS_WIDE : kind == RWKV_SAMPLER_MIROSTAT ? NEEDS_MIRO : NEEDS_NT; }
+// Mirostat below 13 bits of surprise admits fewer than 2^13 tokens (p >= 2^-max_surprise each, plus one): nucleus_kernel's buffer is exact there
+constexpr float MIRO_WIDE_SURPRISE = 13.0f;
+constexpr int NARROW_TOP_K = 256;
 
 struct rwkv_dstate {
     int device = 0;
@@ -374,7 +377,7 @@ struct rwkv_engine {
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
     GenArgs gen_args(int n_rows, bool stops) const;
-    unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind); return k; }
+    unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
     void gen_step(const StepPlan &pl, unsigned needs, bool stops);
     void gen_decode_steps(const std::vector<int> &rows, int n);
@@ -1303,13 +1306,13 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
         if (pl.slot_out_rows[b] == 0) continue;
         const int r = pl.slot_out_begin[b];
         const rwkv_sample_params &p = sp[b];
-        if (p.kind != RWKV_SAMPLER_MIROSTAT && p.top_k > 256) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling supports top_k <= 256");
         if (p.kind != RWKV_SAMPLER_MIROSTAT && !(p.temperature > 0.f)) throw RwkvError(RWKV_ERR_INVALID, "temperature must be > 0");
         if (p.n_adj && (!p.adj_tokens || !p.adj_values)) throw RwkvError(RWKV_ERR_INVALID, "null adjustment arrays");
         if (nadj + p.n_adj > ADJ_CAP) throw RwkvError(RWKV_ERR_INVALID, "too many logit adjustments");
         if (p.kind < RWKV_SAMPLER_NUCLEUS || p.kind > RWKV_SAMPLER_MIROSTAT) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unknown sampler kind");
-        needs |= sampler_need(p.kind);
-        samp.rows[r] = SampleRow{p.top_p, p.top_k, p.temperature, p.uniform, p.kind, p.tau};
+        const bool wide = p.kind == RWKV_SAMPLER_MIROSTAT ? p.tau >= MIRO_WIDE_SURPRISE : p.top_k > NARROW_TOP_K;
+        needs |= sampler_need(p.kind, wide);
+        samp.rows[r] = SampleRow{p.top_p, std::min(p.top_k, info.num_vocab), p.temperature, p.uniform, p.kind | (wide ? SAMPLE_WIDE : 0), p.tau};
         if (p.allow) {                                             // formatter mask: staged row by row, one H2D copy for all
             std::memcpy(h_allow + (size_t)n_allow * info.num_vocab, p.allow, (size_t)info.num_vocab);
             h_allow_row[n_allow++] = r;
@@ -1331,7 +1334,7 @@ void rwkv_engine::infer_sample(const rwkv_slot_input *in, const rwkv_sample_para
             HIP_CHECK(hipMemcpyAsync(d_allow_row, h_allow_row, (size_t)n_allow * 4, hipMemcpyHostToDevice, s_main));
             launch_logit_mask(logits, info.num_vocab, d_allow_row, d_allow, n_allow, s_main);
         }
-        launch_nucleus(logits, pl.n_out, info.num_vocab, samp.dv_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, samp.dv_out_tok, samp.dv_out_prob, s_main);
+        launch_nucleus(logits, pl.n_out, info.num_vocab, samp.dv_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, samp.dv_out_tok, samp.dv_out_prob, s_main);
         HIP_CHECK(hipStreamSynchronize(s_main));
         for (int b = 0; b < max_batch; ++b) {
             if (pl.slot_out_rows[b] == 0) continue;
@@ -1490,7 +1493,8 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     if (p.allow) throw RwkvError(RWKV_ERR_UNSUPPORTED, "a formatter mask needs the host between tokens: use rwkv_infer_sample");
     if (p.kind < RWKV_SAMPLER_NUCLEUS || p.kind > RWKV_SAMPLER_MIROSTAT) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unknown sampler kind");
     const bool miro = p.kind == RWKV_SAMPLER_MIROSTAT;
-    if (!miro && p.top_k > 256) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling supports top_k <= 256");
+    if (!miro && p.top_k > NARROW_TOP_K && !(p.reserved & RWKV_GEN_WIDE_TOP_K))
+        throw RwkvError(RWKV_ERR_UNSUPPORTED, "top_k > 256 in resident generation needs RWKV_GEN_WIDE_TOP_K in `reserved`");
     if (p.n_stop > RWKV_GEN_MAX_STOP) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP stop tokens");
     if (!miro && !(p.temperature > 0.f)) throw RwkvError(RWKV_ERR_INVALID, "temperature must be > 0");
     if (p.max_tokens <= 0) throw RwkvError(RWKV_ERR_INVALID, "max_tokens must be > 0");
@@ -1505,9 +1509,12 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
         HIP_CHECK(hipMemcpy(d_gen_shadow + b, &gen_shadow[b], sizeof(float *), hipMemcpyHostToDevice));
     }
     GenSlot g{};
-    g.top_p = p.top_p; g.top_k = miro ? 1 : p.top_k; g.temperature = miro ? 1.0f : p.temperature; g.tau = p.tau; g.kind = p.kind;
+    g.top_p = p.top_p; g.top_k = miro ? 1 : std::min(p.top_k, info.num_vocab); g.temperature = miro ? 1.0f : p.temperature; g.tau = p.tau; g.kind = p.kind;
     g.presence = p.presence_penalty; g.frequency = p.frequency_penalty; g.decay = p.penalty_decay;
     g.miro_target = p.miro_target; g.miro_rate = p.miro_rate;
+    // wide for the slot's whole life: max_surprise starts at p.tau and every update caps it at 4 * target (mirostat.rs:87), and below
+    // 8192 candidates sample_wide_kernel returns nucleus_kernel's bits, so the run equals the per-token loop that routes by the current value
+    g.wide = (miro ? std::max(p.tau, 4.0f * p.miro_target) >= MIRO_WIDE_SURPRISE : p.top_k > NARROW_TOP_K) ? SAMPLE_WIDE : 0;
     g.seed = p.seed; g.stream = p.stream; g.draws = 0;
     g.max_tokens = p.max_tokens; g.emitted = 0; g.finish = RWKV_GEN_RUNNING; g.freeze_at = -1;
     g.n_stop = (int)p.n_stop;
@@ -1620,7 +1627,7 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops) const {
 // the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
 void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
-    launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, d_gen_tok, d_gen_prob, s_main); });
+    launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
 }

@@ -256,11 +256,13 @@ void launch_state_pack(const StatePackArgs &a, hipStream_t s);
 void launch_softmax(const float *in, float *out, int n_rows, int V, hipStream_t s);
 // out[r] = ln softmax(logits[r])[targets[r]], one pass over each row (n_rows > 0, V % 16 == 0); targets[r] >= V: not scored, out[r] = NaN
 void launch_score_rows(const float *logits, const unsigned *targets, float *out, int n_rows, int V, hipStream_t s);
-// on-device sampling front-end (f-1): V <= 65536, top_k <= 256
-struct SampleRow { float top_p; int top_k; float temperature; float uniform; int kind; float tau; };   // kind 0 nucleus, 1 typical, 2 mirostat (tau = max_surprise)
+// on-device sampling front-end (f-1): V <= 65536.  nucleus_kernel takes top_k <= 256 and Mirostat with fewer than 8192 candidates,
+// sample_wide_kernel the rows that carry SAMPLE_WIDE in `kind` (any top_k, any max_surprise); each row is written by exactly one of them
+constexpr int SAMPLE_WIDE = 4;
+struct SampleRow { float top_p; int top_k; float temperature; float uniform; int kind; float tau; };   // kind 0 nucleus, 1 typical, 2 mirostat (tau = max_surprise), | SAMPLE_WIDE
 void launch_logit_adjust(float *logits, int V, const int *rows, const int *toks, const float *vals, int n, hipStream_t s);
 void launch_logit_mask(float *logits, int V, const int *rows, const unsigned char *allow, int n, hipStream_t s);   // V % 4 == 0
-void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat,
+void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat, bool any_wide,
                     int *out_tok, float *out_prob, hipStream_t s);
 // ---- device-resident sampled generation (rwkv_gen_*, include/rwkv_abi.h): the sampler state machine of sampler/*.rs on the device ----
 constexpr unsigned GEN_ABSENT = 0xFFFFFFFFu;   // bit pattern of "no entry" in a slot's dense penalty row (membership, not value: nucleus.rs:104-119)
@@ -276,8 +278,9 @@ struct GenSlot {                    // one per slot, device-resident; the host k
     int freeze_at;                                          // step of the run in which the slot finished (gen_freeze copies its state then)
     int has_bias, n_stop;
     unsigned stop[GEN_MAX_STOP];
+    int wide;                                               // 0 or SAMPLE_WIDE: gen_pre ors it into the kind of the slot's SampleRow
 };
-struct alignas(16) GenStop {        // one per slot, beside GenSlot (whose size stays): the slot's stop STRINGS and the bytes its matcher still holds
+struct alignas(16) GenStop {        // one per slot, beside GenSlot: the slot's stop STRINGS and the bytes its matcher still holds
     unsigned char str[GEN_MAX_STOP_STR][GEN_STOP_LEN];      // 16-byte aligned: staged into LDS with uint4 loads
     unsigned char buf[GEN_STOP_BUF];                        // `context.buffer` (run.rs:869): written by the device only while the slot goes on
     unsigned short len[GEN_MAX_STOP_STR];

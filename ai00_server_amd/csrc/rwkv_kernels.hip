@@ -3224,7 +3224,7 @@ __device__ __forceinline__ float block_reduce_1024(float v, float *red, bool is_
 
 // NC = candidate capacity; MIRO = the Mirostat instantiation (kind 2 rows only; the other one takes kinds 0 and 1).
 // Mirostat (mirostat.rs:44-90): sort descending, k = 1 + #(tokens whose surprise -log2 p does not exceed max_surprise)
-// (exact while that fits NC = 8192, i.e. max_surprise < 13; beyond, the tail below 2^-13 is cut), no temperature,
+// (exact while that fits NC = 8192, i.e. max_surprise < 13; the engine routes the rows beyond to sample_wide_kernel), no temperature,
 // draw u * sum against the running sum; `out_prob` carries the token surprise log2(sum) - log2(p) the host needs for
 // its update of max_surprise.
 // FULL: V == 65536 exactly (the World vocabulary padded): no bound predicates at all — with them hipcc keeps 64 exec masks
@@ -3240,7 +3240,7 @@ __global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logit
     float *qv = (float *)(cand + NC);                              // [NC]
     const int row = blockIdx.x, tid = threadIdx.x;
     const SampleRow P = sp[row];
-    if ((P.kind == 2) != MIRO) return;                             // uniform per block
+    if ((P.kind & SAMPLE_WIDE) || (P.kind == 2) != MIRO) return;   // uniform per block; a wide row is sample_wide_kernel's
     const float *x = logits + (long)row * V;
     float p[NUC_EPT];
     float m = -INFINITY;
@@ -3428,6 +3428,272 @@ __global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logit
     }
 }
 
+// =====================================================================================
+// The wide sampler: the rows nucleus_kernel cannot hold in one LDS buffer — Nucleus / Typical with top_k > 256 (nucleus.rs:71-101 and
+// typical.rs:70-120 sort the whole vocabulary and `take(top_k)` for any top_k) and Mirostat whose max_surprise admits 8192 candidates or
+// more (mirostat.rs:55-74 truncates at max_surprise only).  Rows carry SAMPLE_WIDE in `kind`; every row is written by exactly one kernel.
+// Softmax, Typical key, threshold search, id-bound search, gather and sort are nucleus_kernel's, operation for operation (key descending,
+// ties to the lower id, zero-probability entries never candidates).  New: the sorted prefix comes in WINDOWS of NC candidates.  A window
+// is the k = min(NC, what top_k / the surprise count still allows) largest live keys; once walked, its entries are retired from the
+// registers (key := 0) by the predicate that admitted them, so the next search finds the next NC in rank order.  Here the id-bound search
+// runs whenever more keys tie at the threshold than k admits (nucleus_kernel: than the buffer holds), so that the admitted set is exactly
+// the walked set; the first k of the sorted buffer are the same entries either way.
+//   pass A  thread 0 walks the windows in rank order: sequential fp32 sums, as the reference and oracle/rwkv_ref.py form them;
+//           p and p^(1/T) (Typical: the recomputed probability) are put into LDS by the whole block first.
+//   pass B  the draw.  A walk that ended in window 0 (the common case) draws from the window still in LDS — then this kernel has
+//           done what nucleus_kernel does.  Otherwise the row is loaded again, the registers are recomputed (same operations, same
+//           bits: every reduction has a fixed order) and the windows are walked a second time; there is no room for a second copy.
+// Bit rule: on a row nucleus_kernel handles exactly (top_k <= 256; Mirostat with fewer than NC candidates) token and out_prob are
+// nucleus_kernel's bits.  Every value is written with plain vector stores.
+// =====================================================================================
+constexpr int WIDE_NC = 8192;
+template <bool FULL>
+__global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *logits, int V, const SampleRow *sp, int *out_tok,
+                                                                   float *out_prob) {
+    constexpr int NC = WIDE_NC;
+    extern __shared__ __attribute__((aligned(16))) unsigned char wide_smem[];
+    __shared__ float red[16];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sel[3];                                    // thread 0's verdict, -, candidate counter
+    unsigned long long *cand = (unsigned long long *)wide_smem;    // [NC] (key bits << 32) | ~id  -> sort descending
+    float *qv = (float *)(cand + NC);                              // [NC]
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const SampleRow P = sp[row];
+    if (!(P.kind & SAMPLE_WIDE)) return;                           // uniform per block
+    const bool miro = (P.kind & 3) == 2, typical = (P.kind & 3) == 1;
+    if (!miro && P.top_k < 1) {                                     // `.take(0)` -> token 0, as nucleus_kernel
+        if (tid == 0) { out_tok[row] = 0; if (out_prob) out_prob[row] = 0.f; }
+        return;
+    }
+    const float *x = logits + (long)row * V;
+    const float cut = typical ? P.tau : P.top_p;
+    float *cnt = (float *)hist;                                     // [2][16 waves][4], see nucleus_kernel
+    auto wcount3 = [](int &c1, int &c2, int &c3, unsigned key, unsigned t1, unsigned t2, unsigned t3) {   // c_i += #lanes(key >= t_i)
+        asm volatile("v_cmp_le_u32 vcc, %3, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %0, %0, vcc_lo\n\t"
+                     "v_cmp_le_u32 vcc, %4, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %1, %1, vcc_lo\n\t"
+                     "v_cmp_le_u32 vcc, %5, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %2, %2, vcc_lo"
+                     : "+s"(c1), "+s"(c2), "+s"(c3) : "s"(t1), "s"(t2), "s"(t3), "v"(key) : "vcc", "scc");
+    };
+    auto count3 = [&](int buf, float c1, float c2, float c3, float &s1, float &s2, float &s3) {
+        float *cb = cnt + buf * 64;
+        if ((tid & 63) == 0) { cb[(tid >> 6) * 4 + 0] = c1; cb[(tid >> 6) * 4 + 1] = c2; cb[(tid >> 6) * 4 + 2] = c3; }
+        __syncthreads();
+        s1 = s2 = s3 = 0.f;
+#pragma unroll
+        for (int w = 0; w < NUC_THREADS / 64; ++w) { s1 += cb[w * 4 + 0]; s2 += cb[w * 4 + 1]; s3 += cb[w * 4 + 2]; }
+    };
+    // thread 0's walk (the other threads carry the values along unused)
+    float cum = 0.f, sum = 0.f, c = 0.f, first_p = 0.f;
+    int n = 0, first_id = 0;
+    auto emit = [&](int id, float pr) {
+        out_tok[row] = id;
+        if (out_prob) out_prob[row] = miro ? log2f(sum) - log2f(pr) : pr;
+    };
+    // pass B over the first `limit` entries of the window in LDS; true when the token is out
+    auto draw = [&](int limit, bool last) {
+        const float r = P.uniform * sum;                            // mirostat.rs:78-79
+        int pick = -1;
+        for (int i0 = 0; i0 < limit && pick < 0; i0 += 8) {
+            float qq[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) qq[u] = qv[min(i0 + u, NC - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (pick < 0 && i0 + u < limit) {
+                    if (miro) { c += qq[u]; if (r <= c) pick = i0 + u; }
+                    else { c += qq[u] / sum; if (P.uniform <= c) pick = i0 + u; }
+                }
+            }
+        }
+        if (pick >= 0) {
+            const unsigned long long e = cand[pick];
+            emit((int)(0xFFFFFFFFu - (unsigned)(e & 0xFFFFFFFFull)), __uint_as_float((unsigned)(e >> 32)));
+            return true;
+        }
+        if (last) emit(first_id, first_p);                          // find_or_first: nothing found -> first element
+        return last;
+    };
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        float p[NUC_EPT];
+        float m = -INFINITY;
+        int lt = tid;                                               // opaque copy: keeps the 64 element ids (and addresses) from being
+        asm volatile("" : "+v"(lt));                                // hoisted out of the loops as 64 live registers beside the row
+#pragma unroll
+        for (int j = 0; j < NUC_EPT; ++j) {
+            const int i = j * NUC_THREADS + lt;
+            const float xv = x[FULL ? i : (i < V ? i : V - 1)];      // clamped, not predicated
+            p[j] = (FULL || i < V) ? xv : -INFINITY;
+            m = fmaxf(m, p[j]);
+        }
+        m = block_reduce_1024(m, red, true);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NUC_EPT; ++j) { p[j] = expf(p[j] - m); s += p[j]; }
+        s = block_reduce_1024(s, red, false);
+#pragma unroll
+        for (int j = 0; j < NUC_EPT; ++j) p[j] = p[j] / s;
+        if (typical) {                                              // typical.rs:70-108, the key as in nucleus_kernel
+            float h = 0.f;
+#pragma unroll
+            for (int j = 0; j < NUC_EPT; ++j) h += p[j] > 0.f ? p[j] * -logf(p[j]) : 0.f;
+            h = block_reduce_1024(h, red, false);
+#pragma unroll
+            for (int j = 0; j < NUC_EPT; ++j)
+                p[j] = __uint_as_float(p[j] > 0.f ? 0xFFFFFFFFu - __float_as_uint(fabsf(-logf(p[j]) - h)) : 0u);
+        }
+        int total_k = P.top_k;                                      // what the whole walk may take
+        if (miro) {
+            float cc = 0.f;
+#pragma unroll
+            for (int j = 0; j < NUC_EPT; ++j) cc += (p[j] > 0.f && !(-log2f(p[j]) > P.tau)) ? 1.f : 0.f;
+            total_k = (int)block_reduce_1024(cc, red, false) + 1;   // ... and the first token beyond max_surprise
+        }
+        if (total_k > V) total_k = V;
+        unsigned verdict = 0u;                                      // 1: pass A ended beyond window 0, 2: the token is out
+#pragma unroll 1
+        for (int w = 0; w < NUC_EPT * NUC_THREADS / NC && verdict == 0u; ++w) {
+            const int base = w * NC;
+            const int k = min(NC, total_k - base);                  // >= 1: the walk goes on only while base + NC < total_k
+            int wt = tid;
+            asm volatile("" : "+v"(wt));
+            unsigned thr = 0u;                                      // invariant: count(key >= thr) >= k
+#pragma unroll 1
+            for (int step = 0; step < 16; ++step) {
+                const int lo = 30 - 2 * step;
+                const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
+                const unsigned t1 = tu | (1u << lo), t2 = tu | (2u << lo), t3 = tu | (3u << lo);
+                int c1 = 0, c2 = 0, c3 = 0;
+#pragma unroll
+                for (int j = 0; j < NUC_EPT; ++j) wcount3(c1, c2, c3, __float_as_uint(p[j]), t1, t2, t3);
+                float s1, s2, s3;
+                count3(step & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
+                thr = s3 >= (float)k ? t3 : (s2 >= (float)k ? t2 : (s1 >= (float)k ? t1 : thr));
+            }
+            float n_ge, n_gt, n_dummy;
+            {
+                const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
+                const unsigned tge = tu < 1u ? 1u : tu, tgt = tu + 1u;
+                int cge = 0, cgt = 0, cxx = 0;
+#pragma unroll
+                for (int j = 0; j < NUC_EPT; ++j) wcount3(cge, cgt, cxx, __float_as_uint(p[j]), tge, tgt, tgt);
+                if (tu == 0xFFFFFFFFu) cgt = 0;
+                count3(0, (float)cge, (float)cgt, 0.f, n_ge, n_gt, n_dummy);
+            }
+            unsigned id_bound = 0xFFFFFFFFu;                        // keys == thr are admitted while id <= id_bound
+            if (n_ge > (float)k) {                                  // more ties than the window takes: the `need` lowest ids
+                const float need = (float)k - n_gt;
+                unsigned lim = 0u;
+#pragma unroll 1
+                for (int step = 0; step < 9; ++step) {
+                    const int lo = 16 - 2 * step;
+                    const unsigned lu = __builtin_amdgcn_readfirstlane(lim);
+                    const unsigned t1 = lu | (1u << lo), t2 = lu | (2u << lo), t3 = lu | (3u << lo);
+                    int c1 = 0, c2 = 0, c3 = 0;
+#pragma unroll
+                    for (int j = 0; j < NUC_EPT; ++j) {
+                        const unsigned id = (unsigned)(j * NUC_THREADS + wt);
+                        const unsigned idv = (__float_as_uint(p[j]) == thr) ? id : 0xFFFFFFFFu;
+                        wcount3(c1, c2, c3, idv, t1, t2, t3);
+                    }
+                    c1 = NUC_EPT * 64 - c1; c2 = NUC_EPT * 64 - c2; c3 = NUC_EPT * 64 - c3;
+                    float s1, s2, s3;
+                    count3((step + 1) & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
+                    lim = s3 < need ? t3 : (s2 < need ? t2 : (s1 < need ? t1 : lim));
+                }
+                id_bound = lim;
+            }
+            if (tid == 0) sel[2] = 0u;
+            for (int i = tid; i < NC; i += NUC_THREADS) cand[i] = 0ull;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < NUC_EPT; ++j) {
+                const int i = j * NUC_THREADS + wt;
+                const unsigned key = __float_as_uint(p[j]);
+                if (key != 0u && (key > thr || (key == thr && (unsigned)i <= id_bound))) {
+                    const unsigned slot = atomicAdd(&sel[2], 1u);   // slot order is arbitrary, the SET is not; sorted below
+                    if (slot < NC) cand[slot] = ((unsigned long long)key << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
+                }
+            }
+            __syncthreads();
+            const int wn = min((int)min(sel[2], (unsigned)NC), k);  // entries of this window (at most k were admitted)
+            int sz = 2;
+            while (sz < wn) sz <<= 1;                               // the zeros behind the entries need no sorting
+            for (int size = 2; size <= sz; size <<= 1) {            // bitonic sort, descending
+                for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (int i = tid; i < sz; i += NUC_THREADS) {
+                        const int j = i ^ stride;
+                        if (j > i) {
+                            const bool desc = (i & size) == 0;
+                            const unsigned long long a = cand[i], b = cand[j];
+                            if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
+            for (int i = tid; i < wn; i += NUC_THREADS) {           // what thread 0 adds up: no transcendental in its loop
+                const unsigned long long e = cand[i];
+                float pr = __uint_as_float((unsigned)(e >> 32));
+                if (typical) {                                      // the probability behind the key, recomputed; it replaces the key
+                    const int id = (int)(0xFFFFFFFFu - (unsigned)(e & 0xFFFFFFFFull));
+                    pr = expf(x[id] - m) / s;
+                    cand[i] = ((unsigned long long)__float_as_uint(pr) << 32) | (e & 0xFFFFFFFFull);
+                }
+                qv[i] = miro ? pr : powf(pr, 1.0f / P.temperature);   // nucleus.rs:92, typical.rs:96
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned v = 0u;
+                if (pass == 0) {
+                    if (w == 0 && wn > 0) {
+                        first_id = (int)(0xFFFFFFFFu - (unsigned)(cand[0] & 0xFFFFFFFFull));
+                        first_p = __uint_as_float((unsigned)(cand[0] >> 32));
+                    }
+                    bool stop = false;
+                    for (int i0 = 0; i0 < wn && !stop; i0 += 8) {
+                        float pp[8], qq[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) {
+                            const int i = min(i0 + u, NC - 1);
+                            pp[u] = __uint_as_float((unsigned)(cand[i] >> 32));
+                            qq[u] = qv[i];
+                        }
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) {
+                            if (!stop && i0 + u < wn) {
+                                if (!miro && cum > cut) stop = true;   // keep while the cumulative BEFORE the element is <= cut
+                                else { cum += pp[u]; sum += qq[u]; ++n; }
+                            }
+                        }
+                    }
+                    if (stop || wn < k || base + wn >= total_k) {   // the cut, the keys ran out, top_k / the surprise bound reached
+                        if (n < 1 && wn > 0) { n = 1; sum = qv[0]; }   // as nucleus_kernel: at least the first element
+                        if (n < 1) { out_tok[row] = 0; if (out_prob) out_prob[row] = 0.f; v = 2u; }   // a row without a single live key
+                        else if (w == 0) { draw(n, true); v = 2u; }
+                        else v = 1u;
+                    }
+                } else {
+                    const int limit = min(wn, n - base);
+                    v = draw(limit, base + limit >= n || wn < k) ? 2u : 0u;
+                }
+                sel[0] = v;
+            }
+            __syncthreads();
+            verdict = sel[0];
+            if (verdict == 0u) {                                    // retire the window: the predicate that admitted its entries
+#pragma unroll
+                for (int j = 0; j < NUC_EPT; ++j) {
+                    const int i = j * NUC_THREADS + wt;
+                    const unsigned key = __float_as_uint(p[j]);
+                    if (key != 0u && (key > thr || (key == thr && (unsigned)i <= id_bound))) p[j] = 0.f;
+                }
+            }
+        }
+        if (verdict == 2u) return;
+    }
+}
+
 // formatter masks (run.rs:676-679, sampler/bnf.rs:35-38): row rows[j] keeps only the tokens with allow[j][token] != 0
 __global__ __launch_bounds__(256) void logit_mask_kernel(float *logits, int V, const int *rows, const unsigned char *allow) {
     const int j = blockIdx.y;
@@ -3453,7 +3719,7 @@ void launch_logit_mask(float *logits, int V, const int *rows, const unsigned cha
 void launch_logit_adjust(float *logits, int V, const int *rows, const int *toks, const float *vals, int n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(logit_adjust_kernel, dim3((n + 255) / 256), dim3(256), 0, s, logits, V, rows, toks, vals, n);
 }
-void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat,
+void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat, bool any_wide,
                     int *out_tok, float *out_prob, hipStream_t s) {
     constexpr int NC0 = NUC_CAND, NC2 = 8192;
     static bool attr_done[16] = {false};
@@ -3462,6 +3728,8 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
     if (!attr_done[dev & 15]) {
         (void)hipFuncSetAttribute((const void *)nucleus_kernel<NC2, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NC2 * 12);
         (void)hipFuncSetAttribute((const void *)nucleus_kernel<NC2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NC2 * 12);
+        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_NC * 12);
+        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_NC * 12);
         attr_done[dev & 15] = true;
     }
     const bool full = V == NUC_EPT * NUC_THREADS;
@@ -3469,6 +3737,10 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
                                   else hipLaunchKernelGGL((nucleus_kernel<nc, miro, false>), dim3(n_rows), dim3(NUC_THREADS), nc * 12, s, logits, V, sp, out_tok, out_prob); } while (0)
     if (any_nucleus_typical) NUC_LAUNCH(NC0, false);
     if (any_mirostat) NUC_LAUNCH(NC2, true);
+    if (any_wide) {                                                // rows with SAMPLE_WIDE; the launches above return at once for them
+        if (full) hipLaunchKernelGGL(sample_wide_kernel<true>, dim3(n_rows), dim3(NUC_THREADS), WIDE_NC * 12, s, logits, V, sp, out_tok, out_prob);
+        else hipLaunchKernelGGL(sample_wide_kernel<false>, dim3(n_rows), dim3(NUC_THREADS), WIDE_NC * 12, s, logits, V, sp, out_tok, out_prob);
+    }
 #undef NUC_LAUNCH
 }
 
@@ -3519,7 +3791,7 @@ __global__ __launch_bounds__(256) void gen_pre_kernel(GenArgs a) {
         return;
     }
     if (blockIdx.x == 0 && tid == 0)
-        a.rows[row] = SampleRow{g.top_p, g.top_k, g.temperature, gen_uniform_draw(g.seed, g.stream, g.draws), g.kind, g.tau};
+        a.rows[row] = SampleRow{g.top_p, g.top_k, g.temperature, gen_uniform_draw(g.seed, g.stream, g.draws), g.kind | g.wide, g.tau};
     const bool pen = g.kind != 2;                                  // Mirostat's transform is a no-op (mirostat.rs:40)
     if (!pen && !g.has_bias) return;
     const int V = a.V;

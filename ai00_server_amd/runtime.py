@@ -251,6 +251,7 @@ class GenFinish(enum.IntEnum):   # RWKV_GEN_*: FinishReason::{Stop, Length} run.
 
 
 GEN_MAX_STOP_STR, GEN_STOP_LEN, GEN_STOP_BUF, GEN_TOKEN_LEN = 8, 128, 512, 256      # RWKV_GEN_* limits of the device's stop-string matcher
+GEN_WIDE_TOP_K = 1               # RWKV_GEN_WIDE_TOP_K: bit of rwkv_gen_params.reserved that arms Nucleus / Typical with top_k > 256
 
 
 def list_adapters() -> list[str]:
@@ -600,7 +601,7 @@ class Runtime:
         return out
 
     # ---- device-resident sampled generation (rwkv_gen_arm / _run / _disarm): the sampler state lives on the device
-    def _gen_params(self, slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow):
+    def _gen_params(self, slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k=False):
         """rwkv_gen_params from the settings AND the current state of a host-side sampler; returns (struct, arrays to keep alive)"""
         kind = int(getattr(sampler, "kind", 0))
         pen = {} if kind == 2 else dict(getattr(sampler, "penalties", {}))
@@ -621,26 +622,27 @@ class Runtime:
                         bt.ctypes.data_as(u32p) if bt.size else None, bv.ctypes.data_as(f32p) if bv.size else None, bt.size,
                         st.ctypes.data_as(u32p) if st.size else None, st.size,
                         allow.ctypes.data_as(C.POINTER(C.c_uint8)) if allow is not None else None,
-                        int(seed), int(slot if stream is None else stream), 0)
+                        int(seed), int(slot if stream is None else stream), GEN_WIDE_TOP_K if wide_top_k else 0)
         return p, (pt, pv, bt, bv, st, allow)
 
     def gen_arm(self, slot: int, first_token: int, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
-                stop_tokens=(), bias: dict | None = None, allow=None):
+                stop_tokens=(), bias: dict | None = None, allow=None, wide_top_k: bool = False):
         """Arm `slot` with the settings AND the current state of a host-side sampler (`harness.NucleusSampler` / `TypicalSampler` /
         `MirostatSampler`, after its `init(prompt)`): the penalty map it holds is handed over, `sampler.bias` (or `bias`) rides along.
         `first_token` is the token the first step consumes; draw `i` of the slot is `gen_uniform(seed, stream, i)` (stream defaults
-        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`)."""
-        p, keep = self._gen_params(slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow)
+        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`).
+        `wide_top_k` sets RWKV_GEN_WIDE_TOP_K: Nucleus / Typical with `top_k > 256` is armed instead of refused."""
+        p, keep = self._gen_params(slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k)
         _check(lib().rwkv_gen_arm(self._h, int(slot), C.byref(p)))
         del keep
 
     def gen_arm_prompt(self, slot: int, tokens, max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
-                       stop_tokens=(), bias: dict | None = None, allow=None):
+                       stop_tokens=(), bias: dict | None = None, allow=None, wide_top_k: bool = False):
         """Admission (rwkv_gen_arm_prompt): arm `slot` with the not-yet-consumed tail of its PROMPT instead of a first token.  The
         following `gen_run` steps prefill it next to the decode rows of the slots that are running and draw its first token on the
         device (draw 0 of (seed, stream)) from the prompt's last row.  `sampler` is the host sampler right after `init(prompt)`,
         before any `update`: its penalty map is handed over as in `gen_arm`."""
-        p, keep = self._gen_params(slot, 0, max_tokens, sampler, seed, stream, stop_tokens, bias, allow)
+        p, keep = self._gen_params(slot, 0, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k)
         toks = np.ascontiguousarray(list(tokens), dtype=np.uint32).reshape(-1)
         _check(lib().rwkv_gen_arm_prompt(self._h, int(slot), toks.ctypes.data_as(C.POINTER(C.c_uint32)) if toks.size else None, toks.size,
                                          C.byref(p)))

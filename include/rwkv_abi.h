@@ -225,8 +225,10 @@ rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const ui
  * The caller keeps the sampler STATE (penalty map, nucleus.rs:104-119) and passes its effect as sparse logit
  * adjustments (-penalty[token] + bias[token], duplicates merged) plus the uniform draw `fastrand::f32()` would make. */
 typedef struct rwkv_sample_params {
-    float top_p;                   /* NucleusParams defaults: 0.5 / 128 / 1.0 (nucleus.rs:13-26); top_k <= 256 */
-    int32_t top_k;
+    float top_p;                   /* NucleusParams defaults: 0.5 / 128 / 1.0 (nucleus.rs:13-26) */
+    int32_t top_k;                 /* any value: above num_vocab it is num_vocab, below 1 nothing is kept and the token is 0.  The candidates */
+                                   /*   are ordered by key descending, TIES TO THE LOWER TOKEN ID (the reference's sort is unstable); tokens  */
+                                   /*   of probability 0 are never candidates.  top_k <= 256 runs the narrow kernel, above it the wide one.  */
     float temperature;
     float uniform;                 /* u in [0,1) */
     const uint32_t *adj_tokens;    /* may be NULL when n_adj == 0 */
@@ -238,7 +240,9 @@ typedef struct rwkv_sample_params {
                                    /* RWKV_SAMPLER_MIROSTAT (mirostat.rs:44-90): tau = the sampler's current `max_surprise`;  */
                                    /*   top_p / top_k / temperature unused; out_probs[b] returns the TOKEN SURPRISE           */
                                    /*   log2(sum) - log2(p) the caller needs for `max_surprise -= rate * (surprise - tau)`.   */
-                                   /*   Exact while max_surprise < 13 (<= 8192 candidates); beyond, the tail below 2^-13 is cut. */
+                                   /*   Exact for every max_surprise: below 13 (fewer than 8192 candidates can qualify) the narrow kernel    */
+                                   /*   holds them all, from 13 on the wide one walks the sorted row in windows of 8192.  BIT RULE: on a row */
+                                   /*   both kernels can hold, the wide one returns the narrow one's token and out_probs bits.              */
     const uint8_t *allow;          /* NULL, or num_vocab bytes: allow[token] == 0 forbids the token (its logit becomes -inf before  */
                                    /*   the softmax).  This is what a `Formatter::transform` leaves behind (run.rs:676-679,         */
                                    /*   sampler/bnf.rs:35-38: kbnf's mask_logits): the grammar state machine stays on the host and  */
@@ -286,8 +290,12 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
  *    finish; the caller, who has every token, replays its own matcher (include/rwkv_scheduler.hpp StopMatcher) and goes on per token.
  *    A slot that finishes — whatever the reason — leaves its buffer as it was before its last token.
  *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a formatter mask (`allow` must be NULL: a grammar needs the
- *    host between two tokens, run.rs:676-679 — keep using rwkv_infer_sample), top_k > 256 (Nucleus / Typical), more than
- *    RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
+ *    host between two tokens, run.rs:676-679 — keep using rwkv_infer_sample), top_k > 256 (Nucleus / Typical) unless `reserved` carries
+ *    RWKV_GEN_WIDE_TOP_K, more than RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
+ *  - RWKV_GEN_WIDE_TOP_K (bit 0 of `reserved`; the other bits are ignored) arms Nucleus / Typical with any top_k (above num_vocab:
+ *    num_vocab); the slot then takes the wide kernel iff top_k > 256.  Mirostat needs no flag: a slot whose max_surprise can reach 13
+ *    (max(tau, 4 * miro_target) >= 13) takes the wide kernel for its whole life, and by the bit rule (rwkv_sample_params) it emits what
+ *    the per-token path emits, which routes by the current max_surprise.
  *  - rwkv_infer on OTHER slots between two runs is allowed (continuous batching: prefill a new request, arm it, carry on).  rwkv_infer /
  *    rwkv_infer_sample with tokens for an armed slot, rwkv_state_load and rwkv_state_write on it disarm it.
  *  Same thread contract as rwkv_infer (the `infer` task). */
@@ -296,6 +304,7 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
 #define RWKV_GEN_STOP_LEN 128     /* bytes per stop string                                  */
 #define RWKV_GEN_STOP_BUF 512     /* bytes of matcher buffer per slot (`context.buffer`)    */
 #define RWKV_GEN_TOKEN_LEN 256    /* bytes per token of the token table                     */
+#define RWKV_GEN_WIDE_TOP_K 1     /* rwkv_gen_params.reserved: top_k > 256 is armed, not refused */
 typedef struct rwkv_gen_params rwkv_gen_params;
 struct rwkv_gen_params {
     uint32_t first_token;          /* the token the first step consumes: the one the caller sampled from the prompt's row (run.rs:809-832)  */
@@ -321,7 +330,7 @@ struct rwkv_gen_params {
     const uint8_t *allow;          /* must be NULL (see above)                                                                              */
     uint64_t seed;                 /* rwkv_gen_uniform(seed, stream, step)                                                                  */
     uint32_t stream;
-    uint32_t reserved;
+    uint32_t reserved;             /* RWKV_GEN_WIDE_TOP_K or 0                                                                              */
 };
 enum { RWKV_GEN_RUNNING = 0, RWKV_GEN_STOP = 1, RWKV_GEN_LENGTH = 2,     /* FinishReason::{Stop, Length} run.rs:905-917; 0 = not finished */
        RWKV_GEN_HANDBACK = 3 };   /* the slot's stop-string buffer is full: the device cannot decide this token, the caller goes on (see above) */

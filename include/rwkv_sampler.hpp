@@ -81,6 +81,7 @@ class NucleusSampler {
         rwkv_gen_params p{};
         p.first_token = first_token; p.max_tokens = max_tokens; p.kind = RWKV_SAMPLER_NUCLEUS;
         p.top_p = top_p; p.top_k = top_k; p.temperature = temperature;
+        p.reserved = top_k > 256 ? RWKV_GEN_WIDE_TOP_K : 0u;        // any top_k, as nucleus.rs:78 / typical.rs:93 take it: the wide kernel's rows
         p.presence_penalty = presence_penalty; p.frequency_penalty = frequency_penalty; p.penalty_decay = penalty_decay;
         p.penalty_tokens = keep.penalty_tokens.empty() ? nullptr : keep.penalty_tokens.data();
         p.penalty_values = keep.penalty_values.empty() ? nullptr : keep.penalty_values.data();

@@ -37,6 +37,7 @@ pub const RWKV_GEN_MAX_STOP_STR: usize = 8;
 pub const RWKV_GEN_STOP_LEN: usize = 128;
 pub const RWKV_GEN_STOP_BUF: usize = 512;
 pub const RWKV_GEN_TOKEN_LEN: usize = 256;
+pub const RWKV_GEN_WIDE_TOP_K: u32 = 1;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 pub const RWKV_SCORE_SKIP: u32 = 4294967295;
 

@@ -263,13 +263,13 @@ impl Engine {
         let (pt, pv): (Vec<u32>, Vec<f32>) = p.penalties.iter().copied().unzip();
         let (bt, bv): (Vec<u32>, Vec<f32>) = p.bias.iter().copied().unzip();
         let raw = sys::rwkv_gen_params {
-            first_token: p.first_token, max_tokens: p.max_tokens as i32, kind: p.kind as i32, top_p: p.top_p, top_k: p.top_k as i32,
+            first_token: p.first_token, max_tokens: p.max_tokens as i32, kind: p.kind as i32, top_p: p.top_p, top_k: p.top_k.min(i32::MAX as usize) as i32,
             temperature: p.temperature, tau: p.tau, presence_penalty: p.presence_penalty, frequency_penalty: p.frequency_penalty,
             penalty_decay: p.penalty_decay, miro_target: p.miro_target, miro_rate: p.miro_rate,
             penalty_tokens: pt.as_ptr(), penalty_values: pv.as_ptr(), n_penalty: pt.len(),
             bias_tokens: bt.as_ptr(), bias_values: bv.as_ptr(), n_bias: bt.len(),
             stop_tokens: p.stop_tokens.as_ptr(), n_stop: p.stop_tokens.len(), allow: ptr::null(),
-            seed: p.seed, stream: p.stream, reserved: 0,
+            seed: p.seed, stream: p.stream, reserved: if p.top_k > 256 { sys::RWKV_GEN_WIDE_TOP_K } else { 0 },
         };
         match prompt {
             None => check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) }),
@@ -313,7 +313,8 @@ impl Engine {
 #[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum SamplerKind { #[default] Nucleus = 0, Typical = 1, Mirostat = 2 }
 /// `rwkv_gen_params`: sampler settings (nucleus.rs:13-26, typical.rs:11-24, mirostat.rs:11-36), the penalty map `init` left over the
 /// prompt (nucleus.rs:49-59), `GenerateRequest::bias` (run.rs:681-683), stop tokens (token 0 always stops, run.rs:855) and the
-/// (seed, stream) of the counter-based uniform draw (`gen_uniform`).
+/// (seed, stream) of the counter-based uniform draw (`gen_uniform`).  `top_k` is any `usize`, as in the reference: above 256 the slot is
+/// armed with `RWKV_GEN_WIDE_TOP_K` and sampled by the wide kernel; Mirostat is exact for every `max_surprise`.
 #[derive(Clone, Debug, Default)]
 pub struct GenParams {
     pub first_token: u32, pub max_tokens: usize, pub kind: SamplerKind, pub top_p: f32, pub top_k: usize, pub temperature: f32, pub tau: f32,
