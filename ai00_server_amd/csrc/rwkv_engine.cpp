@@ -104,11 +104,13 @@ struct PfHeader { char magic[8]; uint32_t version, n_entries; rwkv_model_info in
 struct PfEntry { PfEntryHead h; const uint8_t *data = nullptr, *scales = nullptr; };
 // the dimension rules every loaded model must satisfy (kernel tiling), whether the header comes from tensor shapes or a prefab
 static void validate_info(const rwkv_model_info &i) {
-    if (i.version != 5 && i.version != 6 && i.version != 7) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unsupported model version");
+    if (i.version != 4 && i.version != 5 && i.version != 6 && i.version != 7) throw RwkvError(RWKV_ERR_UNSUPPORTED, "unsupported model version");
     if (i.num_layer <= 0 || i.num_layer > 4096 || i.num_emb <= 0 || i.num_hidden <= 0 || i.num_vocab <= 0 || i.num_head <= 0 ||
         i.num_vocab > (1 << 24) || i.num_hidden > (1 << 20))
         throw RwkvError(RWKV_ERR_FORMAT, "model dimensions out of range");
-    if (i.head_size != 64 || (int64_t)i.num_emb != (int64_t)i.num_head * 64) throw RwkvError(RWKV_ERR_UNSUPPORTED, "head size must be 64");
+    if (i.version == 4) {                                        // V4 has no heads: reported as one head of num_emb channels
+        if (i.num_head != 1 || i.head_size != i.num_emb) throw RwkvError(RWKV_ERR_FORMAT, "a V4 model has num_head 1 and head_size num_emb");
+    } else if (i.head_size != 64 || (int64_t)i.num_emb != (int64_t)i.num_head * 64) throw RwkvError(RWKV_ERR_UNSUPPORTED, "head size must be 64");
     if (i.num_emb % 64 || i.num_hidden % 32 || i.num_vocab % 16)
         throw RwkvError(RWKV_ERR_UNSUPPORTED, "dims must satisfy C%64==0, F%32==0, V%16==0");
     if (i.num_emb > 8192) throw RwkvError(RWKV_ERR_UNSUPPORTED, "num_emb > 8192");
@@ -168,6 +170,22 @@ struct Prefab {
     bool has(const std::string &name) const { return entries.count(name) != 0; }
 };
 
+// V4 is taken on positive evidence only: none of the tensors a later version adds, time_first / time_decay as plain [C] vectors, and the five
+// token-shift mixes of its time mix and channel mix
+static bool looks_like_v4(const SafeTensors &st) {
+    for (const char *n : {"att.ln_x.weight", "att.gate.weight", "att.time_mix_x", "att.x_r"})
+        if (st.find(std::string("blocks.0.") + n)) return false;
+    const StTensor *emb = st.find("emb.weight");
+    if (!emb || emb->shape.size() != 2) return false;
+    for (const char *n : {"att.time_first", "att.time_decay"}) {
+        const StTensor *t = st.find(std::string("blocks.0.") + n);
+        if (!t || (int64_t)t->numel() != (int64_t)emb->shape[1]) return false;
+    }
+    for (const char *n : {"att.time_mix_k", "att.time_mix_v", "att.time_mix_r", "ffn.time_mix_k", "ffn.time_mix_r"})
+        if (!st.find(std::string("blocks.0.") + n)) return false;
+    return true;
+}
+
 static rwkv_model_info detect_info(const SafeTensors &st) {
     rwkv_model_info i{};
     if (st.find("blocks.0.att.x_r")) i.version = 7;
@@ -177,7 +195,8 @@ static rwkv_model_info detect_info(const SafeTensors &st) {
         if (td.shape.size() < 2 || td.shape.back() <= 1)
             throw RwkvError(RWKV_ERR_UNSUPPORTED, "RWKV v5.0/v5.1 checkpoints are not supported (need v5.2)");
         i.version = 5;
-    } else
+    } else if (looks_like_v4(st)) i.version = 4;
+    else
         throw RwkvError(RWKV_ERR_UNSUPPORTED, "unsupported model version (v4 or unknown tensor naming)");
     int L = 0;
     while (st.find("blocks." + std::to_string(L) + ".ln1.weight")) ++L;
@@ -193,7 +212,7 @@ static rwkv_model_info detect_info(const SafeTensors &st) {
     };
     if (emb.shape[0] <= 0 || emb.shape[0] > (1 << 24) || emb.shape[1] <= 0 || emb.shape[1] > (1 << 20)) throw RwkvError(RWKV_ERR_FORMAT, "emb.weight: unexpected shape");
     i.num_hidden = dim0("blocks.0.ffn.key.weight", 2);
-    i.num_head = i.version == 7 ? dim0("blocks.0.att.r_k", 2) : dim0("blocks.0.att.time_first", 2);
+    i.num_head = i.version == 4 ? 1 : i.version == 7 ? dim0("blocks.0.att.r_k", 2) : dim0("blocks.0.att.time_first", 2);
     i.head_size = i.num_emb / std::max(1, i.num_head);
     validate_info(i);
     return i;
@@ -207,11 +226,11 @@ static const char *kFamilyNames[RWKV_PROFILE_FAMILIES] = {"gemm_layers", "gemm_h
 
 struct LayerW {
     const float *ln1w, *ln1b, *ln2w, *ln2b, *lnxw, *lnxb;
-    const float *mu[6];             // att mixes (v5: k,v,r,g; v6: x,w,k,v,r,g; v7: r,w,k,v,a,g)
+    const float *mu[6];             // att mixes (v4: k,v,r; v5: k,v,r,g; v6: x,w,k,v,r,g; v7: r,w,k,v,a,g)
     const float *fmu[2];            // ffn mixes (v5/v6: k,r; v7: k)
     const DMat *Wr, *Wk, *Wv, *Wg, *Wo, *Fk, *Fv, *Fr;
     // v5/v6
-    const float *wdec;              // v5: exp(-exp(decay)); v6: raw time_decay
+    const float *wdec;              // v4: -exp(decay); v5: exp(-exp(decay)); v6: raw time_decay
     const float *u;
     const DMat *W1;                 // v6 time_mix_w1 [5Dm x C]
     const DMat *W2[5];              // v6 time_mix_w2 [C x Dm] x5
@@ -267,7 +286,7 @@ struct rwkv_engine {
     // V7's Wr / Wk / Wv inputs carry 4.7e-3 of its 4.9e-3 at 32 layers).  The mask is chosen from the model version (promote_for_version):
     // that IS RWKV_PRECISION_FP16 since ABI 7; RWKV_PRECISION_FP16_RAW is mask 0; RWKV_PROMOTE=<mask> is a dev override of either.
     enum OpdClass { CLS_ATT = 0, CLS_LORA2 = 1, CLS_WO = 2, CLS_FFN1 = 3, CLS_FV = 4, CLS_HEAD = 5, CLS_NONE = 31 };
-    static int promote_for_version(int version) { return version == 7 ? 7 : 1; }   // V5 / V6: CLS_ATT; V7: CLS_ATT | CLS_LORA2 | CLS_WO
+    static int promote_for_version(int version) { return version == 7 ? 7 : 1; }   // V4 / V5 / V6: CLS_ATT; V7: CLS_ATT | CLS_LORA2 | CLS_WO
     int promote = 0;
     bool wide(int cls) const { return hilo || (cls < 31 && ((promote >> cls) & 1)); }
     int quant_layers = 0, quant_type = 0;
@@ -276,7 +295,7 @@ struct rwkv_engine {
     int cur_layer = -1;                                        //   (grid, rows, K, stored bytes, flops): scripts/roofline_table.py joins it with rocprofv3's CSV
     hipStream_t s_copy = nullptr;                              // rwkv_state_back_layer_async: pack + device-to-host copy beside the compute stream
     hipEvent_t ev_copy_a = nullptr, ev_copy_b = nullptr;
-    float *emb_stage = nullptr;                                // [max_batch][64 * C]: one packed layer slice per slot
+    float *emb_stage = nullptr;                                // [max_batch][64 * C] (V4: [3 * C]): one packed layer slice per slot
     std::vector<void *> allocs, host_allocs;                   // dalloc / hostalloc
     std::map<std::string, DMat> mats;
     std::map<std::string, float *> vecs;
@@ -293,6 +312,18 @@ struct rwkv_engine {
     // state (internal layout)
     float *sxa = nullptr, *sxf = nullptr, *wkv = nullptr;
     long sx_slot_stride = 0, wkv_slot_stride = 0;
+    // The state as the ABI shows it has slab_rows() rows of C floats per layer: the two shift rows around the layer's WKV rows.  V5 / V6 / V7: 64
+    // WKV rows, the H 64 x 64 head matrices (wkv_layer_floats = H * 4096).  V4: three, aa / bb / pp (wkv_layer_floats = 3 * C).
+    int slab_rows() const { return info.version == 4 ? 5 : 66; }
+    long wkv_layer_floats() const { return (long)(slab_rows() - 2) * info.num_emb; }
+    size_t state_len() const { return (size_t)info.num_layer * slab_rows() * info.num_emb; }
+    void fill_init_state(float *dst) const {                     // the slab `state.init()` hands out
+        std::fill(dst, dst + state_len(), 0.f);
+        if (info.version != 4) return;
+        const size_t C = (size_t)info.num_emb;
+        for (int l = 0; l < info.num_layer; ++l) std::fill(dst + ((size_t)l * 5 + 3) * C, dst + ((size_t)l * 5 + 4) * C, V4_PP_INIT);
+    }
+    static constexpr float V4_PP_INIT = -1e30f;                  // [EXT] include/rwkv_abi.h
     float *slab_dev = nullptr;      // staging for pack/unpack
     float *slab_host = nullptr;     // pinned
 
@@ -505,12 +536,15 @@ static bool lora_scope(const std::string &name) {
 
 static bool is_quant_target(int version, const std::string &suffix) {
     static const char *att56[] = {"att.receptance.weight", "att.key.weight", "att.value.weight", "att.output.weight", "att.gate.weight"};
-    static const char *att7[] = {"att.receptance.weight", "att.key.weight", "att.value.weight", "att.output.weight"};
+    static const char *att7[] = {"att.receptance.weight", "att.key.weight", "att.value.weight", "att.output.weight"};   // V4's as well: no gate
     static const char *ffn56[] = {"ffn.key.weight", "ffn.value.weight", "ffn.receptance.weight"};
     static const char *ffn7[] = {"ffn.key.weight", "ffn.value.weight"};
     if (version == 7) {
         for (auto s : att7) if (suffix == s) return true;
         for (auto s : ffn7) if (suffix == s) return true;
+    } else if (version == 4) {
+        for (auto s : att7) if (suffix == s) return true;
+        for (auto s : ffn56) if (suffix == s) return true;
     } else {
         for (auto s : att56) if (suffix == s) return true;
         for (auto s : ffn56) if (suffix == s) return true;
@@ -788,7 +822,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         // forward pass assumes, so a truncated or inconsistent checkpoint fails here with RWKV_ERR_FORMAT
         w.ln1w = load_vec(p + "ln1.weight", 0, nC); w.ln1b = load_vec(p + "ln1.bias", 0, nC);
         w.ln2w = load_vec(p + "ln2.weight", 0, nC); w.ln2b = load_vec(p + "ln2.bias", 0, nC);
-        w.lnxw = load_vec(p + "att.ln_x.weight", 0, nC); w.lnxb = load_vec(p + "att.ln_x.bias", 0, nC);
+        if (info.version != 4) { w.lnxw = load_vec(p + "att.ln_x.weight", 0, nC); w.lnxb = load_vec(p + "att.ln_x.bias", 0, nC); }
         w.Wr = load_mat(p + "att.receptance.weight", qfmt("att.receptance.weight"), -1, "", C, C);
         w.Wk = load_mat(p + "att.key.weight", qfmt("att.key.weight"), -1, "", C, C);
         w.Wv = load_mat(p + "att.value.weight", qfmt("att.value.weight"), -1, "", C, C);
@@ -796,13 +830,17 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         w.Fk = load_mat(p + "ffn.key.weight", qfmt("ffn.key.weight"), -1, "", F, C);
         w.Fv = load_mat(p + "ffn.value.weight", qfmt("ffn.value.weight"), -1, "", C, F);
         if (info.version != 7) {
-            w.Wg = load_mat(p + "att.gate.weight", qfmt("att.gate.weight"), -1, "", C, C);
+            if (info.version != 4) w.Wg = load_mat(p + "att.gate.weight", qfmt("att.gate.weight"), -1, "", C, C);
             w.Fr = load_mat(p + "ffn.receptance.weight", qfmt("ffn.receptance.weight"), -1, "", C, C);
             w.fmu[0] = load_vec(p + "ffn.time_mix_k", 0, nC);
             w.fmu[1] = load_vec(p + "ffn.time_mix_r", 0, nC);
             w.u = load_vec(p + "att.time_first", 0, nC);
         }
-        if (info.version == 5) {
+        if (info.version == 4) {
+            const char *n3[] = {"k", "v", "r"};
+            for (int i = 0; i < 3; ++i) w.mu[i] = load_vec(p + "att.time_mix_" + n3[i], 0, nC);
+            w.wdec = load_vec(p + "att.time_decay", 2, nC);  // -exp(decay), static per channel
+        } else if (info.version == 5) {
             const char *n4[] = {"k", "v", "r", "g"};
             for (int i = 0; i < 4; ++i) w.mu[i] = load_vec(p + "att.time_mix_" + n4[i], 0, nC);
             w.wdec = load_vec(p + "att.time_decay", 1, nC);  // exp(-exp(decay)), static per channel
@@ -862,14 +900,20 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
 
     // ---- state + scratch
     sx_slot_stride = (long)L * C;
-    wkv_slot_stride = (long)L * H * 4096;
+    wkv_slot_stride = (long)L * wkv_layer_floats();
     sxa = dalloc<float>((size_t)max_batch * sx_slot_stride);
     sxf = dalloc<float>((size_t)max_batch * sx_slot_stride);
     wkv = dalloc<float>((size_t)max_batch * wkv_slot_stride);
     HIP_CHECK(hipMemset(sxa, 0, (size_t)max_batch * sx_slot_stride * 4));
     HIP_CHECK(hipMemset(sxf, 0, (size_t)max_batch * sx_slot_stride * 4));
     HIP_CHECK(hipMemset(wkv, 0, (size_t)max_batch * wkv_slot_stride * 4));
-    const size_t slab = (size_t)L * 66 * C;
+    if (info.version == 4) {                                   // a slot nobody loaded holds the initial state: pp = V4_PP_INIT
+        std::vector<float> pp((size_t)C, V4_PP_INIT);
+        for (int b = 0; b < max_batch; ++b)
+            for (int l = 0; l < L; ++l)
+                HIP_CHECK(hipMemcpy(wkv + (size_t)b * wkv_slot_stride + ((size_t)l * 3 + 2) * C, pp.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+    }
+    const size_t slab = state_len();
     slab_dev = dalloc<float>(slab);
     slab_host = hostalloc<float>(slab);
 
@@ -1120,7 +1164,13 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
             log_row("ln_shift_kernel", T, T, (double)T * C * (4.0 * (4 + r.np + (r.xx_out ? 1 : 0) + (r.dx_out ? 1 : 0)) + 2.0 * (r.nmix + nlo)) + 4.0 * C * (2 + r.nmix));
         };
         bool att_fused = false;                                    // a commit of the time-mix shift state is pending
-        if (info.version == 5) {
+        if (info.version == 4) {
+            a.mode = 0; a.nmix = 3;
+            for (int i = 0; i < 3; ++i) { a.mu[i] = w.mu[i]; a.ohi[i] = aA[i].hi; a.olo[i] = aA[i].lo; }
+            ps = {prob(w.Wk, aA[0], ACT_NONE, fk, C), prob(w.Wv, aA[1], ACT_NONE, fv, C), prob(w.Wr, aA[2], ACT_SIGMOID, fr, C)};
+            { launch(FAM_ROW, [&] { launch_ln_shift(a, T, s_main); }); log_ln(a); }
+            gemm(ps, T, FAM_GEMM, nullptr, CLS_ATT);
+        } else if (info.version == 5) {
             a.mode = 0; a.nmix = 4;
             for (int i = 0; i < 4; ++i) { a.mu[i] = w.mu[i]; a.ohi[i] = aA[i].hi; a.olo[i] = aA[i].lo; }
             ps = {prob(w.Wk, aA[0], ACT_NONE, fk, C), prob(w.Wv, aA[1], ACT_NONE, fv, C),
@@ -1197,7 +1247,18 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
             gemm(ps, T, FAM_GEMM, nullptr, CLS_LORA2);
         }
         std::swap(cur, oth);
-        {
+        if (info.version == 4) {
+            Wkv4Args k{};
+            k.C = C; k.n_seq = n_seq;
+            k.seq_slot = dm.seq_slot; k.seq_begin = dm.seq_begin; k.seq_len = dm.seq_len; k.dense = dense ? 1 : 0;
+            k.state = wkv + (long)l * wkv_layer_floats(); k.slot_stride = wkv_slot_stride;
+            k.r = fr; k.k = fk; k.v = fv; k.w = w.wdec; k.u = w.u;
+            k.yhi = aY.hi; k.ylo = aY.lo; k.ldh = C;
+            launch(FAM_WKV, [&] { launch_wkv4(k, T > n_seq, s_main); });
+            // three state rows in and out per sequence, r / k / v of every row in, the Wo operand out
+            log_row(T > n_seq ? "wkv4_chunk_kernel" : "wkv4_kernel", T, T > n_seq ? (long)n_seq * (C / 64) : (long)n_seq * ((C + 255) / 256),
+                    (double)n_seq * C * 24.0 + 8.0 * C + (double)T * C * 12.0 + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+        } else {
             WkvArgs k{};
             k.version = info.version; k.H = H; k.C = C; k.n_seq = n_seq;
             k.seq_slot = dm.seq_slot; k.seq_begin = dm.seq_begin; k.seq_len = dm.seq_len; k.dense = dense ? 1 : 0;
@@ -1227,7 +1288,7 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
         f.lnw = w.ln2w; f.lnb = w.ln2b;
         f.sx = sxf + (long)l * C; f.sx_slot_stride = sx_slot_stride;
         f.rm = rm; f.C = C; f.ldh = C;
-        f.mode = info.version == 5 ? 0 : 1;
+        f.mode = info.version <= 5 ? 0 : 1;
         f.nmix = info.version == 7 ? 1 : 2;
         for (int i = 0; i < f.nmix; ++i) { f.mu[i] = w.fmu[i]; f.ohi[i] = aF[i].hi; f.olo[i] = aF[i].lo; }
         {
@@ -1959,15 +2020,16 @@ rwkv_status rwkv_profile_infer(rwkv_engine *e, const rwkv_slot_input *in, rwkv_s
 }
 
 // ---- state ---------------------------------------------------------------------------------------
-size_t rwkv_state_len(const rwkv_engine *e) { return e ? (size_t)e->info.num_layer * 66 * e->info.num_emb : 0; }
+size_t rwkv_state_len(const rwkv_engine *e) { return e ? e->state_len() : 0; }
 void rwkv_state_shape(const rwkv_engine *e, size_t shape[4]) {
     if (!e || !shape) return;
     shape[0] = (size_t)e->info.num_emb; shape[1] = 66; shape[2] = (size_t)e->info.num_layer; shape[3] = 1;
+    if (e->info.version == 4) { shape[1] = 5 * (size_t)e->info.num_layer; shape[2] = 1; }   // web-rwkv's V4 state is [C, 5L, 1]
 }
 rwkv_status rwkv_state_init(const rwkv_engine *e, float *dst) {
     return guard([&] {
         if (!e || !dst) throw RwkvError(RWKV_ERR_INVALID, "null argument");
-        std::memset(dst, 0, rwkv_state_len(e) * 4);         // v5/v6/v7 initial state is all-zero
+        e->fill_init_state(dst);                            // v5/v6/v7: all-zero; v4: -1e30 in the pp rows
     });
 }
 static StatePackArgs pack_args(rwkv_engine *e, float *sxa, float *sxf, float *wkv, int to_slab, int layer_only) {
@@ -1975,6 +2037,7 @@ static StatePackArgs pack_args(rwkv_engine *e, float *sxa, float *sxf, float *wk
     a.slab = e->slab_dev; a.sxa = sxa; a.sxf = sxf; a.wkv = wkv;
     a.L = e->info.num_layer; a.C = e->info.num_emb; a.H = e->info.num_head;
     a.transposed = e->info.version != 7; a.to_slab = to_slab; a.layer_only = layer_only;
+    a.v4 = e->info.version == 4;
     return a;
 }
 static void check_slot(const rwkv_engine *e, int slot) {
@@ -2013,7 +2076,7 @@ rwkv_status rwkv_state_back_layer(rwkv_engine *e, int32_t slot, int32_t layer, f
         check_slot(e, slot);
         if (!dst || layer < 0 || layer >= e->info.num_layer) throw RwkvError(RWKV_ERR_INVALID, "bad layer/dst");
         HIP_CHECK(hipSetDevice(e->device));
-        const size_t n = (size_t)64 * e->info.num_emb;
+        const size_t n = (size_t)e->wkv_layer_floats();       // the layer's WKV rows: [64][C], V4 [3][C]
         launch_state_pack(pack_args(e, e->sxa + slot * e->sx_slot_stride, e->sxf + slot * e->sx_slot_stride,
                                     e->wkv + slot * e->wkv_slot_stride, 1, layer), e->s_main);
         HIP_CHECK(hipMemcpyAsync(e->slab_host, e->slab_dev, n * 4, hipMemcpyDeviceToHost, e->s_main));
@@ -2031,7 +2094,7 @@ rwkv_status rwkv_state_back_layer_async(rwkv_engine *e, int32_t slot, int32_t la
             (void)hipGetLastError();
             throw RwkvError(RWKV_ERR_INVALID, "rwkv_state_back_layer_async: dst must be pinned host memory (rwkv_host_alloc)");
         }
-        const size_t n = (size_t)64 * e->info.num_emb;
+        const size_t n = (size_t)e->wkv_layer_floats();       // the layer's WKV rows: [64][C], V4 [3][C]
         {
             const size_t left = pinned_bytes_left(dst);
             if (left && left < n * 4) throw RwkvError(RWKV_ERR_INVALID, "rwkv_state_back_layer_async: the rows would end " + std::to_string(n * 4 - left) + " bytes past the pinned block that holds dst");
@@ -2103,6 +2166,7 @@ void rwkv_dstate_free(rwkv_dstate *s) {
 rwkv_status rwkv_read_init_state(const rwkv_engine *e, const uint8_t *st_bytes, size_t st_len, float *dst) {
     return guard([&] {
         if (!e || !dst) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        if (e->info.version == 4) throw RwkvError(RWKV_ERR_UNSUPPORTED, "v4 does not support init state yet");   // lib.rs:384
         SafeTensors st = SafeTensors::parse(st_bytes, st_len);
         const int L = e->info.num_layer, C = e->info.num_emb, H = e->info.num_head, N = 64;
         if (!st.find("blocks.0.att.time_state")) throw RwkvError(RWKV_ERR_NO_STATE, "no `time_state` tensors in file");

@@ -241,15 +241,33 @@ struct WkvArgs {
 };
 void launch_wkv(const WkvArgs &a, bool multi_row, hipStream_t s);   // multi_row: some sequence has > 1 row in this step
 
+// RWKV-4: the per-channel WKV recurrence with a running maximum (aa, bb, pp); no heads, no gate, no group norm.  One thread per channel.
+struct Wkv4Args {
+    int C;
+    int n_seq;                      // active slots in this step
+    const int *seq_slot;            // [n_seq]
+    const int *seq_begin;           // [n_seq] first row
+    const int *seq_len;             // [n_seq]
+    int dense;                      // 1: sequence i = slot i = row i, one row each (seq_* are not read)
+    float *state;                   // this layer's [3][C] rows (aa, bb, pp) of slot 0: state + slot*slot_stride
+    long slot_stride;
+    const float *r, *k, *v;         // [T][C]; r already through ACT_SIGMOID (the GEMM epilogue)
+    const float *w, *u;             // [C]: -exp(time_decay) (load-time transform 2), time_first
+    _Float16 *yhi, *ylo;            // the Wo operand r * wkv, saturated at +-65504 (ylo: null unless the Wo launch reads hi + lo)
+    int ldh;
+};
+void launch_wkv4(const Wkv4Args &a, bool multi_row, hipStream_t s);   // multi_row: wkv4_chunk_kernel; else every sequence has one row: wkv4_kernel
+
 // ---- state slab <-> internal layout ---------------------------------------------------
 struct StatePackArgs {
-    float *slab;                    // public [L][N+2][C]
+    float *slab;                    // public [L][N+2][C]  (V4: [L][5][C])
     float *sxa, *sxf;               // internal [L][C] of this slot
-    float *wkv;                     // internal [L][H][64][64] of this slot (T[p=value][q=key])
+    float *wkv;                     // internal [L][H][64][64] of this slot (T[p=value][q=key]); V4: [L][3][C] (aa, bb, pp), copied row for row
     int L, C, H;
+    int v4;                         // 1: the five-row V4 slab (N = 3)
     int transposed;                 // 1 for v5/v6 (public S[i=key][j=value]), 0 for v7
     int to_slab;                    // 1: internal -> slab, 0: slab -> internal
-    int layer_only;                 // >=0: only this layer's WKV rows, slab points at [N][C]
+    int layer_only;                 // >=0: only this layer's WKV rows, slab points at [N][C]  (V4: [3][C])
 };
 void launch_state_pack(const StatePackArgs &a, hipStream_t s);
 
@@ -327,7 +345,7 @@ void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *
 void launch_tile_f16(const _Float16 *raw, int rows_valid, int rows, int K, void *out, hipStream_t s);
 void launch_quant_int8(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s);
 void launch_quant_nf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s);
-void launch_f16_to_f32(const _Float16 *in, float *out, long n, int op, hipStream_t s); // op 0: copy, 1: exp(-exp(x))
+void launch_f16_to_f32(const _Float16 *in, float *out, long n, int op, hipStream_t s); // op 0: copy, 1: exp(-exp(x)), 2: -exp(x) (V4's time_decay)
 void launch_vec_blend(float *v, const _Float16 *l, long n, float alpha, hipStream_t s);   // v = alpha * l + (1 - alpha) * v   (LoRA file holds a whole vector tensor)
 void launch_vec_op(float *v, long n, int op, hipStream_t s);                              // the load-time transform, in place
 // W[rows][K] (fp16 raw) += alpha * B[rows][r] * A^T  (A stored [K][r]) — LoRA blend, fp32 math

@@ -1,4 +1,4 @@
-// rwkv_kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels for the RWKV V5/V6/V7 forward pass.
+// rwkv_kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels for the RWKV V4/V5/V6/V7 forward pass.
 //
 // Reference arithmetic: the web-rwkv calls behind `runtime.infer` (crates/ai00-core/src/run.rs:1143),
 // restated in SURVEY.md Appendix A.  Kernel inventory:
@@ -7,6 +7,7 @@
 //   embed_kernel     K1             emb gather + ln0
 //   ln_out_kernel    K2             final LayerNorm on the rows whose logits are requested
 //   wkv_kernel       K8-K11,K13     WKV recurrence (+v6 decay LoRA stage 2, +v7 kappa/a/v-mix), GroupNorm, gate
+//   wkv4_kernel      (V4)           per-channel WKV-4 recurrence with a running maximum; wkv4_chunk_kernel walks a sequence's rows
 //   state_pack       K17            public slab [C,N+2,L,1] <-> internal state layout
 //   softmax / argmax K16            batched over the vocabulary
 //   tile/quant       K18,K19        load-time: raw fp16 -> tiled fp16 / int8 / nf4 ; LoRA blend
@@ -3019,15 +3020,94 @@ void launch_wkv(const WkvArgs &a, bool multi_row, hipStream_t s) {
     else hipLaunchKernelGGL(wkv_kernel, dim3(a.n_seq, a.H), dim3(256), 0, s, a);
 }
 
+// =====================================================================================
+// WKV-4 (RWKV-4): per channel, state (aa, bb, pp) = numerator, denominator and their common exponent (a running maximum, so that
+// neither sum overflows whatever k is).  With u = time_first, w = -exp(time_decay):
+//   ww = u + k;  p = max(pp, ww);  wkv = (e^(pp-p) aa + e^(ww-p) v) / (e^(pp-p) bb + e^(ww-p))
+//   ww = pp + w; p = max(ww, k);   aa = e^(ww-p) aa + e^(k-p) v;  bb = e^(ww-p) bb + e^(k-p);  pp = p
+// expf and a true fp32 division: the fast forms (v_exp_f32 on a scaled argument, v_rcp_f32) lose the 2e-5 bound once |k| reaches tens.
+// An initial pp of -1e30 or of -FLT_MAX behaves the same: pp - p and ww - p are then finite-huge or -inf, and expf gives an exact 0 for both.
+// No cross-lane work at all: one thread per channel, consecutive lanes = consecutive channels, every load and the state stores coalesce.
+// =====================================================================================
+__device__ __forceinline__ float wkv4_step(float &aa, float &bb, float &pp, float k, float v, float u, float w) {
+    float ww = u + k;
+    float p = fmaxf(pp, ww);
+    float e1 = expf(pp - p), e2 = expf(ww - p);
+    const float wkv = (e1 * aa + e2 * v) / (e1 * bb + e2);
+    ww = pp + w;
+    p = fmaxf(ww, k);
+    e1 = expf(ww - p); e2 = expf(k - p);
+    aa = e1 * aa + e2 * v;
+    bb = e1 * bb + e2;
+    pp = p;
+    return wkv;
+}
+// y = r * wkv of channel c, row t, into the Wo operand.  Lanes pair up and the even lane stores both halves (channels c, c + 1 are adjacent
+// halfs of one 16-byte piece of the operand layout); every lane of the wave must be active.
+__device__ __forceinline__ void wkv4_emit(act_t byh, act_t byl, bool has_lo, int t, int c, int ldh, float y) {
+    _Float16 hh, ll;
+    split_hilo(y, hh, ll);
+    const unsigned hb = __builtin_bit_cast(unsigned short, hh), lb = __builtin_bit_cast(unsigned short, ll);
+    const unsigned hn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hb, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
+    const unsigned ln2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lb, 0xB1, 0xf, 0xf, true);
+    if ((c & 1) == 0) {
+        const long yo = opd_off(t, c, ldh);
+        __builtin_amdgcn_raw_buffer_store_b32(hb | (hn << 16), byh, (unsigned)(yo * 2), 0, ACT_SC1);
+        if (has_lo) __builtin_amdgcn_raw_buffer_store_b32(lb | (ln2 << 16), byl, (unsigned)(yo * 2), 0, ACT_SC1);
+    }
+}
+// Decode form: every sequence of the step has ONE row.  One thread per (row, channel); aa / bb / pp are read and written once.
+__global__ __launch_bounds__(256) void wkv4_kernel(const Wkv4Args a) {
+    const int c = blockIdx.x * 256 + threadIdx.x, seq = blockIdx.y, C = a.C;
+    if (c >= C) return;                                      // C % 64 == 0: whole waves leave
+    const int slot = a.dense ? seq : a.seq_slot[seq], t = a.dense ? seq : a.seq_begin[seq];
+    float *st = a.state + (long)slot * a.slot_stride + c;
+    const act_t br = act_buf(a.r), bk = act_buf(a.k), bv = act_buf(a.v), byh = act_buf(a.yhi), byl = act_buf(a.ylo);
+    const long rb = (long)t * C + c;
+    const float r = act_ld1(br, rb), k = act_ld1(bk, rb), v = act_ld1(bv, rb);
+    float aa = st[0], bb = st[C], pp = st[2 * C];
+    const float wkv = wkv4_step(aa, bb, pp, k, v, a.u[c], a.w[c]);
+    st[0] = aa; st[C] = bb; st[2 * C] = pp;
+    wkv4_emit(byh, byl, a.ylo != nullptr, t, c, a.ldh, r * wkv);
+}
+// Steps in which a sequence has several rows: one thread per (sequence, channel) walks the sequence's rows in order with the state in
+// registers; the next row's r / k / v are in flight while the current row's two exp pairs and the division run.  64-thread blocks: the
+// walk is latency-bound and a sequence has only C / 64 waves, so they are spread over as many CUs as there are.
+__global__ __launch_bounds__(64) void wkv4_chunk_kernel(const Wkv4Args a) {
+    const int c = blockIdx.x * 64 + threadIdx.x, seq = blockIdx.y, C = a.C;
+    if (c >= C) return;
+    const int slot = a.dense ? seq : a.seq_slot[seq], row0 = a.dense ? seq : a.seq_begin[seq], nrow = a.dense ? 1 : a.seq_len[seq];
+    float *st = a.state + (long)slot * a.slot_stride + c;
+    const act_t br = act_buf(a.r), bk = act_buf(a.k), bv = act_buf(a.v), byh = act_buf(a.yhi), byl = act_buf(a.ylo);
+    const bool has_lo = a.ylo != nullptr;
+    const float u = a.u[c], w = a.w[c];
+    float aa = st[0], bb = st[C], pp = st[2 * C];
+    long rb = (long)row0 * C + c;
+    float rn = 0.f, kn = 0.f, vn = 0.f;
+    if (nrow > 0) { rn = act_ld1(br, rb); kn = act_ld1(bk, rb); vn = act_ld1(bv, rb); }
+    for (int it = 0; it < nrow; ++it) {
+        const float r = rn, k = kn, v = vn;
+        if (it + 1 < nrow) { rb += C; rn = act_ld1(br, rb); kn = act_ld1(bk, rb); vn = act_ld1(bv, rb); }
+        const float wkv = wkv4_step(aa, bb, pp, k, v, u, w);
+        wkv4_emit(byh, byl, has_lo, row0 + it, c, a.ldh, r * wkv);
+    }
+    st[0] = aa; st[C] = bb; st[2 * C] = pp;
+}
+void launch_wkv4(const Wkv4Args &a, bool multi_row, hipStream_t s) {
+    if (multi_row) hipLaunchKernelGGL(wkv4_chunk_kernel, dim3(a.C / 64, a.n_seq), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(wkv4_kernel, dim3((a.C + 255) / 256, a.n_seq), dim3(256), 0, s, a);
+}
+
 #endif  // part 3: row kernels + WKV
 
 #if RWKV_PART_ON(4)
 // =====================================================================================
 // State slab <-> internal.  slab[l][0][c]=sx_att, slab[l][1+i][h*64+j]=S_h[i][j], slab[l][65][c]=sx_ffn
+// V4: slab[l][0]=sx_att, slab[l][1..3]=aa, bb, pp (internal wkv [l][3][C]), slab[l][4]=sx_ffn
 // internal wkv T[l][h][p][q]:  transposed (v5/v6): S[i][j] = T[p=j][q=i];  v7: S[i][j] = T[p=i][q=j]
 // =====================================================================================
 __global__ void state_pack_kernel(const StatePackArgs a) {
-    const int C = a.C, N = 64;
+    const int C = a.C, N = a.v4 ? 3 : 64;
     const long per_layer = (long)(N + 2) * C;
     const long total = a.layer_only >= 0 ? (long)N * C : (long)a.L * per_layer;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -3037,6 +3117,7 @@ __global__ void state_pack_kernel(const StatePackArgs a) {
         float *src;
         if (row == 0) src = a.sxa + (long)l * C + c;
         else if (row == N + 1) src = a.sxf + (long)l * C + c;
+        else if (a.v4) src = a.wkv + ((long)l * 3 + (row - 1)) * C + c;
         else {
             const int i = row - 1, h = c >> 6, j = c & 63;
             const int p = a.transposed ? j : i, q = a.transposed ? i : j;
@@ -4086,6 +4167,7 @@ __global__ void f16_to_f32_kernel(const _Float16 *in, float *out, long n, int op
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         float v = (float)in[i];
         if (op == 1) v = expf(-expf(v));
+        else if (op == 2) v = -expf(v);
         out[i] = v;
     }
 }
@@ -4104,6 +4186,7 @@ __global__ void vec_blend_kernel(float *v, const _Float16 *l, long n, float alph
 __global__ void vec_op_kernel(float *v, long n, int op) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
         if (op == 1) v[i] = expf(-expf(v[i]));
+        else if (op == 2) v[i] = -expf(v[i]);
 }
 void launch_vec_blend(float *v, const _Float16 *l, long n, float alpha, hipStream_t s) {
     const int blocks = (int)std::max<long>(1, std::min<long>(1024, (n + 255) / 256));

@@ -291,7 +291,7 @@ class StateJob:
 
     def run(self, docs: list):
         rt, B = self.rt, self.rt.max_batch
-        N, Cn = rt.info.head_size, rt.info.num_emb
+        N, Cn = getattr(rt.state, "layer_rows", rt.info.head_size), rt.info.num_emb    # rows a layer owns (V4: 3, not head_size)
         if self.out is None or self.out.array.shape[0] < len(docs):
             if self.out is not None:
                 self.out.close()

@@ -177,6 +177,7 @@ def _buf(data) -> tuple[C.c_void_p, int, object]:
 
 # ------------------------------------------------------------------------------------------------
 class ModelVersion(enum.IntEnum):
+    V4 = 4
     V5 = 5
     V6 = 6
     V7 = 7
@@ -295,8 +296,13 @@ class State:
         return tuple(int(v) for v in s)
 
     def _np_shape(self):
-        c, r, l, _ = self.shape
+        c, r, l, _ = self.shape                                    # V5 / V6 / V7: [C, 66, L, 1]; V4: [C, 5L, 1, 1] (rows 5l .. 5l+4 belong to layer l)
         return (l, r, c)
+
+    @property
+    def layer_rows(self) -> int:
+        """WKV rows one layer owns in the slab, between its two shift rows (what `embed` returns): 64, V4: 3 (aa, bb, pp)"""
+        return 3 if self._rt.info.version == ModelVersion.V4 else self.shape[1] - 2
 
     def init(self) -> np.ndarray:                                  # run.rs:477, 950
         a = np.empty(self._np_shape(), np.float32)
@@ -323,10 +329,8 @@ class State:
         _check(lib().rwkv_state_write(self._rt._h, batch, tensor._h))
 
     def embed(self, layer: int, batch: int) -> np.ndarray:
-        """One layer's WKV rows [N, C] of a slot (docs/doc-api/openai.md:376-437 `/embeddings`)."""
-        _, r, _, _ = self.shape
-        c = self.shape[0]
-        a = np.empty((r - 2, c), np.float32)
+        """One layer's WKV rows [N, C] of a slot (docs/doc-api/openai.md:376-437 `/embeddings`); V4: its aa / bb / pp rows [3, C]."""
+        a = np.empty((self.layer_rows, self.shape[0]), np.float32)
         _check(lib().rwkv_state_back_layer(self._rt._h, batch, layer, a.ctypes.data))
         return a
 

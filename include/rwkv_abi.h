@@ -38,14 +38,16 @@ extern "C" {
                               *    additive under 9 (no existing symbol or struct changed): rwkv_infer_score, rwkv_score_rows, RWKV_SCORE_SKIP: target tokens
                               *    are scored on the device, 4 bytes per token come back instead of a logits row
                               *    additive under 9: rwkv_gen_set_token_bytes, rwkv_gen_set_stops, rwkv_gen_stop_tail, RWKV_GEN_HANDBACK: stop STRINGS are
-                              *    matched on the device inside the resident step */
+                              *    matched on the device inside the resident step
+                              *    additive under 9 (no new symbol, no struct changed): RWKV_V4 — RWKV-4 World checkpoints load (version 4 in
+                              *    rwkv_model_info, the five-row state below); they were RWKV_ERR_UNSUPPORTED before */
 
 typedef int32_t rwkv_status;
 enum {
     RWKV_OK = 0,
     RWKV_ERR_INVALID = -1,     /* bad argument / malformed input            */
     RWKV_ERR_FORMAT = -2,      /* not a safetensors file / missing tensor   */
-    RWKV_ERR_UNSUPPORTED = -3, /* model version (v4, v5.0/5.1) or option    */
+    RWKV_ERR_UNSUPPORTED = -3, /* model version (v5.0/5.1, unknown naming), dimensions or option */
     RWKV_ERR_DEVICE = -4,      /* no HIP device / HIP runtime error         */
     RWKV_ERR_OOM = -5,
     RWKV_ERR_NO_STATE = -6     /* file has no `time_state` tensors (lib.rs:442) */
@@ -60,15 +62,20 @@ int32_t rwkv_device_count(void);
 rwkv_status rwkv_device_name(int32_t index, char *buf, size_t buf_len);
 
 /* ---- `Loader::info(&SafeTensors)` lib.rs:587, api/file.rs:113-116 -> `ModelInfo` ---------- */
-enum { RWKV_V5 = 5, RWKV_V6 = 6, RWKV_V7 = 7 };
+enum { RWKV_V4 = 4, RWKV_V5 = 5, RWKV_V6 = 6, RWKV_V7 = 7 };
+/* V4 is detected on positive evidence only: blocks.0 has none of att.ln_x.weight / att.gate.weight / att.time_mix_x / att.x_r, has
+ * att.time_first and att.time_decay with exactly num_emb elements, and att.time_mix_k/v/r and ffn.time_mix_k/r; anything else that is not
+ * V5.2 / V6 / V7 stays RWKV_ERR_UNSUPPORTED.  V4 has no heads: num_head = 1, head_size = num_emb.  The dimension rules (num_emb % 64,
+ * num_hidden % 32, num_vocab % 16 == 0) hold for every version, so the 50277-token Pile models of RWKV-4 are refused here as the World
+ * tokenizer refuses them; the RWKV-4 World models (65536 tokens) load. */
 typedef struct rwkv_model_info {
-    int32_t version;     /* ModelVersion: 5 (=v5.2), 6, 7 */
+    int32_t version;     /* ModelVersion: 4, 5 (=v5.2), 6, 7 */
     int32_t num_layer;
     int32_t num_emb;
     int32_t num_hidden;
     int32_t num_vocab;
     int32_t num_head;
-    int32_t head_size;   /* num_emb / num_head (64) */
+    int32_t head_size;   /* num_emb / num_head (64; V4: num_emb) */
     int32_t reserved;
 } rwkv_model_info;
 rwkv_status rwkv_model_info_from_st(const uint8_t *st_bytes, size_t st_len, rwkv_model_info *out);
@@ -170,15 +177,19 @@ rwkv_status rwkv_plan_chunk(int32_t max_batch, int32_t token_chunk_size, const s
 
 /* ---- `State` trait: run.rs:477,950 (init) 1099 (load) 1101 (back) 1104 (write) 1106 (read) -- */
 size_t rwkv_state_len(const rwkv_engine *e);                       /* floats in one slab      */
-void rwkv_state_shape(const rwkv_engine *e, size_t shape[4]);      /* [C, N+2, L, 1] run.rs:987 */
-rwkv_status rwkv_state_init(const rwkv_engine *e, float *dst);     /* zero slab (CPU)         */
+void rwkv_state_shape(const rwkv_engine *e, size_t shape[4]);      /* [C, N+2, L, 1] run.rs:987; V4: [C, 5L, 1, 1] */
+rwkv_status rwkv_state_init(const rwkv_engine *e, float *dst);     /* zero slab (CPU); V4: see below */
+/* V4 state: 5L rows of C floats, layer l owns rows 5l .. 5l+4 = time-mix shift, aa, bb, pp, channel-mix shift (aa / bb: numerator and
+ * denominator of the WKV average, pp: their common exponent).  rwkv_state_init writes 0 everywhere and -1e30 in the pp rows.
+ * [EXT] The row order and the init constant are web-rwkv's (its V4 state is [C, 5L, 1]; the crate is not vendored in the reference
+ * tree, so neither can be checked against it here).  The kernels give the same bits for pp = -1e30 and pp = -FLT_MAX. */
 rwkv_status rwkv_state_load(rwkv_engine *e, int32_t slot, const float *src);   /* H2D         */
 rwkv_status rwkv_state_back(rwkv_engine *e, int32_t slot, float *dst);         /* D2H, blocks */
 typedef struct rwkv_dstate rwkv_dstate;                            /* TensorGpu snapshot       */
 rwkv_status rwkv_state_read(rwkv_engine *e, int32_t slot, rwkv_dstate **snap); /* D2D copy out */
 rwkv_status rwkv_state_write(rwkv_engine *e, int32_t slot, const rwkv_dstate *snap); /* D2D in; snap reusable */
 void rwkv_dstate_free(rwkv_dstate *snap);
-/* f-2 (docs/doc-api/openai.md:376-437): one layer's WKV rows [N][C] of a slot, D2H */
+/* f-2 (docs/doc-api/openai.md:376-437): one layer's WKV rows [N][C] of a slot, D2H (V4: its aa, bb, pp rows [3][C]) */
 rwkv_status rwkv_state_back_layer(rwkv_engine *e, int32_t slot, int32_t layer, float *dst);
 /* The same read-back, NOT waited for: the layer's rows are packed on a second stream (ordered behind everything issued so far; later
  * work on the slot — rwkv_infer, rwkv_state_load / _write — is ordered behind the pack, a few microseconds) and copied to `dst`, which
@@ -188,7 +199,8 @@ rwkv_status rwkv_state_back_layer(rwkv_engine *e, int32_t slot, int32_t layer, f
 rwkv_status rwkv_state_back_layer_async(rwkv_engine *e, int32_t slot, int32_t layer, float *dst);
 rwkv_status rwkv_state_sync(rwkv_engine *e);                       /* wait for every pending rwkv_state_back_layer_async */
 
-/* ---- `vN::read_state(context, info, model)` lib.rs:378-389 --------------------------------- */
+/* ---- `vN::read_state(context, info, model)` lib.rs:378-389 ---------------------------------
+ * On a V4 engine: RWKV_ERR_UNSUPPORTED, as the reference bails ("v4 does not support init state yet", lib.rs:384). */
 rwkv_status rwkv_read_init_state(const rwkv_engine *e, const uint8_t *st_bytes, size_t st_len, float *dst);
 
 /* ---- `softmax::softmax(&context, Vec<TensorCpu>)` run.rs:1178-1183 -------------------------

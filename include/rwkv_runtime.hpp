@@ -81,8 +81,13 @@ class State {
     TensorGpu read(int batch) { rwkv_dstate *h = nullptr; check(rwkv_state_read(e_, batch, &h)); return TensorGpu(h); }
     void write(const TensorGpu &t, int batch) { check(rwkv_state_write(e_, batch, t.get())); }
     // one layer's WKV rows of a slot, [head_size][num_emb] floats (rwkv_state_shape = [C, N + 2, L, 1]: the N rows between the two
-    // token-shift rows) — what `/embeddings` returns for the chosen layer
-    size_t layer_len() const { auto s = shape(); return s[0] * (s[1] - 2); }
+    // token-shift rows) — what `/embeddings` returns for the chosen layer.  V4 (state [C, 5L, 1, 1]): the layer's aa / bb / pp rows, [3][num_emb]
+    size_t layer_len() const {
+        rwkv_model_info i{};
+        check(rwkv_engine_info(e_, &i));
+        auto s = shape();
+        return s[0] * (i.version == RWKV_V4 ? 3 : s[1] - 2);
+    }
     void embed(int layer, int batch, float *dst) { check(rwkv_state_back_layer(e_, batch, layer, dst)); }
     // not waited for: `dst` is pinned memory (PinnedBuffer), valid after sync(); the slot may take its next request at once
     void embed_async(int layer, int batch, float *dst) { check(rwkv_state_back_layer_async(e_, batch, layer, dst)); }

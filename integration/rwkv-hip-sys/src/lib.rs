@@ -6,6 +6,7 @@ use std::os::raw::{c_char, c_float, c_void};
 pub const RWKV_ABI_VERSION: i32 = 9;
 
 pub type rwkv_status = i32;
+pub const RWKV_V4: i32 = 4;              // rwkv_model_info.version of an RWKV-4 model (5 / 6 / 7 are matched as plain integers)
 pub const RWKV_OK: rwkv_status = 0;
 pub const RWKV_ERR_INVALID: rwkv_status = -1;
 pub const RWKV_ERR_FORMAT: rwkv_status = -2;

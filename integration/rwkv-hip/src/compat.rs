@@ -16,7 +16,7 @@ pub struct ModelInfo { pub version: ModelVersion, pub num_layer: usize, pub num_
                        pub num_vocab: usize, pub num_head: usize }
 impl From<crate::RawInfo> for ModelInfo {
     fn from(i: crate::RawInfo) -> Self {
-        let version = match i.version { 5 => ModelVersion::V5, 6 => ModelVersion::V6, _ => ModelVersion::V7 };
+        let version = match i.version { 4 => ModelVersion::V4, 5 => ModelVersion::V5, 6 => ModelVersion::V6, _ => ModelVersion::V7 };
         Self { version, num_layer: i.num_layer as usize, num_emb: i.num_emb as usize, num_hidden: i.num_hidden as usize,
                num_vocab: i.num_vocab as usize, num_head: i.num_head as usize }
     }
@@ -96,7 +96,7 @@ impl State {
     }
     /// `/embeddings`: one layer's rows instead of the whole slab
     pub fn embed(&self, layer: usize, batch: usize) -> Result<TensorCpu<f32>, Error> {
-        let (n, c) = (self.engine.info.head_size as usize, self.engine.info.num_emb as usize);
+        let (n, c) = (self.engine.layer_rows(), self.engine.info.num_emb as usize);
         Ok(TensorCpu { shape: [c, n, 1, 1], data: Arc::new(self.engine.state_back_layer(batch, layer)?) })
     }
 }

@@ -181,9 +181,11 @@ impl Engine {
         check(unsafe { sys::rwkv_state_read(self.raw, slot as i32, &mut p) })?; Ok(Arc::new(DeviceState(p)))
     }
     pub fn state_write(&self, slot: usize, snap: &DeviceState) -> Result<()> { check(unsafe { sys::rwkv_state_write(self.raw, slot as i32, snap.0) }) }
-    /// `/embeddings` (docs/doc-api/openai.md:376-437): one layer's WKV rows `[head_size][num_emb]`
+    /// WKV rows one layer owns in the state: `head_size` (64), for a V4 model its three rows aa / bb / pp
+    pub fn layer_rows(&self) -> usize { if self.info.version == sys::RWKV_V4 { 3 } else { self.info.head_size as usize } }
+    /// `/embeddings` (docs/doc-api/openai.md:376-437): one layer's WKV rows `[layer_rows][num_emb]`
     pub fn state_back_layer(&self, slot: usize, layer: usize) -> Result<Vec<f32>> {
-        let mut v = vec![0f32; (self.info.head_size * self.info.num_emb) as usize];
+        let mut v = vec![0f32; self.layer_rows() * self.info.num_emb as usize];
         check(unsafe { sys::rwkv_state_back_layer(self.raw, slot as i32, layer as i32, v.as_mut_ptr()) })?; Ok(v)
     }
     /// The same rows, not waited for: they land in the pinned block at float offset `at` and are valid after the copy stream has been
@@ -345,7 +347,7 @@ pub struct PendingRows<'a> {
 }
 impl<'a> PendingRows<'a> {
     fn issue(&mut self, slot: usize, layer: usize, at: usize) -> Result<()> {
-        let n = (self.rt.info.head_size * self.rt.info.num_emb) as usize;
+        let n = self.rt.layer_rows() * self.rt.info.num_emb as usize;
         let end = match at.checked_add(n) { Some(e) if e <= self.dst.floats => e, _ => {
             return Err(Error { code: sys::RWKV_ERR_INVALID, message: format!("pinned block holds {} floats, rows need {}..{}", self.dst.floats, at, at.saturating_add(n)) }) } };
         if self.ranges.iter().any(|&(a, b)| at < b && a < end) {
