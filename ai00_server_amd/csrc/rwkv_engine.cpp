@@ -24,6 +24,7 @@
 #include "../../include/rwkv_abi.h"
 #include "gemm_plan.h"
 #include "graph_cache.h"
+#include "rwkv_dfa.h"
 #include "safetensors.hpp"
 
 using namespace rwkv;
@@ -389,6 +390,16 @@ struct rwkv_engine {
     void gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens, size_t n);
     void gen_set_stops(int slot, const rwkv_gen_stops &s);
     size_t gen_stop_tail(int slot, uint8_t *out, size_t cap);
+    // the byte-automaton constraint (rwkv_gen_set_constraint): beside d_gen, one GenDfa per slot; the slot's table lives in a buffer of its own
+    GenDfa *d_gen_dfa = nullptr;
+    std::vector<char> gen_has_dfa;                               // per slot: it carries a constraint (host knowledge: selects the kernels of a step)
+    std::vector<void *> gen_dfa_buf;                             // per slot: trans | flags on the device; not in `allocs`: a new constraint replaces it
+    unsigned short *d_tok_end = nullptr;                         // [chunk][V] gen_mask -> gen_post; allocated by the first constraint
+    uint8_t tok_single[256] = {};                                // the token table holds the single-byte token c (the liveness rule)
+    void gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, int halt_mode);
+    int gen_constraint_state(int slot);
+    void gen_drop_dfa_buf(int slot) { if (gen_dfa_buf[(size_t)slot]) { (void)hipFree(gen_dfa_buf[(size_t)slot]); gen_dfa_buf[(size_t)slot] = nullptr; } }
+    bool gen_any_dfa(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_dfa[(size_t)b]) return true; return false; }
     bool gen_any_stops(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_stops[(size_t)b]) return true; return false; }
     float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
     float **d_gen_shadow = nullptr;
@@ -403,14 +414,15 @@ struct rwkv_engine {
         if (gen_armed.empty()) return;
         gen_armed[(size_t)slot] = 0;
         gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
+        gen_has_dfa[(size_t)slot] = 0;                             // likewise; the table's buffer is freed by the next arm / constraint / the destructor
         gen_prompt[(size_t)slot].clear();
         gen_ppos[(size_t)slot] = 0;
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows, bool stops) const;
+    GenArgs gen_args(int n_rows, bool stops, bool dfa) const;
     unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs, bool stops);
+    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
@@ -449,6 +461,8 @@ struct rwkv_engine {
         graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
+        for (void *p : gen_dfa_buf) if (p) (void)hipFree(p);
+        if (d_tok_end) (void)hipFree(d_tok_end);
         if (d_tok_off) (void)hipFree(d_tok_off);
         if (d_tok_bytes) (void)hipFree(d_tok_bytes);
         for (void *p : host_allocs) (void)hipHostFree(p);
@@ -1525,6 +1539,10 @@ void rwkv_engine::gen_init() {
     gen_host.assign(B, GenSlot{});
     gen_armed.assign(B, 0);
     gen_has_stops.assign(B, 0);
+    gen_has_dfa.assign(B, 0);
+    gen_dfa_buf.assign(B, nullptr);
+    d_gen_dfa = dalloc<GenDfa>(B);
+    HIP_CHECK(hipMemset(d_gen_dfa, 0, B * sizeof(GenDfa)));
     d_gen_stop = dalloc<GenStop>(B);
     HIP_CHECK(hipMemset(d_gen_stop, 0, B * sizeof(GenStop)));
     gen_prompt.assign(B, {});
@@ -1591,11 +1609,14 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     HIP_CHECK(hipMemcpyAsync(d_gen_bias + b * V, bias.data(), V * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemcpyAsync(d_gen + b, &g, sizeof(GenSlot), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemsetAsync(&d_gen_stop[b].n_str, 0, 2 * sizeof(int), s_main));   // re-arming clears the stop strings and their buffer
+    HIP_CHECK(hipMemsetAsync(d_gen_dfa + b, 0, sizeof(GenDfa), s_main));             // ... and the constraint
     const int first = prompt ? 0 : (int)p.first_token;             // with a prompt the slot's first draw fills it
     HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     gen_host[b] = g;
     gen_has_stops[b] = 0;
+    gen_has_dfa[b] = 0;
+    gen_drop_dfa_buf(slot);                                        // behind the synchronize: no step is in flight
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
     gen_armed[b] = 1;
@@ -1615,6 +1636,7 @@ void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens,
     if (total && !bytes) throw RwkvError(RWKV_ERR_INVALID, "token table: null bytes");
     if (total >= GEN_TOK_UNKNOWN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "token table: more than 2 GiB of bytes");
     for (char h : gen_has_stops) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has stop strings set");
+    for (char h : gen_has_dfa) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a constraint set");
     std::vector<unsigned> off(n + 1);
     size_t pos = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -1632,6 +1654,59 @@ void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens,
     HIP_CHECK(hipMemcpy(d_tok_off, off.data(), (n + 1) * sizeof(unsigned), hipMemcpyHostToDevice));
     if (total) HIP_CHECK(hipMemcpy(d_tok_bytes, bytes, total, hipMemcpyHostToDevice));
     n_tok = (int)n;
+    std::memset(tok_single, 0, sizeof(tok_single));
+    for (size_t i = 0, at = 0; i < n; ++i) {
+        if (lens[i] == 1 && i > 0) tok_single[bytes[at]] = 1;        // token 0 is never allowed (gen_dfa.h)
+        if (lens[i] > 0) at += (size_t)lens[i];
+    }
+}
+
+// The byte-automaton constraint of an armed, unfinished slot (rwkv_gen_set_constraint): the table goes to the device, the GenDfa of the
+// slot points at it.  Between runs: the stream is idle, so the old table can go at once.
+void rwkv_engine::gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, int halt_mode) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs an armed, unfinished slot");
+    GenDfa h{};
+    void *buf = nullptr;
+    if (dfa) {
+        if (!d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs the token table: rwkv_gen_set_token_bytes");
+        if (state < 1 || state >= dfa->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: state 0 (dead) or out of range");
+        if (halt_mode != RWKV_DFA_HALT_FINAL && halt_mode != RWKV_DFA_HALT_ACCEPT) throw RwkvError(RWKV_ERR_INVALID, "constraint: unknown halt mode");
+        if (!dfa_never_stuck(*dfa, state, halt_mode, tok_single))
+            throw RwkvError(RWKV_ERR_UNSUPPORTED, "constraint: a reachable state has no single-byte token that leads on (a row could be masked whole)");
+        const size_t tbytes = (size_t)dfa->n_states * 256 * sizeof(uint16_t), fbytes = (size_t)dfa->n_states;
+        if (!d_tok_end) HIP_CHECK(hipMalloc((void **)&d_tok_end, (size_t)chunk * (size_t)info.num_vocab * sizeof(unsigned short)));
+        HIP_CHECK(hipMalloc(&buf, tbytes + fbytes));
+        if (hipMemcpy(buf, dfa->trans.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy((char *)buf + tbytes, dfa->flags.data(), fbytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(buf);
+            throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the table failed");
+        }
+        h.trans = (const unsigned short *)buf;
+        h.flags = (const unsigned char *)buf + tbytes;
+        h.state = state;
+        h.mode = halt_mode;
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    if (hipMemcpy(d_gen_dfa + b, &h, sizeof(GenDfa), hipMemcpyHostToDevice) != hipSuccess) {
+        if (buf) (void)hipFree(buf);
+        throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the slot's entry failed");
+    }
+    gen_drop_dfa_buf(slot);
+    gen_dfa_buf[b] = buf;
+    gen_has_dfa[b] = dfa ? 1 : 0;
+}
+
+int rwkv_engine::gen_constraint_state(int slot) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    if (!gen_has_dfa[b]) return 0;
+    GenDfa h{};
+    HIP_CHECK(hipMemcpyAsync(&h, d_gen_dfa + b, sizeof(GenDfa), hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    return h.state;
 }
 
 // `GenerateRequest::stop` (run.rs:899-932) of an armed, unfinished slot, and the bytes the caller's matcher holds after the tokens it handled itself
@@ -1673,9 +1748,11 @@ size_t rwkv_engine::gen_stop_tail(int slot, uint8_t *out, size_t cap) {
     return len;
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows, bool stops) const {
+GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa) const {
     GenArgs a{};
-    if (stops) { a.stops = d_gen_stop; a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
+    if (stops) a.stops = d_gen_stop;
+    if (dfa) { a.dfa = d_gen_dfa; a.tok_end = d_tok_end; }
+    if (stops || dfa) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
     a.slots = d_gen; a.row_slot = dm.slot; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
     a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
     a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
@@ -1688,15 +1765,16 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops) const {
 // the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
 void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
+    if (a.dfa) launch(FAM_SAMPLE, [&] { launch_gen_mask(a, s_main); });   // `transform` (run.rs:676-679) of the constrained rows
     launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T, stops), needs);
+    gen_sample(gen_args(pl.T, stops, dfa), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
@@ -1704,6 +1782,7 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
     const unsigned needs = gen_needs(rows);
     const bool stops = gen_any_stops(rows);                        // a slot of this row set has stop strings: gen_post_kernel<., true>
+    const bool dfa = gen_any_dfa(rows);                            // a slot of this row set has a constraint: gen_mask_kernel joins the step
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
@@ -1712,13 +1791,13 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs | (stops ? 1ull << 32 : 0);
+    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -1744,7 +1823,7 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     step_max_rows = pl.max_rows();
     run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (pl.n_out > 0) {
-        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn));
+        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn));
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         gen_sample(a, gen_needs(drawn));
@@ -2341,6 +2420,19 @@ rwkv_status rwkv_gen_stop_tail(rwkv_engine *e, int32_t slot, uint8_t *out, size_
         check_slot(e, slot);
         if (!len || (cap && !out)) throw RwkvError(RWKV_ERR_INVALID, "null out / len");
         *len = e->gen_stop_tail(slot, out, cap);
+    });
+}
+rwkv_status rwkv_gen_set_constraint(rwkv_engine *e, int32_t slot, const rwkv_dfa *dfa, int32_t state, int32_t halt_mode) {
+    return guard([&] {
+        check_slot(e, slot);
+        e->gen_set_constraint(slot, dfa, state, halt_mode);
+    });
+}
+rwkv_status rwkv_gen_constraint_state(rwkv_engine *e, int32_t slot, int32_t *state) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!state) throw RwkvError(RWKV_ERR_INVALID, "null state");
+        *state = e->gen_constraint_state(slot);
     });
 }
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out) {

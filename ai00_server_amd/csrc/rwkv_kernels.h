@@ -13,6 +13,7 @@ typedef unsigned short _Float16;
 #include <stdint.h>
 
 #include "gen_stop.h"                // RWKV_HD, the stop-string matcher and its limits
+#include "gen_dfa.h"                 // the byte-automaton constraint: walk, allowed and halt predicates
 
 namespace rwkv {
 
@@ -304,9 +305,17 @@ struct alignas(16) GenStop {        // one per slot, beside GenSlot: the slot's 
     unsigned short len[GEN_MAX_STOP_STR];
     int n_str, buf_len;                                     // n_str == 0: no strings, the slot takes the token-stop path
 };
+struct GenDfa {                     // one per slot, beside GenSlot: the slot's byte-automaton constraint (gen_dfa.h)
+    const unsigned short *trans;    // [n_states][256] on the device, or null: the slot has no constraint
+    const unsigned char *flags;     // [n_states] GEN_DFA_ACCEPT | GEN_DFA_END
+    int state;                      // the state behind every token the slot has emitted (written by gen_post)
+    int mode;                       // GEN_DFA_HALT_*
+};
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
     GenStop *stops;                 // [max_batch], or null: no slot of this step has stop strings (selects gen_post_kernel<., false>)
+    GenDfa *dfa;                    // [max_batch], or null: no slot of this step has a constraint (gen_mask is not launched, gen_post skips it)
+    unsigned short *tok_end;        // [n_rows][V] with dfa: the state each token of a constrained row ends in, 0 = not allowed (gen_mask -> gen_post)
     const unsigned *tok_off;        // token table: bytes of id i are tok_bytes[off(i) .. off(i + 1)), off = tok_off[] & ~GEN_TOK_UNKNOWN;
     const unsigned char *tok_bytes; //   tok_off[i] & GEN_TOK_UNKNOWN: id i is not in the vocabulary; ids >= n_tok are not either
     int n_tok;
@@ -334,6 +343,7 @@ RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, 
     return (float)(z >> 40) * 5.9604644775390625e-8f;       // 24 bits * 2^-24: exact
 }
 void launch_gen_pre(const GenArgs &a, hipStream_t s);
+void launch_gen_mask(const GenArgs &a, hipStream_t s);                                                               // a.dfa != null
 void launch_gen_post(const GenArgs &a, hipStream_t s);
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);
 void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T > 0

@@ -3830,6 +3830,9 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 // around `nucleus_kernel`, so that a captured step feeds itself.  Per step, after the head GEMM:
 //   gen_pre     penalty (transform, nucleus.rs:61-67) and bias (run.rs:681-683) onto the logits row from the slot's dense penalty /
 //               bias rows, and this step's SampleRow (uniform draw, Mirostat's max_surprise) for nucleus_kernel
+//   gen_mask    only in a step in which a slot has a byte-automaton constraint (rwkv_gen_set_constraint, gen_dfa.h): `Formatter::transform`
+//               (run.rs:676-679) on the device.  Every token id of a constrained row walks its bytes from the slot's state; the logit of
+//               a token that is not allowed becomes -inf, and the state each token ends in is kept for gen_post
 //   nucleus_kernel, as it is
 //   gen_post    the tail of `sample` (nucleus.rs:104-119 / mirostat.rs:85-87), the token into the feedback buffer and the output
 //               ring, stop tokens and max_tokens (run.rs:855, 905-917); with STOPS, the slot's stop STRINGS over the decoded bytes (run.rs:899-932, gen_stop.h)
@@ -3885,6 +3888,36 @@ __global__ __launch_bounds__(256) void gen_pre_kernel(GenArgs a) {
         v.x = gen_adjust(v.x, p.x, b.x); v.y = gen_adjust(v.y, p.y, b.y); v.z = gen_adjust(v.z, p.z, b.z); v.w = gen_adjust(v.w, p.w, b.w);
         *(float4 *)(x + i) = v;
     }
+}
+// One thread per token id: 65,536 independent short walks per row (a token of the World vocabulary has 1 - 128 bytes, 6 on average), each a
+// chain of dependent 2-byte loads from the slot's table in device memory (at most 2 MiB; the handful of rows a walk touches stay in L2).
+// A row without a constraint and a finished rider return at once.  Ids at and above n_tok have no bytes and are masked.
+template <bool MIXED>
+__global__ __launch_bounds__(256) void gen_mask_kernel(GenArgs a) {
+    const int row = blockIdx.y;
+    const int slot = gen_slot_of<MIXED>(a, row);
+    if (a.slots[slot].finish) return;
+    const GenDfa d = a.dfa[slot];
+    if (!d.trans) return;
+    const int V = a.V;
+    float *x = a.logits + (long)row * V;
+    unsigned short *end = a.tok_end + (long)row * V;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256) {
+        const unsigned e = gen_dfa_token_end(d.trans, (unsigned)d.state, a.tok_off, a.tok_bytes, a.n_tok, v);
+        end[v] = (unsigned short)e;
+        if (!e) x[v] = -INFINITY;
+    }
+}
+// `Formatter::update` (run.rs:892-897, bnf.rs:40-48) for the token thread 0 just emitted: the slot's state moves behind it — gen_mask kept
+// the state every token of the row ends in, so this is one load, not a serial walk — and the halt predicate is returned.  A token that
+// was not allowed leaves the state where it was and does not halt.  False for a slot without a constraint.
+__device__ __forceinline__ bool gen_dfa_update(const GenArgs &a, int row, int slot, int tok) {
+    if (!a.dfa) return false;
+    GenDfa &d = a.dfa[slot];
+    if (!d.trans) return false;
+    const unsigned e = (unsigned)tok < (unsigned)a.V ? a.tok_end[(long)row * a.V + tok] : 0u;
+    d.state = (int)gen_dfa_advance((unsigned)d.state, e);
+    return gen_dfa_halt(e, e ? d.flags[e] : (unsigned char)0, d.mode);
 }
 __device__ __forceinline__ unsigned gen_decay(unsigned pbits, int i, int tok, float decay, float freq, float pres) {
 #pragma clang fp contract(off)
@@ -3957,7 +3990,9 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int nstr = STOPS ? a.stops[slot].n_str : 0;
     if (nstr <= 0) {
         if (tid != 0) return;
-        const bool stop = gen_emit<MIXED>(a, g, row, slot, tok, k);
+        const bool halt = gen_dfa_update(a, row, slot, tok);
+        const bool stop_token = gen_emit<MIXED>(a, g, row, slot, tok, k);
+        const bool stop = halt || stop_token;                      // `halt || stop_matched || stop_token`, run.rs:990
         const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
         if (fin) { g.freeze_at = k; g.finish = fin; }
         return;
@@ -3988,7 +4023,9 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
         r = (tid & 4) ? gen_stop_merge(o, r) : gen_stop_merge(r, o);
         int keep_from = -1;                                        // >= 0: the slot goes on and its buffer becomes lds.buf[keep_from .. n)
         if (tid == 0) {
-            const bool stop = gen_emit<MIXED>(a, g, row, slot, tok, k) || unknown;
+            const bool halt = gen_dfa_update(a, row, slot, tok);
+            const bool stop_token = gen_emit<MIXED>(a, g, row, slot, tok, k);
+            const bool stop = halt || stop_token || unknown;
             const int fin = gen_stop_decide(stop, fits, r.matched != 0, g.emitted >= g.max_tokens);
             if (fin) { g.freeze_at = k; g.finish = fin; }
             else keep_from = gen_stop_keep_from(lds.buf, r.safe);  // run.rs:1008-1010: the head leaves only as valid UTF-8
@@ -4019,6 +4056,11 @@ __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
 void launch_gen_pre(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_pre_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_pre_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+}
+void launch_gen_mask(const GenArgs &a, hipStream_t s) {
+    const dim3 grid(min((a.V + 255) / 256, 256), a.n_rows);
+    if (a.out_rows) hipLaunchKernelGGL(gen_mask_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_mask_kernel<false>, grid, dim3(256), 0, s, a);
 }
 // a.stops != null selects the stop-string instantiation
 void launch_gen_post(const GenArgs &a, hipStream_t s) {

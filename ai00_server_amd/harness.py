@@ -186,6 +186,47 @@ class MirostatSampler:
         self.max_surprise = np.float32(min(np.float32(self.max_surprise - self.rate * err), np.float32(4.0) * self.target))
 
 
+class DfaFormatter:
+    """The reference's `Formatter` trait (sampler/bnf.rs:34-48) over a byte-level DFA (`runtime.Dfa`) — the host half of what
+    `Runtime.gen_set_constraint` runs on the device, for the per-token path: `transform(mask)` is the mask `infer_sample` takes as `allow`
+    (run.rs:676-679), `update(token) -> halt` advances and says whether the request stops (run.rs:892-897, 990).  A REGULAR constraint;
+    the reference's kbnf (context-free) is another implementation of the same trait.
+
+    `table[i]` is the bytes of token i, None for an unknown id (`gen_set_token_bytes`' table).  A token that is not allowed — id 0, an
+    empty or unknown token, one whose bytes kill the walk — leaves the state where it was and does not halt (bnf.rs:44)."""
+
+    def __init__(self, dfa, table, num_vocab: int, state: int | None = None, halt: int = 0):
+        self.dfa, self.table, self.num_vocab, self.halt = dfa, list(table), int(num_vocab), int(halt)
+        self.trans, self.accepting = dfa.table()
+        self.state = dfa.start if state is None else int(state)
+
+    def walk(self, state: int, word) -> int:
+        if not word:
+            return 0
+        for c in word:
+            state = int(self.trans[state, c])
+            if not state:
+                break
+        return state
+
+    def transform(self, mask=None):
+        """the allowed-token mask of the current state, written into `mask` (uint8 [num_vocab]) when one is given"""
+        allow = self.dfa.allow(self.state, self.table, self.num_vocab)
+        if mask is not None:
+            mask[:] = allow
+            return mask
+        return allow
+
+    def update(self, token: int) -> bool:
+        end = self.walk(self.state, self.table[token] if 0 < token < len(self.table) else None)      # token 0 is never allowed
+        if not end:
+            return False
+        self.state = end
+        if not self.accepting[end]:
+            return False
+        return self.halt == 1 or not self.trans[end].any()
+
+
 class StopMatcher:
     """The stop-STRING state machine of `process` (run.rs:855-869, 899-932, 990-1011), per token — the reference the device matcher
     (rwkv_gen_set_stops) is held to, and what a caller runs over the tokens it samples itself.

@@ -112,6 +112,18 @@ ABI_SYMBOLS = {
     "rwkv_gen_set_stops": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenStopsC)]),
     "rwkv_gen_stop_tail": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "rwkv_gen_uniform": (C.c_int32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_float)]),
+    "rwkv_dfa_from_table": (C.c_int32, [C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rwkv_dfa_compile": (C.c_int32, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "rwkv_dfa_free": (None, [C.c_void_p]),
+    "rwkv_dfa_num_states": (C.c_int32, [C.c_void_p]),
+    "rwkv_dfa_start": (C.c_int32, [C.c_void_p]),
+    "rwkv_dfa_table": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    "rwkv_dfa_walk": (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]),
+    "rwkv_dfa_allow": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_uint8),
+                                   C.c_size_t]),
+    "rwkv_dfa_check_live": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_size_t]),
+    "rwkv_gen_set_constraint": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "rwkv_gen_constraint_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "rwkv_plan_chunk": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "rwkv_state_len": (C.c_size_t, [C.c_void_p]),
     "rwkv_state_shape": (None, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -253,6 +265,91 @@ class GenFinish(enum.IntEnum):   # RWKV_GEN_*: FinishReason::{Stop, Length} run.
 
 GEN_MAX_STOP_STR, GEN_STOP_LEN, GEN_STOP_BUF, GEN_TOKEN_LEN = 8, 128, 512, 256      # RWKV_GEN_* limits of the device's stop-string matcher
 GEN_WIDE_TOP_K = 1               # RWKV_GEN_WIDE_TOP_K: bit of rwkv_gen_params.reserved that arms Nucleus / Typical with top_k > 256
+
+
+DFA_MAX_STATES = 4096            # RWKV_DFA_MAX_STATES, the dead state 0 included
+
+
+class DfaHalt(enum.IntEnum):     # RWKV_DFA_HALT_*
+    Final = 0                    # halt when the new state accepts and no byte leads from it to a live state
+    Accept = 1                   # halt the first time the new state accepts
+
+
+def _token_table_arrays(table):
+    """(bytes, lens) of a token table as rwkv_gen_set_token_bytes / rwkv_dfa_allow take it: `table[i]` is bytes, or None for an unknown id"""
+    lens = np.array([-1 if b is None else len(b) for b in table], np.int32)
+    data = np.frombuffer(b"".join(b for b in table if b is not None) or b"\0", np.uint8)
+    return data, lens
+
+
+class Dfa:
+    """A byte-level DFA (rwkv_dfa): the constraint resident generation masks on the device, and the same `Formatter` for the per-token
+    path (`allow`).  State 0 is dead.  `Dfa.compile(pattern)` takes the anchored regex dialect of include/rwkv_abi.h, `Dfa.from_table`
+    any compiler's table.  Host only, needs no GPU.  It covers REGULAR constraints; it is not the reference's kbnf."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def compile(cls, pattern) -> "Dfa":
+        data = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+        h = C.c_void_p()
+        _check(lib().rwkv_dfa_compile(data, len(data), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_table(cls, trans, accepting, start: int = 1) -> "Dfa":
+        t = np.ascontiguousarray(trans, dtype=np.uint16).reshape(-1, 256)
+        a = np.ascontiguousarray(accepting, dtype=np.uint8).reshape(-1)
+        if a.size != t.shape[0]:
+            raise RwkvError(-1, "dfa: one accepting flag per row of the table")
+        h = C.c_void_p()
+        _check(lib().rwkv_dfa_from_table(t.ctypes.data_as(C.POINTER(C.c_uint16)), a.ctypes.data_as(C.POINTER(C.c_uint8)), t.shape[0], int(start),
+                                         C.byref(h)))
+        return cls(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().rwkv_dfa_free(self._h)
+            except Exception:
+                pass
+
+    @property
+    def num_states(self) -> int:
+        return int(lib().rwkv_dfa_num_states(self._h))
+
+    @property
+    def start(self) -> int:
+        return int(lib().rwkv_dfa_start(self._h))
+
+    def table(self):
+        """(trans uint16 [num_states, 256], accepting uint8 [num_states])"""
+        n = self.num_states
+        t, a = np.empty((n, 256), np.uint16), np.empty(n, np.uint8)
+        _check(lib().rwkv_dfa_table(self._h, t.ctypes.data_as(C.POINTER(C.c_uint16)), a.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return t, a
+
+    def walk(self, state: int, data: bytes) -> int:
+        nxt = C.c_int32(0)
+        _check(lib().rwkv_dfa_walk(self._h, int(state), bytes(data), len(data), C.byref(nxt)))
+        return int(nxt.value)
+
+    def check_live(self, table, state: int | None = None, halt: "DfaHalt" = DfaHalt.Final):
+        """The liveness rule of `gen_set_constraint` on the host (rwkv_dfa_check_live): raises RwkvError(-3) when a state the request can come
+        to rest in has no single-byte token of `table` that leads on."""
+        data, lens = _token_table_arrays(table)
+        _check(lib().rwkv_dfa_check_live(self._h, int(self.start if state is None else state), int(halt), lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None,
+                                         data.ctypes.data_as(C.POINTER(C.c_uint8)), lens.size))
+
+    def allow(self, state: int, table, num_vocab: int) -> np.ndarray:
+        """The `num_vocab`-byte mask `infer_sample` takes as `allow` (rwkv_dfa_allow): token v is allowed in `state` iff it is in `table`,
+        known, non-empty, and its bytes lead to a live state."""
+        data, lens = _token_table_arrays(table)
+        out = np.empty(int(num_vocab), np.uint8)
+        _check(lib().rwkv_dfa_allow(self._h, int(state), data.ctypes.data_as(C.POINTER(C.c_uint8)), lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None,
+                                    lens.size, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
 
 
 def list_adapters() -> list[str]:
@@ -634,7 +731,8 @@ class Runtime:
         """Arm `slot` with the settings AND the current state of a host-side sampler (`harness.NucleusSampler` / `TypicalSampler` /
         `MirostatSampler`, after its `init(prompt)`): the penalty map it holds is handed over, `sampler.bias` (or `bias`) rides along.
         `first_token` is the token the first step consumes; draw `i` of the slot is `gen_uniform(seed, stream, i)` (stream defaults
-        to the slot index).  `allow` exists to be refused: a formatter mask needs the host between tokens (use `infer_sample`).
+        to the slot index).  `allow` exists to be refused: a host-computed formatter mask needs the host between tokens (use `infer_sample`, or a `Dfa` with
+        `gen_set_constraint`).
         `wide_top_k` sets RWKV_GEN_WIDE_TOP_K: Nucleus / Typical with `top_k > 256` is armed instead of refused."""
         p, keep = self._gen_params(slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k)
         _check(lib().rwkv_gen_arm(self._h, int(slot), C.byref(p)))
@@ -665,8 +763,7 @@ class Runtime:
         """What `tokenizer.decode([token])` yields per id (rwkv_gen_set_token_bytes; run.rs:856): `table[i]` is the bytes of id i, or None
         for an id that is not in the vocabulary (the decode error of run.rs:858-862: empty word, stop).  `Tokenizer.token_index_to_bytes()`
         with its empty entries turned into None is such a table.  The device matches stop strings over these bytes."""
-        lens = np.array([-1 if b is None else len(b) for b in table], np.int32)
-        data = np.frombuffer(b"".join(b for b in table if b is not None) or b"\0", np.uint8)
+        data, lens = _token_table_arrays(table)
         _check(lib().rwkv_gen_set_token_bytes(self._h, data.ctypes.data_as(C.POINTER(C.c_uint8)),
                                               lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None, lens.size))
 
@@ -689,6 +786,22 @@ class Runtime:
         n = C.c_size_t(0)
         _check(lib().rwkv_gen_stop_tail(self._h, int(slot), out, GEN_STOP_BUF, C.byref(n)))
         return bytes(out[:min(int(n.value), GEN_STOP_BUF)])
+
+    def gen_set_constraint(self, slot: int, dfa: "Dfa | None", state: int | None = None, halt: "DfaHalt" = DfaHalt.Final):
+        """The byte-automaton constraint of an armed, unfinished slot (rwkv_gen_set_constraint), set between runs: from then on the slot's
+        row is masked, its state advanced and the halt tested on the device.  `state` defaults to the start state (right after
+        `gen_arm_prompt`); after `gen_arm` it is the state behind `first_token`.  `dfa=None` clears the constraint."""
+        if dfa is None:
+            _check(lib().rwkv_gen_set_constraint(self._h, int(slot), None, 0, 0))
+            return
+        _check(lib().rwkv_gen_set_constraint(self._h, int(slot), dfa._h, int(dfa.start if state is None else state), int(halt)))
+
+    def gen_constraint_state(self, slot: int) -> int:
+        """The automaton state behind every token the slot has emitted (rwkv_gen_constraint_state): what a caller that goes on per token
+        hands its `harness.DfaFormatter`."""
+        st = C.c_int32(0)
+        _check(lib().rwkv_gen_constraint_state(self._h, int(slot), C.byref(st)))
+        return int(st.value)
 
     def gen_run(self, n_steps: int):
         """Up to `n_steps` decode steps of every armed, unfinished slot without a host turn-around.  Returns (tokens uint32

@@ -40,7 +40,9 @@ extern "C" {
                               *    additive under 9: rwkv_gen_set_token_bytes, rwkv_gen_set_stops, rwkv_gen_stop_tail, RWKV_GEN_HANDBACK: stop STRINGS are
                               *    matched on the device inside the resident step
                               *    additive under 9 (no new symbol, no struct changed): RWKV_V4 — RWKV-4 World checkpoints load (version 4 in
-                              *    rwkv_model_info, the five-row state below); they were RWKV_ERR_UNSUPPORTED before */
+                              *    rwkv_model_info, the five-row state below); they were RWKV_ERR_UNSUPPORTED before
+                              *    additive under 9: rwkv_dfa_* (byte automata, host only), rwkv_gen_set_constraint, rwkv_gen_constraint_state: a REGULAR
+                              *    format constraint is masked and advanced on the device inside the resident step */
 
 typedef int32_t rwkv_status;
 enum {
@@ -301,8 +303,11 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
  *    becomes valid UTF-8 keeps growing) the slot finishes with RWKV_GEN_HANDBACK: the token is emitted and the state rule holds as for any
  *    finish; the caller, who has every token, replays its own matcher (include/rwkv_scheduler.hpp StopMatcher) and goes on per token.
  *    A slot that finishes — whatever the reason — leaves its buffer as it was before its last token.
- *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a formatter mask (`allow` must be NULL: a grammar needs the
- *    host between two tokens, run.rs:676-679 — keep using rwkv_infer_sample), top_k > 256 (Nucleus / Typical) unless `reserved` carries
+ *  - FORMAT CONSTRAINTS: a formatter that needs the host between two tokens — kbnf's context-free grammars, sampler/bnf.rs — stays
+ *    refused here; what this mode offers instead is a byte-level DFA (rwkv_dfa_*, rwkv_gen_set_constraint below), masked and advanced on
+ *    the device.  It is a second implementation of the `Formatter` trait (bnf.rs:34-48) for REGULAR constraints, not kbnf and no port of it.
+ *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a host-computed formatter mask (`allow` must be NULL,
+ *    run.rs:676-679 — keep using rwkv_infer_sample for a grammar), top_k > 256 (Nucleus / Typical) unless `reserved` carries
  *    RWKV_GEN_WIDE_TOP_K, more than RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
  *  - RWKV_GEN_WIDE_TOP_K (bit 0 of `reserved`; the other bits are ignored) arms Nucleus / Typical with any top_k (above num_vocab:
  *    num_vocab); the slot then takes the wide kernel iff top_k > 256.  Mirostat needs no flag: a slot whose max_surprise can reach 13
@@ -403,6 +408,71 @@ rwkv_status rwkv_gen_set_stops(rwkv_engine *e, int32_t slot, const rwkv_gen_stop
 rwkv_status rwkv_gen_stop_tail(rwkv_engine *e, int32_t slot, uint8_t *out, size_t cap, size_t *len);
 /* the draws `first_step .. first_step + n - 1` of (seed, stream): pure host function, no device needed */
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out);
+
+/* ---- `Formatter` (sampler/bnf.rs:34-48; run.rs:676-680 `transform`, 892-897 `update`, 990 halt) for REGULAR constraints: a byte-level DFA.
+ * The reference's formatter is kbnf, a context-free engine that lives on the host; this is a second implementation of the same trait for
+ * what a finite automaton can say (enumerations, numbers, dates, fixed-field JSON objects), NOT kbnf and no port of it.
+ *   - The automaton: trans[n_states][256] (uint16, row-major), accepting[n_states], a start state.  State 0 is DEAD: its row is all zeros
+ *     and it accepts nothing.  A state is LIVE when it is not 0.  n_states <= RWKV_DFA_MAX_STATES, DEAD included.
+ *   - ALLOWED (`transform`, bnf.rs:35-38): in state q token v is allowed iff v < n_tokens of the token table, its entry is known and
+ *     NON-EMPTY, and walking its bytes from q ends in a live state.  Token 0 (the end-of-sequence id, run.rs:855, whatever a table says
+ *     of it; the World vocabulary has no entry for it), empty tokens (bnf.rs:18) and unknown ids are never allowed, so a constrained request ends by halt, stop token, stop string or max_tokens, never by a sampled EOS.  A masked logit is -inf before
+ *     the softmax; penalties and bias add to -inf and leave it -inf, so their order against the mask is immaterial (run.rs:676-683).
+ *     DEVIATION from the reference, on purpose: bnf.rs:36 masks only output[..vocab_size] and leaves the ids between the tokenizer's size
+ *     and num_vocab untouched; here they are masked, because they decode to the reference's error-and-stop (run.rs:858-862).
+ *   - ADVANCE (`update`, bnf.rs:40-48): after a draw the state moves over the drawn token's bytes.  A drawn token that is not allowed
+ *     leaves the state where it was and does not halt (kbnf rejects it and goes on, bnf.rs:44).
+ *   - HALT, per slot: RWKV_DFA_HALT_FINAL — the new state accepts and no byte leads from it to a live state; RWKV_DFA_HALT_ACCEPT — the
+ *     new state accepts.  Halt is or-ed into the token-stop predicate (`halt || stop_matched || stop_token`, run.rs:990: FinishReason::Stop,
+ *     before max_tokens).  The halting token is emitted as the slot's last token and the STATE RULE above holds unchanged.
+ * Handles are immutable and thread-safe, like tokenizer handles; every rwkv_dfa_* function is a pure host function, no device needed. */
+#define RWKV_DFA_MAX_STATES 4096
+enum { RWKV_DFA_HALT_FINAL = 0, RWKV_DFA_HALT_ACCEPT = 1 };
+typedef struct rwkv_dfa rwkv_dfa;
+/* any compiler's output (json2kbnf.py-style helpers may target it).  RWKV_ERR_INVALID: state 0 is not dead, a target >= n_states, start
+ * outside [1, n_states), n_states < 2, a NULL array.  RWKV_ERR_UNSUPPORTED: n_states > RWKV_DFA_MAX_STATES.  Nothing is trimmed or
+ * renumbered; accepting[] is read as zero / non-zero.  Copied. */
+rwkv_status rwkv_dfa_from_table(const uint16_t *trans, const uint8_t *accepting, int32_t n_states, int32_t start, rwkv_dfa **out);
+/* A small ANCHORED regex dialect (the whole output must match), `GenerateRequest::bnf_schema`'s regular cousin (docs/doc-guide/features.md "BNF"):
+ *   literals   UTF-8 text (a multi-byte character is one atom)
+ *   escapes    \n \r \t \\ \" \/ \xHH, an escaped metacharacter ( . [ ] ( ) { } | * + ? ^ $ - ), \d = [0-9], \w = [A-Za-z0-9_], \s = [ \t\r\n]
+ *   classes    [...] of ASCII members and ranges; [^...] = any WELL-FORMED UTF-8 character (Unicode table 3-7, the rule of the stop-string
+ *              buffer) that is not in the ASCII set; . = [^\n]
+ *   structure  ( ) | * + ? {m} {m,} {m,n} with counts <= 255; a repeat of a repeat needs a group
+ * Thompson NFA -> subset construction -> trim (a state that cannot reach an accepting state becomes DEAD) -> minimise -> canonical
+ * numbering (breadth-first from the start state, bytes ascending, start = 1): a language has exactly one table, whatever its spelling.
+ * RWKV_ERR_INVALID: a malformed pattern, with the byte offset in rwkv_last_error.  RWKV_ERR_UNSUPPORTED: the pattern matches nothing, or
+ * needs too many states (RWKV_DFA_MAX_STATES after minimisation, or the compiler's own working limits before it). */
+rwkv_status rwkv_dfa_compile(const uint8_t *pattern, size_t len, rwkv_dfa **out);
+void rwkv_dfa_free(rwkv_dfa *d);
+int32_t rwkv_dfa_num_states(const rwkv_dfa *d);
+int32_t rwkv_dfa_start(const rwkv_dfa *d);
+/* reads the table back: trans[num_states * 256], accepting[num_states] (either may be NULL) */
+rwkv_status rwkv_dfa_table(const rwkv_dfa *d, uint16_t *trans, uint8_t *accepting);
+/* the state `n` bytes behind `state` (0 once the walk died) */
+rwkv_status rwkv_dfa_walk(const rwkv_dfa *d, int32_t state, const uint8_t *bytes, size_t n, int32_t *next);
+/* `transform` on the host: the num_vocab-byte mask rwkv_sample_params.allow takes, by the ALLOWED rule above; `bytes` / `lens` / n_tokens as
+ * in rwkv_gen_set_token_bytes.  The per-token path gets the same formatter without a device, and a caller can hand a request over between
+ * the two paths in either direction (rwkv_gen_constraint_state). */
+rwkv_status rwkv_dfa_allow(const rwkv_dfa *d, int32_t state, const uint8_t *bytes, const int32_t *lens, size_t n_tokens, uint8_t *allow,
+                           size_t num_vocab);
+/* The LIVENESS rule of rwkv_gen_set_constraint as a pure host function, over a token table given as to rwkv_gen_set_token_bytes (note
+ * the order: lens first): RWKV_OK, or RWKV_ERR_UNSUPPORTED when a state the slot can come to rest in has no single-byte token that leads to
+ * a live state.  O(states x 256). */
+rwkv_status rwkv_dfa_check_live(const rwkv_dfa *d, int32_t state, int32_t halt_mode, const int32_t *lens, const uint8_t *bytes, size_t n_tokens);
+/* The constraint of an armed, unfinished slot, set between runs like rwkv_gen_set_stops; the table is copied to the device, `dfa` may be
+ * freed on return.  `state`: the start state after rwkv_gen_arm_prompt; after rwkv_gen_arm the state behind first_token, which the
+ * caller sampled and advanced itself.  dfa == NULL clears the constraint; re-arming a slot and everything that disarms it clear it too.
+ * From then on every step masks the slot's row on the device (the tokens that are not ALLOWED become -inf between the penalties and the
+ * sampling kernel), advances the state behind the drawn token and tests HALT; steps in which no slot has a constraint launch what they
+ * launched before.
+ * RWKV_ERR_INVALID: the slot is not armed or has finished, no token table (rwkv_gen_set_token_bytes), state 0 or out of range, a bad
+ * halt_mode.  RWKV_ERR_UNSUPPORTED: LIVENESS — every live state reachable from `state` in which the slot can come to rest (one that does
+ * not halt) must have a SINGLE-BYTE token of the table that leads to a live state, which is what guarantees that a row is never all -inf
+ * (the World vocabulary holds all 256 single-byte tokens).  rwkv_gen_set_token_bytes is refused while any slot has a constraint. */
+rwkv_status rwkv_gen_set_constraint(rwkv_engine *e, int32_t slot, const rwkv_dfa *dfa, int32_t state, int32_t halt_mode);
+/* The state behind every token the slot has emitted, the last one included (0 for a slot without a constraint).  Waits for the device. */
+rwkv_status rwkv_gen_constraint_state(rwkv_engine *e, int32_t slot, int32_t *state);
 
 /* ---- `Tokenizer` lib.rs:375; run.rs:157-168,856; sampler/bnf.rs:14-27 ---------------------- */
 typedef struct rwkv_tokenizer rwkv_tokenizer;

@@ -44,6 +44,40 @@ struct RnnInput {                           // RnnInput::new(batches, token_chun
 };
 using RnnOutputBatch = std::vector<float>;  // n_rows * num_vocab floats (empty: nothing emitted)
 
+// A byte-level DFA (rwkv_dfa): the REGULAR format constraint resident generation masks on the device (Runtime::gen_set_constraint) and the
+// same `Formatter` (sampler/bnf.rs:34-48) for the per-token path (DfaFormatter, include/rwkv_sampler.hpp).  Not kbnf.  Host only.
+class Dfa {
+   public:
+    static Dfa compile(const std::string &pattern) {
+        rwkv_dfa *d = nullptr;
+        check(rwkv_dfa_compile((const uint8_t *)pattern.data(), pattern.size(), &d));
+        return Dfa(d);
+    }
+    static Dfa from_table(const std::vector<uint16_t> &trans, const std::vector<uint8_t> &accepting, int32_t start = 1) {
+        if (trans.size() != accepting.size() * 256) throw std::invalid_argument("Dfa::from_table: 256 transitions per state");
+        rwkv_dfa *d = nullptr;
+        check(rwkv_dfa_from_table(trans.data(), accepting.data(), (int32_t)accepting.size(), start, &d));
+        return Dfa(d);
+    }
+    int32_t num_states() const { return rwkv_dfa_num_states(d_.get()); }
+    int32_t start() const { return rwkv_dfa_start(d_.get()); }
+    int32_t walk(int32_t state, const uint8_t *bytes, size_t n) const {
+        int32_t next = 0;
+        check(rwkv_dfa_walk(d_.get(), state, bytes, n, &next));
+        return next;
+    }
+    bool accepting(int32_t state) const {
+        std::vector<uint8_t> acc((size_t)num_states());
+        check(rwkv_dfa_table(d_.get(), nullptr, acc.data()));
+        return state >= 0 && (size_t)state < acc.size() && acc[(size_t)state] != 0;
+    }
+    const rwkv_dfa *raw() const { return d_.get(); }
+
+   private:
+    explicit Dfa(rwkv_dfa *d) : d_(d, rwkv_dfa_free) {}
+    std::shared_ptr<rwkv_dfa> d_;
+};
+
 class Runtime;
 class TensorGpu {                            // device-resident state snapshot (`state.read`)
    public:
@@ -232,6 +266,19 @@ class Runtime {
         check(rwkv_gen_stop_tail(e_.get(), slot, out.data(), out.size(), &len));
         out.resize(std::min(len, out.size()));
         return out;
+    }
+    // The format constraint of an armed, unfinished slot (rwkv_gen_set_constraint; `Formatter`, run.rs:676-680, 892-897, 990), next to its
+    // stop strings: masked, advanced and halted on the device.  `state`: dfa.start() after gen_arm_prompt; after gen_arm the state behind
+    // first_token (DfaFormatter::state after its update).  Needs the token table (gen_set_token_bytes).
+    void gen_set_constraint(int slot, const Dfa &dfa, int32_t state, int32_t halt_mode = RWKV_DFA_HALT_FINAL) {
+        check(rwkv_gen_set_constraint(e_.get(), slot, dfa.raw(), state, halt_mode));
+    }
+    void gen_clear_constraint(int slot) { check(rwkv_gen_set_constraint(e_.get(), slot, nullptr, 0, 0)); }
+    // the state behind every token the slot has emitted: what a caller that goes on per token hands its DfaFormatter
+    int32_t gen_constraint_state(int slot) {
+        int32_t state = 0;
+        check(rwkv_gen_constraint_state(e_.get(), slot, &state));
+        return state;
     }
     struct Generated {
         std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing

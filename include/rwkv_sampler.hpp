@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdint>
 #include <map>
+#include <utility>
 #include <vector>
 
 #include "rwkv_abi.h"
@@ -31,6 +32,51 @@ struct SamplerAdjust {                 // keeps the arrays rwkv_sample_params po
 struct GenArrays {                     // keeps the arrays rwkv_gen_params points into alive until rwkv_gen_arm returns (it copies them)
     std::vector<uint32_t> penalty_tokens, bias_tokens, stop_tokens;
     std::vector<float> penalty_values, bias_values;
+};
+
+// The reference's `Formatter` trait (sampler/bnf.rs:34-48) over a byte-level DFA (rwkv_dfa_*), for the per-token path: `transform`
+// yields the mask rwkv_sample_params.allow takes (run.rs:676-679), `update` advances and says whether the request halts (run.rs:892-897,
+// 990).  The same automaton runs on the device under rwkv_gen_set_constraint; `state` is what the two paths hand each other
+// (rwkv_gen_constraint_state in one direction, the `state` argument of rwkv_gen_set_constraint in the other).  REGULAR constraints only:
+// the reference's kbnf is another implementation of the trait.  The token table is the one rwkv_gen_set_token_bytes takes.
+class DfaFormatter {
+   public:
+    DfaFormatter(const rwkv_dfa *dfa, std::vector<uint8_t> token_bytes, std::vector<int32_t> token_lens, size_t num_vocab,
+                 int32_t halt_mode = RWKV_DFA_HALT_FINAL)
+        : state(rwkv_dfa_start(dfa)), dfa_(dfa), bytes_(std::move(token_bytes)), lens_(std::move(token_lens)), allow_(num_vocab), halt_(halt_mode) {
+        const size_t n = (size_t)rwkv_dfa_num_states(dfa);
+        trans_.resize(n * 256);
+        accepting_.resize(n);
+        rwkv_dfa_table(dfa, trans_.data(), accepting_.data());
+        off_.resize(lens_.size() + 1, 0);
+        for (size_t i = 0; i < lens_.size(); ++i) off_[i + 1] = off_[i] + (lens_[i] > 0 ? (size_t)lens_[i] : 0);
+    }
+    int32_t state;                     // the state behind every token handled so far
+    // the mask of the current state; valid until the next call
+    const uint8_t *transform() {
+        rwkv_dfa_allow(dfa_, state, bytes_.data(), lens_.data(), lens_.size(), allow_.data(), allow_.size());
+        return allow_.data();
+    }
+    // a token that is not allowed (id 0, an empty or unknown token, bytes that kill the walk) leaves the state and does not halt (bnf.rs:44)
+    bool update(uint32_t token) {
+        if (token == 0 || token >= lens_.size() || lens_[token] <= 0) return false;
+        int32_t end = 0;
+        if (rwkv_dfa_walk(dfa_, state, bytes_.data() + off_[token], (size_t)lens_[token], &end) != RWKV_OK || end == 0) return false;
+        state = end;
+        if (!accepting_[(size_t)end]) return false;
+        if (halt_ == RWKV_DFA_HALT_ACCEPT) return true;
+        for (int c = 0; c < 256; ++c) if (trans_[(size_t)end * 256 + (size_t)c]) return false;
+        return true;
+    }
+
+   private:
+    const rwkv_dfa *dfa_;
+    std::vector<uint8_t> bytes_;
+    std::vector<int32_t> lens_;
+    std::vector<size_t> off_;
+    std::vector<uint16_t> trans_;
+    std::vector<uint8_t> accepting_, allow_;
+    int32_t halt_;
 };
 
 class NucleusSampler {

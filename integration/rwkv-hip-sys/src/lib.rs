@@ -39,12 +39,16 @@ pub const RWKV_GEN_STOP_LEN: usize = 128;
 pub const RWKV_GEN_STOP_BUF: usize = 512;
 pub const RWKV_GEN_TOKEN_LEN: usize = 256;
 pub const RWKV_GEN_WIDE_TOP_K: u32 = 1;
+pub const RWKV_DFA_MAX_STATES: usize = 4096;
+pub const RWKV_DFA_HALT_FINAL: i32 = 0;
+pub const RWKV_DFA_HALT_ACCEPT: i32 = 1;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 pub const RWKV_SCORE_SKIP: u32 = 4294967295;
 
 #[repr(C)] pub struct rwkv_engine { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_dstate { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_tokenizer { _p: [u8; 0] }
+#[repr(C)] pub struct rwkv_dfa { _p: [u8; 0] }
 
 #[repr(C)] #[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
 pub struct rwkv_model_info { pub version: i32, pub num_layer: i32, pub num_emb: i32, pub num_hidden: i32,
@@ -130,6 +134,19 @@ extern "C" {
     pub fn rwkv_gen_set_stops(e: *mut rwkv_engine, slot: i32, s: *const rwkv_gen_stops) -> rwkv_status;
     pub fn rwkv_gen_stop_tail(e: *mut rwkv_engine, slot: i32, out: *mut u8, cap: usize, len: *mut usize) -> rwkv_status;
     pub fn rwkv_gen_uniform(seed: u64, stream: u32, first_step: u32, n: usize, out: *mut c_float) -> rwkv_status;
+    // `Formatter` for regular constraints: byte-level DFAs, masked and advanced on the device (sampler/bnf.rs:34-48, run.rs:676-680, 892-897, 990)
+    pub fn rwkv_dfa_from_table(trans: *const u16, accepting: *const u8, n_states: i32, start: i32, out: *mut *mut rwkv_dfa) -> rwkv_status;
+    pub fn rwkv_dfa_compile(pattern: *const u8, len: usize, out: *mut *mut rwkv_dfa) -> rwkv_status;
+    pub fn rwkv_dfa_free(d: *mut rwkv_dfa);
+    pub fn rwkv_dfa_num_states(d: *const rwkv_dfa) -> i32;
+    pub fn rwkv_dfa_start(d: *const rwkv_dfa) -> i32;
+    pub fn rwkv_dfa_table(d: *const rwkv_dfa, trans: *mut u16, accepting: *mut u8) -> rwkv_status;
+    pub fn rwkv_dfa_walk(d: *const rwkv_dfa, state: i32, bytes: *const u8, n: usize, next: *mut i32) -> rwkv_status;
+    pub fn rwkv_dfa_allow(d: *const rwkv_dfa, state: i32, bytes: *const u8, lens: *const i32, n_tokens: usize, allow: *mut u8,
+                          num_vocab: usize) -> rwkv_status;
+    pub fn rwkv_dfa_check_live(d: *const rwkv_dfa, state: i32, halt_mode: i32, lens: *const i32, bytes: *const u8, n_tokens: usize) -> rwkv_status;
+    pub fn rwkv_gen_set_constraint(e: *mut rwkv_engine, slot: i32, dfa: *const rwkv_dfa, state: i32, halt_mode: i32) -> rwkv_status;
+    pub fn rwkv_gen_constraint_state(e: *mut rwkv_engine, slot: i32, state: *mut i32) -> rwkv_status;
     // Tokenizer  (lib.rs:375, run.rs:157, 856, bnf.rs:15)
     pub fn rwkv_tokenizer_create(vocab_json: *const c_char, len: usize, out: *mut *mut rwkv_tokenizer) -> rwkv_status;
     pub fn rwkv_tokenizer_destroy(t: *mut rwkv_tokenizer);

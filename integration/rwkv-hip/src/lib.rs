@@ -302,6 +302,18 @@ impl Engine {
         out.truncate(len);
         Ok(out)
     }
+    /// The format constraint of an armed, unfinished slot (rwkv_gen_set_constraint): a byte-level DFA masked, advanced and halted on the
+    /// device — the `Formatter` trait (sampler/bnf.rs:34-48) for REGULAR constraints; kbnf's grammars stay on the host.  `state` is
+    /// `dfa.start()` after `gen_arm_prompt`, after `gen_arm` the state behind `first_token`.  `None` clears the constraint.
+    pub fn gen_set_constraint(&self, slot: usize, dfa: Option<&Dfa>, state: i32, halt: DfaHalt) -> Result<()> {
+        let raw = dfa.map_or(ptr::null(), |d| d.raw as *const sys::rwkv_dfa);
+        check(unsafe { sys::rwkv_gen_set_constraint(self.raw, slot as i32, raw, state, halt as i32) })
+    }
+    /// the automaton state behind every token the slot has emitted (rwkv_gen_constraint_state): what the per-token path goes on from
+    pub fn gen_constraint_state(&self, slot: usize) -> Result<i32> {
+        let mut state = 0i32;
+        check(unsafe { sys::rwkv_gen_constraint_state(self.raw, slot as i32, &mut state) })?; Ok(state)
+    }
     /// Up to `n_steps` tokens for every armed, unfinished slot with no host turn-around (rwkv_gen_run).  When it returns a slot's
     /// state has consumed everything it emitted except the last token (what run.rs:990-1005 backs up at a stop).
     pub fn gen_run(&self, n_steps: usize) -> Result<Generated> {
@@ -312,6 +324,41 @@ impl Engine {
     }
 }
 
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum DfaHalt { #[default] Final = 0, Accept = 1 }
+/// A byte-level DFA (rwkv_dfa): state 0 is dead, `compile` takes the anchored regex dialect of include/rwkv_abi.h, `from_table` any
+/// compiler's table.  Immutable; host only.  Not kbnf: regular constraints only.
+#[derive(Debug)]
+pub struct Dfa { raw: *mut sys::rwkv_dfa }
+unsafe impl Send for Dfa {}
+unsafe impl Sync for Dfa {}
+impl Drop for Dfa { fn drop(&mut self) { unsafe { sys::rwkv_dfa_free(self.raw) } } }
+impl Dfa {
+    pub fn compile(pattern: &[u8]) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_dfa_compile(pattern.as_ptr(), pattern.len(), &mut raw) })?; Ok(Self { raw })
+    }
+    pub fn from_table(trans: &[u16], accepting: &[u8], start: i32) -> Result<Self> {
+        if trans.len() != accepting.len() * 256 {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "Dfa::from_table: 256 transitions per state".into() });
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_dfa_from_table(trans.as_ptr(), accepting.as_ptr(), accepting.len() as i32, start, &mut raw) })?; Ok(Self { raw })
+    }
+    pub fn num_states(&self) -> i32 { unsafe { sys::rwkv_dfa_num_states(self.raw) } }
+    pub fn start(&self) -> i32 { unsafe { sys::rwkv_dfa_start(self.raw) } }
+    /// the state `bytes` behind `state` (0 once the walk died)
+    pub fn walk(&self, state: i32, bytes: &[u8]) -> Result<i32> {
+        let mut next = 0i32;
+        check(unsafe { sys::rwkv_dfa_walk(self.raw, state, bytes.as_ptr(), bytes.len(), &mut next) })?; Ok(next)
+    }
+    /// `Formatter::transform` on the host (rwkv_dfa_allow): the mask `SampleParams::allow` takes; `tokens` as for `gen_set_token_bytes`
+    pub fn allow(&self, state: i32, tokens: &[Option<&[u8]>], num_vocab: usize) -> Result<Vec<u8>> {
+        let lens: Vec<i32> = tokens.iter().map(|t| t.map_or(-1, |b| b.len() as i32)).collect();
+        let bytes: Vec<u8> = tokens.iter().flat_map(|t| t.unwrap_or(&[]).iter().copied()).collect();
+        let mut out = vec![0u8; num_vocab];
+        check(unsafe { sys::rwkv_dfa_allow(self.raw, state, bytes.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), num_vocab) })?; Ok(out)
+    }
+}
 #[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum SamplerKind { #[default] Nucleus = 0, Typical = 1, Mirostat = 2 }
 /// `rwkv_gen_params`: sampler settings (nucleus.rs:13-26, typical.rs:11-24, mirostat.rs:11-36), the penalty map `init` left over the
 /// prompt (nucleus.rs:49-59), `GenerateRequest::bias` (run.rs:681-683), stop tokens (token 0 always stops, run.rs:855) and the
