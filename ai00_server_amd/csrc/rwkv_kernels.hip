@@ -3290,7 +3290,9 @@ __global__ void logit_adjust_kernel(float *logits, int V, const int *rows, const
     if (i < n && toks[i] >= 0 && toks[i] < V) logits[(long)rows[i] * V + toks[i]] += vals[i];   // host merges duplicates
 }
 
-constexpr int NUC_THREADS = 1024, NUC_EPT = 64, NUC_CAND = 1024;
+// NUC_CAND_MAX: the candidate slots of the Mirostat instantiation of nucleus_kernel, and of one window of sample_wide_kernel.
+constexpr int NUC_THREADS = 1024, NUC_EPT = 64, NUC_CAND = 1024, NUC_CAND_MAX = 8192;
+constexpr int NUC_SLOT_BYTES = sizeof(unsigned long long) + sizeof(float);   // dynamic LDS per candidate slot: cand[] entry + qv[] entry
 
 __device__ __forceinline__ float block_reduce_1024(float v, float *red, bool is_max) {
 #pragma unroll
@@ -3303,99 +3305,85 @@ __device__ __forceinline__ float block_reduce_1024(float v, float *red, bool is_
     return r;
 }
 
-// NC = candidate capacity; MIRO = the Mirostat instantiation (kind 2 rows only; the other one takes kinds 0 and 1).
-// Mirostat (mirostat.rs:44-90): sort descending, k = 1 + #(tokens whose surprise -log2 p does not exceed max_surprise)
-// (exact while that fits NC = 8192, i.e. max_surprise < 13; the engine routes the rows beyond to sample_wide_kernel), no temperature,
-// draw u * sum against the running sum; `out_prob` carries the token surprise log2(sum) - log2(p) the host needs for
-// its update of max_surprise.
+// =====================================================================================
+// The sampler stages, shared by nucleus_kernel and sample_wide_kernel: both kernels run THESE functions up to the walk over the sorted
+// candidates, which is why a row both can serve gets the same candidates, in the same order, with the same bits, from either.
+// The row is the caller's register array p[NUC_EPT] (element j of thread t is token j * NUC_THREADS + t), taken by reference; `lane` is
+// the caller's thread id as it wants it seen by the element-id arithmetic (sample_wide_kernel passes an opaque copy); `red` is the 16
+// floats of block_reduce_1024, `cnt` the [2][16 waves][4] per-wave partial counts of nuc_count3, double-buffered.
+// `lane` enters the element-id arithmetic ONLY; zeroing, wave leaders and the sort read threadIdx.x — unifying the two moves registers.
+// =====================================================================================
+// per-wave counts arrive as wave-uniform integers: a count is s_bcnt1 of the compare mask (v_cmp -> SALU), no cross-lane sum.
+// Written as asm: left to itself hipcc batches the 192 compares of a step and spills their masks to VGPR lanes (17 k lines).
+// (compare, count and accumulate in one statement: with the count as an asm OUTPUT hipcc still parks every count in a lane)
+__device__ __forceinline__ void nuc_wcount3(int &c1, int &c2, int &c3, unsigned key, unsigned t1, unsigned t2, unsigned t3) {   // c_i += #lanes(key >= t_i)
+    asm volatile("v_cmp_le_u32 vcc, %3, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %0, %0, vcc_lo\n\t"
+                 "v_cmp_le_u32 vcc, %4, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %1, %1, vcc_lo\n\t"
+                 "v_cmp_le_u32 vcc, %5, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %2, %2, vcc_lo"
+                 : "+s"(c1), "+s"(c2), "+s"(c3) : "s"(t1), "s"(t2), "s"(t3), "v"(key) : "vcc", "scc");
+}
+// the three per-wave counts summed over the block, in wave order (one barrier; `buf` alternates so that the next call needs none)
+__device__ __forceinline__ void nuc_count3(float *cnt, int buf, float c1, float c2, float c3, float &s1, float &s2, float &s3) {
+    const int tid = threadIdx.x;
+    float *cb = cnt + buf * 64;
+    if ((tid & 63) == 0) { cb[(tid >> 6) * 4 + 0] = c1; cb[(tid >> 6) * 4 + 1] = c2; cb[(tid >> 6) * 4 + 2] = c3; }
+    __syncthreads();
+    s1 = s2 = s3 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NUC_THREADS / 64; ++w) { s1 += cb[w * 4 + 0]; s2 += cb[w * 4 + 1]; s3 += cb[w * 4 + 2]; }
+}
+
+// p := softmax(x[0..V)); m and s are its max and its sum of exp, which Typical needs to recompute a probability from a logit.
 // FULL: V == 65536 exactly (the World vocabulary padded): no bound predicates at all — with them hipcc keeps 64 exec masks
 // alive across the kernel (spilled to VGPR lanes) and wraps every load in its own branch.
-template <int NC, bool MIRO, bool FULL>
-__global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logits, int V, const SampleRow *sp, int *out_tok,
-                                                               float *out_prob) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char nuc_smem[];
-    __shared__ float red[16];
-    __shared__ unsigned hist[256];
-    __shared__ unsigned sel[3];                                    // prefix, remaining k, candidate counter
-    unsigned long long *cand = (unsigned long long *)nuc_smem;     // [NC] (key bits << 32) | ~id  -> sort descending
-    float *qv = (float *)(cand + NC);                              // [NC]
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const SampleRow P = sp[row];
-    if ((P.kind & SAMPLE_WIDE) || (P.kind == 2) != MIRO) return;   // uniform per block; a wide row is sample_wide_kernel's
-    const float *x = logits + (long)row * V;
-    float p[NUC_EPT];
-    float m = -INFINITY;
+template <bool FULL>
+__device__ __forceinline__ void nuc_softmax(const float *x, int V, int lane, float (&p)[NUC_EPT], float *red, float &m, float &s) {
+    m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < NUC_EPT; ++j) {
-        const int i = j * NUC_THREADS + tid;
+        const int i = j * NUC_THREADS + lane;
         const float xv = x[FULL ? i : (i < V ? i : V - 1)];      // clamped, not predicated: the 64 loads are issued back to back
         p[j] = (FULL || i < V) ? xv : -INFINITY;
         m = fmaxf(m, p[j]);
     }
     m = block_reduce_1024(m, red, true);
-    float s = 0.f;
+    s = 0.f;
 #pragma unroll
     for (int j = 0; j < NUC_EPT; ++j) { p[j] = expf(p[j] - m); s += p[j]; }            // out of range: exp(-inf) = 0
     s = block_reduce_1024(s, red, false);
 #pragma unroll
     for (int j = 0; j < NUC_EPT; ++j) p[j] = p[j] / s;
+}
 
-    // ---- Typical sampling (typical.rs:70-108): the sort key is |(-ln p) - H| ascending over p > 0, H = sum p (-ln p).
-    //      The registers are re-used for the key, stored as 0xFFFFFFFF - bits(key) (0 for p == 0), so that the
-    //      "k largest, descending" machinery below selects the k smallest keys in ascending order; the few surviving
-    //      probabilities are recomputed from the logits with the same two operations.
-    const bool typical = P.kind == 1;
-    if (typical) {
-        float h = 0.f;
+// ---- Typical sampling (typical.rs:70-108): the sort key is |(-ln p) - H| ascending over p > 0, H = sum p (-ln p).
+//      The registers are re-used for the key, stored as 0xFFFFFFFF - bits(key) (0 for p == 0), so that the
+//      "k largest, descending" machinery below selects the k smallest keys in ascending order; the few surviving
+//      probabilities are recomputed from the logits with the same two operations.
+__device__ __forceinline__ void nuc_typical_keys(float (&p)[NUC_EPT], float *red) {
+    float h = 0.f;
 #pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) h += p[j] > 0.f ? p[j] * -logf(p[j]) : 0.f;
-        h = block_reduce_1024(h, red, false);
+    for (int j = 0; j < NUC_EPT; ++j) h += p[j] > 0.f ? p[j] * -logf(p[j]) : 0.f;
+    h = block_reduce_1024(h, red, false);
 #pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j)
-            p[j] = __uint_as_float(p[j] > 0.f ? 0xFFFFFFFFu - __float_as_uint(fabsf(-logf(p[j]) - h)) : 0u);
-    }
-    auto prob_of = [&](unsigned long long e) {                     // probability of a sorted candidate
-        if (!typical) return __uint_as_float((unsigned)(e >> 32));
-        const int id = (int)(0xFFFFFFFFu - (unsigned)(e & 0xFFFFFFFFull));
-        return expf(x[id] - m) / s;
-    };
-    const float cut = typical ? P.tau : P.top_p;
-    // ---- the k-th largest key (positive floats / complemented keys: bit patterns are order-preserving).
-    // A histogram radix select is the textbook choice and was the first version: all 65 536 keys of a row share a handful of
-    // exponent bytes, so its LDS atomics serialise on a few bins (137 us per launch).  Instead: a search over the key bits,
-    // two bits per step; a step counts, per thread over its 64 registers, the keys >= each of three trial thresholds and sums
-    // the three counts over the block (DPP wave sums, one barrier).  16 steps, no atomics, deterministic.
-    if (!MIRO && P.top_k < 1) {                                     // `.take(0)`: nothing kept, find_or_first -> None -> token 0 (nucleus.rs:78-101)
-        if (tid == 0) { out_tok[row] = 0; if (out_prob) out_prob[row] = 0.f; }
-        return;
-    }
-    int k = P.top_k > 256 ? 256 : P.top_k;
-    if (MIRO) {
-        float c = 0.f;
+    for (int j = 0; j < NUC_EPT; ++j)
+        p[j] = __uint_as_float(p[j] > 0.f ? 0xFFFFFFFFu - __float_as_uint(fabsf(-logf(p[j]) - h)) : 0u);
+}
+
+// Mirostat's k (mirostat.rs:55-74): 1 + #(tokens whose surprise -log2 p does not exceed max_surprise `tau`)
+__device__ __forceinline__ int nuc_surprise_k(const float (&p)[NUC_EPT], float tau, float *red) {
+    float c = 0.f;
 #pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) c += (p[j] > 0.f && !(-log2f(p[j]) > P.tau)) ? 1.f : 0.f;   // counts < 2^24: exact in fp32
-        k = (int)block_reduce_1024(c, red, false) + 1;              // ... and the first token beyond max_surprise
-        if (k > NC) k = NC;
-    }
-    if (k > V) k = V;
-    float *cnt = (float *)hist;                                     // [2][16 waves][4] per-wave partial counts, double-buffered
-    // per-wave counts arrive as wave-uniform integers: a count is s_bcnt1 of the compare mask (v_cmp -> SALU), no cross-lane sum.
-    // Written as asm: left to itself hipcc batches the 192 compares of a step and spills their masks to VGPR lanes (17 k lines).
-    // (compare, count and accumulate in one statement: with the count as an asm OUTPUT hipcc still parks every count in a lane)
-    auto wcount3 = [](int &c1, int &c2, int &c3, unsigned key, unsigned t1, unsigned t2, unsigned t3) {   // c_i += #lanes(key >= t_i)
-        asm volatile("v_cmp_le_u32 vcc, %3, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %0, %0, vcc_lo\n\t"
-                     "v_cmp_le_u32 vcc, %4, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %1, %1, vcc_lo\n\t"
-                     "v_cmp_le_u32 vcc, %5, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %2, %2, vcc_lo"
-                     : "+s"(c1), "+s"(c2), "+s"(c3) : "s"(t1), "s"(t2), "s"(t3), "v"(key) : "vcc", "scc");
-    };
-    auto count3 = [&](int buf, float c1, float c2, float c3, float &s1, float &s2, float &s3) {
-        float *cb = cnt + buf * 64;
-        if ((tid & 63) == 0) { cb[(tid >> 6) * 4 + 0] = c1; cb[(tid >> 6) * 4 + 1] = c2; cb[(tid >> 6) * 4 + 2] = c3; }
-        __syncthreads();
-        s1 = s2 = s3 = 0.f;
-#pragma unroll
-        for (int w = 0; w < NUC_THREADS / 64; ++w) { s1 += cb[w * 4 + 0]; s2 += cb[w * 4 + 1]; s3 += cb[w * 4 + 2]; }
-    };
+    for (int j = 0; j < NUC_EPT; ++j) c += (p[j] > 0.f && !(-log2f(p[j]) > tau)) ? 1.f : 0.f;   // counts < 2^24: exact in fp32
+    return (int)block_reduce_1024(c, red, false) + 1;               // ... and the first token beyond max_surprise
+}
+
+// ---- the k-th largest key (positive floats / complemented keys: bit patterns are order-preserving).
+// A histogram radix select is the textbook choice and was the first version: all 65 536 keys of a row share a handful of
+// exponent bytes, so its LDS atomics serialise on a few bins (137 us per launch).  Instead: a search over the key bits,
+// two bits per step; a step counts, per thread over its 64 registers, the keys >= each of three trial thresholds and sums
+// the three counts over the block (DPP wave sums, one barrier).  16 steps, no atomics, deterministic.
+// Returns the bits of the k-th largest key (0 when fewer than k keys are non-zero).
+__device__ __forceinline__ unsigned nuc_kth_key(const float (&p)[NUC_EPT], int k, float *cnt) {
     unsigned thr = 0u;                                              // invariant: count(key >= thr) >= k
 #pragma unroll 1
     for (int step = 0; step < 16; ++step) {
@@ -3404,69 +3392,88 @@ __global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logit
         const unsigned t1 = tu | (1u << lo), t2 = tu | (2u << lo), t3 = tu | (3u << lo);
         int c1 = 0, c2 = 0, c3 = 0;
 #pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) {
-            const unsigned key = __float_as_uint(p[j]);             // elements beyond V hold 0 and never count (thresholds > 0)
-            wcount3(c1, c2, c3, key, t1, t2, t3);
-        }
+        for (int j = 0; j < NUC_EPT; ++j) nuc_wcount3(c1, c2, c3, __float_as_uint(p[j]), t1, t2, t3);   // elements beyond V hold 0 and never count (thresholds > 0)
         float s1, s2, s3;
-        count3(step & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);   // sums <= 65536: exact in fp32
+        nuc_count3(cnt, step & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);   // sums <= 65536: exact in fp32
         thr = s3 >= (float)k ? t3 : (s2 >= (float)k ? t2 : (s1 >= (float)k ? t1 : thr));
     }
-    // thr = bits of the k-th largest key (0 when fewer than k keys are non-zero).  Candidates: every key > thr, and of the keys
-    // == thr the lowest ids (ties order lower id first, as the oracle's restatement does: the reference sorts with an unstable
-    // radix sort, nucleus.rs:76, so its tie order is not defined).  If more keys tie at thr than the candidate buffer holds,
-    // a second search of the same kind over the id picks the id bound, so the set never depends on thread timing.
-    float n_ge, n_gt, n_dummy;
-    {
-        const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
-        const unsigned tge = tu < 1u ? 1u : tu, tgt = tu + 1u;     // key >= thr and non-zero; key > thr  (thr < 2^32 - 1: a key of all ones is never the k-th... guarded below)
-        int cge = 0, cgt = 0, cxx = 0;
+    return thr;
+}
+
+// n_ge = #(key >= thr and non-zero), n_gt = #(key > thr)
+__device__ __forceinline__ void nuc_tie_counts(const float (&p)[NUC_EPT], unsigned thr, float *cnt, float &n_ge, float &n_gt) {
+    const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
+    const unsigned tge = tu < 1u ? 1u : tu, tgt = tu + 1u;         // key >= thr and non-zero; key > thr  (thr < 2^32 - 1: a key of all ones is never the k-th... guarded below)
+    int cge = 0, cgt = 0, cxx = 0;
 #pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) wcount3(cge, cgt, cxx, __float_as_uint(p[j]), tge, tgt, tgt);
-        if (tu == 0xFFFFFFFFu) cgt = 0;                             // tgt wrapped to 0: nothing is greater than all ones
-        count3(0, (float)cge, (float)cgt, 0.f, n_ge, n_gt, n_dummy);
-    }
-    unsigned id_bound = 0xFFFFFFFFu;                                // keys == thr are admitted while id <= id_bound
-    if (n_ge > (float)NC) {
-        const float need = (float)k - n_gt;                         // >= 1 ties needed; there are more than NC - n_gt of them
-        unsigned lim = 0u;                                          // the largest t with count(key == thr, id < t) < need
+    for (int j = 0; j < NUC_EPT; ++j) nuc_wcount3(cge, cgt, cxx, __float_as_uint(p[j]), tge, tgt, tgt);
+    if (tu == 0xFFFFFFFFu) cgt = 0;                                 // tgt wrapped to 0: nothing is greater than all ones
+    float n_dummy;
+    nuc_count3(cnt, 0, (float)cge, (float)cgt, 0.f, n_ge, n_gt, n_dummy);
+}
+
+// Candidates are every key > thr, and of the keys == thr the lowest ids (ties order lower id first, as the oracle's restatement does:
+// the reference sorts with an unstable radix sort, nucleus.rs:76, so its tie order is not defined).  When more keys tie at thr than the
+// caller can take, this second search of the same kind, over the id, picks the id bound, so the set never depends on thread timing.
+// `need` >= 1 ties are wanted and more than that exist.  Returns the id of the need-th tie: the ties with id <= it are exactly `need`.
+__device__ __forceinline__ unsigned nuc_id_bound(const float (&p)[NUC_EPT], unsigned thr, float need, int lane, float *cnt) {
+    unsigned lim = 0u;                                              // the largest t with count(key == thr, id < t) < need
 #pragma unroll 1
-        for (int step = 0; step < 9; ++step) {                      // 18 bits, two per step (ids < 2^16)
-            const int lo = 16 - 2 * step;
-            const unsigned lu = __builtin_amdgcn_readfirstlane(lim);
-            const unsigned t1 = lu | (1u << lo), t2 = lu | (2u << lo), t3 = lu | (3u << lo);
-            int c1 = 0, c2 = 0, c3 = 0;                             // counts of ties with id < t (monotone in t)
+    for (int step = 0; step < 9; ++step) {                          // 18 bits, two per step (ids < 2^16)
+        const int lo = 16 - 2 * step;
+        const unsigned lu = __builtin_amdgcn_readfirstlane(lim);
+        const unsigned t1 = lu | (1u << lo), t2 = lu | (2u << lo), t3 = lu | (3u << lo);
+        int c1 = 0, c2 = 0, c3 = 0;                                 // counts of ties with id < t (monotone in t)
 #pragma unroll
-            for (int j = 0; j < NUC_EPT; ++j) {
-                const unsigned id = (unsigned)(j * NUC_THREADS + tid);
-                // a tie counts when id < t, i.e. NOT (id >= t): fold the tie test into the compared value (non-ties compare as 2^32-1)
-                const unsigned idv = (__float_as_uint(p[j]) == thr) ? id : 0xFFFFFFFFu;   // out-of-range elements hold key 0 != thr
-                wcount3(c1, c2, c3, idv, t1, t2, t3);                // counts of NOT (id < t); flipped below
-            }
-            c1 = NUC_EPT * 64 - c1; c2 = NUC_EPT * 64 - c2; c3 = NUC_EPT * 64 - c3;
-            float s1, s2, s3;
-            count3((step + 1) & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
-            // keep the LARGEST lim whose count is still < need: then lim is the last id bound that is one short
-            lim = s3 < need ? t3 : (s2 < need ? t2 : (s1 < need ? t1 : lim));
+        for (int j = 0; j < NUC_EPT; ++j) {
+            const unsigned id = (unsigned)(j * NUC_THREADS + lane);
+            // a tie counts when id < t, i.e. NOT (id >= t): fold the tie test into the compared value (non-ties compare as 2^32-1)
+            const unsigned idv = (__float_as_uint(p[j]) == thr) ? id : 0xFFFFFFFFu;   // out-of-range elements hold key 0 != thr
+            nuc_wcount3(c1, c2, c3, idv, t1, t2, t3);                // counts of NOT (id < t); flipped below
         }
-        id_bound = lim;                                             // then id `lim` is a tie and the ties with id <= lim are exactly `need`
+        c1 = NUC_EPT * 64 - c1; c2 = NUC_EPT * 64 - c2; c3 = NUC_EPT * 64 - c3;
+        float s1, s2, s3;
+        nuc_count3(cnt, (step + 1) & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
+        // keep the LARGEST lim whose count is still < need: then lim is the last id bound that is one short
+        lim = s3 < need ? t3 : (s2 < need ? t2 : (s1 < need ? t1 : lim));
     }
-    if (tid == 0) sel[2] = 0u;
+    return lim;
+}
+
+// the candidate predicate: a live key above the threshold, or at it while id <= id_bound (out-of-range elements hold key 0).
+// One text, two forms, because where hipcc puts sample_wide_kernel's spills hangs on the form (profiles/r9_sampler_stages.json,
+// admit_predicate_forms; us per 32-row launch): the gather branches on the expression itself and the retire loop takes it as a bool.
+// A bool in both: thread 0's walk reloads spills every 8 entries, multi-window rows +6 %.  The expression in both: a row that ends in
+// window 0 +5 % (299 for 284).  This pairing: 267, and no case slower than before the stages were shared.
+#define NUC_ADMITTED(key, id, thr, id_bound) ((key) != 0u && ((key) > (thr) || ((key) == (thr) && (id) <= (id_bound))))
+__device__ __forceinline__ bool nuc_admitted(unsigned key, unsigned id, unsigned thr, unsigned id_bound) { return NUC_ADMITTED(key, id, thr, id_bound); }
+
+// cand[0..NC) := the admitted entries as (key bits << 32) | ~id, then zeros; *counter := how many were admitted
+template <int NC>
+__device__ __forceinline__ void nuc_gather(const float (&p)[NUC_EPT], unsigned thr, unsigned id_bound, int lane, unsigned long long *cand,
+                                           unsigned *counter) {
+    const int tid = threadIdx.x;
+    if (tid == 0) *counter = 0u;
     for (int i = tid; i < NC; i += NUC_THREADS) cand[i] = 0ull;
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NUC_EPT; ++j) {
-        const int i = j * NUC_THREADS + tid;
+        const int i = j * NUC_THREADS + lane;
         const unsigned key = __float_as_uint(p[j]);
-        if (key != 0u && (key > thr || (key == thr && (unsigned)i <= id_bound))) {   // out-of-range elements hold key 0
-            const unsigned slot = atomicAdd(&sel[2], 1u);           // slot order is arbitrary, the SET is not; sorted below
+        if (NUC_ADMITTED(key, (unsigned)i, thr, id_bound)) {
+            const unsigned slot = atomicAdd(counter, 1u);           // slot order is arbitrary, the SET is not; sorted below
             if (slot < NC) cand[slot] = ((unsigned long long)key << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
         }
     }
     __syncthreads();
-    for (int size = 2; size <= NC; size <<= 1) {                    // bitonic sort, descending
+}
+
+// bitonic sort of cand[0..n), descending; n a power of two
+__device__ __forceinline__ void nuc_sort_desc(unsigned long long *cand, int n) {
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= n; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < NC; i += NUC_THREADS) {
+            for (int i = tid; i < n; i += NUC_THREADS) {
                 const int j = i ^ stride;
                 if (j > i) {
                     const bool desc = (i & size) == 0;
@@ -3477,6 +3484,55 @@ __global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logit
             __syncthreads();
         }
     }
+}
+
+// NC = candidate capacity; MIRO = the Mirostat instantiation (kind 2 rows only; the other one takes kinds 0 and 1).
+// Mirostat (mirostat.rs:44-90): sort descending, k = 1 + #(tokens whose surprise -log2 p does not exceed max_surprise)
+// (exact while that fits NC = 8192, i.e. max_surprise < 13; the engine routes the rows beyond to sample_wide_kernel), no temperature,
+// draw u * sum against the running sum; `out_prob` carries the token surprise log2(sum) - log2(p) the host needs for
+// its update of max_surprise.
+// FULL: see nuc_softmax.
+template <int NC, bool MIRO, bool FULL>
+__global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logits, int V, const SampleRow *sp, int *out_tok,
+                                                               float *out_prob) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char nuc_smem[];
+    __shared__ float red[16];
+    __shared__ float cnt[2 * 16 * 4];                              // nuc_count3's [2][16 waves][4]
+    __shared__ unsigned sel[3];                                    // length of the kept prefix (thread 0's walk), unused, candidate counter
+    unsigned long long *cand = (unsigned long long *)nuc_smem;     // [NC] (key bits << 32) | ~id  -> sort descending
+    float *qv = (float *)(cand + NC);                              // [NC]
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const SampleRow P = sp[row];
+    if ((P.kind & SAMPLE_WIDE) || (P.kind == 2) != MIRO) return;   // uniform per block; a wide row is sample_wide_kernel's
+    const float *x = logits + (long)row * V;
+    float p[NUC_EPT];
+    float m, s;
+    nuc_softmax<FULL>(x, V, tid, p, red, m, s);
+    const bool typical = P.kind == 1;
+    if (typical) nuc_typical_keys(p, red);
+    auto prob_of = [&](unsigned long long e) {                     // probability of a sorted candidate
+        if (!typical) return __uint_as_float((unsigned)(e >> 32));
+        const int id = (int)(0xFFFFFFFFu - (unsigned)(e & 0xFFFFFFFFull));
+        return expf(x[id] - m) / s;
+    };
+    const float cut = typical ? P.tau : P.top_p;
+    if (!MIRO && P.top_k < 1) {                                     // `.take(0)`: nothing kept, find_or_first -> None -> token 0 (nucleus.rs:78-101)
+        if (tid == 0) { out_tok[row] = 0; if (out_prob) out_prob[row] = 0.f; }
+        return;
+    }
+    int k = P.top_k > 256 ? 256 : P.top_k;
+    if (MIRO) {
+        k = nuc_surprise_k(p, P.tau, red);
+        if (k > NC) k = NC;
+    }
+    if (k > V) k = V;
+    const unsigned thr = nuc_kth_key(p, k, cnt);
+    float n_ge, n_gt;
+    nuc_tie_counts(p, thr, cnt, n_ge, n_gt);
+    unsigned id_bound = 0xFFFFFFFFu;                                // keys == thr are admitted while id <= id_bound
+    if (n_ge > (float)NC) id_bound = nuc_id_bound(p, thr, (float)k - n_gt, tid, cnt);   // more ties than the candidate buffer holds
+    nuc_gather<NC>(p, thr, id_bound, tid, cand, &sel[2]);
+    nuc_sort_desc(cand, NC);
     const int ncand = min((int)min(sel[2], (unsigned)NC), k);
     // ---- nucleus: keep while the cumulative probability BEFORE the element is <= top_p (nucleus.rs:84-91)
     if (tid == 0) {
@@ -3513,28 +3569,29 @@ __global__ __launch_bounds__(NUC_THREADS) void nucleus_kernel(const float *logit
 // The wide sampler: the rows nucleus_kernel cannot hold in one LDS buffer — Nucleus / Typical with top_k > 256 (nucleus.rs:71-101 and
 // typical.rs:70-120 sort the whole vocabulary and `take(top_k)` for any top_k) and Mirostat whose max_surprise admits 8192 candidates or
 // more (mirostat.rs:55-74 truncates at max_surprise only).  Rows carry SAMPLE_WIDE in `kind`; every row is written by exactly one kernel.
-// Softmax, Typical key, threshold search, id-bound search, gather and sort are nucleus_kernel's, operation for operation (key descending,
+// Softmax, Typical key, threshold search, id-bound search, gather and sort are the nuc_* stages nucleus_kernel calls (key descending,
 // ties to the lower id, zero-probability entries never candidates).  New: the sorted prefix comes in WINDOWS of NC candidates.  A window
 // is the k = min(NC, what top_k / the surprise count still allows) largest live keys; once walked, its entries are retired from the
-// registers (key := 0) by the predicate that admitted them, so the next search finds the next NC in rank order.  Here the id-bound search
-// runs whenever more keys tie at the threshold than k admits (nucleus_kernel: than the buffer holds), so that the admitted set is exactly
-// the walked set; the first k of the sorted buffer are the same entries either way.
+// registers (key := 0) by nuc_admitted, the predicate that admitted them, so the next search finds the next NC in rank order.  Here the
+// id-bound search runs whenever more keys tie at the threshold than k admits (nucleus_kernel: than the buffer holds), so that the admitted
+// set is exactly the walked set; the first k of the sorted buffer are the same entries either way.
 //   pass A  thread 0 walks the windows in rank order: sequential fp32 sums, as the reference and oracle/rwkv_ref.py form them;
 //           p and p^(1/T) (Typical: the recomputed probability) are put into LDS by the whole block first.
 //   pass B  the draw.  A walk that ended in window 0 (the common case) draws from the window still in LDS — then this kernel has
-//           done what nucleus_kernel does.  Otherwise the row is loaded again, the registers are recomputed (same operations, same
+//           done what nucleus_kernel does.  Otherwise the row is loaded again, the registers are recomputed (same functions, same
 //           bits: every reduction has a fixed order) and the windows are walked a second time; there is no room for a second copy.
 // Bit rule: on a row nucleus_kernel handles exactly (top_k <= 256; Mirostat with fewer than NC candidates) token and out_prob are
-// nucleus_kernel's bits.  Every value is written with plain vector stores.
+// nucleus_kernel's bits.  Up to the sorted window that holds by construction: the same functions on the same row, and the first k
+// entries do not depend on which of the two id-bound conditions ran.  The walk and the draw are each kernel's own and keep the rule by
+// forming the same sequential sums in the same order.  Every value is written with plain vector stores.
 // =====================================================================================
-constexpr int WIDE_NC = 8192;
 template <bool FULL>
 __global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *logits, int V, const SampleRow *sp, int *out_tok,
                                                                    float *out_prob) {
-    constexpr int NC = WIDE_NC;
+    constexpr int NC = NUC_CAND_MAX;
     extern __shared__ __attribute__((aligned(16))) unsigned char wide_smem[];
     __shared__ float red[16];
-    __shared__ unsigned hist[256];
+    __shared__ float cnt[2 * 16 * 4];                              // nuc_count3's [2][16 waves][4]
     __shared__ unsigned sel[3];                                    // thread 0's verdict, -, candidate counter
     unsigned long long *cand = (unsigned long long *)wide_smem;    // [NC] (key bits << 32) | ~id  -> sort descending
     float *qv = (float *)(cand + NC);                              // [NC]
@@ -3548,21 +3605,6 @@ __global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *l
     }
     const float *x = logits + (long)row * V;
     const float cut = typical ? P.tau : P.top_p;
-    float *cnt = (float *)hist;                                     // [2][16 waves][4], see nucleus_kernel
-    auto wcount3 = [](int &c1, int &c2, int &c3, unsigned key, unsigned t1, unsigned t2, unsigned t3) {   // c_i += #lanes(key >= t_i)
-        asm volatile("v_cmp_le_u32 vcc, %3, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %0, %0, vcc_lo\n\t"
-                     "v_cmp_le_u32 vcc, %4, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %1, %1, vcc_lo\n\t"
-                     "v_cmp_le_u32 vcc, %5, %6\n\ts_bcnt1_i32_b64 vcc_lo, vcc\n\ts_add_i32 %2, %2, vcc_lo"
-                     : "+s"(c1), "+s"(c2), "+s"(c3) : "s"(t1), "s"(t2), "s"(t3), "v"(key) : "vcc", "scc");
-    };
-    auto count3 = [&](int buf, float c1, float c2, float c3, float &s1, float &s2, float &s3) {
-        float *cb = cnt + buf * 64;
-        if ((tid & 63) == 0) { cb[(tid >> 6) * 4 + 0] = c1; cb[(tid >> 6) * 4 + 1] = c2; cb[(tid >> 6) * 4 + 2] = c3; }
-        __syncthreads();
-        s1 = s2 = s3 = 0.f;
-#pragma unroll
-        for (int w = 0; w < NUC_THREADS / 64; ++w) { s1 += cb[w * 4 + 0]; s2 += cb[w * 4 + 1]; s3 += cb[w * 4 + 2]; }
-    };
     // thread 0's walk (the other threads carry the values along unused)
     float cum = 0.f, sum = 0.f, c = 0.f, first_p = 0.f;
     int n = 0, first_id = 0;
@@ -3597,39 +3639,12 @@ __global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *l
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         float p[NUC_EPT];
-        float m = -INFINITY;
+        float m, s;
         int lt = tid;                                               // opaque copy: keeps the 64 element ids (and addresses) from being
         asm volatile("" : "+v"(lt));                                // hoisted out of the loops as 64 live registers beside the row
-#pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) {
-            const int i = j * NUC_THREADS + lt;
-            const float xv = x[FULL ? i : (i < V ? i : V - 1)];      // clamped, not predicated
-            p[j] = (FULL || i < V) ? xv : -INFINITY;
-            m = fmaxf(m, p[j]);
-        }
-        m = block_reduce_1024(m, red, true);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) { p[j] = expf(p[j] - m); s += p[j]; }
-        s = block_reduce_1024(s, red, false);
-#pragma unroll
-        for (int j = 0; j < NUC_EPT; ++j) p[j] = p[j] / s;
-        if (typical) {                                              // typical.rs:70-108, the key as in nucleus_kernel
-            float h = 0.f;
-#pragma unroll
-            for (int j = 0; j < NUC_EPT; ++j) h += p[j] > 0.f ? p[j] * -logf(p[j]) : 0.f;
-            h = block_reduce_1024(h, red, false);
-#pragma unroll
-            for (int j = 0; j < NUC_EPT; ++j)
-                p[j] = __uint_as_float(p[j] > 0.f ? 0xFFFFFFFFu - __float_as_uint(fabsf(-logf(p[j]) - h)) : 0u);
-        }
-        int total_k = P.top_k;                                      // what the whole walk may take
-        if (miro) {
-            float cc = 0.f;
-#pragma unroll
-            for (int j = 0; j < NUC_EPT; ++j) cc += (p[j] > 0.f && !(-log2f(p[j]) > P.tau)) ? 1.f : 0.f;
-            total_k = (int)block_reduce_1024(cc, red, false) + 1;   // ... and the first token beyond max_surprise
-        }
+        nuc_softmax<FULL>(x, V, lt, p, red, m, s);
+        if (typical) nuc_typical_keys(p, red);
+        int total_k = miro ? nuc_surprise_k(p, P.tau, red) : P.top_k;   // what the whole walk may take
         if (total_k > V) total_k = V;
         unsigned verdict = 0u;                                      // 1: pass A ended beyond window 0, 2: the token is out
 #pragma unroll 1
@@ -3638,81 +3653,16 @@ __global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *l
             const int k = min(NC, total_k - base);                  // >= 1: the walk goes on only while base + NC < total_k
             int wt = tid;
             asm volatile("" : "+v"(wt));
-            unsigned thr = 0u;                                      // invariant: count(key >= thr) >= k
-#pragma unroll 1
-            for (int step = 0; step < 16; ++step) {
-                const int lo = 30 - 2 * step;
-                const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
-                const unsigned t1 = tu | (1u << lo), t2 = tu | (2u << lo), t3 = tu | (3u << lo);
-                int c1 = 0, c2 = 0, c3 = 0;
-#pragma unroll
-                for (int j = 0; j < NUC_EPT; ++j) wcount3(c1, c2, c3, __float_as_uint(p[j]), t1, t2, t3);
-                float s1, s2, s3;
-                count3(step & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
-                thr = s3 >= (float)k ? t3 : (s2 >= (float)k ? t2 : (s1 >= (float)k ? t1 : thr));
-            }
-            float n_ge, n_gt, n_dummy;
-            {
-                const unsigned tu = __builtin_amdgcn_readfirstlane(thr);
-                const unsigned tge = tu < 1u ? 1u : tu, tgt = tu + 1u;
-                int cge = 0, cgt = 0, cxx = 0;
-#pragma unroll
-                for (int j = 0; j < NUC_EPT; ++j) wcount3(cge, cgt, cxx, __float_as_uint(p[j]), tge, tgt, tgt);
-                if (tu == 0xFFFFFFFFu) cgt = 0;
-                count3(0, (float)cge, (float)cgt, 0.f, n_ge, n_gt, n_dummy);
-            }
+            const unsigned thr = nuc_kth_key(p, k, cnt);
+            float n_ge, n_gt;
+            nuc_tie_counts(p, thr, cnt, n_ge, n_gt);
             unsigned id_bound = 0xFFFFFFFFu;                        // keys == thr are admitted while id <= id_bound
-            if (n_ge > (float)k) {                                  // more ties than the window takes: the `need` lowest ids
-                const float need = (float)k - n_gt;
-                unsigned lim = 0u;
-#pragma unroll 1
-                for (int step = 0; step < 9; ++step) {
-                    const int lo = 16 - 2 * step;
-                    const unsigned lu = __builtin_amdgcn_readfirstlane(lim);
-                    const unsigned t1 = lu | (1u << lo), t2 = lu | (2u << lo), t3 = lu | (3u << lo);
-                    int c1 = 0, c2 = 0, c3 = 0;
-#pragma unroll
-                    for (int j = 0; j < NUC_EPT; ++j) {
-                        const unsigned id = (unsigned)(j * NUC_THREADS + wt);
-                        const unsigned idv = (__float_as_uint(p[j]) == thr) ? id : 0xFFFFFFFFu;
-                        wcount3(c1, c2, c3, idv, t1, t2, t3);
-                    }
-                    c1 = NUC_EPT * 64 - c1; c2 = NUC_EPT * 64 - c2; c3 = NUC_EPT * 64 - c3;
-                    float s1, s2, s3;
-                    count3((step + 1) & 1, (float)c1, (float)c2, (float)c3, s1, s2, s3);
-                    lim = s3 < need ? t3 : (s2 < need ? t2 : (s1 < need ? t1 : lim));
-                }
-                id_bound = lim;
-            }
-            if (tid == 0) sel[2] = 0u;
-            for (int i = tid; i < NC; i += NUC_THREADS) cand[i] = 0ull;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < NUC_EPT; ++j) {
-                const int i = j * NUC_THREADS + wt;
-                const unsigned key = __float_as_uint(p[j]);
-                if (key != 0u && (key > thr || (key == thr && (unsigned)i <= id_bound))) {
-                    const unsigned slot = atomicAdd(&sel[2], 1u);   // slot order is arbitrary, the SET is not; sorted below
-                    if (slot < NC) cand[slot] = ((unsigned long long)key << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
-                }
-            }
-            __syncthreads();
+            if (n_ge > (float)k) id_bound = nuc_id_bound(p, thr, (float)k - n_gt, wt, cnt);   // more ties than the window takes: the `need` lowest ids
+            nuc_gather<NC>(p, thr, id_bound, wt, cand, &sel[2]);
             const int wn = min((int)min(sel[2], (unsigned)NC), k);  // entries of this window (at most k were admitted)
             int sz = 2;
             while (sz < wn) sz <<= 1;                               // the zeros behind the entries need no sorting
-            for (int size = 2; size <= sz; size <<= 1) {            // bitonic sort, descending
-                for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (int i = tid; i < sz; i += NUC_THREADS) {
-                        const int j = i ^ stride;
-                        if (j > i) {
-                            const bool desc = (i & size) == 0;
-                            const unsigned long long a = cand[i], b = cand[j];
-                            if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
+            nuc_sort_desc(cand, sz);
             for (int i = tid; i < wn; i += NUC_THREADS) {           // what thread 0 adds up: no transcendental in its loop
                 const unsigned long long e = cand[i];
                 float pr = __uint_as_float((unsigned)(e >> 32));
@@ -3764,11 +3714,8 @@ __global__ __launch_bounds__(NUC_THREADS) void sample_wide_kernel(const float *l
             verdict = sel[0];
             if (verdict == 0u) {                                    // retire the window: the predicate that admitted its entries
 #pragma unroll
-                for (int j = 0; j < NUC_EPT; ++j) {
-                    const int i = j * NUC_THREADS + wt;
-                    const unsigned key = __float_as_uint(p[j]);
-                    if (key != 0u && (key > thr || (key == thr && (unsigned)i <= id_bound))) p[j] = 0.f;
-                }
+                for (int j = 0; j < NUC_EPT; ++j)
+                    if (nuc_admitted(__float_as_uint(p[j]), (unsigned)(j * NUC_THREADS + wt), thr, id_bound)) p[j] = 0.f;
             }
         }
         if (verdict == 2u) return;
@@ -3802,25 +3749,24 @@ void launch_logit_adjust(float *logits, int V, const int *rows, const int *toks,
 }
 void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp, bool any_nucleus_typical, bool any_mirostat, bool any_wide,
                     int *out_tok, float *out_prob, hipStream_t s) {
-    constexpr int NC0 = NUC_CAND, NC2 = 8192;
     static bool attr_done[16] = {false};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (!attr_done[dev & 15]) {
-        (void)hipFuncSetAttribute((const void *)nucleus_kernel<NC2, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NC2 * 12);
-        (void)hipFuncSetAttribute((const void *)nucleus_kernel<NC2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NC2 * 12);
-        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_NC * 12);
-        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_NC * 12);
+        (void)hipFuncSetAttribute((const void *)nucleus_kernel<NUC_CAND_MAX, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NUC_CAND_MAX * NUC_SLOT_BYTES);
+        (void)hipFuncSetAttribute((const void *)nucleus_kernel<NUC_CAND_MAX, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NUC_CAND_MAX * NUC_SLOT_BYTES);
+        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NUC_CAND_MAX * NUC_SLOT_BYTES);
+        (void)hipFuncSetAttribute((const void *)sample_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NUC_CAND_MAX * NUC_SLOT_BYTES);
         attr_done[dev & 15] = true;
     }
     const bool full = V == NUC_EPT * NUC_THREADS;
-#define NUC_LAUNCH(nc, miro) do { if (full) hipLaunchKernelGGL((nucleus_kernel<nc, miro, true>), dim3(n_rows), dim3(NUC_THREADS), nc * 12, s, logits, V, sp, out_tok, out_prob); \
-                                  else hipLaunchKernelGGL((nucleus_kernel<nc, miro, false>), dim3(n_rows), dim3(NUC_THREADS), nc * 12, s, logits, V, sp, out_tok, out_prob); } while (0)
-    if (any_nucleus_typical) NUC_LAUNCH(NC0, false);
-    if (any_mirostat) NUC_LAUNCH(NC2, true);
+#define NUC_LAUNCH(nc, miro) do { if (full) hipLaunchKernelGGL((nucleus_kernel<nc, miro, true>), dim3(n_rows), dim3(NUC_THREADS), nc * NUC_SLOT_BYTES, s, logits, V, sp, out_tok, out_prob); \
+                                  else hipLaunchKernelGGL((nucleus_kernel<nc, miro, false>), dim3(n_rows), dim3(NUC_THREADS), nc * NUC_SLOT_BYTES, s, logits, V, sp, out_tok, out_prob); } while (0)
+    if (any_nucleus_typical) NUC_LAUNCH(NUC_CAND, false);
+    if (any_mirostat) NUC_LAUNCH(NUC_CAND_MAX, true);
     if (any_wide) {                                                // rows with SAMPLE_WIDE; the launches above return at once for them
-        if (full) hipLaunchKernelGGL(sample_wide_kernel<true>, dim3(n_rows), dim3(NUC_THREADS), WIDE_NC * 12, s, logits, V, sp, out_tok, out_prob);
-        else hipLaunchKernelGGL(sample_wide_kernel<false>, dim3(n_rows), dim3(NUC_THREADS), WIDE_NC * 12, s, logits, V, sp, out_tok, out_prob);
+        if (full) hipLaunchKernelGGL(sample_wide_kernel<true>, dim3(n_rows), dim3(NUC_THREADS), NUC_CAND_MAX * NUC_SLOT_BYTES, s, logits, V, sp, out_tok, out_prob);
+        else hipLaunchKernelGGL(sample_wide_kernel<false>, dim3(n_rows), dim3(NUC_THREADS), NUC_CAND_MAX * NUC_SLOT_BYTES, s, logits, V, sp, out_tok, out_prob);
     }
 #undef NUC_LAUNCH
 }

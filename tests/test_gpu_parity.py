@@ -502,14 +502,16 @@ def test_on_device_nucleus_sampling_matches_reference_sampler():
                 if len(o):
                     rows[b] = o[-1]
         us = [float(rng.random()) for _ in range(3)]
-        want, margin = [], []
+        want, margin, want_prob = [], [], []
         for b in range(3):
             x = orc[b].transform(rows[b])
             for tk, bv in {5: 1.5, 9: -2.0}.items():
                 x[tk] += np.float32(bv)
-            tok, mg = R.nucleus_ref(R.softmax_ref(x[None])[0], orc[b].top_p, orc[b].top_k, orc[b].temperature, us[b])
+            probs = R.softmax_ref(x[None])[0]
+            tok, mg = R.nucleus_ref(probs, orc[b].top_p, orc[b].top_k, orc[b].temperature, us[b])
             want.append(tok)
             margin.append(mg)
+            want_prob.append(float(probs[tok]))
         for b in range(3):
             eng.state.write(snaps[b], b)
         inp = rt.RnnInput([rt.RnnInputBatch(list(pending[b]), rt.RnnOption.Last) for b in range(3)])
@@ -522,6 +524,7 @@ def test_on_device_nucleus_sampling_matches_reference_sampler():
         for b in range(3):
             if margin[b] > 1e-4:                                   # away from a CDF boundary: ids must agree
                 assert got[b][0] == want[b], (step, b, got[b], want[b], margin[b])
+                assert abs(got[b][1] - want_prob[b]) <= 1e-3 * want_prob[b], (step, b, got[b], want_prob[b])   # out_prob: the softmax probability of the token
                 checked += 1
             else:
                 skipped += 1
