@@ -143,6 +143,39 @@ def build_gemm_probe(verbose: bool = True) -> str:
     return PROBE_BIN
 
 
+ROW_PROBE_SRC = os.path.join(PROBE_DIR, "row_probe.hip")
+ROW_PROBE_BIN = os.path.join(PROBE_DIR, "row_probe")
+ROW_PROBE_STAMP = os.path.join(PROBE_DIR, ".row_probe_stamp")
+
+
+def compile_row_probe(obj: str) -> str:
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", ROW_PROBE_SRC, "-o", obj])
+    return obj
+
+
+def build_row_probe(verbose: bool = True) -> str:
+    """tests/cpp/row_probe.hip (the stand-alone row / WKV / state probe of tests/test_gpu_row_exact.py), linked and content-stamped like
+    the GEMM probe above.  Built by the test that runs it, not by build()."""
+    import hashlib
+    build(verbose=verbose)
+    h = hashlib.sha256(_sources_digest().encode())
+    with open(ROW_PROBE_SRC, "rb") as f:
+        h.update(f.read())
+    if os.path.exists(ROW_PROBE_BIN) and os.path.exists(ROW_PROBE_STAMP) and open(ROW_PROBE_STAMP).read().strip() == h.hexdigest():
+        return ROW_PROBE_BIN
+    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+    if not all(os.path.exists(p) for p in parts):
+        build(force=True, verbose=verbose)
+    obj = compile_row_probe(os.path.join(PROBE_DIR, "row_probe.o"))
+    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", ROW_PROBE_BIN]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    with open(ROW_PROBE_STAMP, "w") as f:
+        f.write(h.hexdigest())
+    return ROW_PROBE_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)
