@@ -176,6 +176,40 @@ def build_row_probe(verbose: bool = True) -> str:
     return ROW_PROBE_BIN
 
 
+MIX_PROBE_SRC = os.path.join(PROBE_DIR, "mix_probe.hip")
+MIX_PROBE_BIN = os.path.join(PROBE_DIR, "mix_probe")
+MIX_PROBE_STAMP = os.path.join(PROBE_DIR, ".mix_probe_stamp")
+
+
+def compile_mix_probe(obj: str) -> str:
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", MIX_PROBE_SRC, "-o", obj])
+    return obj
+
+
+def build_mix_probe(verbose: bool = True) -> str:
+    """tests/cpp/mix_probe.hip (the stand-alone V6 mix / LayerNorm prologue / shift commit probe of tests/test_gpu_mix_exact.py), linked and
+    content-stamped like the two probes above.  Built by the test that runs it, not by build()."""
+    import hashlib
+    build(verbose=verbose)
+    h = hashlib.sha256(_sources_digest().encode())
+    for src in (MIX_PROBE_SRC, os.path.join(PROBE_DIR, "mix_probe_plan.h")):
+        with open(src, "rb") as f:
+            h.update(f.read())
+    if os.path.exists(MIX_PROBE_BIN) and os.path.exists(MIX_PROBE_STAMP) and open(MIX_PROBE_STAMP).read().strip() == h.hexdigest():
+        return MIX_PROBE_BIN
+    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+    if not all(os.path.exists(p) for p in parts):
+        build(force=True, verbose=verbose)
+    obj = compile_mix_probe(os.path.join(PROBE_DIR, "mix_probe.o"))
+    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", MIX_PROBE_BIN]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    with open(MIX_PROBE_STAMP, "w") as f:
+        f.write(h.hexdigest())
+    return MIX_PROBE_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)
