@@ -210,6 +210,39 @@ def build_mix_probe(verbose: bool = True) -> str:
     return MIX_PROBE_BIN
 
 
+SAMPLE_PROBE_SRC = os.path.join(PROBE_DIR, "sample_probe.hip")
+SAMPLE_PROBE_BIN = os.path.join(PROBE_DIR, "sample_probe")
+SAMPLE_PROBE_STAMP = os.path.join(PROBE_DIR, ".sample_probe_stamp")
+
+
+def compile_sample_probe(obj: str) -> str:
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", SAMPLE_PROBE_SRC, "-o", obj])
+    return obj
+
+
+def build_sample_probe(verbose: bool = True) -> str:
+    """tests/cpp/sample_probe.hip (the stand-alone sampling / vocabulary-row probe of tests/test_gpu_sample_exact.py), linked and
+    content-stamped like the three probes above.  Built by the test that runs it, not by build()."""
+    import hashlib
+    build(verbose=verbose)
+    h = hashlib.sha256(_sources_digest().encode())
+    with open(SAMPLE_PROBE_SRC, "rb") as f:
+        h.update(f.read())
+    if os.path.exists(SAMPLE_PROBE_BIN) and os.path.exists(SAMPLE_PROBE_STAMP) and open(SAMPLE_PROBE_STAMP).read().strip() == h.hexdigest():
+        return SAMPLE_PROBE_BIN
+    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+    if not all(os.path.exists(p) for p in parts):
+        build(force=True, verbose=verbose)
+    obj = compile_sample_probe(os.path.join(PROBE_DIR, "sample_probe.o"))
+    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", SAMPLE_PROBE_BIN]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    with open(SAMPLE_PROBE_STAMP, "w") as f:
+        f.write(h.hexdigest())
+    return SAMPLE_PROBE_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)

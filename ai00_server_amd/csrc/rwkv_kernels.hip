@@ -3273,7 +3273,8 @@ __global__ __launch_bounds__(64) void argmax_stage2(const float *pv, const int *
         const int oi = __shfl_xor(idx, k, 64);
         if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
     }
-    if (threadIdx.x == 0) out_tok[row] = idx;                // lowest index on ties == np.argmax
+    // lowest index on ties == np.argmax; a row with no entry above -inf leaves stage 1's start value in every segment: token 0, as np.argmax
+    if (threadIdx.x == 0) out_tok[row] = idx == 0x7fffffff ? 0 : idx;
 }
 void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *scratch_v, int *scratch_i, hipStream_t s) {
     hipLaunchKernelGGL(argmax_stage1, dim3(n_rows, ARGMAX_SEG), dim3(256), 0, s, logits, V, scratch_v, scratch_i);
