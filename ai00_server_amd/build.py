@@ -4,6 +4,7 @@
 """
 from __future__ import annotations
 
+import functools
 import os
 import subprocess
 import sys
@@ -107,140 +108,53 @@ def build_harness(verbose: bool = True) -> str:
 
 
 PROBE_DIR = os.path.join(HERE, "..", "tests", "cpp")
-PROBE_SRC = os.path.join(PROBE_DIR, "gemm_probe.hip")
-PROBE_BIN = os.path.join(PROBE_DIR, "gemm_probe")
-PROBE_STAMP = os.path.join(PROBE_DIR, ".gemm_probe_stamp")
+PROBE_SHARED = ("probe_common.h", "probe_case.h")
+# tests/cpp/<name>.hip, the stand-alone kernel probe of tests/test_gpu_<family>_exact.py -> the headers beside it that enter its stamp
+PROBES = {"gemm_probe": ("gemm_probe_plan.h",), "row_probe": (), "mix_probe": ("mix_probe_plan.h",), "sample_probe": ()}
 
 
-def compile_gemm_probe(obj: str) -> str:
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", PROBE_SRC, "-o", obj])
+def kernel_objects() -> list:
+    """The objects the library build leaves behind for rwkv_kernels.hip: self-contained (Knobs, use_knobs and every launch_* live in them)."""
+    return [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+
+
+def compile_probe(name: str, obj: str) -> str:
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", os.path.join(PROBE_DIR, name + ".hip"), "-o", obj])
     return obj
 
 
-def build_gemm_probe(verbose: bool = True) -> str:
-    """tests/cpp/gemm_probe.hip (the stand-alone GEMM probe of tests/test_gpu_gemm_exact.py) linked against the kernel objects of the
-    library build: they are self-contained (Knobs, use_knobs and every launch_* live in them).  The probe is compiled to an object first
-    (object files on the line of a .hip source would be read as HIP source).  Content-stamped like the library.  Built by the test that
-    runs it, not by build(): the library build depends on nothing under tests/."""
+def build_probe(name: str, verbose: bool = True) -> str:
+    """A probe of PROBES linked against the kernel objects of the library build.  The probe is compiled to an object first (object files on
+    the line of a .hip source would be read as HIP source).  Content-stamped like the library.  Built by the test that runs it, not by
+    build(): the library build depends on nothing under tests/."""
     import hashlib
+    exe, stamp = os.path.join(PROBE_DIR, name), os.path.join(PROBE_DIR, f".{name}_stamp")
     build(verbose=verbose)
     h = hashlib.sha256(_sources_digest().encode())
-    for src in (PROBE_SRC, os.path.join(PROBE_DIR, "gemm_probe_plan.h")):
-        with open(src, "rb") as f:
-            h.update(f.read())
-    if os.path.exists(PROBE_BIN) and os.path.exists(PROBE_STAMP) and open(PROBE_STAMP).read().strip() == h.hexdigest():
-        return PROBE_BIN
-    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
+    for src in (name + ".hip",) + PROBES[name] + PROBE_SHARED:
+        path = os.path.join(PROBE_DIR, src)
+        if src.endswith(".hip") or os.path.exists(path):               # a header that is not there is included by nothing that compiles
+            with open(path, "rb") as f:
+                h.update(f.read())
+    if os.path.exists(exe) and os.path.exists(stamp) and open(stamp).read().strip() == h.hexdigest():
+        return exe
+    parts = kernel_objects()
     if not all(os.path.exists(p) for p in parts):
         build(force=True, verbose=verbose)
-    obj = compile_gemm_probe(os.path.join(PROBE_DIR, "gemm_probe.o"))
-    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", PROBE_BIN]
+    obj = compile_probe(name, os.path.join(PROBE_DIR, name + ".o"))
+    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", exe]
     if verbose:
         print("[build]", " ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(PROBE_STAMP, "w") as f:
+    with open(stamp, "w") as f:
         f.write(h.hexdigest())
-    return PROBE_BIN
+    return exe
 
 
-ROW_PROBE_SRC = os.path.join(PROBE_DIR, "row_probe.hip")
-ROW_PROBE_BIN = os.path.join(PROBE_DIR, "row_probe")
-ROW_PROBE_STAMP = os.path.join(PROBE_DIR, ".row_probe_stamp")
-
-
-def compile_row_probe(obj: str) -> str:
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", ROW_PROBE_SRC, "-o", obj])
-    return obj
-
-
-def build_row_probe(verbose: bool = True) -> str:
-    """tests/cpp/row_probe.hip (the stand-alone row / WKV / state probe of tests/test_gpu_row_exact.py), linked and content-stamped like
-    the GEMM probe above.  Built by the test that runs it, not by build()."""
-    import hashlib
-    build(verbose=verbose)
-    h = hashlib.sha256(_sources_digest().encode())
-    with open(ROW_PROBE_SRC, "rb") as f:
-        h.update(f.read())
-    if os.path.exists(ROW_PROBE_BIN) and os.path.exists(ROW_PROBE_STAMP) and open(ROW_PROBE_STAMP).read().strip() == h.hexdigest():
-        return ROW_PROBE_BIN
-    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
-    if not all(os.path.exists(p) for p in parts):
-        build(force=True, verbose=verbose)
-    obj = compile_row_probe(os.path.join(PROBE_DIR, "row_probe.o"))
-    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", ROW_PROBE_BIN]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    with open(ROW_PROBE_STAMP, "w") as f:
-        f.write(h.hexdigest())
-    return ROW_PROBE_BIN
-
-
-MIX_PROBE_SRC = os.path.join(PROBE_DIR, "mix_probe.hip")
-MIX_PROBE_BIN = os.path.join(PROBE_DIR, "mix_probe")
-MIX_PROBE_STAMP = os.path.join(PROBE_DIR, ".mix_probe_stamp")
-
-
-def compile_mix_probe(obj: str) -> str:
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", MIX_PROBE_SRC, "-o", obj])
-    return obj
-
-
-def build_mix_probe(verbose: bool = True) -> str:
-    """tests/cpp/mix_probe.hip (the stand-alone V6 mix / LayerNorm prologue / shift commit probe of tests/test_gpu_mix_exact.py), linked and
-    content-stamped like the two probes above.  Built by the test that runs it, not by build()."""
-    import hashlib
-    build(verbose=verbose)
-    h = hashlib.sha256(_sources_digest().encode())
-    for src in (MIX_PROBE_SRC, os.path.join(PROBE_DIR, "mix_probe_plan.h")):
-        with open(src, "rb") as f:
-            h.update(f.read())
-    if os.path.exists(MIX_PROBE_BIN) and os.path.exists(MIX_PROBE_STAMP) and open(MIX_PROBE_STAMP).read().strip() == h.hexdigest():
-        return MIX_PROBE_BIN
-    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
-    if not all(os.path.exists(p) for p in parts):
-        build(force=True, verbose=verbose)
-    obj = compile_mix_probe(os.path.join(PROBE_DIR, "mix_probe.o"))
-    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", MIX_PROBE_BIN]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    with open(MIX_PROBE_STAMP, "w") as f:
-        f.write(h.hexdigest())
-    return MIX_PROBE_BIN
-
-
-SAMPLE_PROBE_SRC = os.path.join(PROBE_DIR, "sample_probe.hip")
-SAMPLE_PROBE_BIN = os.path.join(PROBE_DIR, "sample_probe")
-SAMPLE_PROBE_STAMP = os.path.join(PROBE_DIR, ".sample_probe_stamp")
-
-
-def compile_sample_probe(obj: str) -> str:
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-c", SAMPLE_PROBE_SRC, "-o", obj])
-    return obj
-
-
-def build_sample_probe(verbose: bool = True) -> str:
-    """tests/cpp/sample_probe.hip (the stand-alone sampling / vocabulary-row probe of tests/test_gpu_sample_exact.py), linked and
-    content-stamped like the three probes above.  Built by the test that runs it, not by build()."""
-    import hashlib
-    build(verbose=verbose)
-    h = hashlib.sha256(_sources_digest().encode())
-    with open(SAMPLE_PROBE_SRC, "rb") as f:
-        h.update(f.read())
-    if os.path.exists(SAMPLE_PROBE_BIN) and os.path.exists(SAMPLE_PROBE_STAMP) and open(SAMPLE_PROBE_STAMP).read().strip() == h.hexdigest():
-        return SAMPLE_PROBE_BIN
-    parts = [os.path.join(CSRC, f"rwkv_kernels.p{k}.o") for k in range(KERNEL_PARTS)]
-    if not all(os.path.exists(p) for p in parts):
-        build(force=True, verbose=verbose)
-    obj = compile_sample_probe(os.path.join(PROBE_DIR, "sample_probe.o"))
-    cmd = [_hipcc(), "--offload-arch=gfx950", obj] + parts + ["-o", SAMPLE_PROBE_BIN]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    with open(SAMPLE_PROBE_STAMP, "w") as f:
-        f.write(h.hexdigest())
-    return SAMPLE_PROBE_BIN
+# The per-probe names of earlier revisions, which test modules of those revisions still call: compile_row_probe(obj), build_row_probe(verbose=False), ...
+for _name in PROBES:
+    globals()["compile_" + _name] = functools.partial(compile_probe, _name)
+    globals()["build_" + _name] = functools.partial(build_probe, _name)
 
 
 if __name__ == "__main__":

@@ -18,14 +18,10 @@ if "--parts" in flags:
     sys.path.insert(0, ROOT)
     from ai00_server_amd import build as B
     B.build(verbose=False)
-    objs = []
-    for k in range(B.KERNEL_PARTS):
-        if k in parts:
-            o = os.path.join(cs, f"rwkv_kernels.{name}.p{k}.o")
-            subprocess.check_call(base + flags + [f"-DRWKV_PART={k}", "-c", os.path.join(cs, "rwkv_kernels.hip"), "-o", o])
-            objs.append(o)
-        else:
-            objs.append(os.path.join(cs, f"rwkv_kernels.p{k}.o"))
+    objs = B.kernel_objects()
+    for k in parts:
+        objs[k] = os.path.join(cs, f"rwkv_kernels.{name}.p{k}.o")
+        subprocess.check_call(base + flags + [f"-DRWKV_PART={k}", "-c", os.path.join(cs, "rwkv_kernels.hip"), "-o", objs[k]])
     objs += [os.path.join(cs, "rwkv_engine.o"), os.path.join(cs, "tokenizer.o")]
     subprocess.check_call(base[:2] + ["-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(cs, "rwkv_abi.map"), "-o", out] + objs)
 else:

@@ -20,27 +20,11 @@
 // Every case is validated BEFORE anything is launched (bounds of every index the kernels form); every HIP call is checked and the first
 // error ends the process with a non-zero status.
 #include "gemm_probe_plan.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "probe_common.h"                                  // HIP_OK, Reader and the patterns; the file format above is this probe's own
 
 using namespace rwkv;
 
-#define HIP_OK(call)                                                                                        \
-    do {                                                                                                    \
-        const hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                             \
-            std::fprintf(stderr, "gemm_probe: %s -> %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            std::fflush(stdout);                                                                            \
-            std::exit(3);                                                                                   \
-        }                                                                                                   \
-    } while (0)
-
 constexpr int GUARD = 256;                                 // elements after every output buffer
-constexpr uint32_t SENT32 = 0x7FC0DEADu;
-constexpr uint16_t SENT16 = 0x7EADu;
 
 __global__ void single_mfma_kernel(const _Float16 *a, const _Float16 *b, float *out) {      // a, b: one fragment tile each (lane l: 8 halfs at 8 l)
     typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -50,13 +34,6 @@ __global__ void single_mfma_kernel(const _Float16 *a, const _Float16 *b, float *
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const h8 *)(a + lane * 8), *(const h8 *)(b + lane * 8), acc, 0, 0, 0);
     for (int r = 0; r < 4; ++r) out[(lane & 15) * 16 + (lane >> 4) * 4 + r] = acc[r];        // out[t][row]
 }
-
-struct Reader {
-    FILE *f;
-    void get(void *dst, size_t bytes) {
-        if (bytes && std::fread(dst, 1, bytes, f) != bytes) { std::fprintf(stderr, "gemm_probe: case file ends early\n"); std::exit(2); }
-    }
-};
 
 struct Prob {
     int rows, K, fmt, xoff, act, post, partial, has_bias, mcol, ocol, hcol, has_lo;
@@ -91,6 +68,7 @@ template <class T> static void put(FILE *f, const T *dev, size_t n) {
 }
 
 int main(int argc, char **argv) {
+    probe_program = "gemm_probe";
     if (argc != 3) { std::fprintf(stderr, "usage: gemm_probe cases.bin results.bin\n"); return 2; }
     FILE *fin = std::fopen(argv[1], "rb"), *fout = std::fopen(argv[2], "wb");
     if (!fin || !fout) { std::fprintf(stderr, "gemm_probe: cannot open the files\n"); return 2; }
@@ -164,10 +142,10 @@ int main(int argc, char **argv) {
         plan.why = why;
         if (why.empty()) probe_plan(req, sh, plan);
         if (!plan.why.empty()) {
-            probe_print(stdout, ci, req, plan);
-            std::fflush(stdout);
             const int status = 1;
             std::fwrite(&status, 4, 1, fout);
+            probe_print(stdout, ci, req, plan);
+            std::fflush(stdout);
             continue;
         }
         GemmLaunch &Lh = plan.Lh;
@@ -202,15 +180,12 @@ int main(int argc, char **argv) {
         // ---- the launch ----
         if (single) {
             single_mfma_kernel<<<1, 64, 0, st>>>((const _Float16 *)d_pay[0], d_xhi, (float *)d_out);
-            std::printf("{\"case\": %d, \"status\": \"ran\", \"path\": \"single_mfma\"}\n", ci);
         } else {
             for (int i = 0; i < n; ++i) fill_prob(Lh.p[i], ps[i], (long)T * ldo);
             if (pl.path == GEMM_SMALLK) launch_smallk(Lh, hilo, st);
             else if (pl.path == GEMM_TILE) launch_gemm_tile(Lh, pl.variant, hilo, st);
             else launch_gemm(Lh, hilo, st);
-            probe_print(stdout, ci, req, plan);
         }
-        std::fflush(stdout);
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(st));
         // ---- everything back, whole ----
@@ -225,6 +200,10 @@ int main(int argc, char **argv) {
         }
         std::fflush(fout);
         for (void *p : bufs) HIP_OK(hipFree(p));
+        // the line only after the case's results are in the file: the number of lines says which case was running when a process ended early
+        if (single) std::printf("{\"case\": %d, \"status\": \"ran\", \"path\": \"single_mfma\"}\n", ci);
+        else probe_print(stdout, ci, req, plan);
+        std::fflush(stdout);
     }
     HIP_OK(hipStreamDestroy(st));
     std::fclose(fin);

@@ -8,37 +8,14 @@
 //                                              here (mix_plan): launch_v6_mix returns nothing, so these fields say what the rule gives, not what
 //                                              was launched — that is constrained by the outputs alone
 //
-// cases.bin (little-endian), tests/mix_cases.py write_cases:
-//   i32 magic 'MPRB', i32 ncases, then per case
-//     i32 name_len, char name[name_len], i32 kind (K_*), i32 nparam, i64 param[nparam] (the order of PARAMS below), i32 nbuf, then per buffer
-//       i32 role (R_*), i32 esize (2 | 4), i32 flags (1: copied back, 2: no bytes follow, the probe fills the NaN pattern of esize),
-//       i64 nbytes (the whole allocation, guard bands included), i64 off (byte offset of the pointer the launcher gets, a multiple of 256),
-//       u8 image[nbytes] unless flags & 2
-//   A role that is absent is a null pointer.
-// results.bin: per case, every buffer with flags & 1, WHOLE (guard bands included), in the order of the case file.
-// NaN patterns: 0x7FC0DEAD (fp32) / 0x7EAD (f16).  Every case of the file is validated BEFORE the GPU is touched: the supported-predicate of its form
-// holds and every index the kernels form from its fields lies inside the buffer allocated for it; a refused case ends the process with its name.
-// Every HIP call is checked; the first error ends the process with a non-zero status.
+// The case file, the result file, the patterns and the order of work per case are those of every role-buffer probe: DESIGN.md "Probe container"
+// (tests/cpp/probe_case.h, probe_common.h).  Here: elements of 2 | 4 bytes, `off` a multiple of 256, and the validation of every case BEFORE the
+// GPU is touched: the supported-predicate of its form holds and every index the kernels form from its fields lies inside the buffer allocated
+// for it; a refused case ends the process with its name.
 #include "mix_probe_plan.h"
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "probe_common.h"
 
 using namespace rwkv;
-
-#define HIP_OK(call)                                                                                        \
-    do {                                                                                                    \
-        const hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                             \
-            std::fprintf(stderr, "mix_probe: %s -> %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            std::fflush(stdout);                                                                            \
-            std::exit(3);                                                                                   \
-        }                                                                                                   \
-    } while (0)
-
-constexpr uint32_t SENT32 = 0x7FC0DEADu;
-constexpr uint16_t SENT16 = 0x7EADu;
 
 enum Kind { K_MIX = 0, K_COMMIT, K_PAIR, K_COUNT };
 enum Role {
@@ -51,55 +28,16 @@ static const char *const PARAMS[P_COUNT] = {"T", "C", "Dm", "hilo", "ldz", "ldh"
                                             "ksp_blocks", "ksp_max", "Dd", "commit_C", "carrier_hilo", "ldo"};
 static const char *const KIND_NAME[K_COUNT] = {"mix", "commit", "pair"};
 
-struct Buf {
-    int role = 0, esize = 0, flags = 0;
-    int64_t nbytes = 0, off = 0;
-    std::vector<uint8_t> host;
-    void *dev = nullptr;
-};
 struct MixPlan { int form = 0, NT = 0, split = 0, ksp = 1, g1[3] = {0, 0, 0}, g2[2] = {0, 0}, apply_nt = 0; };   // form: 0 decode, 1 prologue, 2 wide, 3 split
 static const char *const FORM_NAME[4] = {"decode", "lnp", "wide", "split"};
-struct Case {
-    std::string name;
-    int kind = 0;
-    std::vector<int64_t> p;
-    std::vector<Buf> b;
+struct MixCase : Case {
     MixPlan mp;
     CarrierPlan cp;
     std::vector<void *> tiled;                                        // device: W1, W2_0..4, carrier W0..4 after launch_tile_f16
-    const Buf *find(int role) const {
-        for (const Buf &x : b) if (x.role == role) return &x;
-        return nullptr;
-    }
-    template <class T> T *ptr(int role) const { const Buf *x = find(role); return x ? (T *)((char *)x->dev + x->off) : nullptr; }
-    const int *ints(int role) const { const Buf *x = find(role); return x ? (const int *)(x->host.data() + x->off) : nullptr; }
     int P(int i) const { return (int)p[i]; }
 };
 
-struct Reader {
-    FILE *f;
-    void get(void *dst, size_t bytes) {
-        if (bytes && std::fread(dst, 1, bytes, f) != bytes) { std::fprintf(stderr, "mix_probe: case file ends early\n"); std::exit(2); }
-    }
-    int32_t i32() { int32_t v; get(&v, 4); return v; }
-    int64_t i64() { int64_t v; get(&v, 8); return v; }
-};
-
-[[noreturn]] static void refuse(const Case &c, const std::string &why) {
-    std::fprintf(stderr, "mix_probe: case %s refused before any launch: %s\n", c.name.c_str(), why.c_str());
-    std::exit(4);
-}
-#define REQUIRE(c, cond) do { if (!(cond)) refuse(c, #cond); } while (0)
-
-// `n` elements of `esize` bytes are reachable from the pointer of `role` (which must exist unless optional)
-static void need(const Case &c, int role, int64_t n, int esize, bool optional = false) {
-    const Buf *x = c.find(role);
-    if (!x) { if (optional) return; refuse(c, "missing buffer, role " + std::to_string(role)); }
-    if (x->esize != esize || n < 0 || x->off + n * esize > x->nbytes) refuse(c, "buffer of role " + std::to_string(role) + " is too small for " + std::to_string(n) + " elements");
-}
-static int64_t ceil16(int64_t t) { return (t + 15) / 16 * 16; }
-
-static V6MixArgs mix_args(const Case &c, bool device) {
+static V6MixArgs mix_args(const MixCase &c, bool device) {
     V6MixArgs a{};
     a.T = c.P(P_T); a.C = c.P(P_C); a.Dm = c.P(P_DM); a.ldz = c.P(P_LDZ); a.ldh = c.P(P_LDH);
     a.ksp_min_t = c.P(P_KSP_MIN_T); a.ksp_blocks = c.P(P_KSP_BLOCKS); a.ksp_max = c.P(P_KSP_MAX);
@@ -128,7 +66,7 @@ static V6MixArgs mix_args(const Case &c, bool device) {
 }
 
 // the launcher's rules restated beside v6_mix_split (the product's own): form, token tiles per block, both grids, the apply launch's tile
-static MixPlan mix_plan(const Case &c) {
+static MixPlan mix_plan(const MixCase &c) {
     const V6MixArgs a = mix_args(c, false);
     const bool hilo = c.P(P_HILO) != 0;
     MixPlan m;
@@ -153,7 +91,7 @@ static MixPlan mix_plan(const Case &c) {
     return m;
 }
 
-static void validate_mix(Case &c) {
+static void validate_mix(MixCase &c) {
     const int T = c.P(P_T), C = c.P(P_C), Dm = c.P(P_DM), hilo = c.P(P_HILO), ldz = c.P(P_LDZ), ldh = c.P(P_LDH), lnp = c.P(P_LNP);
     REQUIRE(c, T >= 1 && T <= 4096 && C >= 256 && C <= 8192 && (hilo == 0 || hilo == 1) && (lnp == 0 || lnp == 1));
     REQUIRE(c, ldh % 32 == 0 && ldh >= C);
@@ -183,7 +121,7 @@ static void validate_mix(Case &c) {
         if (dense) REQUIRE(c, T <= nslots);
         else {
             need(c, R_SLOT, T, 4); need(c, R_PREV, T, 4);
-            for (int t = 0; t < T; ++t) REQUIRE(c, c.ints(R_SLOT)[t] >= 0 && c.ints(R_SLOT)[t] < nslots && c.ints(R_PREV)[t] == -1);   // one row per slot: no row to shift from
+            for (int t = 0; t < T; ++t) REQUIRE(c, c.host<int>(R_SLOT)[t] >= 0 && c.host<int>(R_SLOT)[t] < nslots && c.host<int>(R_PREV)[t] == -1);   // one row per slot: no row to shift from
         }
         REQUIRE(c, (size_t)8 * 4 * 64 * 16 + (size_t)2 * 16 * (Dm + 8) * 2 + lnp_lds_bytes(LNP_MAX_T, C, false) <= 160 * 1024);
     }
@@ -196,7 +134,7 @@ static void validate_mix(Case &c) {
     REQUIRE(c, c.mp.g1[0] >= 1 && (long)c.mp.g1[0] * c.mp.g1[1] * c.mp.g1[2] <= (1 << 16));
 }
 
-static void validate_commit(Case &c, bool pair) {
+static void validate_commit(MixCase &c, bool pair) {
     const int T = c.P(P_T), C = c.P(P_C), ldh = c.P(P_LDH), Dd = c.P(P_DD), CC = c.P(P_COMMIT_C), ch = c.P(P_CARRIER_HILO), ldo = c.P(P_LDO);
     const int dense = c.P(P_DENSE), nslots = c.P(P_NSLOTS);
     const int64_t stride = c.p[P_SXSTRIDE];
@@ -217,13 +155,13 @@ static void validate_commit(Case &c, bool pair) {
     need(c, R_SLOT, T, 4); need(c, R_LAST, T, 4);
     std::vector<int> writers(nslots, 0);
     for (int t = 0; t < T; ++t) {
-        const int sl = c.ints(R_SLOT)[t], la = c.ints(R_LAST)[t];
+        const int sl = c.host<int>(R_SLOT)[t], la = c.host<int>(R_LAST)[t];
         REQUIRE(c, sl >= 0 && sl < nslots && la >= -1 && la < T);
         if (la >= 0) REQUIRE(c, ++writers[sl] == 1);
     }
 }
 
-static void validate(Case &c) {
+static void validate(MixCase &c) {
     REQUIRE(c, (int)c.p.size() == P_COUNT);
     for (const Buf &x : c.b) {
         REQUIRE(c, x.role >= 0 && x.role < R_COUNT && (x.esize == 2 || x.esize == 4) && x.off >= 0 && x.off % 256 == 0 && x.off <= x.nbytes);
@@ -238,7 +176,7 @@ static void validate(Case &c) {
 }
 
 // raw fp16 [rows][K] of `role` -> a tiled device buffer, by the product's load-time kernel
-static void *tile(const Case &c, int role, int rows, int K, hipStream_t s) {
+static void *tile(const MixCase &c, int role, int rows, int K, hipStream_t s) {
     void *out = nullptr;
     HIP_OK(hipMalloc(&out, (size_t)rows * K * 2));
     launch_tile_f16(c.ptr<_Float16>(role), rows, rows, K, out, s);
@@ -246,7 +184,7 @@ static void *tile(const Case &c, int role, int rows, int K, hipStream_t s) {
     return out;
 }
 
-static void launch_carrier(Case &c, hipStream_t s) {
+static void launch_carrier(MixCase &c, hipStream_t s) {
     const int T = c.P(P_T), C = c.P(P_C), Dd = c.P(P_DD), ldh = c.P(P_LDH), ldo = c.P(P_LDO);
     const bool ch = c.P(P_CARRIER_HILO) != 0;
     DMat mats[CARRIER_NPROB];
@@ -265,95 +203,44 @@ static void launch_carrier(Case &c, hipStream_t s) {
     cm.T = T; cm.C = c.P(P_COMMIT_C);
     c.cp.Lh.commit = cm;
     launch_gemm(c.cp.Lh, ch, s);
+    launched(s);
+}
+
+// the weights tiled by the product's load-time kernel, then the mix launch, the carrier, or both in that order
+static void launch(MixCase &c, hipStream_t s) {
+    const int C = c.P(P_C), Dm = c.P(P_DM);
+    c.tiled.assign(11, nullptr);
+    if (c.kind != K_COMMIT) {
+        c.tiled[0] = tile(c, R_W1, 5 * Dm, C, s);
+        for (int m = 0; m < 5; ++m) c.tiled[1 + m] = tile(c, R_W2_0 + m, C, Dm, s);
+    }
+    if (c.kind != K_MIX)
+        for (int i = 0; i < CARRIER_NPROB; ++i) c.tiled[6 + i] = tile(c, R_CW0 + i, i == 4 ? c.P(P_DD) : C, C, s);
+    HIP_OK(hipStreamSynchronize(s));
+    if (c.kind != K_COMMIT) {
+        launch_v6_mix(mix_args(c, true), c.P(P_HILO) != 0, s);
+        launched(s);
+    }
+    if (c.kind != K_MIX) launch_carrier(c, s);
+    for (void *p : c.tiled) if (p) HIP_OK(hipFree(p));
+}
+
+static void fields(const MixCase &c) {
+    std::printf(", \"kind\": \"%s\"", KIND_NAME[c.kind]);
+    for (int i = 0; i < P_COUNT; ++i) std::printf(", \"%s\": %lld", PARAMS[i], (long long)c.p[i]);
+    if (c.kind != K_COMMIT) {
+        const MixPlan &m = c.mp;
+        std::printf(", \"form\": \"%s\", \"NT\": %d, \"split\": %d, \"ksp\": %d, \"grid1\": [%d, %d, %d], \"grid2\": [%d, %d], \"apply_nt\": %d",
+                    FORM_NAME[m.form], m.NT, m.split, m.ksp, m.g1[0], m.g1[1], m.g1[2], m.g2[0], m.g2[1], m.apply_nt);
+    }
+    if (c.kind != K_MIX) {
+        std::printf(", \"carrier\": ");
+        carrier_print(stdout, c.cp);
+        std::printf(", \"launch_grid\": %d", c.cp.Lh.total_blocks + 1);
+    }
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: mix_probe <cases.bin> <results.bin>\n"); return 2; }
-    FILE *fi = std::fopen(argv[1], "rb");
-    if (!fi) { std::fprintf(stderr, "mix_probe: cannot read %s\n", argv[1]); return 2; }
-    Reader rd{fi};
-    if (rd.i32() != 0x4252504D) { std::fprintf(stderr, "mix_probe: bad magic\n"); return 2; }
-    const int ncases = rd.i32();
-    if (ncases < 0 || ncases > 4096) { std::fprintf(stderr, "mix_probe: bad case count\n"); return 2; }
-    std::vector<Case> cases(ncases);
-    for (Case &c : cases) {
-        const int nl = rd.i32();
-        if (nl < 0 || nl > 256) { std::fprintf(stderr, "mix_probe: bad name length\n"); return 2; }
-        c.name.resize(nl); rd.get(&c.name[0], nl);
-        c.kind = rd.i32();
-        const int np = rd.i32();
-        if (c.kind < 0 || c.kind >= K_COUNT || np < 0 || np > 32) { std::fprintf(stderr, "mix_probe: bad case header\n"); return 2; }
-        c.p.resize(np); rd.get(c.p.data(), (size_t)np * 8);
-        const int nb = rd.i32();
-        if (nb < 0 || nb > R_COUNT) { std::fprintf(stderr, "mix_probe: bad buffer count\n"); return 2; }
-        c.b.resize(nb);
-        for (Buf &x : c.b) {
-            x.role = rd.i32(); x.esize = rd.i32(); x.flags = rd.i32(); x.nbytes = rd.i64(); x.off = rd.i64();
-            if (x.nbytes <= 0 || x.nbytes >= (int64_t)1 << 31 || (x.esize != 2 && x.esize != 4) || x.nbytes % x.esize) { std::fprintf(stderr, "mix_probe: bad buffer header\n"); return 2; }
-            x.host.resize(x.nbytes);
-            if (x.flags & 2) {
-                if (x.esize == 4) for (int64_t i = 0; i < x.nbytes / 4; ++i) ((uint32_t *)x.host.data())[i] = SENT32;
-                else for (int64_t i = 0; i < x.nbytes / 2; ++i) ((uint16_t *)x.host.data())[i] = SENT16;
-            } else rd.get(x.host.data(), x.nbytes);
-        }
-    }
-    std::fclose(fi);
-    for (Case &c : cases) validate(c);                                 // all of them, before the GPU is touched
-
-    FILE *fo = std::fopen(argv[2], "wb");
-    if (!fo) { std::fprintf(stderr, "mix_probe: cannot write %s\n", argv[2]); return 2; }
-    hipStream_t s;
-    HIP_OK(hipStreamCreate(&s));
-    for (Case &c : cases) {
-        for (Buf &x : c.b) {
-            HIP_OK(hipMalloc(&x.dev, x.nbytes));
-            HIP_OK(hipMemcpy(x.dev, x.host.data(), x.nbytes, hipMemcpyHostToDevice));
-        }
-        const int C = c.P(P_C), Dm = c.P(P_DM);
-        c.tiled.assign(11, nullptr);
-        if (c.kind != K_COMMIT) {
-            c.tiled[0] = tile(c, R_W1, 5 * Dm, C, s);
-            for (int m = 0; m < 5; ++m) c.tiled[1 + m] = tile(c, R_W2_0 + m, C, Dm, s);
-        }
-        if (c.kind != K_MIX)
-            for (int i = 0; i < CARRIER_NPROB; ++i) c.tiled[6 + i] = tile(c, R_CW0 + i, i == 4 ? c.P(P_DD) : C, C, s);
-        HIP_OK(hipStreamSynchronize(s));
-        if (c.kind != K_COMMIT) {
-            launch_v6_mix(mix_args(c, true), c.P(P_HILO) != 0, s);
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipStreamSynchronize(s));
-        }
-        if (c.kind != K_MIX) {
-            launch_carrier(c, s);
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipStreamSynchronize(s));
-        }
-        for (Buf &x : c.b) {
-            if (x.flags & 1) {
-                HIP_OK(hipMemcpy(x.host.data(), x.dev, x.nbytes, hipMemcpyDeviceToHost));
-                if (std::fwrite(x.host.data(), 1, x.nbytes, fo) != (size_t)x.nbytes) { std::fprintf(stderr, "mix_probe: short write\n"); return 2; }
-            }
-            HIP_OK(hipFree(x.dev));
-            x.dev = nullptr;
-            std::vector<uint8_t>().swap(x.host);
-        }
-        for (void *p : c.tiled) if (p) HIP_OK(hipFree(p));
-        std::printf("{\"case\": \"%s\", \"kind\": \"%s\"", c.name.c_str(), KIND_NAME[c.kind]);
-        for (int i = 0; i < P_COUNT; ++i) std::printf(", \"%s\": %lld", PARAMS[i], (long long)c.p[i]);
-        if (c.kind != K_COMMIT) {
-            const MixPlan &m = c.mp;
-            std::printf(", \"form\": \"%s\", \"NT\": %d, \"split\": %d, \"ksp\": %d, \"grid1\": [%d, %d, %d], \"grid2\": [%d, %d], \"apply_nt\": %d",
-                        FORM_NAME[m.form], m.NT, m.split, m.ksp, m.g1[0], m.g1[1], m.g1[2], m.g2[0], m.g2[1], m.apply_nt);
-        }
-        if (c.kind != K_MIX) {
-            std::printf(", \"carrier\": ");
-            carrier_print(stdout, c.cp);
-            std::printf(", \"launch_grid\": %d", c.cp.Lh.total_blocks + 1);
-        }
-        std::printf("}\n");
-        std::fflush(stdout);
-    }
-    HIP_OK(hipStreamDestroy(s));
-    if (std::fclose(fo) != 0) { std::fprintf(stderr, "mix_probe: close failed\n"); return 2; }
-    return 0;
+    return probe_main<MixCase>(argc, argv, ProbeSpec{"mix_probe", 0x4252504D, K_COUNT, 32, R_COUNT, 2}, validate, launch, fields);
 }
+

@@ -4,37 +4,13 @@
 //
 //   row_probe <cases.bin> <results.bin>        one JSON line per case on stdout: the launcher arguments that went in
 //
-// cases.bin (little-endian), tests/row_cases.py write_cases:
-//   i32 magic 'RPRB', i32 ncases, then per case
-//     i32 name_len, char name[name_len], i32 kind (K_*), i32 nparam, i64 param[nparam] (the order of PARAMS below), i32 nbuf, then per buffer
-//       i32 role (R_*), i32 esize (2 | 4), i32 flags (1: copied back, 2: no bytes follow, the probe fills the NaN pattern of esize),
-//       i64 nbytes (the whole allocation, guard bands included), i64 off (byte offset of the pointer the launcher gets, a multiple of 256),
-//       u8 image[nbytes] unless flags & 2
-//   A role that is absent is a null pointer.
-// results.bin: per case, every buffer with flags & 1, WHOLE (guard bands included), in the order of the case file.
-// NaN patterns: 0x7FC0DEAD (fp32) / 0x7EAD (f16).  Every case is validated BEFORE anything is launched: every index the kernel forms from the
-// case's fields lies inside the buffer allocated for it.  Every HIP call is checked; the first error ends the process with a non-zero status.
+// The case file, the result file, the patterns and the order of work per case are those of every role-buffer probe: DESIGN.md "Probe container"
+// (tests/cpp/probe_case.h, probe_common.h).  Here: elements of 2 | 4 bytes, `off` a multiple of 256, and the validation of every case BEFORE
+// anything is launched: every index the kernel forms from the case's fields lies inside the buffer allocated for it.
 #include "../../ai00_server_amd/csrc/rwkv_kernels.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "probe_common.h"
 
 using namespace rwkv;
-
-#define HIP_OK(call)                                                                                        \
-    do {                                                                                                    \
-        const hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                             \
-            std::fprintf(stderr, "row_probe: %s -> %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            std::fflush(stdout);                                                                            \
-            std::exit(3);                                                                                   \
-        }                                                                                                   \
-    } while (0)
-
-constexpr uint32_t SENT32 = 0x7FC0DEADu;
-constexpr uint16_t SENT16 = 0x7EADu;
 
 enum Kind { K_WKV = 0, K_WKV4, K_LN_SHIFT, K_EMBED, K_LN_OUT, K_STATE_PACK, K_COUNT };
 enum Role {
@@ -52,54 +28,12 @@ static const char *const PARAMS[K_COUNT][16] = {
 };
 static const char *const KIND_NAME[K_COUNT] = {"wkv", "wkv4", "ln_shift", "embed", "ln_out", "state_pack"};
 
-struct Buf {
-    int role = 0, esize = 0, flags = 0;
-    int64_t nbytes = 0, off = 0;
-    std::vector<uint8_t> host;
-    void *dev = nullptr;
-};
-struct Case {
-    std::string name;
-    int kind = 0;
-    std::vector<int64_t> p;
-    std::vector<Buf> b;
-    const Buf *find(int role) const {
-        for (const Buf &x : b) if (x.role == role) return &x;
-        return nullptr;
-    }
-    template <class T> T *ptr(int role) const { const Buf *x = find(role); return x ? (T *)((char *)x->dev + x->off) : nullptr; }
-    const int *ints(int role) const { const Buf *x = find(role); return x ? (const int *)(x->host.data() + x->off) : nullptr; }
-};
-
-struct Reader {
-    FILE *f;
-    void get(void *dst, size_t bytes) {
-        if (bytes && std::fread(dst, 1, bytes, f) != bytes) { std::fprintf(stderr, "row_probe: case file ends early\n"); std::exit(2); }
-    }
-    int32_t i32() { int32_t v; get(&v, 4); return v; }
-    int64_t i64() { int64_t v; get(&v, 8); return v; }
-};
-
-[[noreturn]] static void refuse(const Case &c, const std::string &why) {
-    std::fprintf(stderr, "row_probe: case %s refused before any launch: %s\n", c.name.c_str(), why.c_str());
-    std::exit(4);
-}
-#define REQUIRE(c, cond) do { if (!(cond)) refuse(c, #cond); } while (0)
-
-// `n` elements of `esize` bytes are reachable from the pointer of `role` (which must exist unless optional)
-static void need(const Case &c, int role, int64_t n, int esize, bool optional = false) {
-    const Buf *x = c.find(role);
-    if (!x) { if (optional) return; refuse(c, "missing buffer, role " + std::to_string(role)); }
-    if (x->esize != esize || n < 0 || x->off + n * esize > x->nbytes) refuse(c, "buffer of role " + std::to_string(role) + " is too small for " + std::to_string(n) + " elements");
-}
-static int64_t ceil16(int64_t t) { return (t + 15) / 16 * 16; }
-
 // the sequences of a WKV step: distinct slots inside [0, nslots), rows inside [0, T), no row in two sequences
 static void check_seqs(const Case &c, int n_seq, int dense, int T, int nslots, bool one_row_each) {
     REQUIRE(c, n_seq >= 1 && T >= 1 && nslots >= 1);
     if (dense) { REQUIRE(c, n_seq <= T && n_seq <= nslots); return; }
     need(c, R_SEQ_SLOT, n_seq, 4); need(c, R_SEQ_BEGIN, n_seq, 4); need(c, R_SEQ_LEN, n_seq, 4);
-    const int *sl = c.ints(R_SEQ_SLOT), *bg = c.ints(R_SEQ_BEGIN), *ln = c.ints(R_SEQ_LEN);
+    const int *sl = c.host<int>(R_SEQ_SLOT), *bg = c.host<int>(R_SEQ_BEGIN), *ln = c.host<int>(R_SEQ_LEN);
     std::vector<char> slot_used(nslots, 0), row_used(T, 0);
     for (int i = 0; i < n_seq; ++i) {
         REQUIRE(c, sl[i] >= 0 && sl[i] < nslots && !slot_used[sl[i]]);
@@ -165,7 +99,7 @@ static void validate(const Case &c) {
         for (int m = 0; m < nmix; ++m) { need(c, R_MU0 + m, C, 4); need(c, R_OHI0 + m, ceil16(T) * ldh, 2); need(c, R_OLO0 + m, ceil16(T) * ldh, 2, true); }
         if (dense) { REQUIRE(c, T <= nslots); break; }
         need(c, R_SLOT, T, 4); need(c, R_PREV, T, 4); need(c, R_LAST, T, 4);
-        const int *sl = c.ints(R_SLOT), *pv = c.ints(R_PREV), *la = c.ints(R_LAST);
+        const int *sl = c.host<int>(R_SLOT), *pv = c.host<int>(R_PREV), *la = c.host<int>(R_LAST);
         std::vector<int> writers(nslots, 0);
         for (int t = 0; t < T; ++t) {
             REQUIRE(c, sl[t] >= 0 && sl[t] < nslots && pv[t] >= -1 && pv[t] < T && la[t] >= -1 && la[t] < T);
@@ -193,7 +127,7 @@ static void validate(const Case &c) {
         need(c, R_OHI0, ceil16(n_out) * ldh, 2); need(c, R_OLO0, ceil16(n_out) * ldh, 2, true);
         if (c.find(R_OUTROWS)) {
             need(c, R_OUTROWS, n_out, 4);
-            for (int o = 0; o < n_out; ++o) REQUIRE(c, c.ints(R_OUTROWS)[o] >= 0 && c.ints(R_OUTROWS)[o] < T);
+            for (int o = 0; o < n_out; ++o) REQUIRE(c, c.host<int>(R_OUTROWS)[o] >= 0 && c.host<int>(R_OUTROWS)[o] < T);
         } else REQUIRE(c, n_out <= T);
         break;
     }
@@ -269,67 +203,14 @@ static void launch(const Case &c, hipStream_t s) {
         break;
     }
     }
+    launched(s);
+}
+
+static void fields(const Case &c) {
+    std::printf(", \"launcher\": \"%s\"", KIND_NAME[c.kind]);
+    for (size_t i = 0; i < c.p.size() && PARAMS[c.kind][i]; ++i) std::printf(", \"%s\": %lld", PARAMS[c.kind][i], (long long)c.p[i]);
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: row_probe <cases.bin> <results.bin>\n"); return 2; }
-    FILE *fi = std::fopen(argv[1], "rb");
-    if (!fi) { std::fprintf(stderr, "row_probe: cannot read %s\n", argv[1]); return 2; }
-    Reader rd{fi};
-    if (rd.i32() != 0x42525052) { std::fprintf(stderr, "row_probe: bad magic\n"); return 2; }
-    const int ncases = rd.i32();
-    std::vector<Case> cases(ncases);
-    for (Case &c : cases) {
-        const int nl = rd.i32();
-        if (nl < 0 || nl > 256) { std::fprintf(stderr, "row_probe: bad name length\n"); return 2; }
-        c.name.resize(nl); rd.get(&c.name[0], nl);
-        c.kind = rd.i32();
-        const int np = rd.i32();
-        if (c.kind < 0 || c.kind >= K_COUNT || np < 0 || np > 16) { std::fprintf(stderr, "row_probe: bad case header\n"); return 2; }
-        c.p.resize(np); rd.get(c.p.data(), (size_t)np * 8);
-        const int nb = rd.i32();
-        if (nb < 0 || nb > R_COUNT) { std::fprintf(stderr, "row_probe: bad buffer count\n"); return 2; }
-        c.b.resize(nb);
-        for (Buf &x : c.b) {
-            x.role = rd.i32(); x.esize = rd.i32(); x.flags = rd.i32(); x.nbytes = rd.i64(); x.off = rd.i64();
-            if (x.nbytes <= 0 || x.nbytes >= (int64_t)1 << 31 || (x.esize != 2 && x.esize != 4) || x.nbytes % x.esize) { std::fprintf(stderr, "row_probe: bad buffer header\n"); return 2; }
-            x.host.resize(x.nbytes);
-            if (x.flags & 2) {
-                if (x.esize == 4) for (int64_t i = 0; i < x.nbytes / 4; ++i) ((uint32_t *)x.host.data())[i] = SENT32;
-                else for (int64_t i = 0; i < x.nbytes / 2; ++i) ((uint16_t *)x.host.data())[i] = SENT16;
-            } else rd.get(x.host.data(), x.nbytes);
-        }
-    }
-    std::fclose(fi);
-    for (const Case &c : cases) validate(c);                           // all of them, before the GPU is touched
-
-    FILE *fo = std::fopen(argv[2], "wb");
-    if (!fo) { std::fprintf(stderr, "row_probe: cannot write %s\n", argv[2]); return 2; }
-    hipStream_t s;
-    HIP_OK(hipStreamCreate(&s));
-    for (Case &c : cases) {
-        for (Buf &x : c.b) {
-            HIP_OK(hipMalloc(&x.dev, x.nbytes));
-            HIP_OK(hipMemcpy(x.dev, x.host.data(), x.nbytes, hipMemcpyHostToDevice));
-        }
-        launch(c, s);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipStreamSynchronize(s));
-        for (Buf &x : c.b) {
-            if (x.flags & 1) {
-                HIP_OK(hipMemcpy(x.host.data(), x.dev, x.nbytes, hipMemcpyDeviceToHost));
-                if (std::fwrite(x.host.data(), 1, x.nbytes, fo) != (size_t)x.nbytes) { std::fprintf(stderr, "row_probe: short write\n"); return 2; }
-            }
-            HIP_OK(hipFree(x.dev));
-            x.dev = nullptr;
-            std::vector<uint8_t>().swap(x.host);
-        }
-        std::printf("{\"case\": \"%s\", \"launcher\": \"%s\"", c.name.c_str(), KIND_NAME[c.kind]);
-        for (size_t i = 0; i < c.p.size() && PARAMS[c.kind][i]; ++i) std::printf(", \"%s\": %lld", PARAMS[c.kind][i], (long long)c.p[i]);
-        std::printf("}\n");
-        std::fflush(stdout);
-    }
-    HIP_OK(hipStreamDestroy(s));
-    if (std::fclose(fo) != 0) { std::fprintf(stderr, "row_probe: close failed\n"); return 2; }
-    return 0;
+    return probe_main<Case>(argc, argv, ProbeSpec{"row_probe", 0x42525052, K_COUNT, 16, R_COUNT, 2}, validate, launch, fields);
 }

@@ -432,13 +432,13 @@ def plan_cpu(exe, cases):
 def compile_probe(out_dir):
     """hipcc -c of the probe for gfx950 (no GPU needed)."""
     from ai00_server_amd import build as B
-    return B.compile_gemm_probe(os.path.join(str(out_dir), "gemm_probe.o"))
+    return B.compile_probe("gemm_probe", os.path.join(str(out_dir), "gemm_probe.o"))
 
 
 def build_probe():
-    """The probe, linked against the kernel objects the library build leaves in the tree (ai00_server_amd/build.py build_gemm_probe)."""
+    """The probe, linked against the kernel objects the library build leaves in the tree (ai00_server_amd/build.py build_probe)."""
     from ai00_server_amd import build as B
-    return B.build_gemm_probe(verbose=False)
+    return B.build_probe("gemm_probe", verbose=False)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -19,7 +19,6 @@ out_c = xx + dx (mu_c + o_c), written as an f16 hi (+ lo) operand [ceil16(T)][ld
 A plain module, no fixtures."""
 import json
 import os
-import struct
 import subprocess
 import zlib
 from dataclasses import dataclass, field
@@ -27,7 +26,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from tests.gemm_cases import F16 as W_F16, Prob, lattice_weights, pack_opd, split_hilo, unpack_opd   # the operand layout and the carrier's lattice: stated once, there
-from tests.row_cases import GUARD, SENT16, SENT32, Checker, b_in, b_out, bits, ceil16, ew_bound, f16_sat, ln_eval, nan32, ulp16
+from tests.probe_io import GUARD, SENT16, SENT32, b_in, b_out, bits, read_results, write_cases as write_case_file   # the container: stated once, there
+from tests.row_cases import Checker, ceil16, ew_bound, f16_sat, ln_eval, nan32, ulp16
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F64 = np.float32, np.float64
@@ -144,42 +144,16 @@ def carrier_plans(exe, cases):
 
 def compile_probe(out_dir):
     from ai00_server_amd import build as B
-    return B.compile_mix_probe(os.path.join(str(out_dir), "mix_probe.o"))
+    return B.compile_probe("mix_probe", os.path.join(str(out_dir), "mix_probe.o"))
 
 
 def build_probe():
     from ai00_server_amd import build as B
-    return B.build_mix_probe(verbose=False)
+    return B.build_probe("mix_probe", verbose=False)
 
 
 def write_cases(path, cases, datas):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<ii", 0x4252504D, len(cases)))
-        for c, d in zip(cases, datas):
-            nm = c.name.encode()
-            vals = [int(c.p[k]) for k in PARAMS]
-            f.write(struct.pack("<i", len(nm)) + nm + struct.pack("<ii", c.kind, len(vals)) + struct.pack(f"<{len(vals)}q", *vals))
-            f.write(struct.pack("<i", len(d["bufs"])))
-            for b in d["bufs"]:
-                f.write(struct.pack("<iiiqq", ROLE[b.role], b.esize, b.flags, (b.n + 2 * GUARD) * b.esize, GUARD * b.esize))
-                if not b.flags & 2:
-                    f.write(b.image.tobytes())
-
-
-def read_results(path, cases, datas):
-    out = []
-    with open(path, "rb") as f:
-        for c, d in zip(cases, datas):
-            res = {}
-            for b in d["bufs"]:
-                if b.flags & 1:
-                    nb = (b.n + 2 * GUARD) * b.esize
-                    raw = f.read(nb)
-                    assert len(raw) == nb, f"{c.name}: the result file ends inside {b.role}"
-                    res[b.role] = np.frombuffer(raw, np.uint32 if b.esize == 4 else np.uint16)
-            out.append(res)
-        assert f.read(1) == b"", "the result file is longer than the table"
-    return out
+    return write_case_file(path, 0x4252504D, cases, datas, lambda c: PARAMS, ROLE)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -18,16 +18,14 @@ The internal WKV state of a slot is [H][64][64] = T[head][p = value index][q = k
 operand (y, the mixes, ln_out) is read through the operand layout of rwkv_kernels.hip `opd_off`: 1 KiB tiles of 16 tokens x 32 k, tile
 (t / 16, k / 32) of a [ceil16(T)][ld] operand at tile index (t / 16) * (ld / 32) + k / 32, lane ((k / 8) % 4) * 16 + t % 16 owning 8 k."""
 import os
-import struct
 import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from tests.gemm_cases import pack_opd, unpack_opd                   # the operand layout, cross-checked against opd_off by test_gemm_cases_cpu.py
+from tests.probe_io import GUARD, SENT16, SENT32, Buf, b_in, b_out, bits, read_results, write_cases as write_case_file   # the container, stated once, there
 
-GUARD = 256                                                        # elements on BOTH sides of every buffer
-SENT32, SENT16 = 0x7FC0DEAD, 0x7EAD
 FP32_TOL = 2e-5                                                    # the project's Fp32 tolerance (tests/test_gpu_dims.py)
 F32, F64 = np.float32, np.float64
 K_WKV, K_WKV4, K_LN_SHIFT, K_EMBED, K_LN_OUT, K_STATE_PACK = range(6)
@@ -55,36 +53,12 @@ class Case:
     o: dict = field(default_factory=dict)                          # what make() needs beyond the launcher arguments
 
 
-@dataclass
-class Buf:
-    role: str
-    esize: int
-    flags: int                                                     # 1: copied back, 2: the probe fills the NaN pattern
-    n: int                                                         # elements between the guard bands
-    image: np.ndarray = None                                       # uint16 / uint32 bits, guard bands included (None with flags & 2)
-
-
 def seed_of(case):
     return zlib.crc32(case.o.get("seed", case.name).encode())
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype.itemsize == 4 else np.uint16).reshape(-1)
-
-
 def nan32(shape):
     return np.full(shape, SENT32, np.uint32).view(F32)
-
-
-def b_in(role, a, back=False):
-    b = bits(a)
-    g = np.full(GUARD, SENT32 if b.dtype == np.uint32 else SENT16, b.dtype)
-    return Buf(role, b.dtype.itemsize, 1 if back else 0, b.size, np.concatenate([g, b, g]))
-
-
-def b_out(role, n, esize):
-    return Buf(role, esize, 3, int(n))
 
 
 def ceil16(t):
@@ -95,33 +69,7 @@ def ceil16(t):
 # the case file and the result file (tests/cpp/row_probe.hip)
 # ------------------------------------------------------------------------------------------------
 def write_cases(path, cases, datas):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<ii", 0x42525052, len(cases)))
-        for c, d in zip(cases, datas):
-            nm = c.name.encode()
-            vals = [int(c.p[k]) for k in PARAMS[c.kind]]
-            f.write(struct.pack("<i", len(nm)) + nm + struct.pack("<ii", c.kind, len(vals)) + struct.pack(f"<{len(vals)}q", *vals))
-            f.write(struct.pack("<i", len(d["bufs"])))
-            for b in d["bufs"]:
-                f.write(struct.pack("<iiiqq", ROLE[b.role], b.esize, b.flags, (b.n + 2 * GUARD) * b.esize, GUARD * b.esize))
-                if not b.flags & 2:
-                    f.write(b.image.tobytes())
-
-
-def read_results(path, cases, datas):
-    out = []
-    with open(path, "rb") as f:
-        for c, d in zip(cases, datas):
-            res = {}
-            for b in d["bufs"]:
-                if b.flags & 1:
-                    nb = (b.n + 2 * GUARD) * b.esize
-                    raw = f.read(nb)
-                    assert len(raw) == nb, f"{c.name}: the result file ends inside {b.role}"
-                    res[b.role] = np.frombuffer(raw, np.uint32 if b.esize == 4 else np.uint16)
-            out.append(res)
-        assert f.read(1) == b"", "the result file is longer than the table"
-    return out
+    return write_case_file(path, 0x42525052, cases, datas, lambda c: PARAMS[c.kind], ROLE)
 
 
 def plan_line(c):
@@ -131,12 +79,12 @@ def plan_line(c):
 
 def compile_probe(out_dir):
     from ai00_server_amd import build as B
-    return B.compile_row_probe(os.path.join(str(out_dir), "row_probe.o"))
+    return B.compile_probe("row_probe", os.path.join(str(out_dir), "row_probe.o"))
 
 
 def build_probe():
     from ai00_server_amd import build as B
-    return B.build_row_probe(verbose=False)
+    return B.build_probe("row_probe", verbose=False)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -18,15 +18,15 @@ The reference is one function, `emulate` + `draw`: the candidate order (key desc
 of oracle/rwkv_ref.py nucleus_ref / typical_ref / mirostat_ref, stated window by window as the kernels walk it so that the same text can
 be run with one mistake at a time (MISTAKES) and can say which branches a row reaches (the coverage proof)."""
 import os
-import struct
 import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
 
+from tests.probe_io import GUARD, SENT8, SENT32, Buf, b_in, b_out, bits, own, read_results, untouched   # the container: stated once, there
+from tests.probe_io import read_cases as read_case_file, write_cases as write_case_file
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 256                                                        # elements on BOTH sides of every buffer
-SENT32, SENT8 = 0x7FC0DEAD, 0xAD
 FP32_TOL = 2e-5                                                    # the project's Fp32 tolerance (tests/test_gpu_dims.py)
 F32, F64 = np.float32, np.float64
 K_NUCLEUS, K_SOFTMAX, K_SCORE, K_ARGMAX, K_ADJUST, K_MASK = range(6)
@@ -54,106 +54,19 @@ class Case:
     o: dict = field(default_factory=dict)                          # what make() needs beyond the launcher arguments
 
 
-@dataclass
-class Buf:
-    role: str
-    esize: int
-    flags: int                                                     # 1: copied back, 2: the probe fills the pattern
-    n: int                                                         # elements between the guard bands (spare rows included)
-    off: int                                                       # elements from the first guard band's end to the launcher's pointer
-    image: np.ndarray = None                                       # bits, guard bands included (None with flags & 2)
-
-
 def seed_of(case):
     return zlib.crc32(case.name.encode())
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype.itemsize == 4 else np.uint8).reshape(-1)
-
-
-def b_in(role, a, back=False, spare=0):
-    """`a` between guard bands; with spare > 0 one spare row / entry of `spare` pattern elements on both sides, the pointer behind the first."""
-    b = bits(a)
-    s = SENT32 if b.dtype == np.uint32 else SENT8
-    g, sp = np.full(GUARD, s, b.dtype), np.full(spare, s, b.dtype)
-    return Buf(role, b.dtype.itemsize, 1 if back else 0, b.size + 2 * spare, spare, np.concatenate([g, sp, b, sp, g]))
-
-
-def b_out(role, n, spare=0):
-    return Buf(role, 4, 3, int(n) + 2 * spare, spare)
-
-
-def own(res, b):
-    """The elements behind the launcher's pointer, spare rows and guard bands cut off."""
-    a = res[b.role]
-    return a[GUARD + b.off: a.size - GUARD - b.off]
 
 
 # ------------------------------------------------------------------------------------------------
 # the case file and the result file (tests/cpp/sample_probe.hip)
 # ------------------------------------------------------------------------------------------------
 def write_cases(path, cases, datas):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<ii", 0x42525053, len(cases)))
-        for c, d in zip(cases, datas):
-            nm = c.name.encode()
-            vals = [int(c.p[k]) for k in PARAMS[c.kind]]
-            f.write(struct.pack("<i", len(nm)) + nm + struct.pack("<ii", c.kind, len(vals)) + struct.pack(f"<{len(vals)}q", *vals))
-            f.write(struct.pack("<i", len(d["bufs"])))
-            for b in d["bufs"]:
-                f.write(struct.pack("<iiiqq", ROLE[b.role], b.esize, b.flags, (b.n + 2 * GUARD) * b.esize, (GUARD + b.off) * b.esize))
-                if not b.flags & 2:
-                    assert b.image.size == b.n + 2 * GUARD and b.image.dtype.itemsize == b.esize
-                    f.write(b.image.tobytes())
+    return write_case_file(path, 0x42525053, cases, datas, lambda c: PARAMS[c.kind], ROLE)
 
 
 def read_cases(path):
-    """The case file back as (name, kind, params, [(role, esize, flags, nbytes, off, image or None)]): the round trip of write_cases."""
-    out = []
-    with open(path, "rb") as f:
-        magic, n = struct.unpack("<ii", f.read(8))
-        assert magic == 0x42525053
-        for _ in range(n):
-            nl, = struct.unpack("<i", f.read(4))
-            name = f.read(nl).decode()
-            kind, npar = struct.unpack("<ii", f.read(8))
-            par = struct.unpack(f"<{npar}q", f.read(8 * npar))
-            nb, = struct.unpack("<i", f.read(4))
-            bufs = []
-            for _ in range(nb):
-                role, esize, flags, nbytes, off = struct.unpack("<iiiqq", f.read(28))
-                img = None if flags & 2 else np.frombuffer(f.read(nbytes), np.uint32 if esize == 4 else np.uint8)
-                bufs.append((role, esize, flags, nbytes, off, img))
-            out.append((name, kind, par, bufs))
-        assert f.read(1) == b""
-    return out
-
-
-def read_results(path, cases, datas):
-    out = []
-    with open(path, "rb") as f:
-        for c, d in zip(cases, datas):
-            res = {}
-            for b in d["bufs"]:
-                if b.flags & 1:
-                    nb = (b.n + 2 * GUARD) * b.esize
-                    raw = f.read(nb)
-                    assert len(raw) == nb, f"{c.name}: the result file ends inside {b.role}"
-                    res[b.role] = np.frombuffer(raw, np.uint32 if b.esize == 4 else np.uint8)
-            out.append(res)
-        assert f.read(1) == b"", "the result file is longer than the table"
-    return out
-
-
-def untouched(d):
-    """What the probe returns when no kernel writes anything: every copied-back buffer as it went in (the CPU test starts from this)."""
-    res = {}
-    for b in d["bufs"]:
-        if b.flags & 1:
-            res[b.role] = np.full(b.n + 2 * GUARD, SENT32 if b.esize == 4 else SENT8, np.uint32 if b.esize == 4 else np.uint8) if b.flags & 2 else b.image.copy()
-    return res
+    return read_case_file(path, 0x42525053)
 
 
 def plan_line(c):
@@ -163,12 +76,12 @@ def plan_line(c):
 
 def compile_probe(out_dir):
     from ai00_server_amd import build as B
-    return B.compile_sample_probe(os.path.join(str(out_dir), "sample_probe.o"))
+    return B.compile_probe("sample_probe", os.path.join(str(out_dir), "sample_probe.o"))
 
 
 def build_probe():
     from ai00_server_amd import build as B
-    return B.build_sample_probe(verbose=False)
+    return B.build_probe("sample_probe", verbose=False)
 
 
 # ------------------------------------------------------------------------------------------------

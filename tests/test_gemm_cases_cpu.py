@@ -230,7 +230,6 @@ def test_probe_compiles_for_gfx950_and_links_when_the_kernel_objects_are_there(t
     from ai00_server_amd import build as B
     obj = G.compile_probe(tmp_path)
     assert os.path.getsize(obj) > 0
-    parts = [os.path.join(B.CSRC, f"rwkv_kernels.p{k}.o") for k in range(B.KERNEL_PARTS)]
-    if all(os.path.exists(p) for p in parts) and not B.needs_build():
+    if all(os.path.exists(p) for p in B.kernel_objects()) and not B.needs_build():
         exe = G.build_probe()
         assert os.access(exe, os.X_OK)

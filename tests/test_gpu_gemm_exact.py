@@ -12,12 +12,12 @@ pad X must reach no valid output.  Only the transcendental activations are compa
 One probe process per test, each under its own time limit.  A process that ends by a signal, an abort or its time limit is recorded: every
 later test of this module then fails at once and starts nothing on the GPU.  Nothing is retried.  The last test reads the plan lines the
 probe printed and proves that the table reached the paths it exists for, and that the probe planned what the CPU-compiled planner plans."""
-import json
-import subprocess
+import os
 
 import pytest
 
 from tests import gemm_cases as G
+from tests.probe_run import require_alive, run_probe
 
 pytestmark = pytest.mark.gpu
 CASES = G.all_cases()
@@ -30,26 +30,11 @@ def probe():
 
 
 def run_group(probe, tmp_path, group):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
     cases = [c for c in CASES if c.group == group]
     datas = [G.make(c) for c in cases]
-    inp, out = str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")
-    G.write_cases(inp, cases, datas)
-    limit = 30 + len(cases)                                            # seconds: a launch and its copies take milliseconds; the first one loads the code objects
-    try:
-        r = subprocess.run([probe, inp, out], capture_output=True, text=True, timeout=limit)
-    except subprocess.TimeoutExpired as e:
-        _STATE["dead"] = f"{group}: no end after {limit} s; last plan line: {(e.stdout or b'').decode(errors='replace').splitlines()[-1:]}"
-        pytest.fail(_STATE["dead"])
-    lines = r.stdout.splitlines()
-    if r.returncode != 0:                                              # a signal, an abort, or the first failed HIP call (the probe checks every one)
-        at = cases[min(len(lines), len(cases)) - 1].name
-        _STATE["dead"] = f"{group}: the probe ended with status {r.returncode} after {len(lines)} plan lines of {len(cases)} cases (last: {at}, {lines[-1:]}): {r.stderr[-600:]}"
-        pytest.fail(_STATE["dead"])
-    plans = [json.loads(l) for l in lines]
-    assert len(plans) == len(cases)
+    plans, inp, out = run_probe(_STATE, probe, tmp_path, group, cases, lambda path: G.write_cases(path, cases, datas))
     results = G.read_results(out, cases)
+    os.remove(inp), os.remove(out)
     msgs = []
     for c, d, res, plan in zip(cases, datas, results, plans):
         _STATE["plans"][c.name] = plan
@@ -109,8 +94,7 @@ def test_epilogues(probe, tmp_path):
 
 
 def test_the_table_took_the_paths_it_exists_for(tmp_path):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
+    require_alive(_STATE)
     missing = [c.name for c in CASES if c.name not in _STATE["plans"]]
     assert not missing, f"no plan line for {missing[:8]} (run the whole module)"
     plans = [_STATE["plans"][c.name] for c in CASES]

@@ -24,11 +24,11 @@ recorded: every later test of this module then fails at once and starts nothing 
 the lines the probe printed that every instantiation and branch the table exists for was reached."""
 import json
 import os
-import subprocess
 
 import pytest
 
 from tests import mix_cases as M
+from tests.probe_run import require_alive, run_probe
 
 pytestmark = pytest.mark.gpu
 CASES = M.all_cases()
@@ -61,25 +61,9 @@ def record(group, worst):
 
 
 def run_group(probe, tmp_path, group, carriers):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
     cases = [c for c in CASES if c.group == group]
     datas = [M.make(c) for c in cases]
-    inp, out = str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")
-    M.write_cases(inp, cases, datas)
-    limit = 30 + len(cases)                                            # seconds: a launch and its copies take milliseconds; the first one loads the code objects
-    try:
-        r = subprocess.run([probe, inp, out], capture_output=True, text=True, timeout=limit)
-    except subprocess.TimeoutExpired as e:
-        _STATE["dead"] = f"{group}: no end after {limit} s; last line: {(e.stdout or b'').decode(errors='replace').splitlines()[-1:]}"
-        pytest.fail(_STATE["dead"])
-    lines = r.stdout.splitlines()
-    if r.returncode != 0:                                              # a signal, an abort, a refused case, or the first failed HIP call (the probe checks every one)
-        at = cases[min(len(lines), len(cases) - 1)].name
-        _STATE["dead"] = f"{group}: the probe ended with status {r.returncode} after {len(lines)} lines of {len(cases)} cases (at: {at}, {lines[-1:]}): {r.stderr[-600:]}"
-        pytest.fail(_STATE["dead"])
-    plans = [json.loads(l) for l in lines]
-    assert len(plans) == len(cases)
+    plans, inp, out = run_probe(_STATE, probe, tmp_path, group, cases, lambda path: M.write_cases(path, cases, datas))
     results = M.read_results(out, cases, datas)
     os.remove(inp), os.remove(out)
     msgs, before = [], len(_STATE["ratios"])
@@ -119,8 +103,7 @@ def test_commit(probe, tmp_path, carriers):
 
 
 def test_the_table_reached_every_instantiation(carriers):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
+    require_alive(_STATE)
     missing = [c.name for c in CASES if c.name not in _STATE["lines"]]
     assert not missing, f"no line for {missing[:8]} (run the whole module)"
     lines = [_STATE["lines"][c.name] for c in CASES]

@@ -15,13 +15,13 @@ tests/test_row_cases_cpu.py) and copies every buffer back whole.  Asserted, per 
 One probe process per group, each under its own time limit.  A process that ends by a signal, an abort, a HIP error or its time limit is
 recorded: every later test of this module then fails at once and starts nothing on the GPU.  Nothing is retried.  The last test proves from
 the lines the probe printed that every kernel the table exists for was reached."""
-import json
-import subprocess
+import os
 
 import numpy as np
 import pytest
 
 from tests import row_cases as R
+from tests.probe_run import require_alive, run_probe
 
 pytestmark = pytest.mark.gpu
 CASES = R.all_cases()
@@ -34,26 +34,11 @@ def probe():
 
 
 def run_group(probe, tmp_path, group):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
     cases = [c for c in CASES if c.group == group]
     datas = [R.make(c) for c in cases]
-    inp, out = str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")
-    R.write_cases(inp, cases, datas)
-    limit = 30 + len(cases)                                            # seconds: a launch and its copies take milliseconds; the first one loads the code objects
-    try:
-        r = subprocess.run([probe, inp, out], capture_output=True, text=True, timeout=limit)
-    except subprocess.TimeoutExpired as e:
-        _STATE["dead"] = f"{group}: no end after {limit} s; last line: {(e.stdout or b'').decode(errors='replace').splitlines()[-1:]}"
-        pytest.fail(_STATE["dead"])
-    lines = r.stdout.splitlines()
-    if r.returncode != 0:                                              # a signal, an abort, a refused case, or the first failed HIP call (the probe checks every one)
-        at = cases[min(len(lines), len(cases) - 1)].name
-        _STATE["dead"] = f"{group}: the probe ended with status {r.returncode} after {len(lines)} lines of {len(cases)} cases (at: {at}, {lines[-1:]}): {r.stderr[-600:]}"
-        pytest.fail(_STATE["dead"])
-    plans = [json.loads(l) for l in lines]
-    assert len(plans) == len(cases)
+    plans, inp, out = run_probe(_STATE, probe, tmp_path, group, cases, lambda path: R.write_cases(path, cases, datas))
     results = R.read_results(out, cases, datas)
+    os.remove(inp), os.remove(out)
     msgs, before = [], len(_STATE["ratios"])
     for c, d, res, line in zip(cases, datas, results, plans):
         _STATE["lines"][c.name] = line
@@ -100,8 +85,7 @@ def test_state_pack(probe, tmp_path):
 
 
 def test_the_table_reached_every_kernel():
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
+    require_alive(_STATE)
     missing = [c.name for c in CASES if c.name not in _STATE["lines"]]
     assert not missing, f"no line for {missing[:8]} (run the whole module)"
     lines = [_STATE["lines"][c.name] for c in CASES]

@@ -18,11 +18,11 @@ recorded: every later test of this module then fails at once and starts nothing 
 coverage from the lines the probe printed and writes the worst error / bound per group to profiles/r11_sample_probe_ratios.jsonl."""
 import json
 import os
-import subprocess
 
 import pytest
 
 from tests import sample_cases as S
+from tests.probe_run import require_alive, run_probe
 
 pytestmark = pytest.mark.gpu
 CASES = S.all_cases()
@@ -36,25 +36,9 @@ def probe():
 
 
 def run_group(probe, tmp_path, group):
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
     cases = [c for c in CASES if c.group == group]
     datas = [S.make(c) for c in cases]
-    inp, out = str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")
-    S.write_cases(inp, cases, datas)
-    limit = 30 + len(cases)                                            # seconds: a launch and its copies take milliseconds; the first one loads the code objects
-    try:
-        r = subprocess.run([probe, inp, out], capture_output=True, text=True, timeout=limit)
-    except subprocess.TimeoutExpired as e:
-        _STATE["dead"] = f"{group}: no end after {limit} s; last line: {(e.stdout or b'').decode(errors='replace').splitlines()[-1:]}"
-        pytest.fail(_STATE["dead"])
-    lines = r.stdout.splitlines()
-    if r.returncode != 0:                                              # a signal, an abort, a refused case, or the first failed HIP call (the probe checks every one)
-        at = cases[min(len(lines), len(cases) - 1)].name
-        _STATE["dead"] = f"{group}: the probe ended with status {r.returncode} after {len(lines)} lines of {len(cases)} cases (at: {at}, {lines[-1:]}): {r.stderr[-600:]}"
-        pytest.fail(_STATE["dead"])
-    plans = [json.loads(l) for l in lines]
-    assert len(plans) == len(cases)
+    plans, inp, out = run_probe(_STATE, probe, tmp_path, group, cases, lambda path: S.write_cases(path, cases, datas))
     results = S.read_results(out, cases, datas)
     os.remove(inp), os.remove(out)
     msgs, ratios = [], []
@@ -110,8 +94,7 @@ def test_logit_adjust_and_mask(probe, tmp_path):
 
 
 def test_the_table_reached_every_branch():
-    if _STATE["dead"]:
-        pytest.fail(f"not run: an earlier probe process of this module did not end normally ({_STATE['dead']})")
+    require_alive(_STATE)
     missing = [c.name for c in CASES if c.name not in _STATE["lines"]]
     assert not missing, f"no line for {missing[:8]} (run the whole module)"
     assert [_STATE["lines"][c.name] for c in CASES] == [S.plan_line(c) for c in CASES]
