@@ -338,6 +338,9 @@ struct rwkv_engine {
     // scoring (rwkv_infer_score on s_main, rwkv_score_rows on s_soft): one target in and one ln-probability out per logits row; pinned mirrors
     unsigned *d_score_tgt = nullptr, *h_score_tgt = nullptr, *d_soft_tgt = nullptr, *h_soft_tgt = nullptr;
     float *d_score_out = nullptr, *h_score_out = nullptr, *d_soft_score = nullptr, *h_soft_score = nullptr;
+    // top-n lists (rwkv_infer_topn on s_main, rwkv_topn_rows on s_soft): TOPN_MAX ids and ln-probabilities per logits row; pinned mirrors
+    unsigned *d_topn_ids = nullptr, *h_topn_ids = nullptr, *d_soft_topn_ids = nullptr, *h_soft_topn_ids = nullptr;
+    float *d_topn_logp = nullptr, *h_topn_logp = nullptr, *d_soft_topn_logp = nullptr, *h_soft_topn_logp = nullptr;
     Opd opA[6], opM, opY, opK, opO, opL[4];
     long pstride = 0;
     // row meta (device + pinned host)
@@ -407,6 +410,15 @@ struct rwkv_engine {
     int *d_gen_tok = nullptr, *d_gen_runstep = nullptr;
     int *d_gen_held = nullptr;                                   // [max_batch] the token a running slot consumes next (its last emitted one)
     unsigned *d_gen_out = nullptr, *h_gen_out = nullptr;         // [2][GEN_RING_STEPS][max_batch]: tokens, then probabilities
+    // top-n lists of the raw rows (rwkv_gen_set_topn / rwkv_gen_run_topn): everything below is allocated by the first rwkv_gen_set_topn
+    std::vector<int> gen_topn;                                   // per slot: places it lists, 0 = none (host knowledge: selects the kernels of a step)
+    int *d_gen_topn_n = nullptr;                                 // [max_batch] the same, for gen_topn_kernel
+    unsigned *d_gen_top_ids = nullptr, *h_gen_top_ids = nullptr; // [GEN_RING_STEPS][max_batch][TOPN_MAX]
+    float *d_gen_top_logp = nullptr, *h_gen_top_logp = nullptr;  // the same shape
+    float *d_gen_tok_logp = nullptr, *h_gen_tok_logp = nullptr;  // [GEN_RING_STEPS][max_batch]
+    float *d_gen_side_ms = nullptr, *d_gen_side_rows = nullptr;  // [max_batch][2], [max_batch][V]: gen_topn -> gen_post
+    void gen_set_topn(int slot, int n);
+    bool gen_any_topn(const std::vector<int> &slots) const { if (gen_topn.empty()) return false; for (int b : slots) if (gen_topn[(size_t)b]) return true; return false; }
     GraphCacheOf<std::vector<uint64_t>> gen_graphs{64, {}};      // one captured step per set of rows (slot mask + sampler kernels it needs)
     void gen_init();
     void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt);
@@ -419,13 +431,14 @@ struct rwkv_engine {
         gen_ppos[(size_t)slot] = 0;
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows, bool stops, bool dfa) const;
+    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn) const;
     unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa);
+    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
-    void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish);
+    void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish, int n_top = 0,
+                 float *out_tok_logp = nullptr, uint32_t *out_top_ids = nullptr, float *out_top_logp = nullptr);
     Knobs kn;                                                    // experiment switches, frozen at creation (rwkv_kernels.h)
 
     template <class T>
@@ -527,6 +540,8 @@ struct rwkv_engine {
     void infer_sample(const rwkv_slot_input *in, const rwkv_sample_params *sp, uint32_t *out_tokens, float *out_probs,
                       uint8_t *emitted, size_t *n_consumed);
     void infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
+    void infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *out_ids, float *const *out_logp, const uint32_t *const *targets,
+                    float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
     // the input of a step in which each of `slots` feeds one token and asks for its row (`Last`); tokens[i] belongs to slots[i], and steps whose
     // ids come from the device (the feedback buffer, held tokens) pass nullptr: the plan then carries a zero nobody reads
     std::vector<rwkv_slot_input> one_token_each(const std::vector<int> &slots, const uint32_t *tokens) const {
@@ -965,6 +980,10 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     h_score_tgt = hostalloc<unsigned>(chunk); h_score_out = hostalloc<float>(chunk);
     d_soft_tgt = dalloc<unsigned>(soft_rows_cap); d_soft_score = dalloc<float>(soft_rows_cap);
     h_soft_tgt = hostalloc<unsigned>(soft_rows_cap); h_soft_score = hostalloc<float>(soft_rows_cap);
+    d_topn_ids = dalloc<unsigned>((size_t)chunk * TOPN_MAX); d_topn_logp = dalloc<float>((size_t)chunk * TOPN_MAX);
+    h_topn_ids = hostalloc<unsigned>((size_t)chunk * TOPN_MAX); h_topn_logp = hostalloc<float>((size_t)chunk * TOPN_MAX);
+    d_soft_topn_ids = dalloc<unsigned>(soft_rows_cap * TOPN_MAX); d_soft_topn_logp = dalloc<float>(soft_rows_cap * TOPN_MAX);
+    h_soft_topn_ids = hostalloc<unsigned>(soft_rows_cap * TOPN_MAX); h_soft_topn_logp = hostalloc<float>(soft_rows_cap * TOPN_MAX);
     d_adj_row = dalloc<int>(ADJ_CAP); d_adj_tok = dalloc<int>(ADJ_CAP); d_adj_val = dalloc<float>(ADJ_CAP);
     d_allow = dalloc<unsigned char>((size_t)max_batch * V); d_allow_row = dalloc<int>(max_batch);
     h_allow = hostalloc<unsigned char>((size_t)max_batch * V + (size_t)max_batch * 4 + 16);
@@ -1527,6 +1546,75 @@ void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *
         if (targets[b] && pl.slot_out_rows[b]) std::memcpy(out_logp[b], h_score_out + pl.slot_out_begin[b], (size_t)pl.slot_out_rows[b] * 4);
 }
 
+// rwkv_infer_topn: rwkv_infer's step (the caller's options, hence its plan, step shape and captured graph), then topn_rows_kernel over the n_out
+// rows of `logits`: n ids and n ln-probabilities per row come back instead of the row.  Slots with targets are scored as well, by the launch
+// rwkv_infer_score makes, on the same block (the `echo` case: the realised token's ln-probability beside the alternatives, in one pass).
+static_assert(RWKV_TOPN_MAX == TOPN_MAX && RWKV_TOPN_NONE == TOPN_NONE, "rwkv_abi.h and rwkv_kernels.h disagree");
+void rwkv_engine::infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *out_ids, float *const *out_logp, const uint32_t *const *targets,
+                             float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed) {
+    HIP_CHECK(hipSetDevice(device));
+    (void)hipGetLastError();                                   // as in infer(): the poll below must only see THIS call's errors
+    const uint32_t V = (uint32_t)info.num_vocab;
+    bool any_targets = false;
+    for (int b = 0; b < max_batch; ++b) {                      // every refusal comes before anything is launched or disarmed
+        n_rows[b] = 0;
+        n_consumed[b] = 0;
+        if (in[b].n_tokens && !in[b].tokens) throw RwkvError(RWKV_ERR_INVALID, "slot has n_tokens>0 but tokens==NULL");
+        if (in[b].option != RWKV_OPTION_LAST && in[b].option != RWKV_OPTION_FULL && in[b].option != RWKV_OPTION_NONE)
+            throw RwkvError(RWKV_ERR_INVALID, "bad RnnOption");
+        const bool scored = targets && targets[b];
+        if (!out_ids[b]) {
+            if (in[b].n_tokens && in[b].option != RWKV_OPTION_NONE)
+                throw RwkvError(RWKV_ERR_INVALID, "a slot without out_ids must be state-only (RWKV_OPTION_NONE) in rwkv_infer_topn");
+            if (scored) throw RwkvError(RWKV_ERR_INVALID, "targets on slot " + std::to_string(b) + ", which lists nothing");
+            continue;
+        }
+        if (!out_logp[b]) throw RwkvError(RWKV_ERR_INVALID, "listing slot " + std::to_string(b) + " has no out_logp buffer");
+        if (!scored) continue;
+        if (in[b].n_tokens && in[b].option != RWKV_OPTION_FULL)
+            throw RwkvError(RWKV_ERR_INVALID, "targets need RWKV_OPTION_FULL (one row per token) on slot " + std::to_string(b));
+        if (in[b].n_tokens && (!out_tok_logp || !out_tok_logp[b])) throw RwkvError(RWKV_ERR_INVALID, "scored slot " + std::to_string(b) + " has no out_tok_logp buffer");
+        for (size_t i = 0; i < in[b].n_tokens; ++i)
+            if (targets[b][i] >= V && targets[b][i] != RWKV_SCORE_SKIP)
+                throw RwkvError(RWKV_ERR_INVALID, "target " + std::to_string(targets[b][i]) + " of slot " + std::to_string(b) + " is not a token of this vocabulary");
+        any_targets |= in[b].n_tokens > 0;
+    }
+    for (int b = 0; b < max_batch; ++b) if (in[b].n_tokens) gen_disarm_slot(b);
+    StepPlan pl;
+    plan_step(in, pl);
+    if (pl.T == 0) return;
+    if (any_targets) {
+        for (int r = 0; r < pl.n_out; ++r) h_score_tgt[r] = RWKV_SCORE_SKIP;   // rows of slots without targets are not scored
+        for (int b = 0; b < max_batch; ++b)                    // a Full slot emits one row per consumed token: rows and targets line up
+            if (targets[b] && pl.slot_out_rows[b]) std::memcpy(h_score_tgt + pl.slot_out_begin[b], targets[b], (size_t)pl.slot_out_rows[b] * 4);
+    }
+    run_plan(pl);
+    for (int b = 0; b < max_batch; ++b) n_consumed[b] = (size_t)pl.slot_consumed[b];
+    if (pl.n_out == 0) {                                       // no slot reached a row: not waited for, like a row-less rwkv_infer
+        HIP_CHECK(hipPeekAtLastError());
+        return;
+    }
+    const size_t cells = (size_t)pl.n_out * (size_t)n;
+    launch(FAM_SAMPLE, [&] { launch_topn_rows(logits, n, d_topn_ids, d_topn_logp, pl.n_out, (int)V, s_main); });
+    HIP_CHECK(hipMemcpyAsync(h_topn_ids, d_topn_ids, cells * 4, hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipMemcpyAsync(h_topn_logp, d_topn_logp, cells * 4, hipMemcpyDeviceToHost, s_main));
+    if (any_targets) {
+        HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+        launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+        HIP_CHECK(hipMemcpyAsync(h_score_out, d_score_out, (size_t)pl.n_out * 4, hipMemcpyDeviceToHost, s_main));
+    }
+    HIP_CHECK(hipPeekAtLastError());
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    for (int b = 0; b < max_batch; ++b) {
+        const size_t rows = (size_t)pl.slot_out_rows[b], r0 = (size_t)pl.slot_out_begin[b];
+        if (!rows) continue;
+        n_rows[b] = rows;
+        std::memcpy(out_ids[b], h_topn_ids + r0 * n, rows * n * 4);
+        std::memcpy(out_logp[b], h_topn_logp + r0 * n, rows * n * 4);
+        if (targets && targets[b]) std::memcpy(out_tok_logp[b], h_score_out + r0, rows * 4);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // device-resident sampled generation (rwkv_gen_arm / _run, include/rwkv_abi.h): `process` (run.rs:788-1020) with the samplers on the device
 // ------------------------------------------------------------------------------------------------
@@ -1616,6 +1704,10 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     gen_host[b] = g;
     gen_has_stops[b] = 0;
     gen_has_dfa[b] = 0;
+    if (!gen_topn.empty() && gen_topn[b]) {                        // re-arming: the slot lists nothing until rwkv_gen_set_topn says so again
+        gen_topn[b] = 0;
+        HIP_CHECK(hipMemset(d_gen_topn_n + b, 0, sizeof(int)));
+    }
     gen_drop_dfa_buf(slot);                                        // behind the synchronize: no step is in flight
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
@@ -1748,8 +1840,35 @@ size_t rwkv_engine::gen_stop_tail(int slot, uint8_t *out, size_t cap) {
     return len;
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa) const {
+// The places an armed, unfinished slot lists per emitted token (rwkv_gen_set_topn).  Between runs: the stream is idle.
+void rwkv_engine::gen_set_topn(int slot, int n) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot, B = (size_t)max_batch, V = (size_t)info.num_vocab;
+    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "top-n lists need an armed, unfinished slot");
+    if (n < 0 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 0.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
+    if (gen_topn.empty()) {
+        if (n == 0) return;
+        const size_t ring = (size_t)GEN_RING_STEPS * B;
+        d_gen_topn_n = dalloc<int>(B);
+        HIP_CHECK(hipMemset(d_gen_topn_n, 0, B * sizeof(int)));
+        d_gen_top_ids = dalloc<unsigned>(ring * TOPN_MAX); h_gen_top_ids = hostalloc<unsigned>(ring * TOPN_MAX);
+        d_gen_top_logp = dalloc<float>(ring * TOPN_MAX); h_gen_top_logp = hostalloc<float>(ring * TOPN_MAX);
+        d_gen_tok_logp = dalloc<float>(ring); h_gen_tok_logp = hostalloc<float>(ring);
+        d_gen_side_ms = dalloc<float>(B * 2);
+        d_gen_side_rows = dalloc<float>(B * V);
+        gen_topn.assign(B, 0);                                     // last: marks the block as complete
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    HIP_CHECK(hipMemcpy(d_gen_topn_n + b, &n, sizeof(int), hipMemcpyHostToDevice));
+    gen_topn[b] = n;
+}
+
+GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn) const {
     GenArgs a{};
+    if (topn) {
+        a.topn_n = d_gen_topn_n; a.top_ids = d_gen_top_ids; a.top_logp = d_gen_top_logp; a.tok_logp = d_gen_tok_logp;
+        a.side_ms = d_gen_side_ms; a.side_rows = d_gen_side_rows;
+    }
     if (stops) a.stops = d_gen_stop;
     if (dfa) { a.dfa = d_gen_dfa; a.tok_end = d_tok_end; }
     if (stops || dfa) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
@@ -1764,6 +1883,7 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa) const {
 
 // the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
 void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
+    if (a.topn_n) launch(FAM_SAMPLE, [&] { launch_gen_topn(a, s_main); });   // the raw rows: gen_pre edits the block in place
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
     if (a.dfa) launch(FAM_SAMPLE, [&] { launch_gen_mask(a, s_main); });   // `transform` (run.rs:676-679) of the constrained rows
     launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, d_gen_tok, d_gen_prob, s_main); });
@@ -1772,9 +1892,9 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T, stops, dfa), needs);
+    gen_sample(gen_args(pl.T, stops, dfa, topn), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
@@ -1783,6 +1903,7 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     const unsigned needs = gen_needs(rows);
     const bool stops = gen_any_stops(rows);                        // a slot of this row set has stop strings: gen_post_kernel<., true>
     const bool dfa = gen_any_dfa(rows);                            // a slot of this row set has a constraint: gen_mask_kernel joins the step
+    const bool topn = gen_any_topn(rows);                          // a slot of this row set lists: gen_topn_kernel joins the step
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
@@ -1791,13 +1912,13 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0);
+    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -1823,7 +1944,7 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     step_max_rows = pl.max_rows();
     run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (pl.n_out > 0) {
-        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn));
+        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn));
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         gen_sample(a, gen_needs(drawn));
@@ -1835,11 +1956,21 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     }
 }
 
-void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish) {
+// n_top > 0 (rwkv_gen_run_topn): the three top-n outputs are filled as well, n_top places per step and slot.
+void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish, int n_top, float *out_tok_logp,
+                          uint32_t *out_top_ids, float *out_top_logp) {
     HIP_CHECK(hipSetDevice(device));
     (void)hipGetLastError();                                       // the poll behind the enqueue must only see this call's errors
     const int B = max_batch;
     const float nan = std::nanf("");
+    if (n_top) {                                                   // refused before the first step, and before anything is written
+        for (int b = 0; b < B && !gen_topn.empty(); ++b)
+            if (gen_armed[(size_t)b] && !gen_host[(size_t)b].finish && gen_topn[(size_t)b] > n_top)
+                throw RwkvError(RWKV_ERR_INVALID, "slot " + std::to_string(b) + " lists " + std::to_string(gen_topn[(size_t)b]) + " places, n_top is " + std::to_string(n_top));
+        std::fill(out_tok_logp, out_tok_logp + (size_t)n_steps * B, nan);
+        std::fill(out_top_ids, out_top_ids + (size_t)n_steps * B * n_top, RWKV_TOPN_NONE);
+        std::fill(out_top_logp, out_top_logp + (size_t)n_steps * B * n_top, nan);
+    }
     std::fill(out_tokens, out_tokens + (size_t)n_steps * B, 0xFFFFFFFFu);
     if (out_probs) std::fill(out_probs, out_probs + (size_t)n_steps * B, nan);
     if (n_emitted) std::fill(n_emitted, n_emitted + B, 0);
@@ -1863,6 +1994,12 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         HIP_CHECK(hipMemsetAsync(d_gen_runstep, 0xFF, 4, s_main));                          // -1: the first kernel of a step counts up
         HIP_CHECK(hipMemsetAsync(d_gen_out, 0xFF, (size_t)nb * B * 4, s_main));             // 0xFFFFFFFF: nothing emitted
         HIP_CHECK(hipMemsetAsync(d_gen_out + ring, 0xFF, (size_t)nb * B * 4, s_main));      // ... and the same bits are a NaN
+        const bool lists = gen_any_topn(live);                     // the top-n planes of the ring: RWKV_TOPN_NONE / NaN until a slot lists
+        if (lists) {
+            HIP_CHECK(hipMemsetAsync(d_gen_top_ids, 0xFF, (size_t)nb * B * TOPN_MAX * 4, s_main));
+            HIP_CHECK(hipMemsetAsync(d_gen_top_logp, 0xFF, (size_t)nb * B * TOPN_MAX * 4, s_main));
+            HIP_CHECK(hipMemsetAsync(d_gen_tok_logp, 0xFF, (size_t)nb * B * 4, s_main));
+        }
         int k = 0;
         while (k < nb) {
             std::vector<int> dec, pro;                             // ascending slot order
@@ -1887,6 +2024,11 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         if (k > 0) {
             HIP_CHECK(hipMemcpyAsync(h_gen_out, d_gen_out, (size_t)k * B * 4, hipMemcpyDeviceToHost, s_main));
             HIP_CHECK(hipMemcpyAsync(h_gen_out + ring, d_gen_out + ring, (size_t)k * B * 4, hipMemcpyDeviceToHost, s_main));
+            if (lists && n_top) {
+                HIP_CHECK(hipMemcpyAsync(h_gen_top_ids, d_gen_top_ids, (size_t)k * B * TOPN_MAX * 4, hipMemcpyDeviceToHost, s_main));
+                HIP_CHECK(hipMemcpyAsync(h_gen_top_logp, d_gen_top_logp, (size_t)k * B * TOPN_MAX * 4, hipMemcpyDeviceToHost, s_main));
+                HIP_CHECK(hipMemcpyAsync(h_gen_tok_logp, d_gen_tok_logp, (size_t)k * B * 4, hipMemcpyDeviceToHost, s_main));
+            }
         }
         std::vector<GenSlot> back((size_t)B);
         HIP_CHECK(hipMemcpyAsync(back.data(), d_gen, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, s_main));
@@ -1894,6 +2036,19 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         if (k == 0) break;
         std::memcpy(out_tokens + (size_t)done * B, h_gen_out, (size_t)k * B * 4);
         if (out_probs) std::memcpy(out_probs + (size_t)done * B, h_gen_out + ring, (size_t)k * B * 4);
+        // a step in which a slot emitted: its own n places, (RWKV_TOPN_NONE, -inf) up to the caller's stride; the rest keeps (NONE, NaN)
+        for (int s = 0; n_top && s < k; ++s)
+            for (int b : live) {
+                const size_t cell = (size_t)s * B + (size_t)b, to = ((size_t)(done + s) * B + (size_t)b) * (size_t)n_top;
+                if (h_gen_out[cell] == 0xFFFFFFFFu) continue;
+                const int n = gen_topn.empty() ? 0 : gen_topn[(size_t)b];
+                if (n) {
+                    out_tok_logp[(size_t)(done + s) * B + (size_t)b] = h_gen_tok_logp[cell];
+                    std::memcpy(out_top_ids + to, h_gen_top_ids + cell * TOPN_MAX, (size_t)n * 4);
+                    std::memcpy(out_top_logp + to, h_gen_top_logp + cell * TOPN_MAX, (size_t)n * 4);
+                }
+                std::fill(out_top_logp + to + n, out_top_logp + to + n_top, -INFINITY);
+            }
         bool restored = false;
         for (int b : live) {
             const size_t sb = (size_t)b;
@@ -2060,6 +2215,16 @@ rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const ui
         if (!e || !in || !targets || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
         use_knobs(e->kn);
         e->infer_score(in, targets, out_logp, n_consumed);
+    });
+}
+
+rwkv_status rwkv_infer_topn(rwkv_engine *e, const rwkv_slot_input *in, int32_t n, uint32_t *const *out_ids, float *const *out_logp,
+                            const uint32_t *const *targets, float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed) {
+    return guard([&] {
+        if (!e || !in || !out_ids || !out_logp || !n_rows || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        if (n < 1 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 1.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
+        use_knobs(e->kn);
+        e->infer_topn(in, n, out_ids, out_logp, targets, out_tok_logp, n_rows, n_consumed);
     });
 }
 
@@ -2316,6 +2481,33 @@ rwkv_status rwkv_score_rows(rwkv_engine *e, const float *const *in, const uint32
     });
 }
 
+// the n most likely tokens of host rows with their ln-probabilities: rwkv_score_rows's staging, stream and thread rule; n ids and n floats per row
+// come back instead of the row
+rwkv_status rwkv_topn_rows(rwkv_engine *e, const float *const *in, int32_t n, uint32_t *out_ids, float *out_logp, size_t n_rows) {
+    return guard([&] {
+        if (!e || (n_rows && (!in || !out_ids || !out_logp))) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        if (n < 1 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 1.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
+        if (!n_rows) return;
+        const size_t V = (size_t)e->info.num_vocab;
+        for (size_t r = 0; r < n_rows; ++r)                    // before anything is written or launched
+            if (!in[r]) throw RwkvError(RWKV_ERR_INVALID, "null row");
+        HIP_CHECK(hipSetDevice(e->device));
+        std::lock_guard<std::mutex> lk(g_soft_mu);
+        for (size_t r0 = 0; r0 < n_rows; r0 += e->soft_rows_cap) {
+            const size_t rows = std::min(e->soft_rows_cap, n_rows - r0), cells = rows * (size_t)n;
+            for (size_t r = 0; r < rows; ++r) std::memcpy(e->soft_host + r * V, in[r0 + r], V * 4);
+            HIP_CHECK(hipMemcpyAsync(e->soft_in, e->soft_host, rows * V * 4, hipMemcpyHostToDevice, e->s_soft));
+            launch_topn_rows(e->soft_in, n, e->d_soft_topn_ids, e->d_soft_topn_logp, (int)rows, (int)V, e->s_soft);
+            HIP_CHECK(hipMemcpyAsync(e->h_soft_topn_ids, e->d_soft_topn_ids, cells * 4, hipMemcpyDeviceToHost, e->s_soft));
+            HIP_CHECK(hipMemcpyAsync(e->h_soft_topn_logp, e->d_soft_topn_logp, cells * 4, hipMemcpyDeviceToHost, e->s_soft));
+            HIP_CHECK(hipPeekAtLastError());
+            HIP_CHECK(hipStreamSynchronize(e->s_soft));
+            std::memcpy(out_ids + r0 * n, e->h_soft_topn_ids, cells * 4);
+            std::memcpy(out_logp + r0 * n, e->h_soft_topn_logp, cells * 4);
+        }
+    });
+}
+
 // ---- device-resident greedy decode ----------------------------------------------------------------
 rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *first_tokens, int32_t n_steps,
                                uint32_t *out_tokens, float *elapsed_ms) {
@@ -2400,6 +2592,21 @@ rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, 
         if (!e || !out_tokens || n_steps <= 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
         use_knobs(e->kn);
         e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish);
+    });
+}
+rwkv_status rwkv_gen_set_topn(rwkv_engine *e, int32_t slot, int32_t n) {
+    return guard([&] {
+        check_slot(e, slot);
+        e->gen_set_topn(slot, n);
+    });
+}
+rwkv_status rwkv_gen_run_topn(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish,
+                              int32_t n_top, float *out_tok_logp, uint32_t *out_top_ids, float *out_top_logp) {
+    return guard([&] {
+        if (!e || !out_tokens || n_steps <= 0 || !out_tok_logp || !out_top_ids || !out_top_logp) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
+        if (n_top < 1 || n_top > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n_top must be 1.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n_top));
+        use_knobs(e->kn);
+        e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish, n_top, out_tok_logp, out_top_ids, out_top_logp);
     });
 }
 rwkv_status rwkv_gen_set_token_bytes(rwkv_engine *e, const uint8_t *bytes, const int32_t *lens, size_t n_tokens) {

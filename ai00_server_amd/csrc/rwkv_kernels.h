@@ -275,6 +275,13 @@ void launch_state_pack(const StatePackArgs &a, hipStream_t s);
 void launch_softmax(const float *in, float *out, int n_rows, int V, hipStream_t s);
 // out[r] = ln softmax(logits[r])[targets[r]], one pass over each row (n_rows > 0, V % 16 == 0); targets[r] >= V: not scored, out[r] = NaN
 void launch_score_rows(const float *logits, const unsigned *targets, float *out, int n_rows, int V, hipStream_t s);
+// out_ids / out_logp [n_rows][n]: the n (1..TOPN_MAX) largest logits of every row, descending, ties to the lower id, with ln softmax of each as
+// launch_score_rows gives it, bit for bit; fewer than n entries above -inf: (TOPN_NONE, -inf) in the places left; +inf or NaN in the row:
+// (TOPN_NONE, NaN) in all.  side_ms [n_rows][2] = (m, ln S) and side_rows [n_rows][V] = the rows as read are written when non-null.
+constexpr int TOPN_MAX = 32;
+constexpr unsigned TOPN_NONE = 0xFFFFFFFFu;
+void launch_topn_rows(const float *logits, int n, unsigned *out_ids, float *out_logp, int n_rows, int V, hipStream_t s, float *side_ms = nullptr,
+                      float *side_rows = nullptr);
 // on-device sampling front-end (f-1): V <= 65536.  nucleus_kernel takes top_k <= 256 and Mirostat with fewer than 8192 candidates,
 // sample_wide_kernel the rows that carry SAMPLE_WIDE in `kind` (any top_k, any max_surprise); each row is written by exactly one of them
 constexpr int SAMPLE_WIDE = 4;
@@ -334,6 +341,11 @@ struct GenArgs {
     // gen_freeze: the state of a slot that finished in this step -> its shadow
     float *sxa, *sxf, *wkv; long sx_slot_stride, wkv_slot_stride;
     float *const *shadow;           // [max_batch] sxa | sxf | wkv of the slot, or null
+    // top-n lists (rwkv_gen_set_topn); topn_n == null: no slot of this step lists, gen_topn is not launched and gen_post skips it
+    const int *topn_n;              // [max_batch] places each slot lists, 0 = none
+    unsigned *top_ids; float *top_logp;   // [steps][max_batch][TOPN_MAX] output ring of this run
+    float *tok_logp;                // [steps][max_batch] raw ln-probability of the emitted token
+    float *side_ms, *side_rows;     // [max_batch][2], [max_batch][V]: (m, ln S) and the raw row of every logits row that lists (gen_topn -> gen_post)
 };
 RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
@@ -343,6 +355,7 @@ RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, 
     return (float)(z >> 40) * 5.9604644775390625e-8f;       // 24 bits * 2^-24: exact
 }
 void launch_gen_pre(const GenArgs &a, hipStream_t s);
+void launch_gen_topn(const GenArgs &a, hipStream_t s);                                                               // a.topn_n != null
 void launch_gen_mask(const GenArgs &a, hipStream_t s);                                                               // a.dfa != null
 void launch_gen_post(const GenArgs &a, hipStream_t s);
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);

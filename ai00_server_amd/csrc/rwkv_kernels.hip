@@ -3178,6 +3178,45 @@ __device__ __forceinline__ ScorePair score_merge(ScorePair a, ScorePair b) {
     const float t = ml == -INFINITY ? 0.f : expf(ml - mh);
     return ScorePair{mh, a.m == b.m ? a.s + b.s : sh + sl * t};
 }
+// One pass over a row in score_rows_kernel's thread mapping: lane t of the block reads 16 bytes at float4 index base + u * SCORE_THREADS + t and
+// pushes component c into its pair p[c]; `bad` collects +inf / NaN.  `each(i, e)` sees every float4 the lane reads (index i < n4, its four values).
+// score_rows_kernel and topn_rows_kernel both run THIS loop and score_block_merge below: that is why their (m, S) agree bit for bit.
+template <class F>
+__device__ __forceinline__ void score_row_scan(const float4 *x4, int n4, ScorePair (&p)[4], bool &bad, F &&each) {
+    for (int base = 0; base < n4; base += 4 * SCORE_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                          // four 16-byte loads in flight; past the row's end: -inf, which adds nothing
+            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
+            v[u] = i < n4 ? x4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
+            const float e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            if (i < n4) each(i, e);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                bad |= !(e[c] < INFINITY);
+                score_push(p[c], e[c]);
+            }
+        }
+    }
+}
+// the lane's four pairs, then the xor butterfly over the wave, then the four waves through LDS: the row's pair, valid in thread 0 (s = NaN when poisoned)
+__device__ __forceinline__ ScorePair score_block_merge(const ScorePair (&p)[4], bool bad, ScorePair *red) {
+    ScorePair a = score_merge(score_merge(p[0], p[1]), score_merge(p[2], p[3]));
+    if (bad) a.s = __builtin_nanf("");                         // rides the merges: NaN * t and NaN + s stay NaN
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const ScorePair o{__shfl_xor(a.m, k, 64), __shfl_xor(a.s, k, 64)};
+        a = score_merge(a, o);
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) a = score_merge(score_merge(red[0], red[1]), score_merge(red[2], red[3]));
+    return a;
+}
 __global__ __launch_bounds__(SCORE_THREADS) void score_rows_kernel(const float *logits, const unsigned *targets, float *out, int V) {
     __shared__ ScorePair red[SCORE_THREADS / 64];
     __shared__ float red_xt[SCORE_THREADS / 64];
@@ -3192,37 +3231,14 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_rows_kernel(const float *
     ScorePair p[4] = {{-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}};
     float xt = -INFINITY;                                      // the target's logit: kept by the lane that reads it (no second read of the row)
     bool bad = false;                                          // +inf or NaN seen
-    for (int base = 0; base < n4; base += 4 * SCORE_THREADS) {
-        float4 v[4];
+    score_row_scan(x4, n4, p, bad, [&](int i, const float (&e)[4]) {
+        if (i == t4) xt = tc == 0 ? e[0] : tc == 1 ? e[1] : tc == 2 ? e[2] : e[3];
+    });
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {                          // four 16-byte loads in flight; past the row's end: -inf, which adds nothing
-            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
-            v[u] = i < n4 ? x4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = base + u * SCORE_THREADS + (int)threadIdx.x;
-            const float e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            if (i == t4) xt = tc == 0 ? e[0] : tc == 1 ? e[1] : tc == 2 ? e[2] : e[3];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                bad |= !(e[c] < INFINITY);
-                score_push(p[c], e[c]);
-            }
-        }
-    }
-    ScorePair a = score_merge(score_merge(p[0], p[1]), score_merge(p[2], p[3]));
-    if (bad) a.s = __builtin_nanf("");                         // rides the merges: NaN * t and NaN + s stay NaN
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) {
-        const ScorePair o{__shfl_xor(a.m, k, 64), __shfl_xor(a.s, k, 64)};
-        a = score_merge(a, o);
-        xt = fmaxf(xt, __shfl_xor(xt, k, 64));                 // one lane of the block holds the value, all others -inf
-    }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red_xt[threadIdx.x >> 6] = xt; }
-    __syncthreads();
+    for (int k = 32; k >= 1; k >>= 1) xt = fmaxf(xt, __shfl_xor(xt, k, 64));   // one lane of the block holds the value, all others -inf
+    if ((threadIdx.x & 63) == 0) red_xt[threadIdx.x >> 6] = xt;
+    ScorePair a = score_block_merge(p, bad, red);              // its barrier covers red_xt too
     if (threadIdx.x == 0) {
-        a = score_merge(score_merge(red[0], red[1]), score_merge(red[2], red[3]));
         xt = fmaxf(fmaxf(red_xt[0], red_xt[1]), fmaxf(red_xt[2], red_xt[3]));
         // a masked target is -inf whatever the rest of the row holds (a row of nothing but -inf included), unless the row is poisoned
         out[row] = a.s != a.s ? a.s : xt == -INFINITY ? -INFINITY : (xt - a.m) - logf(a.s);
@@ -3230,6 +3246,145 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_rows_kernel(const float *
 }
 void launch_score_rows(const float *logits, const unsigned *targets, float *out, int n_rows, int V, hipStream_t s) {
     hipLaunchKernelGGL(score_rows_kernel, dim3(n_rows), dim3(SCORE_THREADS), 0, s, logits, targets, out, V);
+}
+
+// =====================================================================================
+// topn_rows: the n most likely tokens of every row with their ln-probabilities (the `top_logprobs` of a completion) — n ids and n floats per row
+// instead of the row.  Order: the logit descending as a real number (-0 == +0), ties to the lower id; entries at -inf are no candidates; a row
+// with fewer than n candidates is padded with (TOPN_NONE, -inf); a row holding +inf or NaN gives (TOPN_NONE, NaN) throughout.
+// One 256-thread block per row.  An entry is the 64-bit composite (key << 32) | ~id, key an order-preserving map of the logit: composites of
+// live entries are distinct, so "the n largest composites" IS the definition above and no tie needs a rule of its own.
+//   pass 1  score_rows_kernel's scan and merge -> (m, S), bit for bit; each lane also keeps its largest composite (and copies the row out when
+//           the side outputs are asked for);
+//   bound   the n-th largest of the 256 lane maxima is a lower bound of the n-th largest composite (n entries reach it);
+//   pass 2  the row again (from L2): every composite >= the bound goes to LDS — ~n / (1 - n / 512) entries on a row without structure, 125 on
+//           an all-equal row; more than TOPN_CAND only where a few lanes own most of the large entries.  Then, and only then:
+//   search  the n-th largest composite exactly, two bits per pass over the row (counts only, no atomics), and pass 2 again with it;
+//   rank    a candidate's place is the number of candidates above it; the first n are written, (x - m) - ln S from the logit re-read by id,
+//           which is score_rows_kernel's expression on score_rows_kernel's (m, S).
+// The slot a candidate lands in varies from run to run, the SET and hence every output does not.
+// =====================================================================================
+constexpr int TOPN_CAND = 1024;                                   // candidate slots in LDS (8 KiB); TOPN_MAX, TOPN_NONE: rwkv_kernels.h
+typedef unsigned long long u64;
+// (key << 32) | ~id; 0 for an entry that is no candidate (-inf).  Larger float <-> larger key; -0 takes +0's key.
+__device__ __forceinline__ u64 topn_comp(float x, int id) {
+    if (x == -INFINITY) return 0ull;
+    unsigned u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    const unsigned key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // a finite negative float maps to >= 0x00800000: a live key is never 0
+    return ((u64)key << 32) | (u64)(0xFFFFFFFFu - (unsigned)id);
+}
+// f(composite) over the whole row, in pass 1's thread mapping
+template <class F>
+__device__ __forceinline__ void topn_for_each(const float4 *x4, int n4, F &&f) {
+    for (int i = (int)threadIdx.x; i < n4; i += SCORE_THREADS) {
+        const float4 v = x4[i];
+        f(topn_comp(v.x, 4 * i)); f(topn_comp(v.y, 4 * i + 1)); f(topn_comp(v.z, 4 * i + 2)); f(topn_comp(v.w, 4 * i + 3));
+    }
+}
+// cand[0..min(*counter, TOPN_CAND)) := the composites >= bound (in arbitrary slots); returns how many there are.  Two barriers.
+__device__ __forceinline__ int topn_gather(const float4 *x4, int n4, u64 bound, u64 *cand, unsigned *counter) {
+    if (threadIdx.x == 0) *counter = 0u;
+    __syncthreads();
+    topn_for_each(x4, n4, [&](u64 c) {
+        if (c >= bound) {
+            const unsigned slot = atomicAdd(counter, 1u);
+            if (slot < (unsigned)TOPN_CAND) cand[slot] = c;
+        }
+    });
+    __syncthreads();
+    return (int)*counter;
+}
+// the n-th largest composite of a row that holds at least n live entries: the largest thr with #(composite >= thr) >= n.
+// `cnt` is [2][4 waves][3], alternating so that a step needs one barrier.
+__device__ __forceinline__ u64 topn_nth_comp(const float4 *x4, int n4, int V, int n, int *cnt) {
+    int idbits = 2;
+    while (idbits < 32 && (1u << idbits) < (unsigned)V) idbits += 2;
+    u64 thr = 0ull;
+    int step = 0;
+#pragma unroll 1
+    for (int bit = 62; bit >= 0; bit -= 2, ++step) {
+        if (bit == 30 && idbits < 32) {                            // ~id of an id < V has its bits from idbits up all set: nothing to search there
+            thr |= (u64)(0xFFFFFFFFu << idbits);
+            bit = idbits - 2;
+        }
+        const u64 t1 = thr | (1ull << bit), t2 = thr | (2ull << bit), t3 = thr | (3ull << bit);
+        int c1 = 0, c2 = 0, c3 = 0;
+        topn_for_each(x4, n4, [&](u64 c) { c1 += c >= t1; c2 += c >= t2; c3 += c >= t3; });
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) { c1 += __shfl_xor(c1, k, 64); c2 += __shfl_xor(c2, k, 64); c3 += __shfl_xor(c3, k, 64); }
+        int *cb = cnt + (step & 1) * 12;
+        if ((threadIdx.x & 63) == 0) { cb[(threadIdx.x >> 6) * 3 + 0] = c1; cb[(threadIdx.x >> 6) * 3 + 1] = c2; cb[(threadIdx.x >> 6) * 3 + 2] = c3; }
+        __syncthreads();
+        c1 = cb[0] + cb[3] + cb[6] + cb[9]; c2 = cb[1] + cb[4] + cb[7] + cb[10]; c3 = cb[2] + cb[5] + cb[8] + cb[11];
+        thr = c3 >= n ? t3 : (c2 >= n ? t2 : (c1 >= n ? t1 : thr));
+    }
+    return thr;
+}
+// The list of the row x[0..V) into ids / lp [n], by the whole 256-thread block; ms (the row's (m, ln S)) and copy (the row as read) are written
+// when non-null.  topn_rows_kernel runs it on every row of a launch, gen_topn_kernel on the rows of a generation step that list.
+__device__ __forceinline__ void topn_row(const float *x, int n, unsigned *ids, float *lp, float *ms, float *copy, int V) {
+    __shared__ ScorePair red[SCORE_THREADS / 64];
+    __shared__ u64 cand[TOPN_CAND];
+    __shared__ u64 lane_max[SCORE_THREADS];
+    __shared__ u64 bound_sh;
+    __shared__ float ms_sh[2];
+    __shared__ int cnt[2 * 4 * 3];
+    __shared__ unsigned counter;
+    const int tid = threadIdx.x;
+    const float4 *x4 = (const float4 *)x;                          // V % 16 == 0: every row starts 64-byte aligned
+    float4 *copy4 = (float4 *)copy;
+    const int n4 = V >> 2;
+    ScorePair p[4] = {{-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}, {-INFINITY, 0.f}};
+    bool bad = false;
+    u64 best = 0ull;
+    score_row_scan(x4, n4, p, bad, [&](int i, const float (&e)[4]) {
+        if (copy4) copy4[i] = make_float4(e[0], e[1], e[2], e[3]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const u64 k = topn_comp(e[c], 4 * i + c); best = k > best ? k : best; }
+    });
+    lane_max[tid] = best;
+    const ScorePair a = score_block_merge(p, bad, red);            // its barrier covers lane_max too
+    if (tid == 0) { ms_sh[0] = a.m; ms_sh[1] = logf(a.s); }
+    __syncthreads();
+    const float m = ms_sh[0], lns = ms_sh[1];
+    if (tid == 0 && ms) { ms[0] = m; ms[1] = lns; }
+    if (lns != lns) {                                              // poisoned (block-uniform): nothing is listed
+        if (tid < n) { ids[tid] = TOPN_NONE; lp[tid] = lns; }
+        return;
+    }
+    // the n-th largest lane maximum; fewer than n live lanes: every live entry is a candidate
+    int above = 0;
+    for (int j = 0; j < SCORE_THREADS; ++j) { const u64 o = lane_max[j]; above += (o > best) || (o == best && j < tid); }
+    if (above == n - 1) bound_sh = best ? best : (1ull << 32);
+    __syncthreads();
+    int total = topn_gather(x4, n4, bound_sh, cand, &counter);
+    if (total > TOPN_CAND) {                                       // block-uniform
+        const u64 nth = topn_nth_comp(x4, n4, V, n, cnt);
+        total = topn_gather(x4, n4, nth, cand, &counter);          // exactly n
+    }
+    for (int c = tid; c < total; c += SCORE_THREADS) {
+        const u64 mine = cand[c];
+        int place = 0;
+        for (int j = 0; j < total; ++j) place += cand[j] > mine;
+        if (place < n) {
+            const unsigned id = 0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull);
+            ids[place] = id;
+            lp[place] = (x[id] - m) - lns;
+        }
+    }
+    if (tid < n && tid >= total) { ids[tid] = TOPN_NONE; lp[tid] = -INFINITY; }
+}
+// side_ms (n_rows x (m, ln S)) and side_rows (n_rows x V) are written when non-null
+__global__ __launch_bounds__(SCORE_THREADS) void topn_rows_kernel(const float *logits, int n, unsigned *out_ids, float *out_logp, float *side_ms,
+                                                                   float *side_rows, int V) {
+    const long row = blockIdx.x;
+    topn_row(logits + row * V, n, out_ids + row * n, out_logp + row * n, side_ms ? side_ms + 2 * row : nullptr,
+             side_rows ? side_rows + row * V : nullptr, V);
+}
+void launch_topn_rows(const float *logits, int n, unsigned *out_ids, float *out_logp, int n_rows, int V, hipStream_t s, float *side_ms,
+                      float *side_rows) {
+    hipLaunchKernelGGL(topn_rows_kernel, dim3(n_rows), dim3(SCORE_THREADS), 0, s, logits, n, out_ids, out_logp, side_ms, side_rows, V);
 }
 
 constexpr int ARGMAX_SEG = 32;                                  // segments per row in stage 1
@@ -3836,6 +3991,20 @@ __global__ __launch_bounds__(256) void gen_pre_kernel(GenArgs a) {
         *(float4 *)(x + i) = v;
     }
 }
+// The top-n lists of the slots that ask for them (rwkv_gen_set_topn), of the RAW row: launched in front of gen_pre, which edits the block in
+// place.  The list goes to the step's place in the output ring, the row and its (m, ln S) to the side buffers, from which gen_emit takes the
+// drawn token's ln-probability.  A decode-only step is counted by gen_pre, behind this launch; a mixed one by gen_tokens_kernel, in front.
+// Reads the logits block and the slots, writes only the ring plane and the side buffers: no token, probability or state depends on it.
+template <bool MIXED>
+__global__ __launch_bounds__(SCORE_THREADS) void gen_topn_kernel(GenArgs a) {
+    const int row = blockIdx.x;
+    const int slot = gen_slot_of<MIXED>(a, row);
+    const int n = a.topn_n[slot];
+    if (n <= 0 || n > TOPN_MAX || a.slots[slot].finish) return;   // block-uniform; a finished rider lists nothing
+    const int k = *a.run_step + (MIXED ? 0 : 1);
+    const long at = ((long)k * a.max_batch + slot) * TOPN_MAX;
+    topn_row(a.logits + (long)row * a.V, n, a.top_ids + at, a.top_logp + at, a.side_ms + 2 * row, a.side_rows + (long)row * a.V, a.V);
+}
 // One thread per token id: 65,536 independent short walks per row (a token of the World vocabulary has 1 - 128 bytes, 6 on average), each a
 // chain of dependent 2-byte loads from the slot's table in device memory (at most 2 MiB; the handful of rows a walk touches stay in L2).
 // A row without a constraint and a finished rider return at once.  Ids at and above n_tok have no bytes and are masked.
@@ -3888,6 +4057,11 @@ __device__ __forceinline__ bool gen_emit(const GenArgs &a, GenSlot &g, int row, 
     a.out_tok[(long)k * a.max_batch + slot] = (unsigned)tok;
     a.out_prob[(long)k * a.max_batch + slot] = prob;
     if (MIXED) a.held[slot] = tok; else a.feedback[row] = tok;
+    if (a.topn_n && a.topn_n[slot] > 0) {                          // the RAW ln-probability: gen_topn_kernel kept the row and its (m, ln S) before gen_pre
+        const float m = a.side_ms[2 * row], lns = a.side_ms[2 * row + 1];
+        const float xt = (unsigned)tok < (unsigned)a.V ? a.side_rows[(long)row * a.V + tok] : -INFINITY;
+        a.tok_logp[(long)k * a.max_batch + slot] = lns != lns ? lns : xt == -INFINITY ? -INFINITY : (xt - m) - lns;   // score_rows_kernel's expression
+    }
     g.draws += 1;
     g.emitted += 1;
     if (g.kind == 2) g.tau = gen_mirostat(g.tau, prob, g.miro_target, g.miro_rate);   // `prob` is the token surprise
@@ -4003,6 +4177,10 @@ __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
 void launch_gen_pre(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_pre_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_pre_kernel<false>, dim3(16, a.n_rows), dim3(256), 0, s, a);
+}
+void launch_gen_topn(const GenArgs &a, hipStream_t s) {
+    if (a.out_rows) hipLaunchKernelGGL(gen_topn_kernel<true>, dim3(a.n_rows), dim3(SCORE_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(gen_topn_kernel<false>, dim3(a.n_rows), dim3(SCORE_THREADS), 0, s, a);
 }
 void launch_gen_mask(const GenArgs &a, hipStream_t s) {
     const dim3 grid(min((a.V + 255) / 256, 256), a.n_rows);

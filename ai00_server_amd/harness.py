@@ -6,6 +6,8 @@
                                                        sampler/nucleus.rs:77-89) and token 0 = stop (run.rs:855)
     perplexity                `perplexity`            run.rs:699-755    (RnnOption::Full consumer)
     perplexity_scored         the same request with the realised tokens scored on the device (`Runtime.infer_score`)
+    generate_resident         the decode loop of one request in resident generation (`Runtime.gen_run`), with `top_logprobs` the
+                              `logprobs` object of an OpenAI-style completion: per token (token, logp, [(id, logp) ...])
     ReplicaRouter             SURVEY 8(e)             request-level sharding over N independent engines (no collective)
 
 Works against anything that has `.max_batch`, `.infer(RnnInput)` and `.state` like `runtime.Runtime`.
@@ -18,7 +20,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .runtime import SCORE_SKIP, RnnInput, RnnInputBatch, RnnOption
+from .runtime import SCORE_SKIP, TOPN_NONE, RnnInput, RnnInputBatch, RnnOption
 
 
 @dataclass
@@ -118,6 +120,32 @@ def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = 
             lp = lp[:-1]
         acc += float(lp.sum())
     return float(-acc / len(toks))
+
+
+def generate_resident(runtime, slot: int, prompt, max_tokens: int, sampler, seed: int = 0, stop_tokens=(), top_logprobs: int = 0,
+                      steps_per_run: int = 16) -> list:
+    """One request through resident generation: `slot` is armed with the whole `prompt` (`Runtime.gen_arm_prompt`; `sampler` is the host
+    sampler right after `init(prompt)`) and run until it finishes; nothing but token ids and a few numbers cross PCIe.  Returns one
+    (token, prob) per emitted token; with `top_logprobs` = n > 0 (`Runtime.gen_set_topn`) one (token, logp, [(id, logp), ...]) instead:
+    the token's ln-probability and the n most likely alternatives of the RAW model row (before penalties, bias and temperature), most
+    likely first, as an OpenAI-style `logprobs` object lists them.  Other armed slots ride along; their tokens are dropped here."""
+    runtime.gen_arm_prompt(slot, prompt, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    if top_logprobs:
+        runtime.gen_set_topn(slot, top_logprobs)
+    out = []
+    while True:
+        res = runtime.gen_run(steps_per_run, top=top_logprobs)
+        toks, probs, finish = res[0], res[1], res[3]
+        for k in range(steps_per_run):
+            if toks[k, slot] == 0xFFFFFFFF:
+                continue
+            if not top_logprobs:
+                out.append((int(toks[k, slot]), float(probs[k, slot])))
+                continue
+            tok_logp, ids, lp = res[4][k, slot], res[5][k, slot], res[6][k, slot]
+            out.append((int(toks[k, slot]), float(tok_logp), [(int(i), float(v)) for i, v in zip(ids, lp) if i != TOPN_NONE]))
+        if finish[slot]:
+            return out
 
 
 class NucleusSampler:

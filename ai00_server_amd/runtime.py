@@ -102,6 +102,12 @@ ABI_SYMBOLS = {
     "rwkv_score_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
     "rwkv_infer_score": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
                                      C.POINTER(C.c_size_t)]),
+    "rwkv_topn_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
+    "rwkv_infer_topn": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.c_int32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
+                                    C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rwkv_gen_set_topn": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "rwkv_gen_run_topn": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rwkv_gen_arm": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenParamsC)]),
     "rwkv_gen_arm_prompt": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(_GenParamsC)]),
     "rwkv_gen_prompt_left": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
@@ -153,6 +159,8 @@ ABI_SYMBOLS = {
 }
 PROFILE_FAMILIES = 8
 SCORE_SKIP = 0xFFFFFFFF          # RWKV_SCORE_SKIP: a row that is not scored (its output is NaN)
+TOPN_MAX = 32                    # RWKV_TOPN_MAX: the longest top-n list
+TOPN_NONE = 0xFFFFFFFF           # RWKV_TOPN_NONE: a place of a list that holds no entry
 
 _lib = None
 
@@ -701,6 +709,68 @@ class Runtime:
         _check(lib().rwkv_score_rows(self._h, pi, tg.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(C.POINTER(C.c_float)), len(ins)))
         return out
 
+    def topn_rows(self, rows, n: int):
+        """The `n` most likely tokens of every row and their ln-probabilities on the device (rwkv_topn_rows; the softmax task's stream and
+        thread): `rows` are host rows of num_vocab floats.  Returns (ids uint32 [rows, n], logp float32 [rows, n]): logits descending, ties
+        to the lower id, `TOPN_NONE` / -inf where a row has fewer than n entries above -inf, `TOPN_NONE` / NaN on a row holding +inf or NaN;
+        every logp is `score_rows`' value for that row and id, bit for bit."""
+        ins = [np.ascontiguousarray(r, np.float32).reshape(-1) for r in rows]
+        if any(r.size != self.info.num_vocab for r in ins):
+            raise RwkvError(-1, "topn_rows: num_vocab values per row")
+        w = max(int(n), 0)
+        ids, lp = np.full((len(ins), w), TOPN_NONE, np.uint32), np.full((len(ins), w), np.nan, np.float32)
+        pi = (C.c_void_p * len(ins))(*[r.ctypes.data for r in ins])
+        _check(lib().rwkv_topn_rows(self._h, pi, int(n), ids.ctypes.data_as(C.POINTER(C.c_uint32)), lp.ctypes.data_as(C.POINTER(C.c_float)), len(ins)))
+        return ids, lp
+
+    def infer_topn(self, inp: RnnInput, n: int, targets=None, listing=None):
+        """`infer` with top-n lists instead of rows (rwkv_infer_topn).  Every slot that has tokens and an option other than
+        `RnnOption.NoOutput` lists (`listing[b]` False leaves a slot out: it must then be state-only); a slot keeps its option — `Last`: one
+        list when the call exhausts its tokens, `Full`: one per consumed token.  `targets` is None or per slot None / one target per pending
+        token of a `Full` slot (a token id or `SCORE_SKIP`): the realised token is scored on its row as `infer_score` does.
+        Returns (inp, targets, lists): tokens and targets drained by what the call consumed; `lists[b]` is None for a slot that did not
+        list, else (ids uint32 [rows, n], logp float32 [rows, n], tok_logp float32 [rows] or None)."""
+        B = self.max_batch
+        if len(inp.batches) != B or (targets is not None and len(targets) != B) or (listing is not None and len(listing) != B):
+            raise RwkvError(-1, f"infer_topn needs max_batch={B} entries")
+        ins = (_SlotInC * B)()
+        ip, lp = (C.POINTER(C.c_uint32) * B)(), (C.POINTER(C.c_float) * B)()
+        tp, op = (C.POINTER(C.c_uint32) * B)(), (C.POINTER(C.c_float) * B)()
+        keep, outs = [], []
+        w = max(int(n), 0)
+        for b, ib in enumerate(inp.batches):
+            toks = np.ascontiguousarray(ib.tokens, dtype=np.uint32).reshape(-1)
+            keep.append(toks)
+            ins[b] = _SlotInC(toks.ctypes.data_as(C.POINTER(C.c_uint32)) if toks.size else None, toks.size, int(ib.option), 0)
+            lists = toks.size and int(ib.option) != int(RnnOption.NoOutput) if listing is None else bool(listing[b])
+            if not lists:
+                outs.append(None)
+                continue
+            rows = min(toks.size, self.token_chunk_size) if int(ib.option) == int(RnnOption.Full) else 1
+            o = [np.full((rows, w), TOPN_NONE, np.uint32), np.full((rows, w), np.nan, np.float32), None]
+            ip[b], lp[b] = o[0].ctypes.data_as(C.POINTER(C.c_uint32)), o[1].ctypes.data_as(C.POINTER(C.c_float))
+            if targets is not None and targets[b] is not None:
+                tg = np.ascontiguousarray(targets[b], dtype=np.uint32).reshape(-1)
+                if tg.size != toks.size:
+                    raise RwkvError(-1, f"slot {b}: {tg.size} targets for {toks.size} tokens")
+                o[2] = np.full(rows, np.nan, np.float32)
+                keep.append(tg)
+                tp[b] = tg.ctypes.data_as(C.POINTER(C.c_uint32)) if tg.size else None
+                op[b] = o[2].ctypes.data_as(C.POINTER(C.c_float))
+            outs.append(o)
+        n_rows, consumed = (C.c_size_t * B)(), (C.c_size_t * B)()
+        _check(lib().rwkv_infer_topn(self._h, ins, int(n), ip, lp, tp if targets is not None else None, op if targets is not None else None, n_rows, consumed))
+        del keep
+        rest = None if targets is None else []
+        for b, ib in enumerate(inp.batches):
+            k, r = int(consumed[b]), int(n_rows[b])
+            ib.tokens = ib.tokens[k:] if isinstance(ib.tokens, np.ndarray) else list(ib.tokens[k:])
+            if rest is not None:
+                rest.append(None if targets[b] is None else targets[b][k:])
+            if outs[b] is not None:
+                outs[b] = (outs[b][0][:r], outs[b][1][:r], None if outs[b][2] is None else outs[b][2][:r])
+        return inp, rest, outs
+
     # ---- device-resident sampled generation (rwkv_gen_arm / _run / _disarm): the sampler state lives on the device
     def _gen_params(self, slot, first_token, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k=False):
         """rwkv_gen_params from the settings AND the current state of a host-side sampler; returns (struct, arrays to keep alive)"""
@@ -803,18 +873,34 @@ class Runtime:
         _check(lib().rwkv_gen_constraint_state(self._h, int(slot), C.byref(st)))
         return int(st.value)
 
-    def gen_run(self, n_steps: int):
+    def gen_set_topn(self, slot: int, n: int):
+        """An armed, unfinished slot lists its `n` (0 .. TOPN_MAX; 0 = off) most likely tokens of the RAW model row — before penalties, bias,
+        temperature and any constraint mask — with every token it emits from now on (rwkv_gen_set_topn).  Re-arming the slot resets it."""
+        _check(lib().rwkv_gen_set_topn(self._h, int(slot), int(n)))
+
+    def gen_run(self, n_steps: int, top: int = 0):
         """Up to `n_steps` decode steps of every armed, unfinished slot without a host turn-around.  Returns (tokens uint32
         [n_steps, max_batch] with 0xFFFFFFFF where a slot emitted nothing, probs float32 of the same shape with NaN there,
-        n_emitted [max_batch] of this call, finish [max_batch] of `GenFinish`)."""
+        n_emitted [max_batch] of this call, finish [max_batch] of `GenFinish`).
+        With `top` > 0 (rwkv_gen_run_topn; `top` >= every armed slot's `gen_set_topn` n) three more arrays follow: tok_logp float32
+        [n_steps, max_batch], the raw ln-probability of the emitted token, and top_ids uint32 / top_logp float32 [n_steps, max_batch, top],
+        every slot's list padded with `TOPN_NONE` / -inf up to `top`; `TOPN_NONE` / NaN where a slot emitted nothing."""
         B = self.max_batch
         toks = np.empty((n_steps, B), np.uint32)
         probs = np.empty((n_steps, B), np.float32)
         n_emitted, finish = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        i32p = C.POINTER(C.c_int32)
-        _check(lib().rwkv_gen_run(self._h, int(n_steps), toks.ctypes.data_as(C.POINTER(C.c_uint32)), probs.ctypes.data_as(C.POINTER(C.c_float)),
-                                  n_emitted.ctypes.data_as(i32p), finish.ctypes.data_as(i32p)))
-        return toks, probs, n_emitted, finish
+        i32p, u32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+        if not top:
+            _check(lib().rwkv_gen_run(self._h, int(n_steps), toks.ctypes.data_as(u32p), probs.ctypes.data_as(f32p),
+                                      n_emitted.ctypes.data_as(i32p), finish.ctypes.data_as(i32p)))
+            return toks, probs, n_emitted, finish
+        w = max(int(top), 0)
+        tok_logp = np.full((n_steps, B), np.nan, np.float32)
+        top_ids, top_logp = np.full((n_steps, B, w), TOPN_NONE, np.uint32), np.full((n_steps, B, w), np.nan, np.float32)
+        _check(lib().rwkv_gen_run_topn(self._h, int(n_steps), toks.ctypes.data_as(u32p), probs.ctypes.data_as(f32p), n_emitted.ctypes.data_as(i32p),
+                                       finish.ctypes.data_as(i32p), int(top), tok_logp.ctypes.data_as(f32p), top_ids.ctypes.data_as(u32p),
+                                       top_logp.ctypes.data_as(f32p)))
+        return toks, probs, n_emitted, finish, tok_logp, top_ids, top_logp
 
     gen_uniform = staticmethod(gen_uniform)
 

@@ -42,7 +42,10 @@ extern "C" {
                               *    additive under 9 (no new symbol, no struct changed): RWKV_V4 — RWKV-4 World checkpoints load (version 4 in
                               *    rwkv_model_info, the five-row state below); they were RWKV_ERR_UNSUPPORTED before
                               *    additive under 9: rwkv_dfa_* (byte automata, host only), rwkv_gen_set_constraint, rwkv_gen_constraint_state: a REGULAR
-                              *    format constraint is masked and advanced on the device inside the resident step */
+                              *    format constraint is masked and advanced on the device inside the resident step
+                              *    additive under 9: rwkv_topn_rows, rwkv_infer_topn, rwkv_gen_set_topn, rwkv_gen_run_topn, RWKV_TOPN_MAX, RWKV_TOPN_NONE: the
+                              *    n most likely tokens of a row and their ln-probabilities are listed on the device (host rows, prefill, resident
+                              *    generation), 8 n bytes per row come back instead of the row */
 
 typedef int32_t rwkv_status;
 enum {
@@ -233,6 +236,36 @@ rwkv_status rwkv_score_rows(rwkv_engine *e, const float *const *in, const uint32
  * call in which only state-only slots ride returns when the step is queued, as rwkv_infer does); errors as for a row-emitting rwkv_infer.  Thread
  * contract of rwkv_infer; tokens for an armed generation slot disarm it. */
 rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
+
+/* ---- top-n lists on the device: what the `top_logprobs` of a completion, a classifier over a few label tokens or a per-token
+ * uncertainty estimate need of a logits row is the n most likely tokens and their ln-probabilities.  For a row x[0 .. num_vocab) and
+ * 1 <= n <= RWKV_TOPN_MAX a LIST is n (id, logp) pairs:
+ *  - order: the entries with x[i] > -inf, by x[i] descending as real numbers (-0 equals +0), ties to the lower token id.  The ids are a function
+ *    of the row's bits alone: two different logits never tie, even where their probabilities round to one float or underflow to zero.
+ *  - logp is rwkv_score_rows' value for that row with that id as target, bit for bit (the same reduction in the same order).
+ *  - fewer than n such entries (masked tokens, n > num_vocab, a row of nothing but -inf): the places left hold (RWKV_TOPN_NONE, -inf).
+ *  - a row holding +inf or NaN: all n places hold (RWKV_TOPN_NONE, NaN), as rwkv_score_rows gives NaN.
+ *  - a row's list does not depend on how many rows ride along.
+ * n outside 1 .. RWKV_TOPN_MAX or a null pointer: RWKV_ERR_INVALID before anything is launched or written.
+ * rwkv_infer_sample returns no lists: a caller that samples token by token and wants them takes the row (rwkv_infer) and lists it with
+ * rwkv_topn_rows. */
+#define RWKV_TOPN_MAX 32
+#define RWKV_TOPN_NONE 4294967295u   /* 0xFFFFFFFF */
+/* like rwkv_score_rows: n_rows host rows of num_vocab floats in, out_ids / out_logp [n_rows][n] out; own (softmax) stream and the softmax task's
+ * thread; staged in pieces of max_batch rows. */
+rwkv_status rwkv_topn_rows(rwkv_engine *e, const float *const *in, int32_t n, uint32_t *out_ids, float *out_logp, size_t n_rows);
+/* rwkv_infer with lists instead of rows.  All arrays have max_batch entries.  A slot with out_ids[b] != NULL keeps its option: RWKV_OPTION_LAST
+ * lists the one row of the call that exhausts its tokens, RWKV_OPTION_FULL one row per consumed token; out_ids[b] / out_logp[b] take [rows][n]
+ * entries (room for 1 resp. n_tokens rows) and n_rows[b] says how many lists this call wrote.  The plan, the rwkv_plan_chunk split and the step
+ * shapes are rwkv_infer's: the rows listed are the very rows rwkv_infer would have returned at the same occupancy.  A slot with out_ids[b] ==
+ * NULL must have n_tokens == 0 or option == RWKV_OPTION_NONE, else RWKV_ERR_INVALID.
+ * `targets` may be NULL as a whole or per slot.  Where targets[b] is given the slot must be RWKV_OPTION_FULL and listing; targets[b] has
+ * n_tokens entries (token ids or RWKV_SCORE_SKIP) and out_tok_logp[b][i] is exactly rwkv_infer_score's value for that row: the realised token's
+ * ln-probability beside the alternatives, in one pass (`echo`).  The caller advances tokens, targets and the outputs by n_consumed[b].
+ * No logits row crosses PCIe.  Returns when the lists are in place (a call in which no slot reaches a row returns when the step is queued, as
+ * rwkv_infer does); errors, thread contract and disarming rule of rwkv_infer. */
+rwkv_status rwkv_infer_topn(rwkv_engine *e, const rwkv_slot_input *in, int32_t n, uint32_t *const *out_ids, float *const *out_logp,
+                            const uint32_t *const *targets, float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
 
 /* ---- on-device sampling front-end: what `sample()` run.rs:664-697 + NucleusSampler::sample
  * (sampler/nucleus.rs:69-101) do with three PCIe hops and a 65,536-element CPU sort, done on the device.
@@ -473,6 +506,25 @@ rwkv_status rwkv_dfa_check_live(const rwkv_dfa *d, int32_t state, int32_t halt_m
 rwkv_status rwkv_gen_set_constraint(rwkv_engine *e, int32_t slot, const rwkv_dfa *dfa, int32_t state, int32_t halt_mode);
 /* The state behind every token the slot has emitted, the last one included (0 for a slot without a constraint).  Waits for the device. */
 rwkv_status rwkv_gen_constraint_state(rwkv_engine *e, int32_t slot, int32_t *state);
+
+/* ---- top-n lists in resident generation: what else the model considered, per emitted token, without the row leaving the device.
+ * The distribution is the RAW MODEL ROW — what the head wrote, before penalties, bias, temperature and any constraint mask — the definition
+ * rwkv_infer_score uses, and the one a caller cannot reconstruct from anything else the run returns.
+ * rwkv_gen_set_topn: an armed, unfinished slot lists its n (0 .. RWKV_TOPN_MAX; 0 = off) most likely tokens with every token it emits from now
+ * on; re-arming the slot resets n to 0.  The first call allocates max_batch * num_vocab * 4 bytes of device memory for the raw rows.
+ * rwkv_gen_run_topn is rwkv_gen_run — the first six arguments behave exactly as there — with three more outputs, step-major like out_tokens:
+ *   out_tok_logp [n_steps][max_batch]         the raw ln-probability of the emitted token: rwkv_score_rows' value for the raw row and that token,
+ *                                             bit for bit (and the list's entry, when the token is listed)
+ *   out_top_ids  [n_steps][max_batch][n_top]  the slot's list (see "top-n lists on the device" above), its own n places; the places up to the
+ *   out_top_logp                              caller's stride n_top hold (RWKV_TOPN_NONE, -inf)
+ * Where a slot emitted nothing in a step: (RWKV_TOPN_NONE, NaN) and NaN in out_tok_logp; a slot with n == 0 has NaN in out_tok_logp too.
+ * n_top (1 .. RWKV_TOPN_MAX) must be >= every armed, unfinished slot's n, else RWKV_ERR_INVALID before the first step.
+ * INVARIANT: listing changes no token, probability, finish reason, stop tail, constraint state or state of any slot — the extra launch only
+ * reads the logits block — and a step in which no slot lists is the step rwkv_gen_run ran before, launch for launch.  rwkv_gen_run stays
+ * callable on listing slots and returns what it returned before. */
+rwkv_status rwkv_gen_set_topn(rwkv_engine *e, int32_t slot, int32_t n);
+rwkv_status rwkv_gen_run_topn(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish,
+                              int32_t n_top, float *out_tok_logp, uint32_t *out_top_ids, float *out_top_logp);
 
 /* ---- `Tokenizer` lib.rs:375; run.rs:157-168,856; sampler/bnf.rs:14-27 ---------------------- */
 typedef struct rwkv_tokenizer rwkv_tokenizer;

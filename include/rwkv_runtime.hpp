@@ -226,6 +226,65 @@ class Runtime {
         check(rwkv_score_rows(e_.get(), pi.data(), targets.data(), out.data(), rows.size()));
         return out;
     }
+    // Top-n lists (rwkv_topn_rows / rwkv_infer_topn): `rows` lists of `n` places; ids[r * n + i] / logp[r * n + i] are the i-th most likely
+    // token of row r and its ln-probability (logits descending, ties to the lower id; RWKV_TOPN_NONE / -inf where the row has fewer than n
+    // entries above -inf, RWKV_TOPN_NONE / NaN on a row holding +inf or NaN); tok_logp[r] is the realised token's ln-probability where the
+    // slot had targets.  Every logp is score_rows()'s value for that row and id, bit for bit.
+    struct TopLists { int n = 0; size_t rows = 0; std::vector<uint32_t> ids; std::vector<float> logp, tok_logp; };
+    // The softmax task's stream and thread, like score_rows().
+    TopLists topn_rows(const std::vector<std::vector<float>> &rows, int n) {
+        for (const auto &r : rows) if (r.size() != (size_t)info.num_vocab) throw std::invalid_argument("topn_rows: every row must hold num_vocab values");
+        std::vector<const float *> pi(rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) pi[i] = rows[i].data();
+        const size_t cells = n > 0 ? rows.size() * (size_t)n : 0;
+        TopLists out{n, rows.size(), std::vector<uint32_t>(cells, RWKV_TOPN_NONE), std::vector<float>(cells), {}};
+        check(rwkv_topn_rows(e_.get(), pi.data(), n, out.ids.data(), out.logp.data(), rows.size()));
+        return out;
+    }
+    // One step like infer(), with lists instead of rows: every slot that has tokens and an option other than RnnOption::None lists and keeps
+    // its option (Last: one list when the call exhausts its tokens, Full: one per consumed token).  `targets` is empty, or max_batch entries
+    // of which targets[b] is empty or holds one target per pending token of a Full slot (a token id or RWKV_SCORE_SKIP): the realised token
+    // is scored on its row exactly as infer_score() does.  `input` and `targets` are consumed in place.  No row crosses PCIe.
+    std::vector<TopLists> infer_topn(RnnInput &input, int n, std::vector<std::vector<uint32_t>> &targets) {
+        if ((int)input.batches.size() != max_batch || (!targets.empty() && (int)targets.size() != max_batch)) throw std::invalid_argument("infer_topn: need max_batch entries");
+        if (n < 1 || n > RWKV_TOPN_MAX) throw std::invalid_argument("infer_topn: n must be 1..RWKV_TOPN_MAX");
+        std::vector<rwkv_slot_input> in((size_t)max_batch);
+        std::vector<uint32_t *> ip((size_t)max_batch, nullptr);
+        std::vector<float *> lp((size_t)max_batch, nullptr), op((size_t)max_batch, nullptr);
+        std::vector<const uint32_t *> tp((size_t)max_batch, nullptr);
+        std::vector<TopLists> out((size_t)max_batch);
+        std::vector<size_t> n_rows((size_t)max_batch), consumed((size_t)max_batch);
+        for (size_t b = 0; b < (size_t)max_batch; ++b) {
+            auto &ib = input.batches[b];
+            in[b] = rwkv_slot_input{ib.tokens.data(), ib.tokens.size(), (int32_t)ib.option, 0};
+            out[b].n = n;
+            const size_t rows = ib.tokens.empty() || ib.option == RnnOption::None ? 0
+                               : ib.option == RnnOption::Full ? std::min(ib.tokens.size(), (size_t)token_chunk_size) : 1;
+            if (!rows) continue;
+            out[b].ids.assign(rows * (size_t)n, RWKV_TOPN_NONE);
+            out[b].logp.resize(rows * (size_t)n);
+            ip[b] = out[b].ids.data();
+            lp[b] = out[b].logp.data();
+            if (targets.empty() || targets[b].empty()) continue;
+            if (targets[b].size() != ib.tokens.size()) throw std::invalid_argument("infer_topn: a scored slot needs one target per pending token");
+            out[b].tok_logp.resize(rows);
+            tp[b] = targets[b].data();
+            op[b] = out[b].tok_logp.data();
+        }
+        check(rwkv_infer_topn(e_.get(), in.data(), n, ip.data(), lp.data(), targets.empty() ? nullptr : tp.data(), targets.empty() ? nullptr : op.data(),
+                              n_rows.data(), consumed.data()));
+        for (size_t b = 0; b < (size_t)max_batch; ++b) {
+            auto &t = input.batches[b].tokens;
+            t.erase(t.begin(), t.begin() + (long)consumed[b]);
+            out[b].rows = n_rows[b];
+            out[b].ids.resize(n_rows[b] * (size_t)n);
+            out[b].logp.resize(n_rows[b] * (size_t)n);
+            if (!tp[b]) continue;
+            targets[b].erase(targets[b].begin(), targets[b].begin() + (long)consumed[b]);
+            out[b].tok_logp.resize(n_rows[b]);
+        }
+        return out;
+    }
     // Device-resident sampled generation (rwkv_gen_arm / _run / _disarm): arm a slot with `sampler.gen_params_for(...)`
     // (include/rwkv_sampler.hpp), then every gen_run generates up to n_steps tokens per armed slot without a host turn-around.
     void gen_arm(int slot, const rwkv_gen_params &p) { check(rwkv_gen_arm(e_.get(), slot, &p)); }
@@ -284,15 +343,33 @@ class Runtime {
         std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing
         std::vector<float> probs;                    // same shape, NaN there
         std::vector<int32_t> n_emitted, finish;      // [max_batch]: tokens of this call, RWKV_GEN_* (RWKV_GEN_HANDBACK: replay StopMatcher, go on per token)
+        // gen_run(n_steps, top > 0) only: the emitted token's raw ln-probability [n_steps][max_batch] (NaN where nothing was emitted or the slot
+        // lists nothing) and the lists [n_steps][max_batch][n_top] (RWKV_TOPN_NONE / -inf behind a slot's own n, RWKV_TOPN_NONE / NaN where nothing was emitted)
+        int n_top = 0;
+        std::vector<float> tok_logp, top_logp;
+        std::vector<uint32_t> top_ids;
     };
-    Generated gen_run(int n_steps) {
+    // An armed, unfinished slot lists its n (0 .. RWKV_TOPN_MAX; 0 = off) most likely tokens of the RAW model row with every token it emits
+    // from now on (rwkv_gen_set_topn); re-arming the slot resets it.
+    void gen_set_topn(int slot, int n) { check(rwkv_gen_set_topn(e_.get(), slot, n)); }
+    // `top` > 0 (rwkv_gen_run_topn; `top` >= every armed slot's n): tok_logp / top_ids / top_logp of the result are filled as well.
+    Generated gen_run(int n_steps, int top = 0) {
         if (n_steps <= 0) throw std::invalid_argument("gen_run: n_steps must be > 0");
         Generated g;
         g.tokens.resize((size_t)n_steps * (size_t)max_batch);
         g.probs.resize(g.tokens.size());
         g.n_emitted.resize((size_t)max_batch);
         g.finish.resize((size_t)max_batch);
-        check(rwkv_gen_run(e_.get(), n_steps, g.tokens.data(), g.probs.data(), g.n_emitted.data(), g.finish.data()));
+        if (top <= 0) {
+            check(rwkv_gen_run(e_.get(), n_steps, g.tokens.data(), g.probs.data(), g.n_emitted.data(), g.finish.data()));
+            return g;
+        }
+        g.n_top = top;
+        g.tok_logp.resize(g.tokens.size());
+        g.top_ids.resize(g.tokens.size() * (size_t)top);
+        g.top_logp.resize(g.top_ids.size());
+        check(rwkv_gen_run_topn(e_.get(), n_steps, g.tokens.data(), g.probs.data(), g.n_emitted.data(), g.finish.data(), top, g.tok_logp.data(),
+                                g.top_ids.data(), g.top_logp.data()));
         return g;
     }
     rwkv_engine *raw() const { return e_.get(); }

@@ -378,11 +378,15 @@ class Scheduler {
     // Hand a busy slot whose prompt has been read in to the resident loop WITH its stop strings (run.rs:899-932 on the device): arm it with
     // `p` (its first_token is the token the caller sampled from the prompt's row and has already pushed through `matcher`), then set the
     // strings and the bytes the matcher still holds.  Needs an engine with gen_arm / gen_set_stops (rwkv::Runtime) whose token table is set.
-    void arm_with_stops(int batch, const rwkv_gen_params &p, const std::vector<std::string> &stops, const StopMatcher &matcher) {
+    // `top_logprobs` > 0 (the `top_logprobs` of a completion request): the slot also lists that many alternatives of the raw model row with
+    // every token it emits (gen_set_topn; the caller then runs gen_run(n_steps, top) with top >= every slot's count).
+    void arm_with_stops(int batch, const rwkv_gen_params &p, const std::vector<std::string> &stops, const StopMatcher &matcher, int top_logprobs = 0) {
         need_busy(batch);
         if (!reqs_[(size_t)batch].suffix.empty()) throw std::logic_error("arm_with_stops(): the prompt has not been read in yet");
+        if (top_logprobs < 0 || top_logprobs > RWKV_TOPN_MAX) throw std::invalid_argument("arm_with_stops(): top_logprobs must be 0..RWKV_TOPN_MAX");
         e_.gen_arm(batch, p);
         e_.gen_set_stops(batch, stops, matcher.tail());
+        if (top_logprobs > 0) e_.gen_set_topn(batch, top_logprobs);   // behind the arm: arming resets the slot's count
     }
 
     // feed more tokens to a busy slot (the decode loop appends the sampled token: run.rs:1004-1010)

@@ -44,6 +44,8 @@ pub const RWKV_DFA_HALT_FINAL: i32 = 0;
 pub const RWKV_DFA_HALT_ACCEPT: i32 = 1;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 pub const RWKV_SCORE_SKIP: u32 = 4294967295;
+pub const RWKV_TOPN_MAX: i32 = 32;
+pub const RWKV_TOPN_NONE: u32 = 4294967295;
 
 #[repr(C)] pub struct rwkv_engine { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_dstate { _p: [u8; 0] }
@@ -119,6 +121,13 @@ extern "C" {
     pub fn rwkv_score_rows(e: *mut rwkv_engine, inp: *const *const f32, targets: *const u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
     pub fn rwkv_infer_score(e: *mut rwkv_engine, inp: *const rwkv_slot_input, targets: *const *const u32, out_logp: *const *mut c_float,
                             n_consumed: *mut usize) -> rwkv_status;
+    // top-n lists on the device: the `top_logprobs` of a completion
+    pub fn rwkv_topn_rows(e: *mut rwkv_engine, inp: *const *const f32, n: i32, out_ids: *mut u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
+    pub fn rwkv_infer_topn(e: *mut rwkv_engine, inp: *const rwkv_slot_input, n: i32, out_ids: *const *mut u32, out_logp: *const *mut c_float,
+                           targets: *const *const u32, out_tok_logp: *const *mut c_float, n_rows: *mut usize, n_consumed: *mut usize) -> rwkv_status;
+    pub fn rwkv_gen_set_topn(e: *mut rwkv_engine, slot: i32, n: i32) -> rwkv_status;
+    pub fn rwkv_gen_run_topn(e: *mut rwkv_engine, n_steps: i32, out_tokens: *mut u32, out_probs: *mut c_float, n_emitted: *mut i32, finish: *mut i32,
+                             n_top: i32, out_tok_logp: *mut c_float, out_top_ids: *mut u32, out_top_logp: *mut c_float) -> rwkv_status;
     // on-device sampling front-end (run.rs:664-697 + sampler/*.rs)
     pub fn rwkv_infer_sample(e: *mut rwkv_engine, inp: *const rwkv_slot_input, sp: *const rwkv_sample_params, out_tokens: *mut u32,
                              out_probs: *mut c_float, emitted: *mut u8, n_consumed: *mut usize) -> rwkv_status;

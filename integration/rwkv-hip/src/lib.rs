@@ -91,6 +91,12 @@ impl Drop for PinnedLogits {
 #[derive(Default, Clone, Debug)]
 pub struct SlotInput { pub tokens: Vec<u32>, pub option: OutputOption }
 
+/// what `infer_topn` hands back per slot: `rows` lists of `n` places, `ids[r * n + i]` / `logp[r * n + i]` the i-th most likely token of
+/// row r and its ln-probability (`sys::RWKV_TOPN_NONE` where the place holds no entry); `tok_logp[r]` the realised token's ln-probability
+/// when the slot had targets (empty otherwise)
+#[derive(Default, Clone, Debug)]
+pub struct TopLists { pub n: usize, pub rows: usize, pub ids: Vec<u32>, pub logp: Vec<f32>, pub tok_logp: Vec<f32> }
+
 impl Engine {
     pub fn load(d: &LoadDesc) -> Result<Self> {
         let lora: Vec<_> = d.lora.iter().map(|(b, a)| sys::rwkv_lora_desc { st_bytes: b.as_ptr(), st_len: b.len(), alpha: *a }).collect();
@@ -249,6 +255,53 @@ impl Engine {
         }
         Ok(out)
     }
+    /// `rwkv_topn_rows`: the `n` most likely tokens of every row and their ln-probabilities on the device, `[rows][n]` each: logits
+    /// descending, ties to the lower id; `sys::RWKV_TOPN_NONE` / -inf where a row has fewer than n entries above -inf, `RWKV_TOPN_NONE` /
+    /// NaN on a row holding +inf or NaN.  Every logp is `score_rows`' value for that row and id.  Call from the softmax task's thread.
+    pub fn topn_rows(&self, rows: &[Vec<f32>], n: usize) -> Result<(Vec<u32>, Vec<f32>)> {
+        let v = self.info.num_vocab as usize;
+        if rows.iter().any(|r| r.len() != v) || n < 1 || n > sys::RWKV_TOPN_MAX as usize {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "topn_rows: num_vocab values per row, n in 1..=RWKV_TOPN_MAX".into() });
+        }
+        let inp: Vec<*const f32> = rows.iter().map(|r| r.as_ptr()).collect();
+        let (mut ids, mut lp) = (vec![sys::RWKV_TOPN_NONE; rows.len() * n], vec![f32::NAN; rows.len() * n]);
+        check(unsafe { sys::rwkv_topn_rows(self.raw, inp.as_ptr(), n as i32, ids.as_mut_ptr(), lp.as_mut_ptr(), rows.len()) })?;
+        Ok((ids, lp))
+    }
+    /// `rwkv_infer_topn`: one step like `infer`, with top-n lists instead of rows.  Every slot that has tokens and an option other than
+    /// `OutputOption::None` lists and keeps its option (`Last`: one list when the call exhausts its tokens, `Full`: one per consumed
+    /// token).  `targets[b]` is `None` or one target per pending token of a `Full` slot (a token id or `sys::RWKV_SCORE_SKIP`): the realised
+    /// token's ln-probability, exactly `infer_score`'s, comes back beside the alternatives.  Tokens and targets are drained by what the call
+    /// consumed; returns one `TopLists` per slot (`rows == 0` for a slot that listed nothing).
+    pub fn infer_topn(&self, input: &mut [SlotInput], n: usize, targets: &mut [Option<Vec<u32>>]) -> Result<Vec<TopLists>> {
+        if input.len() != self.max_batch || targets.len() != self.max_batch || n < 1 || n > sys::RWKV_TOPN_MAX as usize {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: format!("infer_topn: {} slot inputs, {} target lists for max_batch {}, n = {}", input.len(), targets.len(), self.max_batch, n) });
+        }
+        if input.iter().zip(targets.iter()).any(|(s, t)| t.as_ref().map_or(false, |t| t.len() != s.tokens.len())) {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "infer_topn: a scored slot needs one target per pending token".into() });
+        }
+        let inp: Vec<_> = input.iter().map(|s| sys::rwkv_slot_input {
+            tokens: if s.tokens.is_empty() { ptr::null() } else { s.tokens.as_ptr() }, n_tokens: s.tokens.len(), option: s.option as i32, reserved: 0 }).collect();
+        let mut out: Vec<TopLists> = input.iter().zip(targets.iter()).map(|(s, t)| {
+            let rows = if s.tokens.is_empty() || s.option as i32 == sys::RWKV_OPTION_NONE { 0 }
+                       else if s.option as i32 == sys::RWKV_OPTION_FULL { s.tokens.len().min(self.token_chunk_size) } else { 1 };
+            TopLists { n, rows, ids: vec![sys::RWKV_TOPN_NONE; rows * n], logp: vec![f32::NAN; rows * n],
+                       tok_logp: if t.is_some() { vec![f32::NAN; rows] } else { Vec::new() } }
+        }).collect();
+        let ip: Vec<*mut u32> = out.iter_mut().map(|o| if o.rows == 0 { ptr::null_mut() } else { o.ids.as_mut_ptr() }).collect();
+        let lp: Vec<*mut f32> = out.iter_mut().map(|o| if o.rows == 0 { ptr::null_mut() } else { o.logp.as_mut_ptr() }).collect();
+        let tp: Vec<*const u32> = targets.iter().map(|t| match t { Some(t) if !t.is_empty() => t.as_ptr(), _ => ptr::null() }).collect();
+        let op: Vec<*mut f32> = out.iter_mut().map(|o| if o.tok_logp.is_empty() { ptr::null_mut() } else { o.tok_logp.as_mut_ptr() }).collect();
+        let (mut n_rows, mut consumed) = (vec![0usize; self.max_batch], vec![0usize; self.max_batch]);
+        check(unsafe { sys::rwkv_infer_topn(self.raw, inp.as_ptr(), n as i32, ip.as_ptr(), lp.as_ptr(), tp.as_ptr(), op.as_ptr(), n_rows.as_mut_ptr(), consumed.as_mut_ptr()) })?;
+        for ((((s, t), o), &r), &k) in input.iter_mut().zip(targets.iter_mut()).zip(out.iter_mut()).zip(&n_rows).zip(&consumed) {
+            s.tokens.drain(..k);
+            if let Some(t) = t { t.drain(..k); }
+            o.rows = r; o.ids.truncate(r * n); o.logp.truncate(r * n);
+            if !o.tok_logp.is_empty() { o.tok_logp.truncate(r); }
+        }
+        Ok(out)
+    }
     /// Arm `slot` for device-resident sampled generation (rwkv_gen_arm): the decode loop of `process` (run.rs:788-1020) with `sample()`
     /// (run.rs:664-697) and the sampler state machine (sampler/*.rs) on the device.  The slot's state is what the prompt left.
     pub fn gen_arm(&self, slot: usize, p: &GenParams) -> Result<()> { self.gen_arm_with(slot, p, None) }
@@ -322,6 +375,18 @@ impl Engine {
         check(unsafe { sys::rwkv_gen_run(self.raw, n_steps as i32, g.tokens.as_mut_ptr(), g.probs.as_mut_ptr(), g.n_emitted.as_mut_ptr(), g.finish.as_mut_ptr()) })?;
         Ok(g)
     }
+    /// An armed, unfinished slot lists its `n` (0 ..= RWKV_TOPN_MAX; 0 = off) most likely tokens of the RAW model row — before penalties,
+    /// bias, temperature and any constraint mask — with every token it emits from now on (rwkv_gen_set_topn).  Re-arming resets it.
+    pub fn gen_set_topn(&self, slot: usize, n: usize) -> Result<()> { check(unsafe { sys::rwkv_gen_set_topn(self.raw, slot as i32, n as i32) }) }
+    /// `gen_run` with the lists (rwkv_gen_run_topn): `n_top` (>= every armed slot's n) is the stride of `top_ids` / `top_logp`.
+    pub fn gen_run_topn(&self, n_steps: usize, n_top: usize) -> Result<GeneratedTop> {
+        let cells = n_steps * self.max_batch;
+        let mut g = Generated { tokens: vec![u32::MAX; cells], probs: vec![f32::NAN; cells], n_emitted: vec![0; self.max_batch], finish: vec![0; self.max_batch] };
+        let (mut tok_logp, mut top_ids, mut top_logp) = (vec![f32::NAN; cells], vec![sys::RWKV_TOPN_NONE; cells * n_top], vec![f32::NAN; cells * n_top]);
+        check(unsafe { sys::rwkv_gen_run_topn(self.raw, n_steps as i32, g.tokens.as_mut_ptr(), g.probs.as_mut_ptr(), g.n_emitted.as_mut_ptr(), g.finish.as_mut_ptr(),
+                                              n_top as i32, tok_logp.as_mut_ptr(), top_ids.as_mut_ptr(), top_logp.as_mut_ptr()) })?;
+        Ok(GeneratedTop { run: g, n_top, tok_logp, top_ids, top_logp })
+    }
 }
 
 #[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum DfaHalt { #[default] Final = 0, Accept = 1 }
@@ -374,6 +439,11 @@ pub struct GenParams {
 /// `n_emitted` counts this call's tokens per slot, `finish` is RWKV_GEN_RUNNING / _STOP / _LENGTH / _HANDBACK
 #[derive(Clone, Debug)]
 pub struct Generated { pub tokens: Vec<u32>, pub probs: Vec<f32>, pub n_emitted: Vec<i32>, pub finish: Vec<i32> }
+/// what `Engine::gen_run_topn` returns beside `gen_run`'s: `tok_logp` [n_steps][max_batch] is the emitted token's raw ln-probability (NaN where
+/// nothing was emitted or the slot lists nothing), `top_ids` / `top_logp` [n_steps][max_batch][n_top] the lists (`sys::RWKV_TOPN_NONE` / -inf
+/// behind a slot's own n, `RWKV_TOPN_NONE` / NaN where nothing was emitted)
+#[derive(Clone, Debug)]
+pub struct GeneratedTop { pub run: Generated, pub n_top: usize, pub tok_logp: Vec<f32>, pub top_ids: Vec<u32>, pub top_logp: Vec<f32> }
 /// draw `step` of (seed, stream): pure host function (rwkv_gen_uniform)
 pub fn gen_uniform(seed: u64, stream: u32, step: u32) -> f32 {
     let mut u = 0f32;

@@ -54,6 +54,7 @@ def main():
     ap.add_argument("--loops", default="greedy,sample_bare,sample_host_samplers,resident")
     ap.add_argument("--admission", action="store_true")
     ap.add_argument("--stops", default=None, help="N,LEN: every resident slot carries N never-matching stop strings of LEN bytes")
+    ap.add_argument("--top", type=int, default=0, help="N: adds the loop resident_top, the resident loop with every slot listing its N most likely tokens")
     a = ap.parse_args()
     batches = [int(x) for x in a.batches.split(",")]
     B = max(batches)
@@ -96,17 +97,20 @@ def main():
 
     arm_s = {}
 
-    def resident(nb):
+    def resident(nb, top=0):
         t = time.perf_counter()
         for b in range(nb):
             eng.gen_arm(b, first[b], n, H.NucleusSampler(), seed=1)
-        arm_s.setdefault(nb, []).append(time.perf_counter() - t)
+        if not top:
+            arm_s.setdefault(nb, []).append(time.perf_counter() - t)
+        for b in range(nb if top else 0):
+            eng.gen_set_topn(b, top)                                # re-arming resets it: the plain loop's slots list nothing
         for b in range(nb if n_stops else 0):
             eng.gen_set_stops(b, stops)
         emitted = 0
         t = time.perf_counter()
         for _ in range(-(-n // spr)):
-            _, _, ne, fin = eng.gen_run(spr)
+            ne = eng.gen_run(spr, top=top)[2]
             emitted += int(ne.sum())
         dt = time.perf_counter() - t
         for b in range(nb if n_stops else 0):
@@ -131,6 +135,8 @@ def main():
 
     loops = {"greedy": greedy, "sample_bare": sample_bare, "sample_host_samplers": sample_host, "resident": resident, "resident_1": resident_1}
     loops = {k: f for k, f in loops.items() if k in a.loops.split(",")}
+    if a.top and "resident" in loops:
+        loops["resident_top"] = lambda nb: resident(nb, a.top)
 
     def admission(mode, running=24, joiners=8, every=16, plen=256, tail=4):
         """One region.  Both modes call gen_run(every) while nobody is being admitted.  `leave_and_prefill` admits between two runs with
