@@ -25,6 +25,7 @@
 #include "gemm_plan.h"
 #include "graph_cache.h"
 #include "rwkv_dfa.h"
+#include "rwkv_pda.h"
 #include "safetensors.hpp"
 
 using namespace rwkv;
@@ -403,6 +404,14 @@ struct rwkv_engine {
     int gen_constraint_state(int slot);
     void gen_drop_dfa_buf(int slot) { if (gen_dfa_buf[(size_t)slot]) { (void)hipFree(gen_dfa_buf[(size_t)slot]); gen_dfa_buf[(size_t)slot] = nullptr; } }
     bool gen_any_dfa(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_dfa[(size_t)b]) return true; return false; }
+    // the stack-automaton constraint (rwkv_gen_set_pda): beside d_gen_dfa, one GenPda per slot; a slot holds a DFA or a stack constraint, never both
+    GenPda *d_gen_pda = nullptr;
+    std::vector<char> gen_has_pda;                               // per slot: it carries a stack constraint (host knowledge: selects the kernels of a step)
+    std::vector<void *> gen_pda_buf;                             // per slot: next | act | flags on the device; not in `allocs`: a new constraint replaces it
+    void gen_set_pda(int slot, const rwkv_pda *pda, int state, const uint16_t *stack, int depth, int halt_mode);
+    void gen_pda_config(int slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth);
+    void gen_drop_pda_buf(int slot) { if (gen_pda_buf[(size_t)slot]) { (void)hipFree(gen_pda_buf[(size_t)slot]); gen_pda_buf[(size_t)slot] = nullptr; } }
+    bool gen_any_pda(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_pda[(size_t)b]) return true; return false; }
     bool gen_any_stops(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_stops[(size_t)b]) return true; return false; }
     float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
     float **d_gen_shadow = nullptr;
@@ -427,14 +436,15 @@ struct rwkv_engine {
         gen_armed[(size_t)slot] = 0;
         gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
         gen_has_dfa[(size_t)slot] = 0;                             // likewise; the table's buffer is freed by the next arm / constraint / the destructor
+        gen_has_pda[(size_t)slot] = 0;                             // likewise
         gen_prompt[(size_t)slot].clear();
         gen_ppos[(size_t)slot] = 0;
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn) const;
+    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda) const;
     unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn);
+    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish, int n_top = 0,
@@ -475,6 +485,7 @@ struct rwkv_engine {
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
         for (void *p : gen_dfa_buf) if (p) (void)hipFree(p);
+        for (void *p : gen_pda_buf) if (p) (void)hipFree(p);
         if (d_tok_end) (void)hipFree(d_tok_end);
         if (d_tok_off) (void)hipFree(d_tok_off);
         if (d_tok_bytes) (void)hipFree(d_tok_bytes);
@@ -1631,6 +1642,10 @@ void rwkv_engine::gen_init() {
     gen_dfa_buf.assign(B, nullptr);
     d_gen_dfa = dalloc<GenDfa>(B);
     HIP_CHECK(hipMemset(d_gen_dfa, 0, B * sizeof(GenDfa)));
+    gen_has_pda.assign(B, 0);
+    gen_pda_buf.assign(B, nullptr);
+    d_gen_pda = dalloc<GenPda>(B);
+    HIP_CHECK(hipMemset(d_gen_pda, 0, B * sizeof(GenPda)));
     d_gen_stop = dalloc<GenStop>(B);
     HIP_CHECK(hipMemset(d_gen_stop, 0, B * sizeof(GenStop)));
     gen_prompt.assign(B, {});
@@ -1698,17 +1713,20 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     HIP_CHECK(hipMemcpyAsync(d_gen + b, &g, sizeof(GenSlot), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipMemsetAsync(&d_gen_stop[b].n_str, 0, 2 * sizeof(int), s_main));   // re-arming clears the stop strings and their buffer
     HIP_CHECK(hipMemsetAsync(d_gen_dfa + b, 0, sizeof(GenDfa), s_main));             // ... and the constraint
+    HIP_CHECK(hipMemsetAsync(d_gen_pda + b, 0, sizeof(GenPda), s_main));             // ... of either kind
     const int first = prompt ? 0 : (int)p.first_token;             // with a prompt the slot's first draw fills it
     HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     gen_host[b] = g;
     gen_has_stops[b] = 0;
     gen_has_dfa[b] = 0;
+    gen_has_pda[b] = 0;
     if (!gen_topn.empty() && gen_topn[b]) {                        // re-arming: the slot lists nothing until rwkv_gen_set_topn says so again
         gen_topn[b] = 0;
         HIP_CHECK(hipMemset(d_gen_topn_n + b, 0, sizeof(int)));
     }
     gen_drop_dfa_buf(slot);                                        // behind the synchronize: no step is in flight
+    gen_drop_pda_buf(slot);
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
     gen_armed[b] = 1;
@@ -1729,6 +1747,7 @@ void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens,
     if (total >= GEN_TOK_UNKNOWN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "token table: more than 2 GiB of bytes");
     for (char h : gen_has_stops) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has stop strings set");
     for (char h : gen_has_dfa) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a constraint set");
+    for (char h : gen_has_pda) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a stack constraint set");
     std::vector<unsigned> off(n + 1);
     size_t pos = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -1762,6 +1781,7 @@ void rwkv_engine::gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, i
     GenDfa h{};
     void *buf = nullptr;
     if (dfa) {
+        if (gen_has_pda[b]) throw RwkvError(RWKV_ERR_INVALID, "constraint: the slot has a stack constraint set (a slot holds one kind)");
         if (!d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs the token table: rwkv_gen_set_token_bytes");
         if (state < 1 || state >= dfa->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: state 0 (dead) or out of range");
         if (halt_mode != RWKV_DFA_HALT_FINAL && halt_mode != RWKV_DFA_HALT_ACCEPT) throw RwkvError(RWKV_ERR_INVALID, "constraint: unknown halt mode");
@@ -1799,6 +1819,66 @@ int rwkv_engine::gen_constraint_state(int slot) {
     HIP_CHECK(hipMemcpyAsync(&h, d_gen_dfa + b, sizeof(GenDfa), hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     return h.state;
+}
+
+// The stack-automaton constraint of an armed, unfinished slot (rwkv_gen_set_pda): the two planes and the flags go to the device, the GenPda
+// of the slot points at them and carries the configuration.  Between runs: the stream is idle, so the old table can go at once.
+void rwkv_engine::gen_set_pda(int slot, const rwkv_pda *pda, int state, const uint16_t *stack, int depth, int halt_mode) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs an armed, unfinished slot");
+    GenPda h{};
+    void *buf = nullptr;
+    if (pda) {
+        if (gen_has_dfa[b]) throw RwkvError(RWKV_ERR_INVALID, "constraint: the slot has a DFA constraint set (a slot holds one kind)");
+        if (!d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs the token table: rwkv_gen_set_token_bytes");
+        if (state < 1 || state >= pda->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: state 0 (dead) or out of range");
+        if (depth < 0 || depth > pda->max_depth || (depth && !stack)) throw RwkvError(RWKV_ERR_INVALID, "constraint: depth outside 0 .. max_depth, or a null stack");
+        for (int i = 0; i < depth; ++i)
+            if (stack[i] < 1 || stack[i] >= pda->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: a stack entry is no live state of the table");
+        if (halt_mode != RWKV_PDA_HALT_FINAL && halt_mode != RWKV_PDA_HALT_ACCEPT) throw RwkvError(RWKV_ERR_INVALID, "constraint: unknown halt mode");
+        if (!pda_never_stuck(*pda, state, stack, depth, tok_single))
+            throw RwkvError(RWKV_ERR_UNSUPPORTED, "constraint: a reachable state has no single-byte token with a plain transition that leads on (a row could be masked whole)");
+        const size_t tbytes = (size_t)pda->n_states * 256 * sizeof(uint16_t), fbytes = (size_t)pda->n_states;
+        HIP_CHECK(hipMalloc(&buf, 2 * tbytes + fbytes));
+        if (hipMemcpy(buf, pda->next.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy((char *)buf + tbytes, pda->act.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy((char *)buf + 2 * tbytes, pda->flags.data(), fbytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(buf);
+            throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the table failed");
+        }
+        h.next = (const unsigned short *)buf;
+        h.act = (const unsigned short *)((const char *)buf + tbytes);
+        h.flags = (const unsigned char *)buf + 2 * tbytes;
+        h.state = state;
+        h.depth = depth;
+        h.mode = halt_mode;
+        h.max_depth = pda->max_depth;
+        for (int i = 0; i < depth; ++i) h.stack[i] = stack[i];
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    if (hipMemcpy(d_gen_pda + b, &h, sizeof(GenPda), hipMemcpyHostToDevice) != hipSuccess) {
+        if (buf) (void)hipFree(buf);
+        throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the slot's entry failed");
+    }
+    gen_drop_pda_buf(slot);
+    gen_pda_buf[b] = buf;
+    gen_has_pda[b] = pda ? 1 : 0;
+}
+
+void rwkv_engine::gen_pda_config(int slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    *state = 0;
+    *depth = 0;
+    if (!gen_has_pda[b]) return;
+    GenPda h{};
+    HIP_CHECK(hipMemcpyAsync(&h, d_gen_pda + b, sizeof(GenPda), hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    *state = h.state;
+    *depth = std::min(std::max(h.depth, 0), (int)GEN_PDA_MAX_DEPTH);
+    for (size_t i = 0; i < std::min((size_t)*depth, cap); ++i) stack[i] = h.stack[i];
 }
 
 // `GenerateRequest::stop` (run.rs:899-932) of an armed, unfinished slot, and the bytes the caller's matcher holds after the tokens it handled itself
@@ -1863,7 +1943,7 @@ void rwkv_engine::gen_set_topn(int slot, int n) {
     gen_topn[b] = n;
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn) const {
+GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda) const {
     GenArgs a{};
     if (topn) {
         a.topn_n = d_gen_topn_n; a.top_ids = d_gen_top_ids; a.top_logp = d_gen_top_logp; a.tok_logp = d_gen_tok_logp;
@@ -1871,7 +1951,8 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn) const
     }
     if (stops) a.stops = d_gen_stop;
     if (dfa) { a.dfa = d_gen_dfa; a.tok_end = d_tok_end; }
-    if (stops || dfa) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
+    if (pda) a.pda = d_gen_pda;
+    if (stops || dfa || pda) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
     a.slots = d_gen; a.row_slot = dm.slot; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
     a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
     a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
@@ -1886,15 +1967,16 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
     if (a.topn_n) launch(FAM_SAMPLE, [&] { launch_gen_topn(a, s_main); });   // the raw rows: gen_pre edits the block in place
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
     if (a.dfa) launch(FAM_SAMPLE, [&] { launch_gen_mask(a, s_main); });   // `transform` (run.rs:676-679) of the constrained rows
+    if (a.pda) launch(FAM_SAMPLE, [&] { launch_gen_pda_mask(a, s_main); });   // ... and of the rows under a stack constraint
     launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T, stops, dfa, topn), needs);
+    gen_sample(gen_args(pl.T, stops, dfa, topn, pda), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
@@ -1904,6 +1986,7 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     const bool stops = gen_any_stops(rows);                        // a slot of this row set has stop strings: gen_post_kernel<., true>
     const bool dfa = gen_any_dfa(rows);                            // a slot of this row set has a constraint: gen_mask_kernel joins the step
     const bool topn = gen_any_topn(rows);                          // a slot of this row set lists: gen_topn_kernel joins the step
+    const bool pda = gen_any_pda(rows);                            // a slot of this row set has a stack constraint: gen_pda_mask_kernel joins the step
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
@@ -1912,13 +1995,13 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0);
+    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0) | (pda ? 1ull << 35 : 0);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn, pda); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn, pda); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -1944,7 +2027,7 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     step_max_rows = pl.max_rows();
     run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (pl.n_out > 0) {
-        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn));
+        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn), gen_any_pda(drawn));
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         gen_sample(a, gen_needs(drawn));
@@ -2640,6 +2723,19 @@ rwkv_status rwkv_gen_constraint_state(rwkv_engine *e, int32_t slot, int32_t *sta
         check_slot(e, slot);
         if (!state) throw RwkvError(RWKV_ERR_INVALID, "null state");
         *state = e->gen_constraint_state(slot);
+    });
+}
+rwkv_status rwkv_gen_set_pda(rwkv_engine *e, int32_t slot, const rwkv_pda *pda, int32_t state, const uint16_t *stack, int32_t depth, int32_t halt_mode) {
+    return guard([&] {
+        check_slot(e, slot);
+        e->gen_set_pda(slot, pda, state, stack, depth, halt_mode);
+    });
+}
+rwkv_status rwkv_gen_pda_config(rwkv_engine *e, int32_t slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!state || !depth || (cap && !stack)) throw RwkvError(RWKV_ERR_INVALID, "null state / depth / stack");
+        e->gen_pda_config(slot, state, stack, cap, depth);
     });
 }
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out) {

@@ -14,6 +14,7 @@ typedef unsigned short _Float16;
 
 #include "gen_stop.h"                // RWKV_HD, the stop-string matcher and its limits
 #include "gen_dfa.h"                 // the byte-automaton constraint: walk, allowed and halt predicates
+#include "gen_pda.h"                 // the stack-automaton constraint: token walk, commit and halt predicate
 
 namespace rwkv {
 
@@ -318,6 +319,14 @@ struct GenDfa {                     // one per slot, beside GenSlot: the slot's 
     int state;                      // the state behind every token the slot has emitted (written by gen_post)
     int mode;                       // GEN_DFA_HALT_*
 };
+struct alignas(16) GenPda {         // one per slot, beside GenDfa: the slot's stack-automaton constraint (gen_pda.h); a slot holds one or the other
+    unsigned short stack[GEN_PDA_MAX_DEPTH];   // the return states, bottom first (written by gen_post; staged in LDS by gen_pda_mask)
+    const unsigned short *next;     // [n_states][256] on the device, or null: the slot has no stack constraint
+    const unsigned short *act;      // [n_states][256]: 0 plain, GEN_PDA_POP, else the return state a push pushes
+    const unsigned char *flags;     // [n_states] GEN_PDA_ACCEPT | GEN_PDA_END
+    int state, depth;               // the configuration behind every token the slot has emitted (written by gen_post)
+    int mode, max_depth;            // GEN_PDA_HALT_*; 1 .. GEN_PDA_MAX_DEPTH
+};
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
     GenStop *stops;                 // [max_batch], or null: no slot of this step has stop strings (selects gen_post_kernel<., false>)
@@ -346,6 +355,7 @@ struct GenArgs {
     unsigned *top_ids; float *top_logp;   // [steps][max_batch][TOPN_MAX] output ring of this run
     float *tok_logp;                // [steps][max_batch] raw ln-probability of the emitted token
     float *side_ms, *side_rows;     // [max_batch][2], [max_batch][V]: (m, ln S) and the raw row of every logits row that lists (gen_topn -> gen_post)
+    GenPda *pda;                    // [max_batch], or null: no slot of this step has a stack constraint (gen_pda_mask is not launched, gen_post skips it)
 };
 RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
@@ -357,6 +367,7 @@ RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, 
 void launch_gen_pre(const GenArgs &a, hipStream_t s);
 void launch_gen_topn(const GenArgs &a, hipStream_t s);                                                               // a.topn_n != null
 void launch_gen_mask(const GenArgs &a, hipStream_t s);                                                               // a.dfa != null
+void launch_gen_pda_mask(const GenArgs &a, hipStream_t s);                                                           // a.pda != null
 void launch_gen_post(const GenArgs &a, hipStream_t s);
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);
 void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T > 0

@@ -3935,6 +3935,8 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 //   gen_mask    only in a step in which a slot has a byte-automaton constraint (rwkv_gen_set_constraint, gen_dfa.h): `Formatter::transform`
 //               (run.rs:676-679) on the device.  Every token id of a constrained row walks its bytes from the slot's state; the logit of
 //               a token that is not allowed becomes -inf, and the state each token ends in is kept for gen_post
+//   gen_pda_mask only in a step in which a slot has a stack-automaton constraint (rwkv_gen_set_pda, gen_pda.h): the same `transform` for a
+//               configuration (state, stack); keeps nothing for gen_post, which commits the drawn token by a serial walk of its own
 //   nucleus_kernel, as it is
 //   gen_post    the tail of `sample` (nucleus.rs:104-119 / mirostat.rs:85-87), the token into the feedback buffer and the output
 //               ring, stop tokens and max_tokens (run.rs:855, 905-917); with STOPS, the slot's stop STRINGS over the decoded bytes (run.rs:899-932, gen_stop.h)
@@ -4035,6 +4037,38 @@ __device__ __forceinline__ bool gen_dfa_update(const GenArgs &a, int row, int sl
     d.state = (int)gen_dfa_advance((unsigned)d.state, e);
     return gen_dfa_halt(e, e ? d.flags[e] : (unsigned char)0, d.mode);
 }
+// gen_pda_mask: `Formatter::transform` of the rows whose slot has a STACK constraint (rwkv_gen_set_pda, gen_pda.h), launched beside gen_mask
+// only in a step in which a slot has one.  One thread per token id, as in gen_mask_kernel; what a walk needs beyond the two table planes is
+// the slot's stack, which no token writes: its 128 bytes are staged in LDS once per block, and the at most GEN_PDA_TOKEN_SPAN entries a
+// token pushes itself live in a 128-bit shift register of the thread (gen_pda_token_walk: no dynamic indexing, nothing for scratch).
+// It writes -inf where a token is not allowed and nothing else: gen_post walks the one drawn token again on the real stack.
+template <bool MIXED>
+__global__ __launch_bounds__(256) void gen_pda_mask_kernel(GenArgs a) {
+    const int row = blockIdx.y;
+    const int slot = gen_slot_of<MIXED>(a, row);
+    if (a.slots[slot].finish) return;
+    const GenPda &d = a.pda[slot];
+    const unsigned short *next = d.next;
+    if (!next) return;                                             // block-uniform, like the return above: no thread waits at the barrier below
+    __shared__ unsigned short stack[GEN_PDA_MAX_DEPTH];
+    if (threadIdx.x < GEN_PDA_MAX_DEPTH / 2) ((unsigned *)stack)[threadIdx.x] = ((const unsigned *)d.stack)[threadIdx.x];
+    const unsigned short *act = d.act;
+    const int max_depth = d.max_depth, state = d.state, depth = min(max(d.depth, 0), GEN_PDA_MAX_DEPTH);
+    __syncthreads();
+    const int V = a.V;
+    float *x = a.logits + (long)row * V;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256)
+        if (!gen_pda_token_end(next, act, max_depth, (unsigned)state, stack, depth, a.tok_off, a.tok_bytes, a.n_tok, v).state) x[v] = -INFINITY;
+}
+// `Formatter::update` of a slot with a stack constraint for the token thread 0 just emitted: the serial walk of its bytes on the slot's real
+// stack (gen_pda_commit) and the halt predicate.  False for a slot without one.
+__device__ __forceinline__ bool gen_pda_update(const GenArgs &a, int slot, int tok) {
+    if (!a.pda) return false;
+    GenPda &d = a.pda[slot];
+    if (!d.next) return false;
+    return gen_pda_commit(d.next, d.act, d.flags, d.max_depth, d.mode, &d.state, d.stack, &d.depth, a.tok_off, a.tok_bytes, a.n_tok,
+                          (unsigned)tok < (unsigned)a.V ? tok : -1);
+}
 __device__ __forceinline__ unsigned gen_decay(unsigned pbits, int i, int tok, float decay, float freq, float pres) {
 #pragma clang fp contract(off)
     float p = __uint_as_float(pbits);
@@ -4111,7 +4145,7 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
     const int nstr = STOPS ? a.stops[slot].n_str : 0;
     if (nstr <= 0) {
         if (tid != 0) return;
-        const bool halt = gen_dfa_update(a, row, slot, tok);
+        const bool halt = gen_dfa_update(a, row, slot, tok) || gen_pda_update(a, slot, tok);   // a slot holds one kind or neither
         const bool stop_token = gen_emit<MIXED>(a, g, row, slot, tok, k);
         const bool stop = halt || stop_token;                      // `halt || stop_matched || stop_token`, run.rs:990
         const int fin = stop ? 1 : (g.emitted >= g.max_tokens ? 2 : 0);
@@ -4144,7 +4178,7 @@ __global__ __launch_bounds__(256) void gen_post_kernel(GenArgs a) {
         r = (tid & 4) ? gen_stop_merge(o, r) : gen_stop_merge(r, o);
         int keep_from = -1;                                        // >= 0: the slot goes on and its buffer becomes lds.buf[keep_from .. n)
         if (tid == 0) {
-            const bool halt = gen_dfa_update(a, row, slot, tok);
+            const bool halt = gen_dfa_update(a, row, slot, tok) || gen_pda_update(a, slot, tok);   // a slot holds one kind or neither
             const bool stop_token = gen_emit<MIXED>(a, g, row, slot, tok, k);
             const bool stop = halt || stop_token || unknown;
             const int fin = gen_stop_decide(stop, fits, r.matched != 0, g.emitted >= g.max_tokens);
@@ -4186,6 +4220,11 @@ void launch_gen_mask(const GenArgs &a, hipStream_t s) {
     const dim3 grid(min((a.V + 255) / 256, 256), a.n_rows);
     if (a.out_rows) hipLaunchKernelGGL(gen_mask_kernel<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_mask_kernel<false>, grid, dim3(256), 0, s, a);
+}
+void launch_gen_pda_mask(const GenArgs &a, hipStream_t s) {
+    const dim3 grid(min((a.V + 255) / 256, 256), a.n_rows);
+    if (a.out_rows) hipLaunchKernelGGL(gen_pda_mask_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_pda_mask_kernel<false>, grid, dim3(256), 0, s, a);
 }
 // a.stops != null selects the stop-string instantiation
 void launch_gen_post(const GenArgs &a, hipStream_t s) {

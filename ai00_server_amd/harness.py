@@ -123,13 +123,20 @@ def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = 
 
 
 def generate_resident(runtime, slot: int, prompt, max_tokens: int, sampler, seed: int = 0, stop_tokens=(), top_logprobs: int = 0,
-                      steps_per_run: int = 16) -> list:
+                      steps_per_run: int = 16, constraint=None, halt: int = 0) -> list:
     """One request through resident generation: `slot` is armed with the whole `prompt` (`Runtime.gen_arm_prompt`; `sampler` is the host
     sampler right after `init(prompt)`) and run until it finishes; nothing but token ids and a few numbers cross PCIe.  Returns one
     (token, prob) per emitted token; with `top_logprobs` = n > 0 (`Runtime.gen_set_topn`) one (token, logp, [(id, logp), ...]) instead:
     the token's ln-probability and the n most likely alternatives of the RAW model row (before penalties, bias and temperature), most
-    likely first, as an OpenAI-style `logprobs` object lists them.  Other armed slots ride along; their tokens are dropped here."""
+    likely first, as an OpenAI-style `logprobs` object lists them.  Other armed slots ride along; their tokens are dropped here.
+    `constraint` is a `runtime.Dfa` or a `runtime.Pda` (`Pda.json(...)` for "answer in JSON"), set from its start with halt mode `halt`;
+    it needs the token table (`Runtime.gen_set_token_bytes`)."""
     runtime.gen_arm_prompt(slot, prompt, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    if constraint is not None:
+        if hasattr(constraint, "max_depth"):
+            runtime.gen_set_pda(slot, constraint, halt=halt)
+        else:
+            runtime.gen_set_constraint(slot, constraint, halt=halt)
     if top_logprobs:
         runtime.gen_set_topn(slot, top_logprobs)
     out = []
@@ -253,6 +260,34 @@ class DfaFormatter:
         if not self.accepting[end]:
             return False
         return self.halt == 1 or not self.trans[end].any()
+
+
+class PdaFormatter:
+    """The `Formatter` trait over a byte automaton with a return-state stack (`runtime.Pda`) — the host half of what `Runtime.gen_set_pda`
+    runs on the device, for the per-token path: `transform()` is the `allow` mask of the configuration (rwkv_pda_allow), `update(token) ->
+    halt` commits the token and says whether the request stops.  A token that is not allowed leaves the configuration where it was and
+    does not halt; the mask decides what is allowed, so the span rule holds here as on the device."""
+
+    def __init__(self, pda, table, num_vocab: int, state: int | None = None, stack=(), halt: int = 0):
+        self.pda, self.table, self.num_vocab, self.halt = pda, list(table), int(num_vocab), int(halt)
+        self.next, self.act, self.accepting = pda.table()
+        self.state, self.stack = pda.start if state is None else int(state), [int(x) for x in stack]
+
+    def transform(self, mask=None):
+        allow = self.pda.allow(self.state, self.stack, self.table, self.num_vocab)
+        if mask is not None:
+            mask[:] = allow
+            return mask
+        return allow
+
+    def update(self, token: int) -> bool:
+        if not 0 < token < self.num_vocab or not self.transform()[token]:
+            return False
+        self.state, self.stack = self.pda.walk(self.table[token], self.state, self.stack)
+        if self.stack or not self.accepting[self.state]:
+            return False
+        row_n, row_a = self.next[self.state], self.act[self.state]
+        return self.halt == 1 or not ((row_a != 0xFFFF) & (row_n != 0)).any()
 
 
 class StopMatcher:

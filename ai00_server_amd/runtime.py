@@ -130,6 +130,21 @@ ABI_SYMBOLS = {
     "rwkv_dfa_check_live": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_size_t]),
     "rwkv_gen_set_constraint": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "rwkv_gen_constraint_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "rwkv_pda_from_table": (C.c_int32, [C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_void_p)]),
+    "rwkv_pda_json": (C.c_int32, [C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rwkv_pda_free": (None, [C.c_void_p]),
+    "rwkv_pda_num_states": (C.c_int32, [C.c_void_p]),
+    "rwkv_pda_start": (C.c_int32, [C.c_void_p]),
+    "rwkv_pda_max_depth": (C.c_int32, [C.c_void_p]),
+    "rwkv_pda_table": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    "rwkv_pda_walk": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_uint16), C.POINTER(C.c_int32)]),
+    "rwkv_pda_allow": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t,
+                                   C.POINTER(C.c_uint8), C.c_size_t]),
+    "rwkv_pda_check_live": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_size_t]),
+    "rwkv_gen_set_pda": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.c_int32]),
+    "rwkv_gen_pda_config": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_int32)]),
     "rwkv_plan_chunk": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "rwkv_state_len": (C.c_size_t, [C.c_void_p]),
     "rwkv_state_shape": (None, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -357,6 +372,106 @@ class Dfa:
         out = np.empty(int(num_vocab), np.uint8)
         _check(lib().rwkv_dfa_allow(self._h, int(state), data.ctypes.data_as(C.POINTER(C.c_uint8)), lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None,
                                     lens.size, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+
+PDA_MAX_STATES, PDA_MAX_DEPTH, PDA_TOKEN_SPAN, PDA_POP = 4096, 64, 8, 0xFFFF      # RWKV_PDA_*
+
+
+class PdaHalt(enum.IntEnum):     # RWKV_PDA_HALT_*
+    Final = 0                    # halt when the new configuration accepts (empty stack) and its state is END
+    Accept = 1                   # halt the first time the new configuration accepts
+
+
+class PdaJson(enum.IntFlag):     # RWKV_PDA_JSON_*
+    Object = 1                   # the top-level value must be an object or an array
+    Compact = 2                  # no whitespace outside strings
+
+
+def _stack_array(stack):
+    s = np.ascontiguousarray(list(stack) if stack is not None else [], dtype=np.uint16).reshape(-1)
+    return s, (s.ctypes.data_as(C.POINTER(C.c_uint16)) if s.size else None)
+
+
+class Pda:
+    """A byte automaton with a return-state stack (rwkv_pda): the constraint resident generation masks on the device for NESTED formats,
+    JSON above all, and the same `Formatter` for the per-token path (`allow`).  State 0 is dead; a configuration is (state, stack).
+    `Pda.json(flags, max_depth)` is RFC 8259, `Pda.from_table` takes any compiler's two planes (`act`: 0 plain, PDA_POP pop, else the
+    return state a push pushes).  Host only, needs no GPU.  It is not the reference's kbnf: general grammars keep the per-token path."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def json(cls, flags: int = 0, max_depth: int = PDA_MAX_DEPTH) -> "Pda":
+        h = C.c_void_p()
+        _check(lib().rwkv_pda_json(int(flags), int(max_depth), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_table(cls, next, act, accepting, start: int = 1, max_depth: int = PDA_MAX_DEPTH) -> "Pda":
+        n = np.ascontiguousarray(next, dtype=np.uint16).reshape(-1, 256)
+        a = np.ascontiguousarray(act, dtype=np.uint16).reshape(-1, 256)
+        f = np.ascontiguousarray(accepting, dtype=np.uint8).reshape(-1)
+        if f.size != n.shape[0] or a.shape != n.shape:
+            raise RwkvError(-1, "pda: two planes of one shape and one accepting flag per row")
+        h = C.c_void_p()
+        _check(lib().rwkv_pda_from_table(n.ctypes.data_as(C.POINTER(C.c_uint16)), a.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                         f.ctypes.data_as(C.POINTER(C.c_uint8)), n.shape[0], int(start), int(max_depth), C.byref(h)))
+        return cls(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().rwkv_pda_free(self._h)
+            except Exception:
+                pass
+
+    @property
+    def num_states(self) -> int:
+        return int(lib().rwkv_pda_num_states(self._h))
+
+    @property
+    def start(self) -> int:
+        return int(lib().rwkv_pda_start(self._h))
+
+    @property
+    def max_depth(self) -> int:
+        return int(lib().rwkv_pda_max_depth(self._h))
+
+    def table(self):
+        """(next uint16 [num_states, 256], act uint16 [num_states, 256], accepting uint8 [num_states])"""
+        n = self.num_states
+        t, a, f = np.empty((n, 256), np.uint16), np.empty((n, 256), np.uint16), np.empty(n, np.uint8)
+        _check(lib().rwkv_pda_table(self._h, t.ctypes.data_as(C.POINTER(C.c_uint16)), a.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                    f.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return t, a, f
+
+    def walk(self, data: bytes, state: int | None = None, stack=()):
+        """(state, stack) `data` behind the configuration (default: the start state, empty stack); state 0 once the walk died.  Bytes,
+        not tokens: the span rule of `allow` does not apply."""
+        s, sp = _stack_array(stack)
+        out = (C.c_uint16 * PDA_MAX_DEPTH)()
+        q, d = C.c_int32(0), C.c_int32(0)
+        _check(lib().rwkv_pda_walk(self._h, int(self.start if state is None else state), sp, s.size, bytes(data), len(data), C.byref(q), out, C.byref(d)))
+        return int(q.value), [int(x) for x in out[:d.value]]
+
+    def check_live(self, table, state: int | None = None, stack=()):
+        """The liveness rule of `gen_set_pda` on the host (rwkv_pda_check_live): raises RwkvError(-3) when a state the request can enter has
+        no single-byte token of `table` with a plain transition that leads on."""
+        data, lens = _token_table_arrays(table)
+        s, sp = _stack_array(stack)
+        _check(lib().rwkv_pda_check_live(self._h, int(self.start if state is None else state), sp, s.size,
+                                         lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None, data.ctypes.data_as(C.POINTER(C.c_uint8)), lens.size))
+
+    def allow(self, state: int, stack, table, num_vocab: int) -> np.ndarray:
+        """The `num_vocab`-byte mask `infer_sample` takes as `allow` (rwkv_pda_allow): token v is allowed in (state, stack) iff it is in
+        `table`, known, non-empty, not id 0, and its bytes lead to a live state without owning more than PDA_TOKEN_SPAN stack entries."""
+        data, lens = _token_table_arrays(table)
+        s, sp = _stack_array(stack)
+        out = np.empty(int(num_vocab), np.uint8)
+        _check(lib().rwkv_pda_allow(self._h, int(state), sp, s.size, data.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    lens.ctypes.data_as(C.POINTER(C.c_int32)) if lens.size else None, lens.size, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
         return out
 
 
@@ -872,6 +987,25 @@ class Runtime:
         st = C.c_int32(0)
         _check(lib().rwkv_gen_constraint_state(self._h, int(slot), C.byref(st)))
         return int(st.value)
+
+    def gen_set_pda(self, slot: int, pda: "Pda | None", state: int | None = None, stack=(), halt: "PdaHalt" = PdaHalt.Final):
+        """The stack-automaton constraint of an armed, unfinished slot (rwkv_gen_set_pda), set between runs: from then on the slot's row is
+        masked, the drawn token committed to its configuration and the halt tested on the device.  (`state`, `stack`) defaults to the start
+        state with an empty stack (right after `gen_arm_prompt`); after `gen_arm` or a hand-over it is the caller's own.  `pda=None` clears
+        it.  A slot holds a `Dfa` or a `Pda`, not both."""
+        if pda is None:
+            _check(lib().rwkv_gen_set_pda(self._h, int(slot), None, 0, None, 0, 0))
+            return
+        s, sp = _stack_array(stack)
+        _check(lib().rwkv_gen_set_pda(self._h, int(slot), pda._h, int(pda.start if state is None else state), sp, s.size, int(halt)))
+
+    def gen_pda_config(self, slot: int):
+        """(state, stack) behind every token the slot has emitted (rwkv_gen_pda_config; (0, []) without a stack constraint): what a caller
+        that goes on per token hands its `harness.PdaFormatter`."""
+        out = (C.c_uint16 * PDA_MAX_DEPTH)()
+        q, d = C.c_int32(0), C.c_int32(0)
+        _check(lib().rwkv_gen_pda_config(self._h, int(slot), C.byref(q), out, PDA_MAX_DEPTH, C.byref(d)))
+        return int(q.value), [int(x) for x in out[:d.value]]
 
     def gen_set_topn(self, slot: int, n: int):
         """An armed, unfinished slot lists its `n` (0 .. TOPN_MAX; 0 = off) most likely tokens of the RAW model row — before penalties, bias,

@@ -45,7 +45,10 @@ extern "C" {
                               *    format constraint is masked and advanced on the device inside the resident step
                               *    additive under 9: rwkv_topn_rows, rwkv_infer_topn, rwkv_gen_set_topn, rwkv_gen_run_topn, RWKV_TOPN_MAX, RWKV_TOPN_NONE: the
                               *    n most likely tokens of a row and their ln-probabilities are listed on the device (host rows, prefill, resident
-                              *    generation), 8 n bytes per row come back instead of the row */
+                              *    generation), 8 n bytes per row come back instead of the row
+                              *    additive under 9: rwkv_pda_* (byte automata with a return-state stack, host only; rwkv_pda_json is RFC 8259),
+                              *    rwkv_gen_set_pda, rwkv_gen_pda_config: a NESTED format constraint ("answer in JSON") is masked and advanced on the
+                              *    device inside the resident step */
 
 typedef int32_t rwkv_status;
 enum {
@@ -338,7 +341,9 @@ rwkv_status rwkv_infer_sample(rwkv_engine *e, const rwkv_slot_input *in, const r
  *    A slot that finishes — whatever the reason — leaves its buffer as it was before its last token.
  *  - FORMAT CONSTRAINTS: a formatter that needs the host between two tokens — kbnf's context-free grammars, sampler/bnf.rs — stays
  *    refused here; what this mode offers instead is a byte-level DFA (rwkv_dfa_*, rwkv_gen_set_constraint below), masked and advanced on
- *    the device.  It is a second implementation of the `Formatter` trait (bnf.rs:34-48) for REGULAR constraints, not kbnf and no port of it.
+ *    the device, and a byte automaton with a return-state stack (rwkv_pda_*, rwkv_gen_set_pda below) for nesting, JSON above all.  They
+ *    are a second and a third implementation of the `Formatter` trait (bnf.rs:34-48), for REGULAR constraints and for what a return-state
+ *    stack expresses; neither is kbnf or a port of it, and context-free grammars beyond that keep the per-token path.
  *  - Not available in this mode (RWKV_ERR_UNSUPPORTED from rwkv_gen_arm): a host-computed formatter mask (`allow` must be NULL,
  *    run.rs:676-679 — keep using rwkv_infer_sample for a grammar), top_k > 256 (Nucleus / Typical) unless `reserved` carries
  *    RWKV_GEN_WIDE_TOP_K, more than RWKV_GEN_MAX_STOP stop tokens, num_vocab > 65536.
@@ -502,10 +507,93 @@ rwkv_status rwkv_dfa_check_live(const rwkv_dfa *d, int32_t state, int32_t halt_m
  * RWKV_ERR_INVALID: the slot is not armed or has finished, no token table (rwkv_gen_set_token_bytes), state 0 or out of range, a bad
  * halt_mode.  RWKV_ERR_UNSUPPORTED: LIVENESS — every live state reachable from `state` in which the slot can come to rest (one that does
  * not halt) must have a SINGLE-BYTE token of the table that leads to a live state, which is what guarantees that a row is never all -inf
- * (the World vocabulary holds all 256 single-byte tokens).  rwkv_gen_set_token_bytes is refused while any slot has a constraint. */
+ * (the World vocabulary holds all 256 single-byte tokens).  rwkv_gen_set_token_bytes is refused while any slot has a constraint.
+ * Also RWKV_ERR_INVALID: the slot has a stack constraint (rwkv_gen_set_pda below) — a slot holds one kind or the other. */
 rwkv_status rwkv_gen_set_constraint(rwkv_engine *e, int32_t slot, const rwkv_dfa *dfa, int32_t state, int32_t halt_mode);
 /* The state behind every token the slot has emitted, the last one included (0 for a slot without a constraint).  Waits for the device. */
 rwkv_status rwkv_gen_constraint_state(rwkv_engine *e, int32_t slot, int32_t *state);
+
+/* ---- `Formatter` for NESTED constraints: a byte automaton whose `{` / `[` transitions push a return state and whose `}` / `]` transitions
+ * pop one.  A third implementation of the trait, beside kbnf on the host and the DFA above; NOT kbnf and no port of it.  It exists because
+ * nesting has no finite automaton of useful size (the object-or-array context of every level doubles the states of a DFA), and "answer in
+ * JSON" is the request an OpenAI-style server gets most.  General context-free grammars keep the per-token path.
+ *   - TABLES: states 0 .. n_states - 1, n_states <= RWKV_PDA_MAX_STATES.  State 0 is DEAD: both of its rows are zero and it accepts
+ *     nothing.  Two uint16 planes [n_states][256] (row-major), `next` and `act`, accepting[n_states], a start state, and max_depth in
+ *     1 .. RWKV_PDA_MAX_DEPTH.
+ *   - TRANSITIONS, for state q and byte b:  act == 0 is PLAIN: go to next; next == 0 is dead.  act == RWKV_PDA_POP is a POP: the next state
+ *     is the popped entry; an empty stack is dead; `next` is ignored.  Any other act is a PUSH: act must be a live state id and next must be
+ *     non-zero; act is pushed as the return state and the automaton goes to next; a stack that already holds max_depth entries is dead.
+ *   - CONFIGURATION: (state, stack of uint16, bottom first).  LIVE: state != 0.  ACCEPTS: accepting[state] and an empty stack.  END, a
+ *     per-state flag computed on the host: no plain or push entry with a live target (pops do not count: the stack is empty where it matters).
+ *   - ALLOWED follows the DFA rule — token v is in the table, known, non-empty and not id 0, and walking its bytes ends LIVE — with one
+ *     addition, THE SPAN RULE: while a token is walked, let `low` be the smallest depth reached so far; a push that would make
+ *     depth - low > RWKV_PDA_TOKEN_SPAN makes the token not allowed.  Host (rwkv_pda_allow) and device apply the same rule, so it is
+ *     part of the language, not an implementation limit.  (rwkv_pda_walk walks BYTES and knows no tokens: no span rule there.)
+ *   - ADVANCE: a drawn token that is not allowed leaves the configuration where it was and does not halt.
+ *   - HALT: RWKV_PDA_HALT_FINAL — the new configuration ACCEPTS and its state is END; RWKV_PDA_HALT_ACCEPT — it ACCEPTS.  Or-ed into the
+ *     stop predicate exactly where the DFA's halt is; the STATE RULE of rwkv_gen_run is unchanged.
+ *   - LIVENESS, checked when the constraint is set (and by rwkv_pda_check_live), else RWKV_ERR_UNSUPPORTED.  Conservative and static,
+ *     O(states x 256): from the configuration, every state any sequence of transitions could enter is collected (plain and push targets,
+ *     and every return state a collected state pushes), each with one bit: whether it is only ever entered WITH AN EMPTY STACK.  Every
+ *     collected state must have a single-byte token of the table with a PLAIN live transition — plain works at every depth, max_depth
+ *     included, where every push is dead.  A state only ever entered with an empty stack may use a PUSH instead (it cannot fail there:
+ *     max_depth >= 1).  The only exempt state is one that is only ever entered ACCEPTING-and-END (accepting, END, empty stack: it halts
+ *     in both modes), and never the configuration's own state.  This guarantees that no row is all -inf at any depth.  The JSON automaton
+ *     below satisfies it over the World vocabulary, which holds all 256 single-byte tokens.
+ * Handles are immutable and thread-safe; every rwkv_pda_* function is a pure host function, no device needed. */
+#define RWKV_PDA_MAX_STATES 4096
+#define RWKV_PDA_MAX_DEPTH 64
+#define RWKV_PDA_TOKEN_SPAN 8
+#define RWKV_PDA_POP 65535                    /* 0xFFFF in `act` */
+enum { RWKV_PDA_HALT_FINAL = 0, RWKV_PDA_HALT_ACCEPT = 1 };
+enum { RWKV_PDA_JSON_OBJECT = 1, RWKV_PDA_JSON_COMPACT = 2 };     /* flags of rwkv_pda_json */
+typedef struct rwkv_pda rwkv_pda;
+/* any compiler's output (a schema-to-automaton compiler may target it).  RWKV_ERR_INVALID: the rwkv_dfa_from_table conditions (state 0
+ * not dead in either plane, a target >= n_states, start outside [1, n_states), n_states < 2, a NULL array), an act that is neither 0,
+ * RWKV_PDA_POP nor a live state id, a push with next == 0, max_depth outside 1 .. RWKV_PDA_MAX_DEPTH.  RWKV_ERR_UNSUPPORTED:
+ * n_states > RWKV_PDA_MAX_STATES.  Nothing is trimmed or renumbered.  Copied. */
+rwkv_status rwkv_pda_from_table(const uint16_t *next, const uint16_t *act, const uint8_t *accepting, int32_t n_states, int32_t start,
+                                int32_t max_depth, rwkv_pda **out);
+/* RFC 8259 over bytes.  Strings hold well-formed UTF-8 only (Unicode table 3-7, the rule rwkv_dfa_compile uses for [^...]) and no byte
+ * below 0x20; escapes are \" \\ \/ \b \f \n \r \t \uXXXX.  Numbers are -?(0|[1-9]\d*)(\.\d+)?([eE][+-]?\d+)?; a number has no terminator,
+ * so the states it may end in take over the row of the state behind a value.  Nesting deeper than max_depth is refused (dead).
+ *   RWKV_PDA_JSON_OBJECT   the top-level value must be an object or an array (without it `1` accepts behind its first digit, which
+ *                          together with RWKV_PDA_HALT_ACCEPT is rarely wanted)
+ *   RWKV_PDA_JSON_COMPACT  no whitespace outside strings (the usual failure of JSON mode is a run of newlines until max_tokens)
+ * The numbering is canonical — breadth-first from the start state (= 1), bytes ascending, a push's target before its return state — one
+ * table per `flags`, independent of max_depth.  RWKV_ERR_INVALID: an unknown flag, max_depth out of range. */
+rwkv_status rwkv_pda_json(uint32_t flags, int32_t max_depth, rwkv_pda **out);
+void rwkv_pda_free(rwkv_pda *p);
+int32_t rwkv_pda_num_states(const rwkv_pda *p);
+int32_t rwkv_pda_start(const rwkv_pda *p);
+int32_t rwkv_pda_max_depth(const rwkv_pda *p);
+/* reads the table back: next[num_states * 256], act[num_states * 256], accepting[num_states] (each may be NULL) */
+rwkv_status rwkv_pda_table(const rwkv_pda *p, uint16_t *next, uint16_t *act, uint8_t *accepting);
+/* the configuration `n` bytes behind (state, stack[0 .. depth)): *state_out is 0 once the walk died (the stack is then what it was at the
+ * byte that killed it).  stack_out has room for max_depth entries and may be `stack` itself.  RWKV_ERR_INVALID: a state, depth or stack
+ * entry out of range. */
+rwkv_status rwkv_pda_walk(const rwkv_pda *p, int32_t state, const uint16_t *stack, int32_t depth, const uint8_t *bytes, size_t n,
+                          int32_t *state_out, uint16_t *stack_out, int32_t *depth_out);
+/* `transform` on the host: the num_vocab-byte mask rwkv_sample_params.allow takes, by the ALLOWED rule above (the span rule included), so
+ * the per-token path gets the same formatter and a request can be handed over in either direction (rwkv_gen_pda_config). */
+rwkv_status rwkv_pda_allow(const rwkv_pda *p, int32_t state, const uint16_t *stack, int32_t depth, const uint8_t *bytes, const int32_t *lens,
+                           size_t n_tokens, uint8_t *allow, size_t num_vocab);
+/* the LIVENESS rule as a pure host function, over a token table given as to rwkv_gen_set_token_bytes (note the order: lens first) */
+rwkv_status rwkv_pda_check_live(const rwkv_pda *p, int32_t state, const uint16_t *stack, int32_t depth, const int32_t *lens, const uint8_t *bytes,
+                                size_t n_tokens);
+/* The stack constraint of an armed, unfinished slot, set between runs like rwkv_gen_set_constraint; the table is copied to the device,
+ * `pda` may be freed on return.  Any configuration is accepted: the start state with an empty stack after rwkv_gen_arm_prompt, or the
+ * caller's own after rwkv_gen_arm or a hand-over.  pda == NULL clears the constraint; re-arming a slot and everything that disarms it
+ * clear it too.  From then on every step masks the slot's row on the device, commits the drawn token to the slot's configuration and tests
+ * HALT; a step in which no slot has a stack constraint launches what it launched before.
+ * A slot holds a DFA or a stack constraint: setting one while the other is set is RWKV_ERR_INVALID.  Also RWKV_ERR_INVALID: the slot is not
+ * armed or has finished, no token table, state 0 or out of range, depth outside 0 .. max_depth, a stack entry that is no live state, a bad
+ * halt_mode.  RWKV_ERR_UNSUPPORTED: LIVENESS.  rwkv_gen_set_token_bytes is refused while any slot has a constraint of either kind. */
+rwkv_status rwkv_gen_set_pda(rwkv_engine *e, int32_t slot, const rwkv_pda *pda, int32_t state, const uint16_t *stack, int32_t depth,
+                             int32_t halt_mode);
+/* The configuration behind every token the slot has emitted, the last one included: *state (0 for a slot without a stack constraint),
+ * *depth, and min(*depth, cap) entries of the stack, bottom first (stack may be NULL with cap = 0).  Waits for the device. */
+rwkv_status rwkv_gen_pda_config(rwkv_engine *e, int32_t slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth);
 
 /* ---- top-n lists in resident generation: what else the model considered, per emitted token, without the row leaving the device.
  * The distribution is the RAW MODEL ROW — what the head wrote, before penalties, bias, temperature and any constraint mask — the definition

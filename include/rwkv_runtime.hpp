@@ -78,6 +78,51 @@ class Dfa {
     std::shared_ptr<rwkv_dfa> d_;
 };
 
+// A byte automaton with a return-state stack (rwkv_pda): the NESTED format constraint resident generation masks on the device
+// (Runtime::gen_set_pda) — Pda::json is RFC 8259, "answer in JSON" — and the same `Formatter` for the per-token path (allow).  A
+// configuration is (state, stack).  Not kbnf: general context-free grammars keep the per-token path.  Host only.
+class Pda {
+   public:
+    struct Config {
+        int32_t state = 0;
+        std::vector<uint16_t> stack;                 // bottom first
+    };
+    static Pda json(uint32_t flags = 0, int32_t max_depth = RWKV_PDA_MAX_DEPTH) {
+        rwkv_pda *p = nullptr;
+        check(rwkv_pda_json(flags, max_depth, &p));
+        return Pda(p);
+    }
+    static Pda from_table(const std::vector<uint16_t> &next, const std::vector<uint16_t> &act, const std::vector<uint8_t> &accepting, int32_t start = 1,
+                          int32_t max_depth = RWKV_PDA_MAX_DEPTH) {
+        if (next.size() != accepting.size() * 256 || act.size() != next.size()) throw std::invalid_argument("Pda::from_table: two planes of 256 entries per state");
+        rwkv_pda *p = nullptr;
+        check(rwkv_pda_from_table(next.data(), act.data(), accepting.data(), (int32_t)accepting.size(), start, max_depth, &p));
+        return Pda(p);
+    }
+    int32_t num_states() const { return rwkv_pda_num_states(p_.get()); }
+    int32_t start() const { return rwkv_pda_start(p_.get()); }
+    int32_t max_depth() const { return rwkv_pda_max_depth(p_.get()); }
+    Config walk(const Config &from, const uint8_t *bytes, size_t n) const {
+        Config to;
+        to.stack.resize(RWKV_PDA_MAX_DEPTH);
+        int32_t depth = 0;
+        check(rwkv_pda_walk(p_.get(), from.state, from.stack.data(), (int32_t)from.stack.size(), bytes, n, &to.state, to.stack.data(), &depth));
+        to.stack.resize((size_t)std::max(depth, 0));
+        return to;
+    }
+    // the num_vocab-byte mask rwkv_sample_params.allow takes; `bytes` / `lens` as for Runtime::gen_set_token_bytes
+    std::vector<uint8_t> allow(const Config &at, const uint8_t *bytes, const int32_t *lens, size_t n_tokens, size_t num_vocab) const {
+        std::vector<uint8_t> out(num_vocab);
+        check(rwkv_pda_allow(p_.get(), at.state, at.stack.data(), (int32_t)at.stack.size(), bytes, lens, n_tokens, out.data(), num_vocab));
+        return out;
+    }
+    const rwkv_pda *raw() const { return p_.get(); }
+
+   private:
+    explicit Pda(rwkv_pda *p) : p_(p, rwkv_pda_free) {}
+    std::shared_ptr<rwkv_pda> p_;
+};
+
 class Runtime;
 class TensorGpu {                            // device-resident state snapshot (`state.read`)
    public:
@@ -338,6 +383,21 @@ class Runtime {
         int32_t state = 0;
         check(rwkv_gen_constraint_state(e_.get(), slot, &state));
         return state;
+    }
+    // The stack constraint of an armed, unfinished slot (rwkv_gen_set_pda): masked, committed and halted on the device.  `at`: {pda.start(), {}}
+    // after gen_arm_prompt; the caller's own configuration after gen_arm or a hand-over.  A slot holds a Dfa or a Pda, not both.
+    void gen_set_pda(int slot, const Pda &pda, const Pda::Config &at, int32_t halt_mode = RWKV_PDA_HALT_FINAL) {
+        check(rwkv_gen_set_pda(e_.get(), slot, pda.raw(), at.state, at.stack.data(), (int32_t)at.stack.size(), halt_mode));
+    }
+    void gen_clear_pda(int slot) { check(rwkv_gen_set_pda(e_.get(), slot, nullptr, 0, nullptr, 0, 0)); }
+    // the configuration behind every token the slot has emitted: what a caller that goes on per token starts its own formatter from
+    Pda::Config gen_pda_config(int slot) {
+        Pda::Config c;
+        c.stack.resize(RWKV_PDA_MAX_DEPTH);
+        int32_t depth = 0;
+        check(rwkv_gen_pda_config(e_.get(), slot, &c.state, c.stack.data(), c.stack.size(), &depth));
+        c.stack.resize((size_t)std::max(depth, 0));
+        return c;
     }
     struct Generated {
         std::vector<uint32_t> tokens;                // [n_steps][max_batch], 0xFFFFFFFF where a slot emitted nothing

@@ -42,6 +42,14 @@ pub const RWKV_GEN_WIDE_TOP_K: u32 = 1;
 pub const RWKV_DFA_MAX_STATES: usize = 4096;
 pub const RWKV_DFA_HALT_FINAL: i32 = 0;
 pub const RWKV_DFA_HALT_ACCEPT: i32 = 1;
+pub const RWKV_PDA_MAX_STATES: usize = 4096;
+pub const RWKV_PDA_MAX_DEPTH: usize = 64;
+pub const RWKV_PDA_TOKEN_SPAN: usize = 8;
+pub const RWKV_PDA_POP: u16 = 65535;
+pub const RWKV_PDA_HALT_FINAL: i32 = 0;
+pub const RWKV_PDA_HALT_ACCEPT: i32 = 1;
+pub const RWKV_PDA_JSON_OBJECT: u32 = 1;
+pub const RWKV_PDA_JSON_COMPACT: u32 = 2;
 pub const RWKV_PROFILE_FAMILIES: usize = 8;
 pub const RWKV_SCORE_SKIP: u32 = 4294967295;
 pub const RWKV_TOPN_MAX: i32 = 32;
@@ -51,6 +59,7 @@ pub const RWKV_TOPN_NONE: u32 = 4294967295;
 #[repr(C)] pub struct rwkv_dstate { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_tokenizer { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_dfa { _p: [u8; 0] }
+#[repr(C)] pub struct rwkv_pda { _p: [u8; 0] }
 
 #[repr(C)] #[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
 pub struct rwkv_model_info { pub version: i32, pub num_layer: i32, pub num_emb: i32, pub num_hidden: i32,
@@ -156,6 +165,24 @@ extern "C" {
     pub fn rwkv_dfa_check_live(d: *const rwkv_dfa, state: i32, halt_mode: i32, lens: *const i32, bytes: *const u8, n_tokens: usize) -> rwkv_status;
     pub fn rwkv_gen_set_constraint(e: *mut rwkv_engine, slot: i32, dfa: *const rwkv_dfa, state: i32, halt_mode: i32) -> rwkv_status;
     pub fn rwkv_gen_constraint_state(e: *mut rwkv_engine, slot: i32, state: *mut i32) -> rwkv_status;
+    // `Formatter` for nested constraints: byte automata with a return-state stack (JSON), masked and committed on the device
+    pub fn rwkv_pda_from_table(next: *const u16, act: *const u16, accepting: *const u8, n_states: i32, start: i32, max_depth: i32,
+                               out: *mut *mut rwkv_pda) -> rwkv_status;
+    pub fn rwkv_pda_json(flags: u32, max_depth: i32, out: *mut *mut rwkv_pda) -> rwkv_status;
+    pub fn rwkv_pda_free(p: *mut rwkv_pda);
+    pub fn rwkv_pda_num_states(p: *const rwkv_pda) -> i32;
+    pub fn rwkv_pda_start(p: *const rwkv_pda) -> i32;
+    pub fn rwkv_pda_max_depth(p: *const rwkv_pda) -> i32;
+    pub fn rwkv_pda_table(p: *const rwkv_pda, next: *mut u16, act: *mut u16, accepting: *mut u8) -> rwkv_status;
+    pub fn rwkv_pda_walk(p: *const rwkv_pda, state: i32, stack: *const u16, depth: i32, bytes: *const u8, n: usize, state_out: *mut i32,
+                         stack_out: *mut u16, depth_out: *mut i32) -> rwkv_status;
+    pub fn rwkv_pda_allow(p: *const rwkv_pda, state: i32, stack: *const u16, depth: i32, bytes: *const u8, lens: *const i32, n_tokens: usize,
+                          allow: *mut u8, num_vocab: usize) -> rwkv_status;
+    pub fn rwkv_pda_check_live(p: *const rwkv_pda, state: i32, stack: *const u16, depth: i32, lens: *const i32, bytes: *const u8,
+                               n_tokens: usize) -> rwkv_status;
+    pub fn rwkv_gen_set_pda(e: *mut rwkv_engine, slot: i32, pda: *const rwkv_pda, state: i32, stack: *const u16, depth: i32,
+                            halt_mode: i32) -> rwkv_status;
+    pub fn rwkv_gen_pda_config(e: *mut rwkv_engine, slot: i32, state: *mut i32, stack: *mut u16, cap: usize, depth: *mut i32) -> rwkv_status;
     // Tokenizer  (lib.rs:375, run.rs:157, 856, bnf.rs:15)
     pub fn rwkv_tokenizer_create(vocab_json: *const c_char, len: usize, out: *mut *mut rwkv_tokenizer) -> rwkv_status;
     pub fn rwkv_tokenizer_destroy(t: *mut rwkv_tokenizer);

@@ -367,6 +367,21 @@ impl Engine {
         let mut state = 0i32;
         check(unsafe { sys::rwkv_gen_constraint_state(self.raw, slot as i32, &mut state) })?; Ok(state)
     }
+    /// The stack constraint of an armed, unfinished slot (rwkv_gen_set_pda): a byte automaton with a return-state stack (`Pda::json` for
+    /// "answer in JSON") masked, committed and halted on the device.  `(state, stack)` is `(pda.start(), &[])` after `gen_arm_prompt`, the
+    /// caller's own configuration after `gen_arm` or a hand-over.  `None` clears it.  A slot holds a `Dfa` or a `Pda`, not both.
+    pub fn gen_set_pda(&self, slot: usize, pda: Option<&Pda>, state: i32, stack: &[u16], halt: PdaHalt) -> Result<()> {
+        let raw = pda.map_or(ptr::null(), |p| p.raw as *const sys::rwkv_pda);
+        check(unsafe { sys::rwkv_gen_set_pda(self.raw, slot as i32, raw, state, stack.as_ptr(), stack.len() as i32, halt as i32) })
+    }
+    /// the configuration behind every token the slot has emitted (rwkv_gen_pda_config): what the per-token path goes on from
+    pub fn gen_pda_config(&self, slot: usize) -> Result<(i32, Vec<u16>)> {
+        let (mut state, mut depth) = (0i32, 0i32);
+        let mut stack = vec![0u16; sys::RWKV_PDA_MAX_DEPTH];
+        check(unsafe { sys::rwkv_gen_pda_config(self.raw, slot as i32, &mut state, stack.as_mut_ptr(), stack.len(), &mut depth) })?;
+        stack.truncate(depth.max(0) as usize);
+        Ok((state, stack))
+    }
     /// Up to `n_steps` tokens for every armed, unfinished slot with no host turn-around (rwkv_gen_run).  When it returns a slot's
     /// state has consumed everything it emitted except the last token (what run.rs:990-1005 backs up at a stop).
     pub fn gen_run(&self, n_steps: usize) -> Result<Generated> {
@@ -422,6 +437,48 @@ impl Dfa {
         let bytes: Vec<u8> = tokens.iter().flat_map(|t| t.unwrap_or(&[]).iter().copied()).collect();
         let mut out = vec![0u8; num_vocab];
         check(unsafe { sys::rwkv_dfa_allow(self.raw, state, bytes.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), num_vocab) })?; Ok(out)
+    }
+}
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum PdaHalt { #[default] Final = 0, Accept = 1 }
+/// A byte automaton with a return-state stack (rwkv_pda): state 0 is dead, a configuration is (state, stack).  `json` is RFC 8259
+/// (`flags`: `RWKV_PDA_JSON_OBJECT | RWKV_PDA_JSON_COMPACT`), `from_table` takes any compiler's two planes.  Immutable; host only.
+/// Not kbnf: what a return-state stack expresses, nested brackets above all.
+#[derive(Debug)]
+pub struct Pda { raw: *mut sys::rwkv_pda }
+unsafe impl Send for Pda {}
+unsafe impl Sync for Pda {}
+impl Drop for Pda { fn drop(&mut self) { unsafe { sys::rwkv_pda_free(self.raw) } } }
+impl Pda {
+    pub fn json(flags: u32, max_depth: i32) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_pda_json(flags, max_depth, &mut raw) })?; Ok(Self { raw })
+    }
+    pub fn from_table(next: &[u16], act: &[u16], accepting: &[u8], start: i32, max_depth: i32) -> Result<Self> {
+        if next.len() != accepting.len() * 256 || act.len() != next.len() {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "Pda::from_table: two planes of 256 entries per state".into() });
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_pda_from_table(next.as_ptr(), act.as_ptr(), accepting.as_ptr(), accepting.len() as i32, start, max_depth, &mut raw) })?;
+        Ok(Self { raw })
+    }
+    pub fn num_states(&self) -> i32 { unsafe { sys::rwkv_pda_num_states(self.raw) } }
+    pub fn start(&self) -> i32 { unsafe { sys::rwkv_pda_start(self.raw) } }
+    pub fn max_depth(&self) -> i32 { unsafe { sys::rwkv_pda_max_depth(self.raw) } }
+    /// the configuration `bytes` behind `(state, stack)` (state 0 once the walk died)
+    pub fn walk(&self, state: i32, stack: &[u16], bytes: &[u8]) -> Result<(i32, Vec<u16>)> {
+        let (mut q, mut depth) = (0i32, 0i32);
+        let mut out = vec![0u16; sys::RWKV_PDA_MAX_DEPTH];
+        check(unsafe { sys::rwkv_pda_walk(self.raw, state, stack.as_ptr(), stack.len() as i32, bytes.as_ptr(), bytes.len(), &mut q, out.as_mut_ptr(), &mut depth) })?;
+        out.truncate(depth.max(0) as usize);
+        Ok((q, out))
+    }
+    /// `Formatter::transform` on the host (rwkv_pda_allow): the mask `SampleParams::allow` takes; `tokens` as for `gen_set_token_bytes`
+    pub fn allow(&self, state: i32, stack: &[u16], tokens: &[Option<&[u8]>], num_vocab: usize) -> Result<Vec<u8>> {
+        let lens: Vec<i32> = tokens.iter().map(|t| t.map_or(-1, |b| b.len() as i32)).collect();
+        let bytes: Vec<u8> = tokens.iter().flat_map(|t| t.unwrap_or(&[]).iter().copied()).collect();
+        let mut out = vec![0u8; num_vocab];
+        check(unsafe { sys::rwkv_pda_allow(self.raw, state, stack.as_ptr(), stack.len() as i32, bytes.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), num_vocab) })?;
+        Ok(out)
     }
 }
 #[derive(Clone, Copy, Debug, PartialEq, Eq, Default)] pub enum SamplerKind { #[default] Nucleus = 0, Typical = 1, Mirostat = 2 }
