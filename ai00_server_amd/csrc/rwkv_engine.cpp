@@ -278,6 +278,14 @@ struct rwkv_dstate {
     float *sxa = nullptr, *sxf = nullptr, *wkv = nullptr;
 };
 
+// An open watch (rwkv_gen_watch_open): one mapped, coherent host block laid out by gen_watch.h, which the steps write through its device
+// alias.  read / head / cancel touch nothing but this block: no HIP call, no lock, nothing the infer thread holds.
+struct rwkv_gen_watch {
+    unsigned char *ring = nullptr;                             // records | head | cancel words
+    int ring_steps = 0, B = 0;
+    unsigned *cancel() const { return gen_watch_cancel_ptr(ring, ring_steps, B); }
+};
+
 struct rwkv_engine {
     rwkv_model_info info{};
     int device = 0;
@@ -429,9 +437,19 @@ struct rwkv_engine {
     void gen_set_topn(int slot, int n);
     bool gen_any_topn(const std::vector<int> &slots) const { if (gen_topn.empty()) return false; for (int b : slots) if (gen_topn[(size_t)b]) return true; return false; }
     GraphCacheOf<std::vector<uint64_t>> gen_graphs{64, {}};      // one captured step per set of rows (slot mask + sampler kernels it needs)
+    // the watch (rwkv_gen_watch_*, gen_watch.h): at most one.  Captured steps hold the ADDRESS of d_gen_watch, never the ring's: open
+    // rewrites the descriptor, so a step captured under one watch publishes into the next; steps captured with no watch open do not
+    // launch gen_publish at all (bit 36 of their key is clear) and stay what they were
+    rwkv_gen_watch *gen_watch = nullptr;
+    GenWatchDev *d_gen_watch = nullptr;                          // allocated by the first rwkv_gen_watch_open
+    void gen_watch_open(int ring_steps, rwkv_gen_watch **out);
+    void gen_watch_close(rwkv_gen_watch *w);
+    bool gen_cancel_set(int slot) const { return gen_watch && __atomic_load_n(gen_watch->cancel() + slot, __ATOMIC_ACQUIRE) != 0; }
+    void gen_cancel_clear(int slot) { if (gen_watch) __atomic_store_n(gen_watch->cancel() + slot, 0u, __ATOMIC_RELEASE); }
     void gen_init();
     void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt);
     void gen_disarm_slot(int slot) {
+        gen_cancel_clear(slot);
         if (gen_armed.empty()) return;
         gen_armed[(size_t)slot] = 0;
         gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
@@ -482,6 +500,7 @@ struct rwkv_engine {
         if (s_soft) (void)hipStreamSynchronize(s_soft);
         if (s_copy) (void)hipStreamSynchronize(s_copy);
         graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
+        if (gen_watch) { (void)hipHostFree(gen_watch->ring); delete gen_watch; gen_watch = nullptr; }   // the destructor closes an open watch
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
         for (void *p : gen_dfa_buf) if (p) (void)hipFree(p);
@@ -1632,6 +1651,8 @@ void rwkv_engine::infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *
 static_assert(RWKV_GEN_MAX_STOP_STR == GEN_MAX_STOP_STR && RWKV_GEN_STOP_LEN == GEN_STOP_LEN && RWKV_GEN_STOP_BUF == GEN_STOP_BUF &&
               RWKV_GEN_TOKEN_LEN == GEN_TOKEN_LEN && RWKV_GEN_HANDBACK == GEN_FIN_HANDBACK && RWKV_GEN_STOP == GEN_FIN_STOP &&
               RWKV_GEN_LENGTH == GEN_FIN_LENGTH, "include/rwkv_abi.h and csrc/gen_stop.h spell the same limits");
+static_assert(RWKV_GEN_CANCELLED == GEN_FIN_CANCELLED && RWKV_GEN_WATCH_MAX_STEPS == GEN_WATCH_MAX_STEPS,
+              "include/rwkv_abi.h and csrc/gen_watch.h spell the same limits");
 void rwkv_engine::gen_init() {
     if (d_gen) return;
     const size_t B = (size_t)max_batch, V = (size_t)info.num_vocab;
@@ -1730,6 +1751,7 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
     gen_armed[b] = 1;
+    gen_cancel_clear(slot);                                        // a flag set for the request that held the slot before is not this one's
 }
 
 // The token-bytes table of the stop-string matcher: what `tokenizer.decode(&[token])` (run.rs:856) yields per id.  Captured steps hold the
@@ -1943,6 +1965,42 @@ void rwkv_engine::gen_set_topn(int slot, int n) {
     gen_topn[b] = n;
 }
 
+// A watch: the block is mapped and coherent like h_tok (uncached on the device: a store is the host's to see at once, a load is the
+// host's latest store).  Between runs: the stream is idle, so the descriptor may be rewritten under the captured steps that read it.
+void rwkv_engine::gen_watch_open(int ring_steps, rwkv_gen_watch **out) {
+    HIP_CHECK(hipSetDevice(device));
+    if (gen_watch) throw RwkvError(RWKV_ERR_INVALID, "the engine already has a watch open");
+    if (ring_steps < 1 || ring_steps > RWKV_GEN_WATCH_MAX_STEPS)
+        throw RwkvError(RWKV_ERR_INVALID, "ring_steps must be 1.." + std::to_string(RWKV_GEN_WATCH_MAX_STEPS) + ", got " + std::to_string(ring_steps));
+    gen_init();
+    if (!d_gen_watch) d_gen_watch = dalloc<GenWatchDev>(1);
+    auto w = std::make_unique<rwkv_gen_watch>();
+    w->ring_steps = ring_steps; w->B = max_batch;
+    const size_t bytes = gen_watch_bytes(ring_steps, max_batch);
+    void *p = nullptr, *dv = nullptr;
+    HIP_CHECK(hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(p, 0, bytes);                                      // stamps 0 (no record), head 0, no cancel word set
+    if (hipHostGetDevicePointer(&dv, p, 0) != hipSuccess) { (void)hipHostFree(p); throw RwkvError(RWKV_ERR_DEVICE, "no device alias for the watch's ring"); }
+    w->ring = (unsigned char *)p;
+    GenWatchDev d{};
+    d.ring = (unsigned char *)dv; d.cancel = gen_watch_cancel_ptr((unsigned char *)dv, ring_steps, max_batch); d.seq = 0; d.ring_steps = ring_steps;
+    hipError_t err = hipStreamSynchronize(s_main);
+    if (err == hipSuccess) err = hipMemcpy(d_gen_watch, &d, sizeof d, hipMemcpyHostToDevice);
+    if (err != hipSuccess) { (void)hipHostFree(p); HIP_CHECK(err); }
+    gen_watch = w.release();
+    *out = gen_watch;
+}
+void rwkv_engine::gen_watch_close(rwkv_gen_watch *w) {
+    HIP_CHECK(hipSetDevice(device));
+    if (!w || w != gen_watch) throw RwkvError(RWKV_ERR_INVALID, "not this engine's open watch");
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    const GenWatchDev d{};                                         // ring null: a step that still reached gen_publish would write nothing
+    HIP_CHECK(hipMemcpy(d_gen_watch, &d, sizeof d, hipMemcpyHostToDevice));
+    (void)hipHostFree(w->ring);
+    delete w;
+    gen_watch = nullptr;
+}
+
 GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda) const {
     GenArgs a{};
     if (topn) {
@@ -1959,6 +2017,7 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool 
     a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = n_rows;
     a.sxa = sxa; a.sxf = sxf; a.wkv = wkv; a.sx_slot_stride = sx_slot_stride; a.wkv_slot_stride = wkv_slot_stride;
     a.shadow = d_gen_shadow;
+    a.watch = gen_watch ? d_gen_watch : nullptr;
     return a;
 }
 
@@ -1970,6 +2029,7 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
     if (a.pda) launch(FAM_SAMPLE, [&] { launch_gen_pda_mask(a, s_main); });   // ... and of the rows under a stack constraint
     launch(FAM_SAMPLE, [&] { launch_nucleus(logits, a.n_rows, info.num_vocab, d_gen_rows, needs & NEEDS_NT, needs & NEEDS_MIRO, needs & NEEDS_WIDE, d_gen_tok, d_gen_prob, s_main); });
     launch(FAM_SAMPLE, [&] { launch_gen_post(a, s_main); });
+    if (a.watch) launch(FAM_SAMPLE, [&] { launch_gen_publish(a, s_main); });   // behind gen_post (a slot's own reason stands), before gen_freeze (a cancel freezes here)
     launch(FAM_COPY, [&] { launch_gen_freeze(a, s_main); });
 }
 
@@ -1995,7 +2055,8 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0) | (pda ? 1ull << 35 : 0);
+    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0) | (pda ? 1ull << 35 : 0) |
+                 (gen_watch ? 1ull << 36 : 0);                     // a step under a watch launches gen_publish as well
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
@@ -2031,6 +2092,9 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         gen_sample(a, gen_needs(drawn));
+    } else if (gen_watch) {                                        // a step without a row still publishes its (all padding) record
+        const GenArgs a = gen_args(0, false, false, false, false);
+        launch(FAM_SAMPLE, [&] { launch_gen_publish(a, s_main); });
     }
     for (int b : dec) remain[(size_t)b] -= 1;
     for (int b : pro) {
@@ -2064,8 +2128,12 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         // prompt ends (the plan says so); what it cannot know is who finished on the device, so a slot rides until the enqueue ends or
         // until it can emit nothing more (`remain`: max_tokens less what it has emitted for certain).
         const int nb = std::min(n_steps - done, (int)GEN_RING_STEPS);
-        std::vector<int> live, remain((size_t)B, 0);
+        std::vector<int> live, remain((size_t)B, 0), cancelled;
         for (int b = 0; b < B; ++b) {
+            if (gen_watch && !gen_armed[(size_t)b] && gen_host[(size_t)b].finish) {   // a record shows 0 for a slot that is not armed: drop the word
+                gen_host[(size_t)b].finish = RWKV_GEN_RUNNING;                        // its last request left behind (nothing else reads it)
+                HIP_CHECK(hipMemsetAsync(&d_gen[b].finish, 0, sizeof(int), s_main));
+            }
             if (!gen_armed[(size_t)b] || gen_host[(size_t)b].finish) continue;
             live.push_back(b);
             remain[(size_t)b] = gen_host[(size_t)b].max_tokens - gen_host[(size_t)b].emitted;
@@ -2085,6 +2153,13 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         }
         int k = 0;
         while (k < nb) {
+            // A cancel word on a slot still INSIDE ITS PROMPT is the host's to see: the slot has no row a kernel could end.  It leaves
+            // `live` here — it is planned no more, and the shadow restore below must not touch it: it was never frozen.
+            for (size_t i = 0; gen_watch && i < live.size();) {
+                const int b = live[i];
+                if (gen_prompt_left(b) && gen_cancel_set(b)) { cancelled.push_back(b); live.erase(live.begin() + (long)i); }
+                else ++i;
+            }
             std::vector<int> dec, pro;                             // ascending slot order
             for (int b : live) {
                 if (gen_prompt_left(b)) pro.push_back(b);
@@ -2116,6 +2191,11 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         std::vector<GenSlot> back((size_t)B);
         HIP_CHECK(hipMemcpyAsync(back.data(), d_gen, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, s_main));
         HIP_CHECK(hipStreamSynchronize(s_main));
+        for (int b : cancelled) {                                  // the stream is idle (as where gen_set_topn writes its word); not in `live`: no restore
+            const int fin = RWKV_GEN_CANCELLED;
+            gen_host[(size_t)b].finish = fin;
+            HIP_CHECK(hipMemcpy(&d_gen[b].finish, &fin, sizeof(int), hipMemcpyHostToDevice));
+        }
         if (k == 0) break;
         std::memcpy(out_tokens + (size_t)done * B, h_gen_out, (size_t)k * B * 4);
         if (out_probs) std::memcpy(out_probs + (size_t)done * B, h_gen_out + ring, (size_t)k * B * 4);
@@ -2675,6 +2755,42 @@ rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, 
         if (!e || !out_tokens || n_steps <= 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
         use_knobs(e->kn);
         e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish);
+    });
+}
+// ---- the watch: open / close on the infer thread between runs; head / read / cancel from ANY thread, on the watch's host block alone ----
+rwkv_status rwkv_gen_watch_open(rwkv_engine *e, int32_t ring_steps, rwkv_gen_watch **out) {
+    return guard([&] {
+        if (!e || !out) throw RwkvError(RWKV_ERR_INVALID, "null engine / out");
+        *out = nullptr;
+        e->gen_watch_open(ring_steps, out);
+    });
+}
+rwkv_status rwkv_gen_watch_close(rwkv_engine *e, rwkv_gen_watch *w) {
+    return guard([&] {
+        if (!e || !w) throw RwkvError(RWKV_ERR_INVALID, "null engine / watch");
+        e->gen_watch_close(w);
+    });
+}
+rwkv_status rwkv_gen_watch_head(const rwkv_gen_watch *w, uint64_t *seq) {
+    return guard([&] {
+        if (!w || !seq) throw RwkvError(RWKV_ERR_INVALID, "null watch / seq");
+        *seq = gen_watch_head(w->ring, w->ring_steps, w->B);
+    });
+}
+rwkv_status rwkv_gen_watch_read(rwkv_gen_watch *w, uint64_t *cursor, int32_t max_steps, uint32_t *tokens, float *probs, int32_t *finish,
+                                int32_t *n_steps, uint64_t *lost) {
+    return guard([&] {
+        if (!w || !cursor || !tokens || !n_steps || !lost || max_steps < 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
+        unsigned long long c = *cursor, l = 0;
+        *n_steps = gen_watch_read(w->ring, w->ring_steps, w->B, &c, max_steps, tokens, (unsigned *)probs, finish, &l);
+        *cursor = c; *lost = l;
+    });
+}
+rwkv_status rwkv_gen_watch_cancel(rwkv_gen_watch *w, int32_t slot) {
+    return guard([&] {
+        if (!w) throw RwkvError(RWKV_ERR_INVALID, "null watch");
+        if (slot < 0 || slot >= w->B) throw RwkvError(RWKV_ERR_INVALID, "slot out of range");
+        __atomic_store_n(w->cancel() + slot, 1u, __ATOMIC_RELEASE);
     });
 }
 rwkv_status rwkv_gen_set_topn(rwkv_engine *e, int32_t slot, int32_t n) {

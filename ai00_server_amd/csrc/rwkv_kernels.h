@@ -15,6 +15,7 @@ typedef unsigned short _Float16;
 #include "gen_stop.h"                // RWKV_HD, the stop-string matcher and its limits
 #include "gen_dfa.h"                 // the byte-automaton constraint: walk, allowed and halt predicates
 #include "gen_pda.h"                 // the stack-automaton constraint: token walk, commit and halt predicate
+#include "gen_watch.h"               // the record ring of a watch: layout, writer and reader of the sequence lock
 
 namespace rwkv {
 
@@ -327,6 +328,13 @@ struct alignas(16) GenPda {         // one per slot, beside GenDfa: the slot's s
     int state, depth;               // the configuration behind every token the slot has emitted (written by gen_post)
     int mode, max_depth;            // GEN_PDA_HALT_*; 1 .. GEN_PDA_MAX_DEPTH
 };
+struct GenWatchDev {                // one per engine, DEVICE-RESIDENT: captured steps hold its address, rwkv_gen_watch_open rewrites its contents
+    unsigned char *ring;            // device alias of the watch's mapped, coherent host block (gen_watch.h), or null: no watch open
+    const unsigned *cancel;         // [max_batch] in the same block: non-zero = the slot's request is gone
+    unsigned long long seq;         // records published since the watch was opened (advanced by gen_publish)
+    int ring_steps;
+    int reserved;
+};
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
     GenStop *stops;                 // [max_batch], or null: no slot of this step has stop strings (selects gen_post_kernel<., false>)
@@ -356,6 +364,7 @@ struct GenArgs {
     float *tok_logp;                // [steps][max_batch] raw ln-probability of the emitted token
     float *side_ms, *side_rows;     // [max_batch][2], [max_batch][V]: (m, ln S) and the raw row of every logits row that lists (gen_topn -> gen_post)
     GenPda *pda;                    // [max_batch], or null: no slot of this step has a stack constraint (gen_pda_mask is not launched, gen_post skips it)
+    GenWatchDev *watch;             // the engine's descriptor, or null: no watch is open (gen_publish is not launched)
 };
 RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
@@ -369,6 +378,7 @@ void launch_gen_topn(const GenArgs &a, hipStream_t s);                          
 void launch_gen_mask(const GenArgs &a, hipStream_t s);                                                               // a.dfa != null
 void launch_gen_pda_mask(const GenArgs &a, hipStream_t s);                                                           // a.pda != null
 void launch_gen_post(const GenArgs &a, hipStream_t s);
+void launch_gen_publish(const GenArgs &a, hipStream_t s);                                                            // a.watch != null; reads slots, out_tok / out_prob, run_step, max_batch
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);
 void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T > 0
 void launch_gen_handover(int *feedback, int *held, const int *row_slot, int T, bool to_held, hipStream_t s);         // T > 0

@@ -3940,6 +3940,8 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 //   nucleus_kernel, as it is
 //   gen_post    the tail of `sample` (nucleus.rs:104-119 / mirostat.rs:85-87), the token into the feedback buffer and the output
 //               ring, stop tokens and max_tokens (run.rs:855, 905-917); with STOPS, the slot's stop STRINGS over the decoded bytes (run.rs:899-932, gen_stop.h)
+//   gen_publish only while a watch is open (rwkv_gen_watch_open, gen_watch.h): the step's record into the watch's ring in host memory, and
+//               the cancel words (`context.sender.is_disconnected()`, run.rs:934-935) — a running slot whose word is set ends here
 //   gen_freeze  the state of a slot that finished IN THIS STEP into its shadow (the step keeps its shape until the run ends; the host
 //               puts the shadow back)
 // Every value is written with plain vector stores.  All arithmetic is the per-token path's, operation for operation: the host
@@ -4207,6 +4209,40 @@ __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
         for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < len[part]; i += (long)gridDim.x * 1024)
             *(float4 *)(dst[part] + i) = *(const float4 *)(src[part] + i);
 }
+// The step's RECORD into the ring of the open watch (rwkv_gen_watch_open, gen_watch.h), and the cancel words.  One block, launched in
+// every step while a watch is open: behind gen_post (the step's cells of the output ring are written, a slot that finished by itself has
+// its reason) and in front of gen_freeze (a slot cancelled here is frozen in this very step, exactly like a stop); alone in a mixed step
+// that emits no row.  Thread b takes slot b: its cell of the step (padding where the slot had no row: the ring is memset per enqueue), its
+// `finish`, and its cancel word — ONE system-scope load from the mapped host block, never a wait.  A slot that is running, drew in this
+// step and has its word set ends here: the token it drew is its last, everything gen_post did for a running slot stands.
+// The record follows the sequence lock of gen_watch.h; the stores go to uncached host memory with plain vector stores.
+__global__ __launch_bounds__(256) void gen_publish_kernel(GenArgs a) {
+    GenWatchDev &w = *a.watch;
+    unsigned char *ring = w.ring;
+    if (!ring) return;                                             // block-uniform: no watch behind the descriptor
+    const int B = a.max_batch, k = *a.run_step, tid = threadIdx.x, steps = w.ring_steps;
+    const unsigned long long seq = w.seq;                          // every thread reads it in front of the barriers, thread 0 advances it behind them
+    unsigned char *rec = gen_watch_rec(ring, steps, B, seq);
+    if (tid == 0) gen_watch_open_rec(rec);
+    __syncthreads();
+    for (int b = tid; b < B; b += 256) {
+        unsigned tok = GEN_WATCH_NO_TOKEN, prob = 0xFFFFFFFFu;
+        if (k >= 0) { tok = a.out_tok[(long)k * B + b]; prob = __float_as_uint(a.out_prob[(long)k * B + b]); }
+        GenSlot &g = a.slots[b];
+        int fin = g.finish;
+        if (fin == 0 && tok != GEN_WATCH_NO_TOKEN && gen_watch_load32(w.cancel + b) != 0) {
+            fin = GEN_FIN_CANCELLED;
+            g.freeze_at = k; g.finish = fin;
+        }
+        gen_watch_put(rec, B, b, tok, prob, fin);
+    }
+    __threadfence_system();                                        // each thread's payload is out before the barrier lets thread 0 stamp it
+    __syncthreads();
+    if (tid == 0) {
+        gen_watch_commit(rec, gen_watch_head_ptr(ring, steps, B), seq);
+        w.seq = seq + 1;
+    }
+}
 // a.n_rows: rows of the logits block (> 0); a.out_rows != null selects the mixed-step instantiation
 void launch_gen_pre(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_pre_kernel<true>, dim3(16, a.n_rows), dim3(256), 0, s, a);
@@ -4234,6 +4270,7 @@ void launch_gen_post(const GenArgs &a, hipStream_t s) {
     } else if (a.out_rows) hipLaunchKernelGGL((gen_post_kernel<true, false>), dim3(16, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((gen_post_kernel<false, false>), dim3(16, a.n_rows), dim3(256), 0, s, a);
 }
+void launch_gen_publish(const GenArgs &a, hipStream_t s) { hipLaunchKernelGGL(gen_publish_kernel, dim3(1), dim3(256), 0, s, a); }
 void launch_gen_freeze(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_freeze_kernel<true>, dim3(64, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_freeze_kernel<false>, dim3(64, a.n_rows), dim3(256), 0, s, a);

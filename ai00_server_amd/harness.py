@@ -155,6 +155,63 @@ def generate_resident(runtime, slot: int, prompt, max_tokens: int, sampler, seed
             return out
 
 
+def generate_resident_stream(runtime, slot: int, prompt, max_tokens: int, sampler, seed: int = 0, stop_tokens=(), top_logprobs: int = 0,
+                             steps_per_run: int = 1024, constraint=None, halt: int = 0):
+    """`generate_resident` as a GENERATOR that yields every (token, prob) as it is drawn (run.rs:1009), not when the run returns: a worker
+    thread sits in `Runtime.gen_run` with a large `steps_per_run` (ctypes releases the GIL there) and this thread reads the records of a
+    watch (`Runtime.gen_watch_open`).  It yields exactly the list `generate_resident` returns.  Closing the generator early cancels the
+    slot (`GenWatch.cancel`, run.rs:934-935): it ends with `GenFinish.Cancelled` in the first step that sees the flag.
+    The engine's watch is opened here and closed when the generator ends; top-n lists are not published, so `top_logprobs` must be 0."""
+    import threading
+    import time
+    if top_logprobs:
+        raise ValueError("a watch does not publish top-n lists: use generate_resident")
+    runtime.gen_arm_prompt(slot, prompt, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    if constraint is not None:
+        if hasattr(constraint, "max_depth"):
+            runtime.gen_set_pda(slot, constraint, halt=halt)
+        else:
+            runtime.gen_set_constraint(slot, constraint, halt=halt)
+    watch = runtime.gen_watch_open(min(max(int(steps_per_run), 1024), 65536))
+    done, failure = threading.Event(), []
+
+    def work():
+        try:
+            while not runtime.gen_run(steps_per_run)[3][slot]:
+                pass
+        except BaseException as e:                                    # handed to the consumer below
+            failure.append(e)
+        finally:
+            done.set()
+
+    worker = threading.Thread(target=work, name="gen_run", daemon=True)
+    worker.start()
+    try:
+        finished = False
+        while not finished:
+            drained = done.is_set()                                   # looked at BEFORE the read: a record published behind it is seen next time
+            toks, probs, fin, lost = watch.read(64)
+            if lost:
+                raise RuntimeError(f"the reader fell {lost} records behind the watch's ring")
+            for k in range(len(toks)):
+                if toks[k, slot] != 0xFFFFFFFF:
+                    yield int(toks[k, slot]), float(probs[k, slot])
+                if fin[k, slot]:
+                    finished = True
+                    break
+            if len(toks) == 0:
+                if drained:
+                    break
+                time.sleep(0.0002)
+    finally:
+        if worker.is_alive():
+            watch.cancel(slot)                                        # closed early (or failed): the request is gone
+        worker.join()
+        watch.close()
+    if failure:
+        raise failure[0]
+
+
 class NucleusSampler:
     """Host-side STATE of `NucleusSampler` (sampler/nucleus.rs:13-122) for the on-device sampling front-end: the
     penalty map lives here, its effect reaches the device as sparse logit adjustments (`adjustments()`), and the

@@ -118,6 +118,12 @@ ABI_SYMBOLS = {
     "rwkv_gen_set_stops": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_GenStopsC)]),
     "rwkv_gen_stop_tail": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "rwkv_gen_uniform": (C.c_int32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_float)]),
+    "rwkv_gen_watch_open": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rwkv_gen_watch_close": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "rwkv_gen_watch_head": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rwkv_gen_watch_read": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "rwkv_gen_watch_cancel": (C.c_int32, [C.c_void_p, C.c_int32]),
     "rwkv_dfa_from_table": (C.c_int32, [C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "rwkv_dfa_compile": (C.c_int32, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rwkv_dfa_free": (None, [C.c_void_p]),
@@ -284,9 +290,11 @@ class GenFinish(enum.IntEnum):   # RWKV_GEN_*: FinishReason::{Stop, Length} run.
     Stop = 1
     Length = 2
     Handback = 3                 # the slot's stop-string buffer is full: the caller replays its own matcher and goes on per token
+    Cancelled = 4                # RWKV_GEN_CANCELLED: the request was cancelled through a watch (`GenWatch.cancel`)
 
 
 GEN_MAX_STOP_STR, GEN_STOP_LEN, GEN_STOP_BUF, GEN_TOKEN_LEN = 8, 128, 512, 256      # RWKV_GEN_* limits of the device's stop-string matcher
+GEN_WATCH_MAX_STEPS = 65536      # RWKV_GEN_WATCH_MAX_STEPS
 GEN_WIDE_TOP_K = 1               # RWKV_GEN_WIDE_TOP_K: bit of rwkv_gen_params.reserved that arms Nucleus / Typical with top_k > 256
 
 
@@ -587,6 +595,59 @@ class PinnedArena:
             pass
 
 
+class GenWatch:
+    """A watch on an engine's resident generation (rwkv_gen_watch_*).  `read`, `head` and `cancel` may be called from any thread while
+    another sits in `Runtime.gen_run`; `close` belongs to the thread that runs the engine, between runs.  One reader per GenWatch object:
+    the cursor lives here."""
+
+    def __init__(self, rt: "Runtime", handle):
+        self._rt, self._h, self.cursor, self.lost = rt, handle, 0, 0
+
+    def _handle(self):
+        if not self._h:
+            raise RwkvError(-1, "the watch is closed")
+        return self._h
+
+    def head(self) -> int:
+        """records published since the watch was opened"""
+        seq = C.c_uint64()
+        _check(lib().rwkv_gen_watch_head(self._handle(), C.byref(seq)))
+        return int(seq.value)
+
+    def read(self, max_steps: int):
+        """The records behind this watch's cursor, at most `max_steps`: (tokens uint32 [n, max_batch], probs float32 [n, max_batch],
+        finish int32 [n, max_batch], lost) — the rows of `gen_run`'s outputs as the steps end, 0xFFFFFFFF / NaN where a slot emitted
+        nothing; `lost` counts the records a reader that fell behind the ring has skipped in this call (`self.lost` adds them up).
+        Never blocks; n may be 0."""
+        B, n = self._rt.max_batch, max(int(max_steps), 0)
+        toks, probs, fin = np.empty((n, B), np.uint32), np.empty((n, B), np.float32), np.empty((n, B), np.int32)
+        cur, got, lost = C.c_uint64(self.cursor), C.c_int32(), C.c_uint64()
+        _check(lib().rwkv_gen_watch_read(self._handle(), C.byref(cur), n, toks.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         probs.ctypes.data_as(C.POINTER(C.c_float)), fin.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got),
+                                         C.byref(lost)))
+        self.cursor = int(cur.value)
+        self.lost += int(lost.value)
+        k = int(got.value)
+        return toks[:k], probs[:k], fin[:k], int(lost.value)
+
+    def cancel(self, slot: int):
+        """The slot's request is gone (rwkv_gen_watch_cancel): a decoding slot ends in the first step that sees the flag, with the token it
+        drew there as its last and `GenFinish.Cancelled`; a slot inside its prompt is dropped when the next step is planned."""
+        _check(lib().rwkv_gen_watch_cancel(self._handle(), int(slot)))
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            self._rt._watch = None
+            _check(lib().rwkv_gen_watch_close(self._rt._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class TensorGpu:
     """Device-resident state snapshot (`state.read` result); reusable for many `state.write`s."""
 
@@ -663,6 +724,10 @@ class Runtime:
 
     def close(self):
         if self._h:
+            w = getattr(self, "_watch", None)
+            if w is not None:
+                w._h = None                                           # the engine's destructor closes an open watch
+                self._watch = None
             lib().rwkv_engine_destroy(self._h)
             self._h = None
             self._arena = None
@@ -1035,6 +1100,15 @@ class Runtime:
                                        finish.ctypes.data_as(i32p), int(top), tok_logp.ctypes.data_as(f32p), top_ids.ctypes.data_as(u32p),
                                        top_logp.ctypes.data_as(f32p)))
         return toks, probs, n_emitted, finish, tok_logp, top_ids, top_logp
+
+    def gen_watch_open(self, ring_steps: int) -> "GenWatch":
+        """Open the engine's watch (rwkv_gen_watch_open; at most one, between runs): from now on every step of `gen_run` publishes a record
+        into a ring of `ring_steps` that ANOTHER THREAD reads while the run goes on — ctypes releases the GIL inside `gen_run` — and
+        through which it cancels slots."""
+        h = C.c_void_p()
+        _check(lib().rwkv_gen_watch_open(self._h, int(ring_steps), C.byref(h)))
+        self._watch = GenWatch(self, h)
+        return self._watch
 
     gen_uniform = staticmethod(gen_uniform)
 

@@ -48,7 +48,9 @@ extern "C" {
                               *    generation), 8 n bytes per row come back instead of the row
                               *    additive under 9: rwkv_pda_* (byte automata with a return-state stack, host only; rwkv_pda_json is RFC 8259),
                               *    rwkv_gen_set_pda, rwkv_gen_pda_config: a NESTED format constraint ("answer in JSON") is masked and advanced on the
-                              *    device inside the resident step */
+                              *    device inside the resident step
+                              *    additive under 9: rwkv_gen_watch_open / _close / _head / _read / _cancel, RWKV_GEN_CANCELLED, RWKV_GEN_WATCH_MAX_STEPS:
+                              *    another thread streams the tokens of a running rwkv_gen_run and cancels slots inside it */
 
 typedef int32_t rwkv_status;
 enum {
@@ -446,6 +448,51 @@ rwkv_status rwkv_gen_set_stops(rwkv_engine *e, int32_t slot, const rwkv_gen_stop
 rwkv_status rwkv_gen_stop_tail(rwkv_engine *e, int32_t slot, uint8_t *out, size_t cap, size_t *len);
 /* the draws `first_step .. first_step + n - 1` of (seed, stream): pure host function, no device needed */
 rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step, size_t n, float *out);
+
+/* ---- A WATCH: stream tokens out of a running rwkv_gen_run and cancel slots inside it.  The reference sends every token to the client as
+ * it is drawn (run.rs:1009, `sender.send(Token::Content(word))`) and ends a request as soon as its client is gone (run.rs:934-935,
+ * `context.sender.is_disconnected()` -> `done`); rwkv_gen_run shows nothing until it returns and could drop a request only between runs.
+ * With a watch open another thread sees every step as it ends and can reach into the run — without a HIP call, and without the device
+ * ever waiting for the host.  With no watch open a step launches what it launched before, from the same cached graphs.
+ *   LIFETIME.  At most one watch per engine: a second open is RWKV_ERR_INVALID, and so is ring_steps outside 1 .. RWKV_GEN_WATCH_MAX_STEPS.
+ *     open and close run on the infer thread, between runs; the engine's destructor closes an open watch.  open, close and rwkv_engine_destroy
+ *     must not run concurrently with read, head or cancel: the caller's duty, as for every handle here.  A watch holds
+ *     ring_steps x (8 + 12 max_batch, padded to 16) + 16 + 4 max_batch bytes of pinned host memory, mapped and coherent.
+ *   PUBLISHING.  While a watch is open every step of rwkv_gen_run / rwkv_gen_run_topn publishes one RECORD, a step that emits no row
+ *     included (a step in which every slot is still inside its prompt).  A record holds, per slot, the step's cell of out_tokens
+ *     (0xFFFFFFFF where the slot emitted nothing), its cell of out_probs, and the slot's `finish` after the step (0 for a slot that was
+ *     never armed).  Records carry a sequence number that counts from 0 at open and runs on across the engine's internal ring splits and
+ *     across runs.  The records of a run are, bit for bit and in order, the rows of out_tokens / out_probs the run executed; rows it did
+ *     not execute stay padding and have no record.  Top-n lists are not published: they arrive with rwkv_gen_run_topn as before.
+ *     rwkv_gen_run's own outputs stay authoritative and complete.
+ *   READING.  rwkv_gen_watch_read copies the records *cursor .. (at most max_steps; tokens / probs / finish are [max_steps][max_batch],
+ *     probs and finish may be NULL), sets *n_steps and advances *cursor; a fresh reader starts with *cursor = 0.  It never blocks, makes
+ *     no HIP call and takes no lock.  The device never waits for a reader: one that fell more than ring_steps behind gets *lost = the
+ *     number of records it skipped and continues at the oldest record still intact.  A record is NEVER returned torn or overwritten
+ *     (a sequence lock per record, csrc/gen_watch.h).  One reader per cursor; any number of cursors.  rwkv_gen_watch_head: the number of
+ *     records published so far.
+ *   CANCELLING.  rwkv_gen_watch_cancel sets the slot's flag; arming the slot (rwkv_gen_arm, rwkv_gen_arm_prompt) and everything that
+ *     disarms it (rwkv_gen_disarm, a rwkv_infer / state call on the slot) clear it.  A flag on an unarmed or finished slot does nothing.
+ *     With no watch open flags do not exist: cancellation is a facility of the watch.
+ *      - A DECODING slot whose flag is seen ends in the first step that sees it: the token it drew in that step is emitted as its last
+ *        token, finish = RWKV_GEN_CANCELLED, and the STATE RULE holds unchanged — everything consumed except that last token, the state
+ *        the reference caches on `done`.  If the slot finished by itself in that very step its own reason stands.
+ *        Its penalties, stop-string buffer (rwkv_gen_stop_tail), DFA state and stack configuration are those of a RUNNING slot at that
+ *        point, i.e. BEHIND the last token — not the "buffer as before the last token" of a slot that finished by a stop.
+ *      - A slot still INSIDE ITS PROMPT is cancelled by the host when it plans the next step: it is planned no more, emits nothing, its
+ *        state has consumed the prompt tokens fed so far, rwkv_gen_prompt_left keeps what was left, and finish = RWKV_GEN_CANCELLED when
+ *        the run returns (the records show its finish from the next run on).
+ *      - Which step sees a flag set during a run is not deterministic.  Everything returned is a prefix of the uncancelled output, and
+ *        no other slot changes by a bit. */
+#define RWKV_GEN_CANCELLED 4            /* joins RWKV_GEN_RUNNING / _STOP / _LENGTH / _HANDBACK: the request was cancelled through a watch */
+#define RWKV_GEN_WATCH_MAX_STEPS 65536
+typedef struct rwkv_gen_watch rwkv_gen_watch;
+rwkv_status rwkv_gen_watch_open(rwkv_engine *e, int32_t ring_steps, rwkv_gen_watch **out);   /* infer thread, between runs */
+rwkv_status rwkv_gen_watch_close(rwkv_engine *e, rwkv_gen_watch *w);                         /* infer thread, between runs */
+rwkv_status rwkv_gen_watch_head(const rwkv_gen_watch *w, uint64_t *seq);                     /* ANY thread */
+rwkv_status rwkv_gen_watch_read(rwkv_gen_watch *w, uint64_t *cursor, int32_t max_steps, uint32_t *tokens, float *probs, int32_t *finish,
+                                int32_t *n_steps, uint64_t *lost);                           /* ANY thread, one reader per cursor */
+rwkv_status rwkv_gen_watch_cancel(rwkv_gen_watch *w, int32_t slot);                          /* ANY thread */
 
 /* ---- `Formatter` (sampler/bnf.rs:34-48; run.rs:676-680 `transform`, 892-897 `update`, 990 halt) for REGULAR constraints: a byte-level DFA.
  * The reference's formatter is kbnf, a context-free engine that lives on the host; this is a second implementation of the same trait for

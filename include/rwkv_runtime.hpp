@@ -432,6 +432,43 @@ class Runtime {
                                 g.top_ids.data(), g.top_logp.data()));
         return g;
     }
+    // A watch on the engine's resident generation (rwkv_gen_watch_*): while one thread sits in gen_run, ANOTHER reads every step's record
+    // as it ends (read, head) and cancels slots (cancel) — no HIP call, no lock, the device never waits.  RAII: the destructor closes the
+    // watch, on the thread that runs the engine and between runs; it keeps the engine alive.  One reader per Cursor.
+    class GenWatch {
+       public:
+        struct Records {
+            int n = 0;                                   // records returned
+            uint64_t lost = 0;                           // records skipped in this call: the reader fell more than ring_steps behind
+            std::vector<uint32_t> tokens;                // [n][max_batch]: the rows of gen_run's outputs, 0xFFFFFFFF where a slot emitted nothing
+            std::vector<float> probs;                    // same shape, NaN there
+            std::vector<int32_t> finish;                 // same shape: RWKV_GEN_* after the step
+        };
+        GenWatch(std::shared_ptr<rwkv_engine> e, int max_batch, int ring_steps) : e_(std::move(e)), max_batch_(max_batch) {
+            check(rwkv_gen_watch_open(e_.get(), ring_steps, &w_));
+        }
+        GenWatch(const GenWatch &) = delete;
+        GenWatch &operator=(const GenWatch &) = delete;
+        ~GenWatch() { if (w_) (void)rwkv_gen_watch_close(e_.get(), w_); }
+        uint64_t head() const { uint64_t s = 0; check(rwkv_gen_watch_head(w_, &s)); return s; }
+        Records read(uint64_t &cursor, int max_steps) {
+            Records r;
+            const size_t cells = (size_t)std::max(max_steps, 0) * (size_t)max_batch_;
+            r.tokens.resize(cells); r.probs.resize(cells); r.finish.resize(cells);
+            int32_t n = 0;
+            check(rwkv_gen_watch_read(w_, &cursor, std::max(max_steps, 0), r.tokens.data(), r.probs.data(), r.finish.data(), &n, &r.lost));
+            r.n = n;
+            r.tokens.resize((size_t)n * (size_t)max_batch_); r.probs.resize(r.tokens.size()); r.finish.resize(r.tokens.size());
+            return r;
+        }
+        void cancel(int slot) { check(rwkv_gen_watch_cancel(w_, slot)); }
+        rwkv_gen_watch *raw() const { return w_; }
+       private:
+        std::shared_ptr<rwkv_engine> e_;
+        rwkv_gen_watch *w_ = nullptr;
+        int max_batch_ = 0;
+    };
+    std::unique_ptr<GenWatch> gen_watch_open(int ring_steps) { return std::make_unique<GenWatch>(e_, max_batch, ring_steps); }
     rwkv_engine *raw() const { return e_.get(); }
     ModelInfo info{};
     int max_batch = 0;

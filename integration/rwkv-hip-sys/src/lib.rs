@@ -34,6 +34,8 @@ pub const RWKV_GEN_RUNNING: i32 = 0;
 pub const RWKV_GEN_STOP: i32 = 1;
 pub const RWKV_GEN_LENGTH: i32 = 2;
 pub const RWKV_GEN_HANDBACK: i32 = 3;
+pub const RWKV_GEN_CANCELLED: i32 = 4;
+pub const RWKV_GEN_WATCH_MAX_STEPS: i32 = 65536;
 pub const RWKV_GEN_MAX_STOP_STR: usize = 8;
 pub const RWKV_GEN_STOP_LEN: usize = 128;
 pub const RWKV_GEN_STOP_BUF: usize = 512;
@@ -60,6 +62,7 @@ pub const RWKV_TOPN_NONE: u32 = 4294967295;
 #[repr(C)] pub struct rwkv_tokenizer { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_dfa { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_pda { _p: [u8; 0] }
+#[repr(C)] pub struct rwkv_gen_watch { _p: [u8; 0] }
 
 #[repr(C)] #[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
 pub struct rwkv_model_info { pub version: i32, pub num_layer: i32, pub num_emb: i32, pub num_hidden: i32,
@@ -152,6 +155,13 @@ extern "C" {
     pub fn rwkv_gen_set_stops(e: *mut rwkv_engine, slot: i32, s: *const rwkv_gen_stops) -> rwkv_status;
     pub fn rwkv_gen_stop_tail(e: *mut rwkv_engine, slot: i32, out: *mut u8, cap: usize, len: *mut usize) -> rwkv_status;
     pub fn rwkv_gen_uniform(seed: u64, stream: u32, first_step: u32, n: usize, out: *mut c_float) -> rwkv_status;
+    // a watch: open / close on the infer thread between runs; head / read / cancel from any thread, no HIP call behind them
+    pub fn rwkv_gen_watch_open(e: *mut rwkv_engine, ring_steps: i32, out: *mut *mut rwkv_gen_watch) -> rwkv_status;
+    pub fn rwkv_gen_watch_close(e: *mut rwkv_engine, w: *mut rwkv_gen_watch) -> rwkv_status;
+    pub fn rwkv_gen_watch_head(w: *const rwkv_gen_watch, seq: *mut u64) -> rwkv_status;
+    pub fn rwkv_gen_watch_read(w: *mut rwkv_gen_watch, cursor: *mut u64, max_steps: i32, tokens: *mut u32, probs: *mut c_float, finish: *mut i32,
+                               n_steps: *mut i32, lost: *mut u64) -> rwkv_status;
+    pub fn rwkv_gen_watch_cancel(w: *mut rwkv_gen_watch, slot: i32) -> rwkv_status;
     // `Formatter` for regular constraints: byte-level DFAs, masked and advanced on the device (sampler/bnf.rs:34-48, run.rs:676-680, 892-897, 990)
     pub fn rwkv_dfa_from_table(trans: *const u16, accepting: *const u8, n_states: i32, start: i32, out: *mut *mut rwkv_dfa) -> rwkv_status;
     pub fn rwkv_dfa_compile(pattern: *const u8, len: usize, out: *mut *mut rwkv_dfa) -> rwkv_status;

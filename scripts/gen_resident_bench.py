@@ -25,12 +25,17 @@ is timed on its own).
 
 `--stops N,LEN` gives every slot of the resident loop N stop strings of LEN bytes that never match, over a synthetic token table (ids map
 to 1-4 letters): the price of matching stop strings on the device (rwkv_gen_set_stops).  `--loops resident_1` is what a caller with stop
-strings had to do before: rwkv_gen_run(1) per token and `harness.StopMatcher` over every slot's token on the host."""
+strings had to do before: rwkv_gen_run(1) per token and `harness.StopMatcher` over every slot's token on the host.
+
+`--watch` adds the loop `resident_watch`: the resident loop with a watch open (rwkv_gen_watch_open; every step publishes its record into
+host memory and loads the slots' cancel words) and a reader thread that drains it while the run goes on.  Its regions alternate with
+`resident`'s in the same process; the result also carries `resident_watch_vs_resident` and the records the reader got and lost."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import threading
 import time
 
 import numpy as np
@@ -55,6 +60,7 @@ def main():
     ap.add_argument("--admission", action="store_true")
     ap.add_argument("--stops", default=None, help="N,LEN: every resident slot carries N never-matching stop strings of LEN bytes")
     ap.add_argument("--top", type=int, default=0, help="N: adds the loop resident_top, the resident loop with every slot listing its N most likely tokens")
+    ap.add_argument("--watch", action="store_true", help="adds the loop resident_watch: the resident loop with a watch open and a reader thread draining it")
     a = ap.parse_args()
     batches = [int(x) for x in a.batches.split(",")]
     B = max(batches)
@@ -97,7 +103,26 @@ def main():
 
     arm_s = {}
 
-    def resident(nb, top=0):
+    watch_stats = {}
+
+    def resident(nb, top=0, watch=False):
+        w = stop = reader = None
+        if watch:                                                    # opened and closed outside the timed region, like the arming
+            w, stop, got = eng.gen_watch_open(4096), threading.Event(), watch_stats.setdefault(nb, {"records": 0, "lost": 0})
+
+            def drain():
+                while True:
+                    done = stop.is_set()
+                    t_, _, _, lost = w.read(256)
+                    got["records"] += len(t_)
+                    got["lost"] += lost
+                    if not len(t_):
+                        if done:
+                            return
+                        time.sleep(0.0002)
+
+            reader = threading.Thread(target=drain, daemon=True)
+            reader.start()
         t = time.perf_counter()
         for b in range(nb):
             eng.gen_arm(b, first[b], n, H.NucleusSampler(), seed=1)
@@ -113,6 +138,10 @@ def main():
             ne = eng.gen_run(spr, top=top)[2]
             emitted += int(ne.sum())
         dt = time.perf_counter() - t
+        if watch:
+            stop.set()
+            reader.join()
+            w.close()
         for b in range(nb if n_stops else 0):
             eng.gen_disarm(b)                                       # the next loop's slots carry no strings
         return dt, emitted
@@ -137,6 +166,8 @@ def main():
     loops = {k: f for k, f in loops.items() if k in a.loops.split(",")}
     if a.top and "resident" in loops:
         loops["resident_top"] = lambda nb: resident(nb, a.top)
+    if a.watch and "resident" in loops:
+        loops["resident_watch"] = lambda nb: resident(nb, watch=True)
 
     def admission(mode, running=24, joiners=8, every=16, plen=256, tail=4):
         """One region.  Both modes call gen_run(every) while nobody is being admitted.  `leave_and_prefill` admits between two runs with
@@ -217,6 +248,9 @@ def main():
             for other in ("sample_bare", "greedy"):
                 if other in res:
                     res["resident_vs_" + other] = res["resident"]["tokens_per_s"] / res[other]["tokens_per_s"]
+        if "resident_watch" in res and "resident" in res:
+            res["resident_watch_vs_resident"] = res["resident_watch"]["tokens_per_s"] / res["resident"]["tokens_per_s"]
+            res["resident_watch"].update(watch_stats.get(nb, {}))   # over all regions, the warm-up included
         out["batches"][str(nb)] = res
     if a.admission:
         adm = {}
