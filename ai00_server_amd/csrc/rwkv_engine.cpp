@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -286,6 +287,21 @@ struct rwkv_gen_watch {
     unsigned *cancel() const { return gen_watch_cancel_ptr(ring, ring_steps, B); }
 };
 
+// A cached (state, output) pair on the device (rwkv_gen_take_item / rwkv_gen_item_from_host; CachedItem, run.rs:201-223).  It owns its
+// memory and belongs to no engine: `st` is the borrowed view rwkv_gen_item_state hands out, into `state`.
+struct rwkv_gen_item {
+    rwkv_dstate st;                                            // device; sxa | sxf | wkv inside `state` (internal layout, as a slot's)
+    float *state = nullptr, *row = nullptr;                    // [2 * nsx + nw], [V] the RAW head row
+    int version = 0, L = 0, C = 0, V = 0;
+    long nsx = 0, nw = 0;
+};
+static void gen_item_destroy(rwkv_gen_item *it) {
+    if (!it) return;
+    (void)hipSetDevice(it->st.device);
+    (void)hipFree(it->state); (void)hipFree(it->row);
+    delete it;
+}
+
 struct rwkv_engine {
     rwkv_model_info info{};
     int device = 0;
@@ -446,11 +462,35 @@ struct rwkv_engine {
     void gen_watch_close(rwkv_gen_watch *w);
     bool gen_cancel_set(int slot) const { return gen_watch && __atomic_load_n(gen_watch->cancel() + slot, __ATOMIC_ACQUIRE) != 0; }
     void gen_cancel_clear(int slot) { if (gen_watch) __atomic_store_n(gen_watch->cancel() + slot, 0u, __ATOMIC_RELEASE); }
+    // captures and items (rwkv_gen_set_capture / _take_item / _arm_item): beside d_gen, one GenCap per slot.  The host keeps what each
+    // slot was asked for, the items that wait to be taken, and which of them are complete or gone; a step launches gen_capture only
+    // when one of its slots captures (bit 37 of a decode graph's key)
+    GenCap *d_gen_cap = nullptr;
+    std::vector<unsigned> gen_capture, gen_cap_done, gen_cap_taken;   // per slot: RWKV_GEN_CAPTURE_* asked for / PROMPT written / handed over
+    std::vector<std::array<rwkv_gen_item *, 2>> gen_cap_item;         // per slot: the PROMPT and the FINISH item until they are taken
+    std::vector<float *> gen_inj_row;                                 // per slot: [V] the row of the item that armed it (allocated by its first rwkv_gen_arm_item)
+    std::vector<char> gen_inj;                                        // per slot: its first draw, from that row, is still to come
+    rwkv_gen_item *gen_item_new() const;
+    bool gen_item_fits(const rwkv_gen_item *it) const {
+        return it && it->st.device == device && it->version == info.version && it->L == info.num_layer && it->C == info.num_emb &&
+               it->V == info.num_vocab && it->nsx == sx_slot_stride && it->nw == wkv_slot_stride;
+    }
+    void gen_cap_upload(int slot);
+    void gen_drop_captures(int slot) {                                // host side; the device copy is rewritten by the next arm, nothing reads it before
+        for (rwkv_gen_item *&it : gen_cap_item[(size_t)slot]) { gen_item_destroy(it); it = nullptr; }
+        gen_capture[(size_t)slot] = gen_cap_done[(size_t)slot] = gen_cap_taken[(size_t)slot] = 0;
+        gen_inj[(size_t)slot] = 0;
+    }
+    bool gen_any_capture(const std::vector<int> &slots, unsigned bits) const { for (int b : slots) if (gen_capture[(size_t)b] & ~gen_cap_taken[(size_t)b] & bits) return true; return false; }
+    void gen_set_capture(int slot, unsigned what);
+    rwkv_gen_item *gen_take_item(int slot, unsigned which);
+    void gen_arm_item(int slot, const rwkv_gen_item *it, const rwkv_gen_params &p);
     void gen_init();
-    void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt);
+    void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt, bool from_item = false);
     void gen_disarm_slot(int slot) {
         gen_cancel_clear(slot);
         if (gen_armed.empty()) return;
+        gen_drop_captures(slot);
         gen_armed[(size_t)slot] = 0;
         gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
         gen_has_dfa[(size_t)slot] = 0;                             // likewise; the table's buffer is freed by the next arm / constraint / the destructor
@@ -459,12 +499,12 @@ struct rwkv_engine {
         gen_ppos[(size_t)slot] = 0;
     }
     size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda) const;
+    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda, bool cap = false) const;
     unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda);
+    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda, bool cap);
     void gen_decode_steps(const std::vector<int> &rows, int n);
-    void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain);
+    void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, const std::vector<int> &inj, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish, int n_top = 0,
                  float *out_tok_logp = nullptr, uint32_t *out_top_ids = nullptr, float *out_top_logp = nullptr);
     Knobs kn;                                                    // experiment switches, frozen at creation (rwkv_kernels.h)
@@ -505,6 +545,7 @@ struct rwkv_engine {
         for (void *p : allocs) (void)hipFree(p);
         for (void *p : gen_dfa_buf) if (p) (void)hipFree(p);
         for (void *p : gen_pda_buf) if (p) (void)hipFree(p);
+        for (auto &pair : gen_cap_item) for (rwkv_gen_item *it : pair) gen_item_destroy(it);   // asked for, never taken
         if (d_tok_end) (void)hipFree(d_tok_end);
         if (d_tok_off) (void)hipFree(d_tok_off);
         if (d_tok_bytes) (void)hipFree(d_tok_bytes);
@@ -562,8 +603,8 @@ struct rwkv_engine {
     void log_row(const char *kernel, int T, long grid, double bytes);   // RWKV_LAUNCH_LOG: algorithmic bytes of a non-GEMM launch of layer 0 / 1
     int step_max_rows = 0;                                // most rows any sequence has in the step being enqueued (run_plan)
     float *lnp_xx_att = nullptr;                          // normalised rows published by the V6 mix's LN-prologue launch (for the commit)
-    void plan_step(const rwkv_slot_input *in, StepPlan &pl);
-    void upload_plan(const StepPlan &pl);
+    void plan_step(const rwkv_slot_input *in, StepPlan &pl, int reserve = 0);   // reserve: rows of the chunk that are spoken for (gen_mixed_step)
+    void upload_plan(const StepPlan &pl, const std::vector<int> &pseudo = {});
     void run_layers(int T, int n_seq, int n_out, const int *d_token, bool dense);
     void infer(const rwkv_slot_input *in, rwkv_slot_output *out);
     void run_plan(const StepPlan &pl);
@@ -1104,7 +1145,7 @@ static void water_fill(long budget, const std::vector<size_t> &pending, std::vec
     }
 }
 
-void rwkv_engine::plan_step(const rwkv_slot_input *in, StepPlan &pl) {
+void rwkv_engine::plan_step(const rwkv_slot_input *in, StepPlan &pl, int reserve) {
     const int B = max_batch;
     // A decode loop hands the same pattern (the same slots, one token each, every row emitted) step after step: the plan of
     // the previous call is reused with the new token ids (dense: row index == slot index).
@@ -1122,7 +1163,7 @@ void rwkv_engine::plan_step(const rwkv_slot_input *in, StepPlan &pl) {
     pl.slot_out_rows.assign(B, 0);
     std::vector<size_t> pending(B);
     for (int b = 0; b < B; ++b) pending[b] = in[b].n_tokens;
-    water_fill(chunk, pending, pl.slot_consumed);
+    water_fill(chunk - reserve, pending, pl.slot_consumed);
     pl.token.clear(); pl.slot.clear(); pl.prev.clear(); pl.last.clear();
     pl.seq_slot.clear(); pl.seq_begin.clear(); pl.seq_len.clear(); pl.out_rows.clear();
     for (int b = 0; b < B; ++b) {
@@ -1154,7 +1195,9 @@ void rwkv_engine::plan_step(const rwkv_slot_input *in, StepPlan &pl) {
     for (int b = 0; b < B; ++b) { last_ntok[b] = in[b].n_tokens; last_opt[b] = in[b].option; }
 }
 
-void rwkv_engine::upload_plan(const StepPlan &pl) {
+// pseudo: slots that have a logits row but no step row (rwkv_gen_arm_item's first draw).  Their rows stand behind the plan's in `slot`
+// and `out_rows`, where the sampler stage finds them; the forward pass keeps seeing T rows.  T + pseudo.size() <= chunk (plan_step's reserve).
+void rwkv_engine::upload_plan(const StepPlan &pl, const std::vector<int> &pseudo) {
     // a staging buffer is free again when the copy that read it has run (a step that emits nothing returns without waiting for the device,
     // so the previous copies may still be queued: four buffers, each guarded by the event recorded behind its copy)
     const int slot = meta_next;
@@ -1169,6 +1212,7 @@ void rwkv_engine::upload_plan(const StepPlan &pl) {
     std::memcpy(h.seq_slot, pl.seq_slot.data(), pl.n_seq * 4);
     std::memcpy(h.seq_begin, pl.seq_begin.data(), pl.n_seq * 4);
     std::memcpy(h.seq_len, pl.seq_len.data(), pl.n_seq * 4);
+    for (size_t j = 0; j < pseudo.size(); ++j) { h.slot[(size_t)pl.T + j] = pseudo[j]; h.out_rows[(size_t)pl.n_out + j] = pl.T + (int)j; }
     HIP_CHECK(hipMemcpyAsync(d_meta, h.token, meta_cap * 4, hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipEventRecord(meta_ev[slot], s_main));
     uploaded_id = pl.id;
@@ -1685,11 +1729,17 @@ void rwkv_engine::gen_init() {
     d_gen_out = dalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
     h_gen_out = hostalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
     HIP_CHECK(hipMemset(d_gen_shadow, 0, B * sizeof(float *)));
+    gen_capture.assign(B, 0); gen_cap_done.assign(B, 0); gen_cap_taken.assign(B, 0);
+    gen_cap_item.assign(B, {nullptr, nullptr});
+    gen_inj_row.assign(B, nullptr);
+    gen_inj.assign(B, 0);
+    d_gen_cap = dalloc<GenCap>(B);
+    HIP_CHECK(hipMemset(d_gen_cap, 0, B * sizeof(GenCap)));
     d_gen = dalloc<GenSlot>(B);                                   // last: marks the block as complete
     HIP_CHECK(hipMemset(d_gen, 0, B * sizeof(GenSlot)));
 }
 
-void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt) {
+void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt, bool from_item) {
     HIP_CHECK(hipSetDevice(device));
     const size_t V = (size_t)info.num_vocab;
     if (V > 65536) throw RwkvError(RWKV_ERR_UNSUPPORTED, "on-device sampling needs num_vocab <= 65536");
@@ -1701,7 +1751,7 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     if (p.n_stop > RWKV_GEN_MAX_STOP) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP stop tokens");
     if (!miro && !(p.temperature > 0.f)) throw RwkvError(RWKV_ERR_INVALID, "temperature must be > 0");
     if (p.max_tokens <= 0) throw RwkvError(RWKV_ERR_INVALID, "max_tokens must be > 0");
-    if (!prompt && p.first_token >= V) throw RwkvError(RWKV_ERR_INVALID, "first_token out of range");
+    if (!prompt && !from_item && p.first_token >= V) throw RwkvError(RWKV_ERR_INVALID, "first_token out of range");
     for (size_t i = 0; i < n_prompt; ++i) if (prompt[i] >= V) throw RwkvError(RWKV_ERR_INVALID, "prompt token out of range");
     if ((p.n_penalty && (!p.penalty_tokens || !p.penalty_values)) || (p.n_bias && (!p.bias_tokens || !p.bias_values)) || (p.n_stop && !p.stop_tokens))
         throw RwkvError(RWKV_ERR_INVALID, "null penalty / bias / stop array");
@@ -1735,7 +1785,8 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     HIP_CHECK(hipMemsetAsync(&d_gen_stop[b].n_str, 0, 2 * sizeof(int), s_main));   // re-arming clears the stop strings and their buffer
     HIP_CHECK(hipMemsetAsync(d_gen_dfa + b, 0, sizeof(GenDfa), s_main));             // ... and the constraint
     HIP_CHECK(hipMemsetAsync(d_gen_pda + b, 0, sizeof(GenPda), s_main));             // ... of either kind
-    const int first = prompt ? 0 : (int)p.first_token;             // with a prompt the slot's first draw fills it
+    HIP_CHECK(hipMemsetAsync(d_gen_cap + b, 0, sizeof(GenCap), s_main));             // ... and what it captured or started from
+    const int first = prompt || from_item ? 0 : (int)p.first_token;   // with a prompt, or an item, the slot's first draw fills it
     HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     gen_host[b] = g;
@@ -1748,6 +1799,7 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     }
     gen_drop_dfa_buf(slot);                                        // behind the synchronize: no step is in flight
     gen_drop_pda_buf(slot);
+    gen_drop_captures(slot);                                       // an item nobody took goes with the request that asked for it
     gen_prompt[b].assign(prompt, prompt + n_prompt);
     gen_ppos[b] = 0;
     gen_armed[b] = 1;
@@ -2001,8 +2053,102 @@ void rwkv_engine::gen_watch_close(rwkv_gen_watch *w) {
     gen_watch = nullptr;
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda) const {
+// ---- captures and items: the prefix cache's two fill points (run.rs:834-845, 995-1001) and its full hit (run.rs:809-810) ----
+static_assert(RWKV_GEN_CAPTURE_PROMPT == GEN_CAPTURE_PROMPT && RWKV_GEN_CAPTURE_FINISH == GEN_CAPTURE_FINISH, "rwkv_abi.h and rwkv_kernels.h disagree");
+rwkv_gen_item *rwkv_engine::gen_item_new() const {
+    std::unique_ptr<rwkv_gen_item, void (*)(rwkv_gen_item *)> it(new rwkv_gen_item(), gen_item_destroy);
+    it->st.device = device;
+    it->version = info.version; it->L = info.num_layer; it->C = info.num_emb; it->V = info.num_vocab;
+    it->nsx = sx_slot_stride; it->nw = wkv_slot_stride;
+    HIP_CHECK(hipMalloc((void **)&it->state, (size_t)(2 * it->nsx + it->nw) * 4));
+    HIP_CHECK(hipMalloc((void **)&it->row, (size_t)it->V * 4));
+    it->st.sxa = it->state; it->st.sxf = it->state + it->nsx; it->st.wkv = it->state + 2 * it->nsx;
+    return it.release();
+}
+// the slot's GenCap as the host knows it.  Between runs: the stream is idle.
+void rwkv_engine::gen_cap_upload(int slot) {
+    const size_t b = (size_t)slot;
+    GenCap c{};
+    if (const rwkv_gen_item *it = gen_cap_item[b][0]) { c.p_state = it->state; c.p_row = it->row; }
+    if (const rwkv_gen_item *it = gen_cap_item[b][1]) c.f_row = it->row;
+    if (gen_inj[b]) c.inj_row = gen_inj_row[b];
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    HIP_CHECK(hipMemcpy(d_gen_cap + b, &c, sizeof c, hipMemcpyHostToDevice));
+}
+void rwkv_engine::gen_set_capture(int slot, unsigned what) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a capture needs an armed, unfinished slot");
+    if (what & ~(unsigned)(RWKV_GEN_CAPTURE_PROMPT | RWKV_GEN_CAPTURE_FINISH)) throw RwkvError(RWKV_ERR_INVALID, "unknown capture bit");
+    if ((what & RWKV_GEN_CAPTURE_PROMPT) && gen_prompt_left(slot) == 0)
+        throw RwkvError(RWKV_ERR_INVALID, "RWKV_GEN_CAPTURE_PROMPT: the slot has no prompt left, its end has passed");
+    std::array<rwkv_gen_item *, 2> fresh{nullptr, nullptr};         // everything is allocated before anything changes
+    try {
+        for (int i = 0; i < 2; ++i) if ((what >> i & 1) && !gen_cap_item[b][(size_t)i]) fresh[(size_t)i] = gen_item_new();
+    } catch (...) {
+        for (rwkv_gen_item *it : fresh) gen_item_destroy(it);
+        throw;
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    for (int i = 0; i < 2; ++i) {
+        rwkv_gen_item *&it = gen_cap_item[b][(size_t)i];
+        if (fresh[(size_t)i]) { it = fresh[(size_t)i]; gen_cap_taken[b] &= ~(1u << i); gen_cap_done[b] &= ~(1u << i); }
+        else if (!(what >> i & 1)) { gen_item_destroy(it); it = nullptr; gen_cap_taken[b] &= ~(1u << i); gen_cap_done[b] &= ~(1u << i); }
+    }
+    gen_capture[b] = what;
+    gen_cap_upload(slot);
+}
+rwkv_gen_item *rwkv_engine::gen_take_item(int slot, unsigned which) {
+    HIP_CHECK(hipSetDevice(device));
+    const size_t b = (size_t)slot;
+    if (which != RWKV_GEN_CAPTURE_PROMPT && which != RWKV_GEN_CAPTURE_FINISH) throw RwkvError(RWKV_ERR_INVALID, "`which` must be exactly one RWKV_GEN_CAPTURE_* bit");
+    if (gen_armed.empty() || !(gen_capture[b] & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot was not asked to capture this item");
+    if (gen_cap_taken[b] & which) throw RwkvError(RWKV_ERR_INVALID, "the item was already taken");
+    const int i = which == RWKV_GEN_CAPTURE_PROMPT ? 0 : 1;
+    rwkv_gen_item *it = gen_cap_item[b][(size_t)i];
+    if (i == 0) {
+        if (!(gen_cap_done[b] & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot's prompt is not exhausted yet");
+    } else {
+        const int fin = gen_host[b].finish;
+        if (!fin) throw RwkvError(RWKV_ERR_INVALID, "the slot is still running");
+        if (fin == RWKV_GEN_CANCELLED && gen_prompt_left(slot)) throw RwkvError(RWKV_ERR_INVALID, "the slot was cancelled inside its prompt: it never drew");
+        // the state rule's state: gen_freeze kept it, the end of the run put it back into the slot, and nothing has run the slot since
+        HIP_CHECK(hipMemcpyAsync(it->st.sxa, sxa + slot * sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(it->st.sxf, sxf + slot * sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(it->st.wkv, wkv + slot * wkv_slot_stride, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipStreamSynchronize(s_main));
+    }
+    gen_cap_item[b][(size_t)i] = nullptr;
+    gen_cap_taken[b] |= which;
+    try { gen_cap_upload(slot); } catch (...) { gen_cap_item[b][(size_t)i] = it; gen_cap_taken[b] &= ~which; throw; }   // no step may write what the caller owns
+    return it;
+}
+// rwkv_gen_arm_prompt for a prompt that is wholly cached: the slot takes the item's state, and the item's row waits in a buffer of the
+// slot's own for the first step (gen_mixed_step), so the item may be freed as soon as this returns.
+void rwkv_engine::gen_arm_item(int slot, const rwkv_gen_item *it, const rwkv_gen_params &p) {
+    HIP_CHECK(hipSetDevice(device));
+    if (!gen_item_fits(it)) throw RwkvError(RWKV_ERR_INVALID, "the item is null or was made for another device, model version or dimensions");
+    // the refusals of rwkv_gen_arm, all as RWKV_ERR_INVALID: an item is a resident-only object, there is no other path to name
+    try { gen_arm(slot, p, nullptr, 0, true); }
+    catch (const RwkvError &err) { if (err.code == RWKV_ERR_UNSUPPORTED) throw RwkvError(RWKV_ERR_INVALID, err.what()); throw; }
+    const size_t b = (size_t)slot;
+    try {
+        if (!gen_inj_row[b]) gen_inj_row[b] = dalloc<float>((size_t)info.num_vocab);
+        HIP_CHECK(hipMemcpyAsync(gen_inj_row[b], it->row, (size_t)it->V * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(sxa + slot * sx_slot_stride, it->st.sxa, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(sxf + slot * sx_slot_stride, it->st.sxf, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(wkv + slot * wkv_slot_stride, it->st.wkv, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        gen_inj[b] = 1;
+        gen_cap_upload(slot);
+    } catch (...) {
+        gen_disarm_slot(slot);
+        throw;
+    }
+}
+
+GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda, bool cap) const {
     GenArgs a{};
+    if (cap) a.cap = d_gen_cap;
     if (topn) {
         a.topn_n = d_gen_topn_n; a.top_ids = d_gen_top_ids; a.top_logp = d_gen_top_logp; a.tok_logp = d_gen_tok_logp;
         a.side_ms = d_gen_side_ms; a.side_rows = d_gen_side_rows;
@@ -2023,6 +2169,7 @@ GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool 
 
 // the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
 void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
+    if (a.cap) launch(FAM_COPY, [&] { launch_gen_capture(a, s_main); });   // the raw rows, like gen_topn: in front of gen_pre
     if (a.topn_n) launch(FAM_SAMPLE, [&] { launch_gen_topn(a, s_main); });   // the raw rows: gen_pre edits the block in place
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
     if (a.dfa) launch(FAM_SAMPLE, [&] { launch_gen_mask(a, s_main); });   // `transform` (run.rs:676-679) of the constrained rows
@@ -2034,9 +2181,9 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda, bool cap) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T, stops, dfa, topn, pda), needs);
+    gen_sample(gen_args(pl.T, stops, dfa, topn, pda, cap), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
@@ -2047,6 +2194,7 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     const bool dfa = gen_any_dfa(rows);                            // a slot of this row set has a constraint: gen_mask_kernel joins the step
     const bool topn = gen_any_topn(rows);                          // a slot of this row set lists: gen_topn_kernel joins the step
     const bool pda = gen_any_pda(rows);                            // a slot of this row set has a stack constraint: gen_pda_mask_kernel joins the step
+    const bool cap = gen_any_capture(rows, RWKV_GEN_CAPTURE_FINISH);   // a slot of this row set keeps its rows for a FINISH item: gen_capture_kernel joins the step
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
@@ -2056,13 +2204,14 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
     for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
     key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0) | (pda ? 1ull << 35 : 0) |
-                 (gen_watch ? 1ull << 36 : 0);                     // a step under a watch launches gen_publish as well
+                 (gen_watch ? 1ull << 36 : 0) |                    // a step under a watch launches gen_publish as well
+                 (cap ? 1ull << 37 : 0);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn, pda); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn, pda); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn, pda, cap); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn, pda, cap); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -2072,25 +2221,35 @@ void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
 // left of the chunk (plan_step's water-filling: a pending count of 1 is always served first, so decode rows are never starved).  The
 // logits block holds the decode rows and the last row of every prompt that ends here; the <true> kernels sample exactly those.  Runs
 // uncaptured through the plan path, like the first step of a new row set: its shape is a one-off.
-void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, std::vector<int> &remain) {
+// A slot of `inj` (rwkv_gen_arm_item, its first step) consumes nothing: it has no step row, only a logits row behind the forward pass's,
+// into which gen_inject copies its item's row; it takes one row of the chunk all the same.  With nothing but such slots the step runs
+// no forward pass at all.
+void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, const std::vector<int> &inj, std::vector<int> &remain) {
     const int B = max_batch;
     // dec.size() < chunk: gen_run checked, before its first step, that all live slots together fit one chunk
     std::vector<rwkv_slot_input> in = one_token_each(dec, nullptr);
     for (int b : pro) in[(size_t)b] = rwkv_slot_input{gen_prompt[(size_t)b].data() + gen_ppos[(size_t)b], gen_prompt_left(b), RWKV_OPTION_LAST, 0};
     StepPlan pl;
-    plan_step(in.data(), pl);
+    plan_step(in.data(), pl, (int)inj.size());
     for (int i = 0; i < pl.n_seq; ++i) if (!gen_prompt_left(pl.seq_slot[i])) pl.token[(size_t)pl.seq_begin[i]] = -1;   // a decode row; gen_tokens_kernel: held[slot]
     std::vector<int> drawn;                                        // the slots that sample here: every decode row, every prompt that ends
     for (int b = 0; b < B; ++b) if (pl.slot_out_rows[(size_t)b]) drawn.push_back(b);
-    upload_plan(pl);
+    bool cap = gen_any_capture(drawn, RWKV_GEN_CAPTURE_FINISH) || gen_any_capture(inj, RWKV_GEN_CAPTURE_FINISH);
+    for (int b : pro)                                              // the prompts that end here and are to be kept: complete once this step has run
+        if (pl.slot_out_rows[(size_t)b] && (gen_capture[(size_t)b] & RWKV_GEN_CAPTURE_PROMPT)) { gen_cap_done[(size_t)b] |= RWKV_GEN_CAPTURE_PROMPT; cap = true; }
+    drawn.insert(drawn.end(), inj.begin(), inj.end());
+    const int n_rows = pl.n_out + (int)inj.size();
+    upload_plan(pl, inj);
     uploaded_id = 0;                                               // the uploaded token row is not the plan's: nobody may skip an upload on it
     launch(FAM_ROW, [&] { launch_gen_tokens(dm.token, dm.slot, d_gen_held, d_gen_runstep, pl.T, s_main); });
     step_max_rows = pl.max_rows();
-    run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
-    if (pl.n_out > 0) {
-        GenArgs a = gen_args(pl.n_out, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn), gen_any_pda(drawn));
+    if (pl.T > 0) run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
+    if (n_rows > 0) {
+        GenArgs a = gen_args(n_rows, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn), gen_any_pda(drawn), cap || !inj.empty());
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
+        if (!inj.empty()) launch(FAM_COPY, [&] { launch_gen_inject(a, pl.n_out, s_main); });
+        if (!cap) a.cap = nullptr;                                 // gen_inject alone needed it
         gen_sample(a, gen_needs(drawn));
     } else if (gen_watch) {                                        // a step without a row still publishes its (all padding) record
         const GenArgs a = gen_args(0, false, false, false, false);
@@ -2101,6 +2260,7 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
         gen_ppos[(size_t)b] += (size_t)pl.slot_consumed[(size_t)b];
         if (pl.slot_out_rows[(size_t)b]) remain[(size_t)b] -= 1;      // the prompt ended: its last row was the slot's first draw
     }
+    for (int b : inj) { gen_inj[(size_t)b] = 0; remain[(size_t)b] -= 1; }
 }
 
 // n_top > 0 (rwkv_gen_run_topn): the three top-n outputs are filled as well, n_top places per step and slot.
@@ -2160,13 +2320,14 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
                 if (gen_prompt_left(b) && gen_cancel_set(b)) { cancelled.push_back(b); live.erase(live.begin() + (long)i); }
                 else ++i;
             }
-            std::vector<int> dec, pro;                             // ascending slot order
+            std::vector<int> dec, pro, inj;                        // ascending slot order
             for (int b : live) {
                 if (gen_prompt_left(b)) pro.push_back(b);
+                else if (gen_inj[(size_t)b]) inj.push_back(b);         // armed from an item: its first draw needs no forward row
                 else if (remain[(size_t)b] > 0) dec.push_back(b);
             }
-            if (!pro.empty()) {
-                gen_mixed_step(dec, pro, remain);
+            if (!pro.empty() || !inj.empty()) {
+                gen_mixed_step(dec, pro, inj, remain);
                 k += 1;
                 continue;
             }
@@ -2755,6 +2916,59 @@ rwkv_status rwkv_gen_run(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, 
         if (!e || !out_tokens || n_steps <= 0) throw RwkvError(RWKV_ERR_INVALID, "bad arguments");
         use_knobs(e->kn);
         e->gen_run(n_steps, out_tokens, out_probs, n_emitted, finish);
+    });
+}
+// ---- captures and items ----
+rwkv_status rwkv_gen_set_capture(rwkv_engine *e, int32_t slot, uint32_t what) {
+    return guard([&] {
+        check_slot(e, slot);
+        e->gen_set_capture(slot, what);
+    });
+}
+rwkv_status rwkv_gen_take_item(rwkv_engine *e, int32_t slot, uint32_t which, rwkv_gen_item **out) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!out) throw RwkvError(RWKV_ERR_INVALID, "null out");
+        *out = e->gen_take_item(slot, which);
+    });
+}
+void rwkv_gen_item_free(rwkv_gen_item *it) { gen_item_destroy(it); }
+const void *rwkv_gen_item_state(const rwkv_gen_item *it) { return it ? &it->st : nullptr; }
+rwkv_status rwkv_gen_item_back(rwkv_engine *e, const rwkv_gen_item *it, float *state_dst, float *row_dst) {
+    return guard([&] {
+        if (!e) throw RwkvError(RWKV_ERR_INVALID, "null engine");
+        if (!e->gen_item_fits(it)) throw RwkvError(RWKV_ERR_INVALID, "the item is null or was made for another device, model version or dimensions");
+        HIP_CHECK(hipSetDevice(e->device));
+        if (state_dst) {
+            const size_t n = rwkv_state_len(e);
+            launch_state_pack(pack_args(e, it->st.sxa, it->st.sxf, it->st.wkv, 1, -1), e->s_main);   // to_slab: the item is only read
+            HIP_CHECK(hipMemcpyAsync(e->slab_host, e->slab_dev, n * 4, hipMemcpyDeviceToHost, e->s_main));
+            HIP_CHECK(hipStreamSynchronize(e->s_main));
+            std::memcpy(state_dst, e->slab_host, n * 4);
+        }
+        if (row_dst) HIP_CHECK(hipMemcpy(row_dst, it->row, (size_t)it->V * 4, hipMemcpyDeviceToHost));
+    });
+}
+rwkv_status rwkv_gen_item_from_host(rwkv_engine *e, const float *state, const float *row, rwkv_gen_item **out) {
+    return guard([&] {
+        if (!e || !state || !row || !out) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        HIP_CHECK(hipSetDevice(e->device));
+        std::unique_ptr<rwkv_gen_item, void (*)(rwkv_gen_item *)> it(e->gen_item_new(), gen_item_destroy);
+        const size_t n = rwkv_state_len(e);
+        std::memcpy(e->slab_host, state, n * 4);
+        HIP_CHECK(hipMemcpyAsync(e->slab_dev, e->slab_host, n * 4, hipMemcpyHostToDevice, e->s_main));
+        launch_state_pack(pack_args(e, it->st.sxa, it->st.sxf, it->st.wkv, 0, -1), e->s_main);
+        HIP_CHECK(hipStreamSynchronize(e->s_main));
+        HIP_CHECK(hipMemcpy(it->row, row, (size_t)it->V * 4, hipMemcpyHostToDevice));
+        *out = it.release();
+    });
+}
+rwkv_status rwkv_gen_arm_item(rwkv_engine *e, int32_t slot, const rwkv_gen_item *it, const rwkv_gen_params *p) {
+    return guard([&] {
+        check_slot(e, slot);
+        if (!p) throw RwkvError(RWKV_ERR_INVALID, "null params");
+        use_knobs(e->kn);
+        e->gen_arm_item(slot, it, *p);
     });
 }
 // ---- the watch: open / close on the infer thread between runs; head / read / cancel from ANY thread, on the watch's host block alone ----

@@ -335,6 +335,12 @@ struct GenWatchDev {                // one per engine, DEVICE-RESIDENT: captured
     int ring_steps;
     int reserved;
 };
+constexpr unsigned GEN_CAPTURE_PROMPT = 1u, GEN_CAPTURE_FINISH = 2u;
+struct GenCap {                     // one per slot, beside GenSlot: where the slot's captures go (rwkv_gen_set_capture) and the row it starts from (rwkv_gen_arm_item)
+    float *p_state, *p_row;         // the PROMPT item's sxa | sxf | wkv and raw row, or null: not asked for, or already taken
+    float *f_row;                   // the FINISH item's raw row, or null
+    const float *inj_row;           // [V] the row an item-armed slot draws its first token from
+};
 struct GenArgs {
     GenSlot *slots;                 // [max_batch]
     GenStop *stops;                 // [max_batch], or null: no slot of this step has stop strings (selects gen_post_kernel<., false>)
@@ -365,6 +371,7 @@ struct GenArgs {
     float *side_ms, *side_rows;     // [max_batch][2], [max_batch][V]: (m, ln S) and the raw row of every logits row that lists (gen_topn -> gen_post)
     GenPda *pda;                    // [max_batch], or null: no slot of this step has a stack constraint (gen_pda_mask is not launched, gen_post skips it)
     GenWatchDev *watch;             // the engine's descriptor, or null: no watch is open (gen_publish is not launched)
+    const GenCap *cap;              // [max_batch], or null: no slot of this step captures (gen_capture is not launched)
 };
 RWKV_HD inline float gen_uniform_draw(unsigned long long seed, unsigned stream, unsigned step) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((((unsigned long long)stream << 32) | step) + 1ull);
@@ -380,7 +387,9 @@ void launch_gen_pda_mask(const GenArgs &a, hipStream_t s);                      
 void launch_gen_post(const GenArgs &a, hipStream_t s);
 void launch_gen_publish(const GenArgs &a, hipStream_t s);                                                            // a.watch != null; reads slots, out_tok / out_prob, run_step, max_batch
 void launch_gen_freeze(const GenArgs &a, hipStream_t s);
-void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T > 0
+void launch_gen_capture(const GenArgs &a, hipStream_t s);                                                            // a.cap != null; in front of gen_pre
+void launch_gen_inject(const GenArgs &a, int first_row, hipStream_t s);                                              // a.cap, a.out_rows != null; rows first_row .. n_rows
+void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s);       // T >= 0
 void launch_gen_handover(int *feedback, int *held, const int *row_slot, int T, bool to_held, hipStream_t s);         // T > 0
 // two-stage arg-max; scratch_v / scratch_i hold n_rows*32 partial (value, index) pairs
 void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *scratch_v, int *scratch_i, hipStream_t s);

@@ -3930,6 +3930,10 @@ void launch_nucleus(const float *logits, int n_rows, int V, const SampleRow *sp,
 // =====================================================================================
 // Device-resident sampled generation (rwkv_gen_run): the sampler state machine of sampler/nucleus.rs, typical.rs and mirostat.rs
 // around `nucleus_kernel`, so that a captured step feeds itself.  Per step, after the head GEMM:
+//   gen_inject  only in a mixed step with a slot armed from an item (rwkv_gen_arm_item): the item's raw row into the logits block, behind
+//               the rows the head wrote
+//   gen_capture only in a step in which a slot captures (rwkv_gen_set_capture): the RAW rows — and, where a prompt ends, the state —
+//               into the slots' items, before gen_pre edits the block
 //   gen_pre     penalty (transform, nucleus.rs:61-67) and bias (run.rs:681-683) onto the logits row from the slot's dense penalty /
 //               bias rows, and this step's SampleRow (uniform draw, Mirostat's max_surprise) for nucleus_kernel
 //   gen_mask    only in a step in which a slot has a byte-automaton constraint (rwkv_gen_set_constraint, gen_dfa.h): `Formatter::transform`
@@ -4209,6 +4213,48 @@ __global__ __launch_bounds__(256) void gen_freeze_kernel(GenArgs a) {
         for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < len[part]; i += (long)gridDim.x * 1024)
             *(float4 *)(dst[part] + i) = *(const float4 *)(src[part] + i);
 }
+// The captures of rwkv_gen_set_capture (CachedItem, run.rs:201-223), launched in front of gen_pre — which edits the block in place — and
+// only in a step in which a slot captures.  Block (., row) looks at the slot of its logits row; a slot that captures nothing costs its
+// block one 32-byte load.  FINISH: a slot that has not finished copies its RAW row into the item's row, step after step, so the row
+// that stays is the one of the step it finishes in (gen_post / gen_publish set `finish` behind this launch; a rider no longer writes).
+// PROMPT: only a mixed step ends a prompt, and the row of a slot that has drawn nothing yet (draws == 0) is its prompt's last — the
+// host launches this kernel for such a step and leaves p_row null on every slot that may not capture (an item- or token-armed one);
+// the slot's sxa | sxf | wkv, which have consumed exactly the prompt here, and the raw row go into the item.
+// Reads the logits block, the slots and the state; writes only item memory: no token, probability or state depends on it.
+template <bool MIXED>
+__global__ __launch_bounds__(256) void gen_capture_kernel(GenArgs a) {
+    const int row = blockIdx.y;
+    const int slot = gen_slot_of<MIXED>(a, row);
+    const GenCap c = a.cap[slot];
+    if (!c.f_row && !(MIXED && c.p_row)) return;                   // the common case: one load per block and out
+    const GenSlot &g = a.slots[slot];
+    if (g.finish) return;
+    const bool prompt = MIXED && c.p_row && g.draws == 0;
+    if (!c.f_row && !prompt) return;
+    const long first = ((long)blockIdx.x * 256 + threadIdx.x) * 4, stride = (long)gridDim.x * 1024;
+    const float *x = a.logits + (long)row * a.V;                   // V % 16 == 0 (validate_info): whole float4s
+    for (long i = first; i < a.V; i += stride) {
+        const float4 v = *(const float4 *)(x + i);
+        if (c.f_row) *(float4 *)(c.f_row + i) = v;
+        if (prompt) *(float4 *)(c.p_row + i) = v;
+    }
+    if (!prompt) return;
+    const long nsx = a.sx_slot_stride, nw = a.wkv_slot_stride;      // multiples of 64 floats
+    const float *src[3] = {a.sxa + slot * nsx, a.sxf + slot * nsx, a.wkv + slot * nw};
+    float *dst[3] = {c.p_state, c.p_state + nsx, c.p_state + 2 * nsx};
+    const long len[3] = {nsx, nsx, nw};
+    for (int part = 0; part < 3; ++part)
+        for (long i = first; i < len[part]; i += stride) *(float4 *)(dst[part] + i) = *(const float4 *)(src[part] + i);
+}
+// The capture run the other way (rwkv_gen_arm_item): logits row first_row + blockIdx.y of a mixed step belongs to a slot armed from an
+// item, has no step row behind it, and takes the item's raw row — from there on it is a row like any other of the block.
+__global__ __launch_bounds__(256) void gen_inject_kernel(GenArgs a, int first_row) {
+    const int row = first_row + blockIdx.y;
+    const float *src = a.cap[gen_slot_of<true>(a, row)].inj_row;
+    if (!src) return;
+    float *x = a.logits + (long)row * a.V;
+    for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < a.V; i += (long)gridDim.x * 1024) *(float4 *)(x + i) = *(const float4 *)(src + i);
+}
 // The step's RECORD into the ring of the open watch (rwkv_gen_watch_open, gen_watch.h), and the cancel words.  One block, launched in
 // every step while a watch is open: behind gen_post (the step's cells of the output ring are written, a slot that finished by itself has
 // its reason) and in front of gen_freeze (a slot cancelled here is frozen in this very step, exactly like a stop); alone in a mixed step
@@ -4275,6 +4321,13 @@ void launch_gen_freeze(const GenArgs &a, hipStream_t s) {
     if (a.out_rows) hipLaunchKernelGGL(gen_freeze_kernel<true>, dim3(64, a.n_rows), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gen_freeze_kernel<false>, dim3(64, a.n_rows), dim3(256), 0, s, a);
 }
+void launch_gen_capture(const GenArgs &a, hipStream_t s) {
+    if (a.out_rows) hipLaunchKernelGGL(gen_capture_kernel<true>, dim3(64, a.n_rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gen_capture_kernel<false>, dim3(64, a.n_rows), dim3(256), 0, s, a);
+}
+void launch_gen_inject(const GenArgs &a, int first_row, hipStream_t s) {
+    hipLaunchKernelGGL(gen_inject_kernel, dim3(16, a.n_rows - first_row), dim3(256), 0, s, a, first_row);
+}
 // The token ids of a mixed step: the plan carries the prompt rows' ids and -1 in the row of every slot that feeds itself; that row
 // takes the token its slot drew last (held[slot]).  Also counts the run's step: a mixed step may emit no row at all.
 __global__ __launch_bounds__(256) void gen_tokens_kernel(int *token, const int *row_slot, const int *held, int *run_step, int T) {
@@ -4290,7 +4343,7 @@ __global__ __launch_bounds__(256) void gen_handover_kernel(int *feedback, int *h
     else feedback[r] = held[row_slot[r]];
 }
 void launch_gen_tokens(int *token, const int *row_slot, const int *held, int *run_step, int T, hipStream_t s) {
-    hipLaunchKernelGGL(gen_tokens_kernel, dim3((T + 255) / 256), dim3(256), 0, s, token, row_slot, held, run_step, T);
+    hipLaunchKernelGGL(gen_tokens_kernel, dim3(max(1, (T + 255) / 256)), dim3(256), 0, s, token, row_slot, held, run_step, T);   // T == 0: the step is counted all the same
 }
 void launch_gen_handover(int *feedback, int *held, const int *row_slot, int T, bool to_held, hipStream_t s) {
     hipLaunchKernelGGL(gen_handover_kernel, dim3((T + 255) / 256), dim3(256), 0, s, feedback, held, row_slot, T, to_held ? 1 : 0);

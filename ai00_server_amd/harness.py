@@ -20,7 +20,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .runtime import SCORE_SKIP, TOPN_NONE, RnnInput, RnnInputBatch, RnnOption
+from .runtime import SCORE_SKIP, TOPN_NONE, GenCapture, RnnInput, RnnInputBatch, RnnOption
 
 
 @dataclass
@@ -123,15 +123,25 @@ def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = 
 
 
 def generate_resident(runtime, slot: int, prompt, max_tokens: int, sampler, seed: int = 0, stop_tokens=(), top_logprobs: int = 0,
-                      steps_per_run: int = 16, constraint=None, halt: int = 0) -> list:
+                      steps_per_run: int = 16, constraint=None, halt: int = 0, capture=GenCapture(0), item=None):
     """One request through resident generation: `slot` is armed with the whole `prompt` (`Runtime.gen_arm_prompt`; `sampler` is the host
     sampler right after `init(prompt)`) and run until it finishes; nothing but token ids and a few numbers cross PCIe.  Returns one
     (token, prob) per emitted token; with `top_logprobs` = n > 0 (`Runtime.gen_set_topn`) one (token, logp, [(id, logp), ...]) instead:
     the token's ln-probability and the n most likely alternatives of the RAW model row (before penalties, bias and temperature), most
     likely first, as an OpenAI-style `logprobs` object lists them.  Other armed slots ride along; their tokens are dropped here.
     `constraint` is a `runtime.Dfa` or a `runtime.Pda` (`Pda.json(...)` for "answer in JSON"), set from its start with halt mode `halt`;
-    it needs the token table (`Runtime.gen_set_token_bytes`)."""
-    runtime.gen_arm_prompt(slot, prompt, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    it needs the token table (`Runtime.gen_set_token_bytes`).
+    The prefix cache (run.rs:809-810, 834-845, 995-1001): with `item` (a `runtime.GenItem` that holds the whole prompt) the slot is armed by
+    `Runtime.gen_arm_item` — no prefill, the first token is drawn from the item's row — and `prompt` is only the sampler's history.  With
+    `capture` (`GenCapture.Prompt`, `.Finish` or both; `Prompt` needs a prompt to run, so not with `item`) the call returns
+    (out, {flag: GenItem}) with the items the slot made."""
+    if item is not None:
+        runtime.gen_arm_item(slot, item, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    else:
+        runtime.gen_arm_prompt(slot, prompt, max_tokens, sampler, seed=seed, stop_tokens=stop_tokens)
+    capture = GenCapture(capture)
+    if capture:
+        runtime.gen_set_capture(slot, capture)
     if constraint is not None:
         if hasattr(constraint, "max_depth"):
             runtime.gen_set_pda(slot, constraint, halt=halt)
@@ -152,7 +162,9 @@ def generate_resident(runtime, slot: int, prompt, max_tokens: int, sampler, seed
             tok_logp, ids, lp = res[4][k, slot], res[5][k, slot], res[6][k, slot]
             out.append((int(toks[k, slot]), float(tok_logp), [(int(i), float(v)) for i, v in zip(ids, lp) if i != TOPN_NONE]))
         if finish[slot]:
-            return out
+            if not capture:
+                return out
+            return out, {flag: runtime.gen_take_item(slot, flag) for flag in (GenCapture.Prompt, GenCapture.Finish) if capture & flag}
 
 
 def generate_resident_stream(runtime, slot: int, prompt, max_tokens: int, sampler, seed: int = 0, stop_tokens=(), top_logprobs: int = 0,

@@ -124,6 +124,13 @@ ABI_SYMBOLS = {
     "rwkv_gen_watch_read": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "rwkv_gen_watch_cancel": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "rwkv_gen_set_capture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32]),
+    "rwkv_gen_take_item": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rwkv_gen_item_free": (None, [C.c_void_p]),
+    "rwkv_gen_item_state": (C.c_void_p, [C.c_void_p]),
+    "rwkv_gen_item_back": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rwkv_gen_item_from_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rwkv_gen_arm_item": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(_GenParamsC)]),
     "rwkv_dfa_from_table": (C.c_int32, [C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "rwkv_dfa_compile": (C.c_int32, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rwkv_dfa_free": (None, [C.c_void_p]),
@@ -649,18 +656,77 @@ class GenWatch:
 
 
 class TensorGpu:
-    """Device-resident state snapshot (`state.read` result); reusable for many `state.write`s."""
+    """Device-resident state snapshot (`state.read` result); reusable for many `state.write`s.  With `owner` it is a view into memory
+    the owner frees (`GenItem.state()`), kept alive by the reference."""
 
-    def __init__(self, h):
+    def __init__(self, h, owner=None):
         self._h = h
+        self._owner = owner
 
     def __del__(self):
-        if getattr(self, "_h", None):
+        if getattr(self, "_h", None) and getattr(self, "_owner", None) is None:
             try:
                 lib().rwkv_dstate_free(self._h)
             except Exception:
                 pass
             self._h = None
+
+
+class GenCapture(enum.IntFlag):   # RWKV_GEN_CAPTURE_*: the two points at which `process` fills the prefix cache
+    Prompt = 1                    # run.rs:834-845: the state behind the whole prompt and the prompt's last row
+    Finish = 2                    # run.rs:995-1001: the state the STATE RULE prescribes and the row the last token was drawn from
+
+
+class GenItem:
+    """A cached (state, raw logits row) pair on the device (rwkv_gen_item; CachedItem, run.rs:201-223): what `Runtime.gen_take_item`
+    hands out and `Runtime.gen_arm_item` starts a slot from.  Immutable; it outlives the slot and the engine that made it, and any
+    engine of the same device, model version and dimensions reads it.  `close()` (or garbage collection) frees it."""
+
+    def __init__(self, rt: "Runtime", h):
+        self._rt, self._h = rt, h
+
+    def _handle(self):
+        if not self._h:
+            raise RwkvError(-1, "the item is closed")
+        return self._h
+
+    def state(self) -> "TensorGpu":
+        """the item's state as `State.write` takes it (rwkv_gen_item_state; a PARTIAL prefix hit); a view, valid while the item is"""
+        return TensorGpu(C.c_void_p(lib().rwkv_gen_item_state(self._handle())), owner=self)
+
+    def back(self, rt: "Runtime | None" = None):
+        """(state in the layout of `State.back`, row float32 [num_vocab]) on the host (rwkv_gen_item_back), bit for bit"""
+        rt = rt or self._rt
+        st, row = np.empty(rt.state._np_shape(), np.float32), np.empty(rt.info.num_vocab, np.float32)
+        _check(lib().rwkv_gen_item_back(rt._h, self._handle(), st.ctypes.data, row.ctypes.data))
+        return st, row
+
+    def row(self) -> np.ndarray:
+        """the RAW head row: before penalties, bias, temperature and masks"""
+        row = np.empty(self._rt.info.num_vocab, np.float32)
+        _check(lib().rwkv_gen_item_back(self._rt._h, self._handle(), None, row.ctypes.data))
+        return row
+
+    @staticmethod
+    def from_host(rt: "Runtime", state: np.ndarray, row: np.ndarray) -> "GenItem":
+        """An item of `rt`'s device from what `back()` returned (rwkv_gen_item_from_host): the way into another engine, or back from disk"""
+        st, r = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(row, np.float32).reshape(-1)
+        if st.size != int(np.prod(rt.state._np_shape())) or r.size != rt.info.num_vocab:
+            raise RwkvError(-1, "state or row has the wrong size")
+        h = C.c_void_p()
+        _check(lib().rwkv_gen_item_from_host(rt._h, st.ctypes.data, r.ctypes.data, C.byref(h)))
+        return GenItem(rt, h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            h, self._h = self._h, None
+            lib().rwkv_gen_item_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ModelBuilder:
@@ -999,6 +1065,27 @@ class Runtime:
         _check(lib().rwkv_gen_arm_prompt(self._h, int(slot), toks.ctypes.data_as(C.POINTER(C.c_uint32)) if toks.size else None, toks.size,
                                          C.byref(p)))
         del keep
+
+    def gen_arm_item(self, slot: int, item: "GenItem", max_tokens: int, sampler, seed: int = 0, stream: int | None = None,
+                     stop_tokens=(), bias: dict | None = None, allow=None, wide_top_k: bool = False):
+        """`gen_arm_prompt` for a prompt that is wholly cached (rwkv_gen_arm_item; run.rs:809-810): the slot's state becomes the item's and
+        its first token is drawn on the device from the item's row, draw 0 of (seed, stream), in its first step, which consumes nothing.
+        `sampler` is the host sampler right after `init(prompt)`, as for `gen_arm_prompt`.  The item is only read."""
+        p, keep = self._gen_params(slot, 0, max_tokens, sampler, seed, stream, stop_tokens, bias, allow, wide_top_k)
+        _check(lib().rwkv_gen_arm_item(self._h, int(slot), item._handle() if item is not None else None, C.byref(p)))
+        del keep
+
+    def gen_set_capture(self, slot: int, what: "GenCapture"):
+        """What an armed, unfinished slot keeps for the prefix cache (rwkv_gen_set_capture), set between runs: `GenCapture.Prompt` (only
+        while the slot still has prompt left), `GenCapture.Finish`, both, or `GenCapture(0)` to clear.  Re-arming the slot resets it."""
+        _check(lib().rwkv_gen_set_capture(self._h, int(slot), int(what)))
+
+    def gen_take_item(self, slot: int, which: "GenCapture") -> "GenItem":
+        """The slot's captured item (rwkv_gen_take_item), exactly one flag: `Prompt` once the run that exhausted the prompt has returned,
+        `Finish` once the slot has finished.  Each can be taken once; the item is the caller's."""
+        h = C.c_void_p()
+        _check(lib().rwkv_gen_take_item(self._h, int(slot), int(which), C.byref(h)))
+        return GenItem(self, h)
 
     def gen_prompt_left(self, slot: int) -> int:
         """Prompt tokens of `slot` the resident steps have not consumed yet (0 once it is decoding, or when it is not armed)."""

@@ -50,7 +50,10 @@ extern "C" {
                               *    rwkv_gen_set_pda, rwkv_gen_pda_config: a NESTED format constraint ("answer in JSON") is masked and advanced on the
                               *    device inside the resident step
                               *    additive under 9: rwkv_gen_watch_open / _close / _head / _read / _cancel, RWKV_GEN_CANCELLED, RWKV_GEN_WATCH_MAX_STEPS:
-                              *    another thread streams the tokens of a running rwkv_gen_run and cancels slots inside it */
+                              *    another thread streams the tokens of a running rwkv_gen_run and cancels slots inside it
+                              *    additive under 9: rwkv_gen_set_capture, rwkv_gen_take_item, rwkv_gen_item_free / _state / _back / _from_host,
+                              *    rwkv_gen_arm_item, RWKV_GEN_CAPTURE_PROMPT / _FINISH: resident generation fills the prefix cache (the state and raw
+                              *    row at the prompt's end and at a stop) and arms a slot from a cached item */
 
 typedef int32_t rwkv_status;
 enum {
@@ -660,6 +663,51 @@ rwkv_status rwkv_gen_pda_config(rwkv_engine *e, int32_t slot, int32_t *state, ui
 rwkv_status rwkv_gen_set_topn(rwkv_engine *e, int32_t slot, int32_t n);
 rwkv_status rwkv_gen_run_topn(rwkv_engine *e, int32_t n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish,
                               int32_t n_top, float *out_tok_logp, uint32_t *out_top_ids, float *out_top_logp);
+
+/* ---- captures and items: resident generation fills and uses the prefix cache.  The reference caches CachedItem(state, output) pairs
+ * (run.rs:201-223) at two points of `process`: when the prompt's last row arrives (run.rs:834-845) and when a request stops
+ * (run.rs:995-1001); a request whose whole prompt is cached samples straight from the cached row, `(0, Some(output)) => output`
+ * (run.rs:809-810).  An ITEM is such a pair on the device: a state and the RAW head row — before penalties, bias, temperature and masks,
+ * the definition rwkv_gen_set_topn uses.  It is immutable, owns its memory, and outlives the slot and the engine that made it.
+ * The threading contract is that of rwkv_infer.
+ *   rwkv_gen_set_capture: what an armed, unfinished slot keeps, set between runs like rwkv_gen_set_stops.  `what` is a set of
+ *     RWKV_GEN_CAPTURE_* bits; a bit that is clear drops that item if nobody took it, so 0 clears everything; an unknown bit is RWKV_ERR_INVALID, and so is PROMPT on a slot with
+ *     rwkv_gen_prompt_left == 0.  Re-arming the slot and everything that disarms it clear the setting and drop any item not taken.  The
+ *     call allocates what the capture needs (one state and one row per bit); nothing is allocated inside a run.
+ *   The PROMPT item: the slot's state after it has consumed exactly its prompt, on top of the state the prompt was armed on, and the raw
+ *     row of the prompt's last token.  Both are taken in the step that exhausts the prompt; the item can be taken as soon as that run has
+ *     returned, while the slot goes on decoding.
+ *   The FINISH item: complete when the slot finishes, for any reason but a cancel inside its prompt.  The state the STATE RULE prescribes
+ *     (everything consumed except the last emitted token) and the raw row of the step the slot finished in — the row its last token was
+ *     drawn from.  A slot that finishes on its first draw has FINISH == PROMPT, bit for bit.  Taken while the slot stays armed and finished.
+ *   rwkv_gen_take_item: `which` is exactly one bit.  RWKV_ERR_INVALID when the item was not asked for, is not complete yet (the prompt is
+ *     not exhausted, the slot still runs, it was cancelled inside its prompt) or was already taken.  Ownership passes to the caller
+ *     (rwkv_gen_item_free; NULL is fine).
+ *   INVARIANT: capturing changes no token, probability, finish reason, stop tail, constraint state, top-n list, watch record or state of
+ *     any slot — the extra launch reads the logits block and the state and writes item memory only — and a step in which no slot captures
+ *     launches what it launched before, from the same captured graphs.
+ *   rwkv_gen_item_state: the item's state, borrowed, for rwkv_state_write (a PARTIAL prefix hit continues with rwkv_gen_arm_prompt).  It is
+ *     a const rwkv_dstate * that lives as long as the item and must not go to rwkv_dstate_free; NULL for a NULL item.
+ *   rwkv_gen_item_back / _from_host: `state` in the slab layout of rwkv_state_back (rwkv_state_len floats), `row` num_vocab floats; either
+ *     destination of _back may be NULL.  The round trip is bit-exact.  An item is accepted by any engine whose device, model version
+ *     and dimensions match its maker's, else RWKV_ERR_INVALID.
+ *   rwkv_gen_arm_item: rwkv_gen_arm_prompt for a prompt that is wholly cached.  The slot's state becomes the item's; `p` is read as
+ *     rwkv_gen_arm_prompt reads it (first_token ignored, the penalty arrays are the map after `init(prompt)`).  In its FIRST STEP the slot
+ *     consumes nothing: its first token is drawn on the device from the item's row with draw counter 0 of (seed, stream), by the
+ *     arithmetic of any draw; penalty and Mirostat updates, the stop, constraint and max_tokens tests follow as after any draw.  From the
+ *     next step on it is a decoding slot.  It counts as one row towards token_chunk_size; a step whose only participants are such slots
+ *     runs no forward pass.  The refusals of rwkv_gen_arm apply, every one as RWKV_ERR_INVALID, and leave the slot as it was.  The item is only read and is free again when the call returns; it may
+ *     arm any number of slots. */
+#define RWKV_GEN_CAPTURE_PROMPT 1u
+#define RWKV_GEN_CAPTURE_FINISH 2u
+typedef struct rwkv_gen_item rwkv_gen_item;     /* CachedItem run.rs:201-223: a device-resident (state, raw logits row) pair; immutable */
+rwkv_status rwkv_gen_set_capture(rwkv_engine *e, int32_t slot, uint32_t what);
+rwkv_status rwkv_gen_take_item(rwkv_engine *e, int32_t slot, uint32_t which, rwkv_gen_item **out);
+void rwkv_gen_item_free(rwkv_gen_item *it);
+const void *rwkv_gen_item_state(const rwkv_gen_item *it);   /* a const rwkv_dstate *, owned by the item: hand it to rwkv_state_write */
+rwkv_status rwkv_gen_item_back(rwkv_engine *e, const rwkv_gen_item *it, float *state_dst, float *row_dst);
+rwkv_status rwkv_gen_item_from_host(rwkv_engine *e, const float *state, const float *row, rwkv_gen_item **out);
+rwkv_status rwkv_gen_arm_item(rwkv_engine *e, int32_t slot, const rwkv_gen_item *it, const rwkv_gen_params *p);
 
 /* ---- `Tokenizer` lib.rs:375; run.rs:157-168,856; sampler/bnf.rs:14-27 ---------------------- */
 typedef struct rwkv_tokenizer rwkv_tokenizer;

@@ -469,6 +469,43 @@ class Runtime {
         int max_batch_ = 0;
     };
     std::unique_ptr<GenWatch> gen_watch_open(int ring_steps) { return std::make_unique<GenWatch>(e_, max_batch, ring_steps); }
+    // A cached (state, raw logits row) pair on the device (rwkv_gen_item; CachedItem, run.rs:201-223): what a slot captures at its prompt's
+    // end or when it finishes, and what gen_arm_item starts a slot from.  Immutable; clone == share, like TensorGpu; the last copy frees it.
+    // It outlives the Runtime that made it; back() wants a Runtime of the same device, model version and dimensions.
+    class GenItem {
+       public:
+        struct Host { std::vector<float> state, row; };   // `state` as State::back lays it out, `row` num_vocab floats
+        explicit GenItem(rwkv_gen_item *h) : h_(h, rwkv_gen_item_free) {}
+        static GenItem from_host(const Runtime &rt, const std::vector<float> &state, const std::vector<float> &row) {
+            if (state.size() != rwkv_state_len(rt.raw()) || row.size() != (size_t)rt.info.num_vocab) throw Error(RWKV_ERR_INVALID);
+            rwkv_gen_item *h = nullptr;
+            check(rwkv_gen_item_from_host(rt.raw(), state.data(), row.data(), &h));
+            return GenItem(h);
+        }
+        Host back(const Runtime &rt) const {
+            Host o{std::vector<float>(rwkv_state_len(rt.raw())), std::vector<float>((size_t)rt.info.num_vocab)};
+            check(rwkv_gen_item_back(rt.raw(), h_.get(), o.state.data(), o.row.data()));
+            return o;
+        }
+        // the item's state into a slot (rwkv_state_write of rwkv_gen_item_state): a PARTIAL prefix hit, continued with gen_arm_prompt
+        void write_state(const Runtime &rt, int batch) const {
+            check(rwkv_state_write(rt.raw(), batch, static_cast<const rwkv_dstate *>(rwkv_gen_item_state(h_.get()))));
+        }
+        const rwkv_gen_item *get() const { return h_.get(); }
+       private:
+        std::shared_ptr<rwkv_gen_item> h_;
+    };
+    // what an armed, unfinished slot keeps for the prefix cache, between runs: RWKV_GEN_CAPTURE_PROMPT | RWKV_GEN_CAPTURE_FINISH, 0 clears
+    void gen_set_capture(int slot, uint32_t what) { check(rwkv_gen_set_capture(e_.get(), slot, what)); }
+    // `which` is exactly one bit: PROMPT once the run that exhausted the prompt has returned, FINISH once the slot has finished; each once
+    GenItem gen_take_item(int slot, uint32_t which) {
+        rwkv_gen_item *h = nullptr;
+        check(rwkv_gen_take_item(e_.get(), slot, which, &h));
+        return GenItem(h);
+    }
+    // gen_arm_prompt for a prompt that is wholly cached (run.rs:809-810): `p` as for gen_arm_prompt; the first token is drawn on the device
+    // from the item's row in the slot's first step, which consumes nothing
+    void gen_arm_item(int slot, const GenItem &item, const rwkv_gen_params &p) { check(rwkv_gen_arm_item(e_.get(), slot, item.get(), &p)); }
     rwkv_engine *raw() const { return e_.get(); }
     ModelInfo info{};
     int max_batch = 0;

@@ -63,6 +63,9 @@ pub const RWKV_TOPN_NONE: u32 = 4294967295;
 #[repr(C)] pub struct rwkv_dfa { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_pda { _p: [u8; 0] }
 #[repr(C)] pub struct rwkv_gen_watch { _p: [u8; 0] }
+#[repr(C)] pub struct rwkv_gen_item { _p: [u8; 0] }
+pub const RWKV_GEN_CAPTURE_PROMPT: u32 = 1;
+pub const RWKV_GEN_CAPTURE_FINISH: u32 = 2;
 
 #[repr(C)] #[derive(Debug, Default, Clone, Copy, PartialEq, Eq)]
 pub struct rwkv_model_info { pub version: i32, pub num_layer: i32, pub num_emb: i32, pub num_hidden: i32,
@@ -162,6 +165,13 @@ extern "C" {
     pub fn rwkv_gen_watch_read(w: *mut rwkv_gen_watch, cursor: *mut u64, max_steps: i32, tokens: *mut u32, probs: *mut c_float, finish: *mut i32,
                                n_steps: *mut i32, lost: *mut u64) -> rwkv_status;
     pub fn rwkv_gen_watch_cancel(w: *mut rwkv_gen_watch, slot: i32) -> rwkv_status;
+    pub fn rwkv_gen_set_capture(e: *mut rwkv_engine, slot: i32, what: u32) -> rwkv_status;
+    pub fn rwkv_gen_take_item(e: *mut rwkv_engine, slot: i32, which: u32, out: *mut *mut rwkv_gen_item) -> rwkv_status;
+    pub fn rwkv_gen_item_free(it: *mut rwkv_gen_item);
+    pub fn rwkv_gen_item_state(it: *const rwkv_gen_item) -> *const rwkv_dstate;
+    pub fn rwkv_gen_item_back(e: *mut rwkv_engine, it: *const rwkv_gen_item, state_dst: *mut c_float, row_dst: *mut c_float) -> rwkv_status;
+    pub fn rwkv_gen_item_from_host(e: *mut rwkv_engine, state: *const c_float, row: *const c_float, out: *mut *mut rwkv_gen_item) -> rwkv_status;
+    pub fn rwkv_gen_arm_item(e: *mut rwkv_engine, slot: i32, it: *const rwkv_gen_item, p: *const rwkv_gen_params) -> rwkv_status;
     // `Formatter` for regular constraints: byte-level DFAs, masked and advanced on the device (sampler/bnf.rs:34-48, run.rs:676-680, 892-897, 990)
     pub fn rwkv_dfa_from_table(trans: *const u16, accepting: *const u8, n_states: i32, start: i32, out: *mut *mut rwkv_dfa) -> rwkv_status;
     pub fn rwkv_dfa_compile(pattern: *const u8, len: usize, out: *mut *mut rwkv_dfa) -> rwkv_status;

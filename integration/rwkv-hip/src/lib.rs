@@ -65,6 +65,17 @@ unsafe impl Send for DeviceState {}
 unsafe impl Sync for DeviceState {}
 impl Drop for DeviceState { fn drop(&mut self) { unsafe { sys::rwkv_dstate_free(self.0) } } }
 
+/// Which of the two cache fill points of `process` a slot keeps (rwkv_gen_set_capture): the prompt's end (run.rs:834-845), the stop
+/// (run.rs:995-1001).  `gen_set_capture` takes a sum of them, `gen_take_item` exactly one.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum GenCapture { Prompt = 1, Finish = 2 }
+/// `CachedItem` (run.rs:201-223) on the device: a state and the RAW head row it was followed by (rwkv_gen_item).  Immutable; it outlives
+/// the slot and the engine that made it; clone the `Arc` to share it, as the reference shares its `TensorGpu`s.
+#[derive(Debug)]
+pub struct GenItem(*mut sys::rwkv_gen_item);
+unsafe impl Send for GenItem {}
+unsafe impl Sync for GenItem {}
+impl Drop for GenItem { fn drop(&mut self) { unsafe { sys::rwkv_gen_item_free(self.0) } } }
+
 /// pinned host block for the logits of one `infer` call (rwkv_host_alloc): rows land here in one device-to-host copy
 #[derive(Debug)]
 pub struct PinnedLogits { ptr: *mut f32, floats: usize, in_flight: usize }
@@ -314,7 +325,41 @@ impl Engine {
         let mut left = 0usize;
         check(unsafe { sys::rwkv_gen_prompt_left(self.raw, slot as i32, &mut left) })?; Ok(left)
     }
-    fn gen_arm_with(&self, slot: usize, p: &GenParams, prompt: Option<&[u32]>) -> Result<()> {
+    /// `gen_arm_prompt` for a prompt that is wholly cached (rwkv_gen_arm_item, run.rs:809-810): the slot's state becomes the item's and its
+    /// first token is drawn on the device from the item's row, draw 0 of (seed, stream), in a first step that consumes nothing.
+    pub fn gen_arm_item(&self, slot: usize, item: &GenItem, p: &GenParams) -> Result<()> { self.gen_arm_from(slot, p, None, Some(item)) }
+    /// What an armed, unfinished slot keeps for the prefix cache (rwkv_gen_set_capture), between runs; an empty slice clears it.
+    pub fn gen_set_capture(&self, slot: usize, what: &[GenCapture]) -> Result<()> {
+        check(unsafe { sys::rwkv_gen_set_capture(self.raw, slot as i32, what.iter().fold(0u32, |m, &w| m | w as u32)) })
+    }
+    /// The slot's captured item (rwkv_gen_take_item): `Prompt` once the run that exhausted the prompt has returned, `Finish` once the slot
+    /// has finished; each once.
+    pub fn gen_take_item(&self, slot: usize, which: GenCapture) -> Result<std::sync::Arc<GenItem>> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_gen_take_item(self.raw, slot as i32, which as u32, &mut raw) })?;
+        Ok(std::sync::Arc::new(GenItem(raw)))
+    }
+    /// (state in the layout of `state_back`, row of num_vocab floats) of an item on the host (rwkv_gen_item_back), bit for bit
+    pub fn gen_item_back(&self, item: &GenItem) -> Result<(Vec<f32>, Vec<f32>)> {
+        let (mut state, mut row) = (vec![0f32; unsafe { sys::rwkv_state_len(self.raw) }], vec![0f32; self.info.num_vocab as usize]);
+        check(unsafe { sys::rwkv_gen_item_back(self.raw, item.0, state.as_mut_ptr(), row.as_mut_ptr()) })?;
+        Ok((state, row))
+    }
+    /// an item of this engine's device from what `gen_item_back` returned (rwkv_gen_item_from_host)
+    pub fn gen_item_from_host(&self, state: &[f32], row: &[f32]) -> Result<std::sync::Arc<GenItem>> {
+        if state.len() != unsafe { sys::rwkv_state_len(self.raw) } || row.len() != self.info.num_vocab as usize {
+            return Err(Error { code: sys::RWKV_ERR_INVALID, message: "gen_item_from_host: state or row has the wrong length".into() });
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::rwkv_gen_item_from_host(self.raw, state.as_ptr(), row.as_ptr(), &mut raw) })?;
+        Ok(std::sync::Arc::new(GenItem(raw)))
+    }
+    /// the item's state into `slot` (rwkv_state_write of rwkv_gen_item_state): a PARTIAL prefix hit, continued with `gen_arm_prompt`
+    pub fn gen_item_state_to(&self, item: &GenItem, slot: usize) -> Result<()> {
+        check(unsafe { sys::rwkv_state_write(self.raw, slot as i32, sys::rwkv_gen_item_state(item.0)) })
+    }
+    fn gen_arm_with(&self, slot: usize, p: &GenParams, prompt: Option<&[u32]>) -> Result<()> { self.gen_arm_from(slot, p, prompt, None) }
+    fn gen_arm_from(&self, slot: usize, p: &GenParams, prompt: Option<&[u32]>, item: Option<&GenItem>) -> Result<()> {
         let (pt, pv): (Vec<u32>, Vec<f32>) = p.penalties.iter().copied().unzip();
         let (bt, bv): (Vec<u32>, Vec<f32>) = p.bias.iter().copied().unzip();
         let raw = sys::rwkv_gen_params {
@@ -326,9 +371,10 @@ impl Engine {
             stop_tokens: p.stop_tokens.as_ptr(), n_stop: p.stop_tokens.len(), allow: ptr::null(),
             seed: p.seed, stream: p.stream, reserved: if p.top_k > 256 { sys::RWKV_GEN_WIDE_TOP_K } else { 0 },
         };
-        match prompt {
-            None => check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) }),
-            Some(t) => check(unsafe { sys::rwkv_gen_arm_prompt(self.raw, slot as i32, t.as_ptr(), t.len(), &raw) }),
+        match (prompt, item) {
+            (_, Some(it)) => check(unsafe { sys::rwkv_gen_arm_item(self.raw, slot as i32, it.0, &raw) }),
+            (None, None) => check(unsafe { sys::rwkv_gen_arm(self.raw, slot as i32, &raw) }),
+            (Some(t), None) => check(unsafe { sys::rwkv_gen_arm_prompt(self.raw, slot as i32, t.as_ptr(), t.len(), &raw) }),
         }
     }
     pub fn gen_disarm(&self, slot: usize) -> Result<()> { check(unsafe { sys::rwkv_gen_disarm(self.raw, slot as i32) }) }

@@ -29,7 +29,11 @@ strings had to do before: rwkv_gen_run(1) per token and `harness.StopMatcher` ov
 
 `--watch` adds the loop `resident_watch`: the resident loop with a watch open (rwkv_gen_watch_open; every step publishes its record into
 host memory and loads the slots' cancel words) and a reader thread that drains it while the run goes on.  Its regions alternate with
-`resident`'s in the same process; the result also carries `resident_watch_vs_resident` and the records the reader got and lost."""
+`resident`'s in the same process; the result also carries `resident_watch_vs_resident` and the records the reader got and lost.
+
+`--capture` adds the loop `resident_capture`: the resident loop with RWKV_GEN_CAPTURE_FINISH set on every slot (rwkv_gen_set_capture; one
+more launch per step that copies each running slot's raw row aside).  Its regions alternate with `resident`'s in the same process; the
+result also carries `resident_capture_vs_resident`."""
 import argparse
 import json
 import os
@@ -61,6 +65,7 @@ def main():
     ap.add_argument("--stops", default=None, help="N,LEN: every resident slot carries N never-matching stop strings of LEN bytes")
     ap.add_argument("--top", type=int, default=0, help="N: adds the loop resident_top, the resident loop with every slot listing its N most likely tokens")
     ap.add_argument("--watch", action="store_true", help="adds the loop resident_watch: the resident loop with a watch open and a reader thread draining it")
+    ap.add_argument("--capture", action="store_true", help="adds the loop resident_capture: the resident loop with every slot capturing its FINISH item")
     a = ap.parse_args()
     batches = [int(x) for x in a.batches.split(",")]
     B = max(batches)
@@ -105,7 +110,7 @@ def main():
 
     watch_stats = {}
 
-    def resident(nb, top=0, watch=False):
+    def resident(nb, top=0, watch=False, capture=False):
         w = stop = reader = None
         if watch:                                                    # opened and closed outside the timed region, like the arming
             w, stop, got = eng.gen_watch_open(4096), threading.Event(), watch_stats.setdefault(nb, {"records": 0, "lost": 0})
@@ -132,6 +137,8 @@ def main():
             eng.gen_set_topn(b, top)                                # re-arming resets it: the plain loop's slots list nothing
         for b in range(nb if n_stops else 0):
             eng.gen_set_stops(b, stops)
+        for b in range(nb if capture else 0):
+            eng.gen_set_capture(b, rt.GenCapture.Finish)            # re-arming resets it, and drops the item the region before left untaken
         emitted = 0
         t = time.perf_counter()
         for _ in range(-(-n // spr)):
@@ -168,6 +175,8 @@ def main():
         loops["resident_top"] = lambda nb: resident(nb, a.top)
     if a.watch and "resident" in loops:
         loops["resident_watch"] = lambda nb: resident(nb, watch=True)
+    if a.capture and "resident" in loops:
+        loops["resident_capture"] = lambda nb: resident(nb, capture=True)
 
     def admission(mode, running=24, joiners=8, every=16, plen=256, tail=4):
         """One region.  Both modes call gen_run(every) while nobody is being admitted.  `leave_and_prefill` admits between two runs with
@@ -251,6 +260,8 @@ def main():
         if "resident_watch" in res and "resident" in res:
             res["resident_watch_vs_resident"] = res["resident_watch"]["tokens_per_s"] / res["resident"]["tokens_per_s"]
             res["resident_watch"].update(watch_stats.get(nb, {}))   # over all regions, the warm-up included
+        if "resident_capture" in res and "resident" in res:
+            res["resident_capture_vs_resident"] = res["resident_capture"]["tokens_per_s"] / res["resident"]["tokens_per_s"]
         out["batches"][str(nb)] = res
     if a.admission:
         adm = {}
