@@ -12,13 +12,15 @@ import zlib
 import numpy as np
 import pytest
 
-from tests import mix_cases as M, probe_io as P, row_cases as R, sample_cases as S
+from tests import gen_cases as G, mix_cases as M, probe_io as P, row_cases as R, sample_cases as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # program, magic, K_COUNT, the parameter-count limit, R_COUNT, the small element size: the ProbeSpec of each probe's main()
 SPEC = {"row": ("row_probe", 0x42525052, len(R.KIND_NAME), 16, len(R.ROLE), 2), "mix": ("mix_probe", 0x4252504D, len(M.KIND_NAME), 32, len(M.ROLE), 2),
-        "sample": ("sample_probe", 0x42525053, len(S.KIND_NAME), 8, len(S.ROLE), 1)}
-SMALLEST = {"row": (R, "state_pack"), "mix": (M, "commit"), "sample": (S, "routing")}      # the smallest group of each family
+        "sample": ("sample_probe", 0x42525053, len(S.KIND_NAME), 8, len(S.ROLE), 1), "gen": ("gen_probe", G.MAGIC, len(G.KIND_NAME), len(G.PARAMS), len(G.ROLE), 1)}
+SMALLEST = {"row": (R, "state_pack"), "mix": (M, "commit"), "sample": (S, "routing"), "gen": (G, "step")}
+# the smallest group of each family that holds buffers with an image and buffers the probe fills with the pattern (gen: `tokens` and `publish` are
+# smaller, but every buffer of theirs carries an image)
 
 
 @pytest.fixture(scope="module")
