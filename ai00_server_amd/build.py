@@ -109,9 +109,9 @@ def build_harness(verbose: bool = True) -> str:
 
 PROBE_DIR = os.path.join(HERE, "..", "tests", "cpp")
 PROBE_SHARED = ("probe_common.h", "probe_case.h")
-# tests/cpp/<name>.hip, the stand-alone kernel probe of tests/test_gpu_<family>_exact.py -> the headers beside it that enter its stamp
+# tests/cpp/<name>.hip, the stand-alone kernel probe of tests/test_gpu_<family>_exact.py (sf4_probe: tests/test_gpu_sf4.py) -> the headers beside it that enter its stamp
 PROBES = {"gemm_probe": ("gemm_probe_plan.h",), "row_probe": (), "mix_probe": ("mix_probe_plan.h",), "sample_probe": (), "topn_probe": (),
-          "gen_probe": ()}
+          "gen_probe": (), "sf4_probe": ("gemm_probe_plan.h",)}
 
 
 def kernel_objects() -> list:

@@ -239,10 +239,10 @@ inline TilePlan plan_tile(GemmLaunch &Lh, const ProbShape *ps, int n, int T, boo
         const ProbShape &s = ps[i];
         tot64 += gemm_tile_blocks(3, s.rows, T); t3 += gemm_tile_blocks(GEMM_TILE3, s.rows, T);
         maxK = std::max(maxK, s.K);
-        all_f16 = all_f16 && s.fmt == W_F16; all_nf4 = all_nf4 && s.fmt == W_NF4;
+        all_f16 = all_f16 && s.fmt == W_F16; all_nf4 = all_nf4 && fmt_is_4bit(s.fmt);   // (SF4 is NF4 to every rule: the same bytes, the same instructions)
         ok3 = ok3 && gemm_tile3_supported(hilo, s.K); ok4 = ok4 && gemm_tile4_supported(hilo, s.K);
         if (s.rows <= 512) continue;                            // (the fp16 LoRA stages — V6's decay, V7's w / a / g / v: 64..320 rows — ride along)
-        big_f16 = big_f16 || s.fmt == W_F16; big_not_nf4 = big_not_nf4 || s.fmt != W_NF4;
+        big_f16 = big_f16 || s.fmt == W_F16; big_not_nf4 = big_not_nf4 || !fmt_is_4bit(s.fmt);
     }
     int shape = tot64 <= 1536 ? 4 : 3;
     // fp16 weights fill a wave's registers twice as fast as Int8: the 128-k chunks (more blocks per CU) win at every grid size

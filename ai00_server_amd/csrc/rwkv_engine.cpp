@@ -157,7 +157,7 @@ struct Prefab {
                 uint64_t db = 0, sb = 0;
                 if (ok && e.h.fmt == W_F16) { ok = K % 32 == 0; db = (uint64_t)rows * K * 2; }
                 else if (ok && e.h.fmt == W_INT8) { ok = K % 256 == 0; db = (uint64_t)rows * K; sb = (uint64_t)rows * (K / 128) * 4; }
-                else if (ok && e.h.fmt == W_NF4) { ok = K % 256 == 0; db = (uint64_t)rows * K / 2; sb = (uint64_t)rows * (K / 64) * 2; }
+                else if (ok && fmt_is_4bit(e.h.fmt)) { ok = K % 256 == 0; db = (uint64_t)rows * K / 2; sb = (uint64_t)rows * (K / 64) * 2; }
                 else ok = false;
                 if (!ok || e.h.data_bytes != db || e.h.scale_bytes != sb) throw RwkvError(RWKV_ERR_FORMAT, "prefab: bad matrix entry " + name);
             } else throw RwkvError(RWKV_ERR_FORMAT, "prefab: unknown entry kind");
@@ -724,8 +724,8 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         quant_layers = prefab.hdr.quant_layers; quant_type = prefab.hdr.quant_type;
         if (d.n_lora) throw RwkvError(RWKV_ERR_UNSUPPORTED, "LoRA adapters cannot be applied to a prefab image");
     }
-    if (quant_type != RWKV_QUANT_NONE && quant_type != RWKV_QUANT_INT8 && quant_type != RWKV_QUANT_NF4)
-        throw RwkvError(RWKV_ERR_UNSUPPORTED, "quant_type must be None, Int8 or NF4 (SF4 is not supported)");
+    if (quant_type != RWKV_QUANT_NONE && quant_type != RWKV_QUANT_INT8 && quant_type != RWKV_QUANT_NF4 && quant_type != RWKV_QUANT_SF4)
+        throw RwkvError(RWKV_ERR_UNSUPPORTED, "quant_type must be None, Int8, NF4 or SF4");
     if (quant_type != RWKV_QUANT_NONE && quant_layers > 0 && (C % 256 || F % 256))
         throw RwkvError(RWKV_ERR_UNSUPPORTED, "quantisation needs num_emb and num_hidden to be multiples of 256");
 
@@ -892,7 +892,8 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         } else {
             void *p = dalloc<uint8_t>((size_t)m.rows * K / 2);
             void *sc = dalloc<uint8_t>((size_t)m.rows * (K / 64) * 2);
-            launch_quant_nf4(src, m.rows, K, p, sc, s_main);
+            if (fmt == W_SF4) launch_quant_sf4(src, m.rows, K, p, sc, s_main);   // NF4's bytes and sizes, the other code book
+            else launch_quant_nf4(src, m.rows, K, p, sc, s_main);
             m.data = p; m.scales = sc;
             m.bytes = (uint64_t)m.rows * K / 2 + (uint64_t)m.rows * (K / 64) * 2;
         }
@@ -916,7 +917,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         LayerW &w = layers[l];
         std::memset(&w, 0, sizeof(w));
         const std::string p = "blocks." + std::to_string(l) + ".";
-        const int qf = (quant_type != RWKV_QUANT_NONE && l < quant_layers) ? (quant_type == RWKV_QUANT_INT8 ? W_INT8 : W_NF4) : W_F16;
+        const int qf = (quant_type != RWKV_QUANT_NONE && l < quant_layers) ? (quant_type == RWKV_QUANT_INT8 ? W_INT8 : quant_type == RWKV_QUANT_SF4 ? W_SF4 : W_NF4) : W_F16;
         auto qfmt = [&](const char *suffix) { return is_quant_target(info.version, suffix) ? qf : W_F16; };
         // every vector is [C] (time_decay / time_first / r_k are [H, 64]); every matrix is checked against the shape the
         // forward pass assumes, so a truncated or inconsistent checkpoint fails here with RWKV_ERR_FORMAT
@@ -3080,11 +3081,11 @@ rwkv_status rwkv_gen_uniform(uint64_t seed, uint32_t stream, uint32_t first_step
 rwkv_status rwkv_bench_gemm(int32_t rows, int32_t K, int32_t fmt, int32_t T, int32_t hilo, int32_t spb, int32_t nmat,
                             int32_t iters, float *us_per_launch, float *lds_kib) {
     return guard([&] {
-        if (rows % 16 || K % 256 || T < 1 || nmat < 1 || iters < 1 || iters > 2000) throw RwkvError(RWKV_ERR_INVALID, "bad args");
+        if (rows % 16 || K % 256 || T < 1 || nmat < 1 || iters < 1 || iters > 2000 || fmt < W_F16 || fmt > W_SF4) throw RwkvError(RWKV_ERR_INVALID, "bad args");
         use_knobs(Knobs::from_env());                            // no engine here: the microbenchmark reads the environment per call
         hipStream_t st;
         HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t wbytes = fmt == W_F16 ? (size_t)rows * K * 2 : fmt == W_INT8 ? (size_t)rows * K : (size_t)rows * K / 2;
+        const size_t wbytes = fmt == W_F16 ? (size_t)rows * K * 2 : fmt == W_INT8 ? (size_t)rows * K : (size_t)rows * K / 2;   // NF4, SF4
         const size_t sbytes = fmt == W_F16 ? 16 : fmt == W_INT8 ? (size_t)rows * (K / 128) * 4 : (size_t)rows * (K / 64) * 2;
         std::vector<void *> bufs;
         auto dal = [&](size_t n) { void *p = nullptr; HIP_CHECK(hipMalloc(&p, n)); bufs.push_back(p); return p; };

@@ -19,7 +19,8 @@ typedef unsigned short _Float16;
 
 namespace rwkv {
 
-enum WFmt : int { W_F16 = 0, W_INT8 = 1, W_NF4 = 2 };
+enum WFmt : int { W_F16 = 0, W_INT8 = 1, W_NF4 = 2, W_SF4 = 3 };   // W_SF4: NF4's storage, read through the Student-t code book
+inline bool fmt_is_4bit(int fmt) { return fmt == W_NF4 || fmt == W_SF4; }   // one payload / scale layout, one kernel body, one planner rule
 enum Act : int { ACT_NONE = 0, ACT_TANH = 1, ACT_SIGMOID = 2, ACT_RELU2 = 3, ACT_SILU = 4, ACT_DECAY7 = 5 };
 enum Post : int { POST_NONE = 0, POST_MUL = 1, POST_MIX = 2 };
 
@@ -54,7 +55,7 @@ constexpr int NF4_BLOCK = 64;
 // A weight matrix W[rows][K] resident in HBM in the pre-tiled MFMA-A layout:
 //   fp16: tile = 16 rows x 32 k  = 1 KiB ; lane l holds row (l&15), k = kt*32 + (l>>4)*8 + [0,8)
 //   int8: tile = 16 rows x 64 k  = 1 KiB ; lane bytes [0,8) -> k-step 0, [8,16) -> k-step 1
-//   nf4 : tile = 16 rows x 128 k = 1 KiB ; lane byte m: k-step m/4, e = (m%4)*2 + {lo,hi nibble}
+//   nf4 : tile = 16 rows x 128 k = 1 KiB ; lane byte m: k-step m/4, e = (m%4)*2 + {lo,hi nibble}   (sf4: the same bytes)
 // tiles of one strip are contiguous along K: tile index = strip*KT + kt.
 struct DMat {
     const void *data = nullptr;     // tiled payload
@@ -398,6 +399,7 @@ void launch_argmax(const float *logits, int n_rows, int V, int *out_tok, float *
 void launch_tile_f16(const _Float16 *raw, int rows_valid, int rows, int K, void *out, hipStream_t s);
 void launch_quant_int8(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s);
 void launch_quant_nf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s);
+void launch_quant_sf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s);   // launch_quant_nf4 with the SF4 midpoints
 void launch_f16_to_f32(const _Float16 *in, float *out, long n, int op, hipStream_t s); // op 0: copy, 1: exp(-exp(x)), 2: -exp(x) (V4's time_decay)
 void launch_vec_blend(float *v, const _Float16 *l, long n, float alpha, hipStream_t s);   // v = alpha * l + (1 - alpha) * v   (LoRA file holds a whole vector tensor)
 void launch_vec_op(float *v, long n, int op, hipStream_t s);                              // the load-time transform, in place

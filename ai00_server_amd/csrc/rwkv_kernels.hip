@@ -250,25 +250,33 @@ __device__ __forceinline__ u32 dq8(u32 d, u32 sel, f16x2 a2, f16x2 b2) {
     return as_u32(__builtin_elementwise_fma(h, a2, b2));
 }
 
-// NF4 code points rounded to fp16 (oracle: NF4_TABLE_F16), as byte tables for v_perm lookups.
-static __device__ __constant__ unsigned short nf4_f16_bits[16] = {
+// The two 4-bit code books rounded to fp16, as byte tables for v_perm lookups: [0..16) NF4 (oracle: NF4_TABLE_F16), [16..32) SF4
+// (Student's t, 5 degrees of freedom; tests/sf4_ref.py SF4_TABLE_F16).  A W_SF4 problem is a W_NF4 problem that reads the second
+// table: the choice is made once per block from the problem's format (uniform), before the K loop.  The table words are compile-time
+// constants and the choice is a scalar select between two literals: no memory load stands between a block's start and its first fragment
+// (a table read from constant memory cost the NF4 decode step 1.7 %, profiles/r14_sf4_nf4_decode_ab_table_in_memory.jsonl).
+constexpr unsigned short nf4_f16_bits[32] = {
     0xBC00, 0xB992, 0xB833, 0xB652, 0xB48D, 0xB1EA, 0xADD4, 0x0000,
-    0x2D18, 0x3126, 0x33E0, 0x3568, 0x370D, 0x3880, 0x39C9, 0x3C00};
+    0x2D18, 0x3126, 0x33E0, 0x3568, 0x370D, 0x3880, 0x39C9, 0x3C00,
+    0xBC00, 0xB906, 0xB747, 0xB559, 0xB399, 0xB0E5, 0xACCD, 0x0000,
+    0x2C31, 0x3041, 0x328D, 0x348B, 0x3603, 0x37DB, 0x3941, 0x3C00};
+// byte `hi` (0 low, 1 high) of code points 4 d .. 4 d + 3 of table `book` (0 NF4, 1 SF4), one per byte of the word
+constexpr u32 nf4_lut_word(int book, int d, int hi) {
+    u32 w = 0;
+    for (int b = 0; b < 4; ++b) w |= (u32)((nf4_f16_bits[book * 16 + d * 4 + b] >> (8 * hi)) & 0xFF) << (8 * b);
+    return w;
+}
 
 struct Nf4Lut { u32 tl[4], th[4]; };
-__device__ __forceinline__ Nf4Lut make_nf4_lut() {
+template <int D>
+__device__ __forceinline__ void nf4_lut_pick(Nf4Lut &t, bool sf4) {
+    constexpr u32 nl = nf4_lut_word(0, D, 0), nh = nf4_lut_word(0, D, 1), sl = nf4_lut_word(1, D, 0), sh = nf4_lut_word(1, D, 1);
+    t.tl[D] = sf4 ? sl : nl; t.th[D] = sf4 ? sh : nh;
+}
+__device__ __forceinline__ Nf4Lut make_nf4_lut(int fmt) {
+    const bool sf4 = fmt == W_SF4;
     Nf4Lut t;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        u32 lo = 0, hi = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            u32 v = nf4_f16_bits[d * 4 + b];
-            lo |= (v & 0xFF) << (8 * b);
-            hi |= (v >> 8) << (8 * b);
-        }
-        t.tl[d] = lo; t.th[d] = hi;
-    }
+    nf4_lut_pick<0>(t, sf4); nf4_lut_pick<1>(t, sf4); nf4_lut_pick<2>(t, sf4); nf4_lut_pick<3>(t, sf4);
     return t;
 }
 // 4 nibble indices (one per byte of n) -> 4 fp16 code points as two half2 words
@@ -540,7 +548,7 @@ __device__ __forceinline__ void gemm_body(const GemmLaunch &L, const GemmProb &P
     f32x4 *red = (f32x4 *)smem;                                   // [spb][nw][NT][64 lanes]
 
     Nf4Lut lut;
-    if constexpr (FMT == W_NF4) lut = make_nf4_lut();
+    if constexpr (FMT == W_NF4) lut = make_nf4_lut(P.fmt);
 
     // one 256-k round of MFMAs: acc += W(round) * X(sub).  Two accumulators per n-tile (even / odd k-steps) halve the
     // MFMA read-after-write stalls of the otherwise serial chain.
@@ -781,7 +789,7 @@ __global__ __launch_bounds__(((NT == 4 || (NT == 2 && HILO)) ? GEMM_MAX_WAVES_K1
     // profiles/r5_exp_single_format_kernel.log — so code size is not where a launch's fixed cost goes.)
     if (P.fmt == W_F16) gemm_body<NT, KSW, HILO, SHOT, TAIL, W_F16>(L, P, smem);
     else if (P.fmt == W_INT8) gemm_body<NT, KSW, HILO, SHOT, false, W_INT8>(L, P, smem);   // quantised K is a multiple of 256
-    else gemm_body<NT, KSW, HILO, SHOT, false, W_NF4>(L, P, smem);
+    else gemm_body<NT, KSW, HILO, SHOT, false, W_NF4>(L, P, smem);   // W_NF4 and W_SF4: one body, the code book by P.fmt
 }
 
 void launch_gemm(const GemmLaunch &L, bool hilo, hipStream_t s) {
@@ -1475,7 +1483,7 @@ __device__ __forceinline__ void tg_body(const GemmLaunch &L, const GemmProb &P, 
     _Float16 *xs = (_Float16 *)smem;                              // [buf][hi|lo][token tile][k-tile][lane][8]
     constexpr int XP = BT * TG_KC / 8 / THREADS;                  // 16-byte pieces per thread per part
     Nf4Lut lut;
-    if constexpr (FMT == W_NF4) lut = make_nf4_lut();
+    if constexpr (FMT == W_NF4) lut = make_nf4_lut(P.fmt);
 
     f32x4 acc[SPW][NTL];
 #pragma unroll
@@ -1651,7 +1659,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_tile_kernel(const GemmLaunch 
     const GemmProb &P = L.p[pi];
     if (P.fmt == W_F16) tg_body<HILO, WAVES, SPW, NTL, KC, W_F16, GLDS>(L, P, smem);
     else if (P.fmt == W_INT8) tg_body<HILO, WAVES, SPW, NTL, KC, W_INT8, GLDS>(L, P, smem);
-    else tg_body<HILO, WAVES, SPW, NTL, KC, W_NF4, GLDS>(L, P, smem);
+    else tg_body<HILO, WAVES, SPW, NTL, KC, W_NF4, GLDS>(L, P, smem);   // W_NF4 and W_SF4: one body, the code book by P.fmt
 }
 
 #endif
@@ -1833,7 +1841,7 @@ __device__ __forceinline__ void tg3_body(const GemmLaunch &L, const GemmProb &P,
     const unsigned xs_byte = (unsigned)(uintptr_t)smem;           // LDS byte address of the ring (dynamic LDS starts at 0 here, kept general)
     const int last_tile = (L.T - 1) >> 4;
     Nf4Lut lut;
-    if constexpr (FMT == W_NF4) lut = make_nf4_lut();
+    if constexpr (FMT == W_NF4) lut = make_nf4_lut(P.fmt);
 
     f32x4 acc[SPW][NTW];
 #pragma unroll
@@ -1979,7 +1987,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile3_kernel(const GemmLaunch L) 
     const GemmProb &P = L.p[pi];
     if (P.fmt == W_F16) tg3_body<W_F16, NTL>(L, P, smem);
     else if (P.fmt == W_INT8) tg3_body<W_INT8, NTL>(L, P, smem);
-    else tg3_body<W_NF4, NTL>(L, P, smem);
+    else tg3_body<W_NF4, NTL>(L, P, smem);   // W_NF4 and W_SF4: one body, the code book by P.fmt
 }
 
 #endif
@@ -2116,7 +2124,7 @@ __device__ __forceinline__ void tg4_body(const GemmLaunch &L, const GemmProb &P,
     const unsigned xs_byte = (unsigned)(uintptr_t)smem;
     const int last_tile = (L.T - 1) >> 4;
     Nf4Lut lut;
-    if constexpr (FMT == W_NF4) lut = make_nf4_lut();
+    if constexpr (FMT == W_NF4) lut = make_nf4_lut(P.fmt);
 
     f32x4 acc[SPW][NTL];
 #pragma unroll
@@ -2253,7 +2261,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile4_kernel(const GemmLaunch L) 
     const GemmProb &P = L.p[pi];
     if (P.fmt == W_F16) tg4_body<W_F16, 4, true>(L, P, smem);
     else if (P.fmt == W_INT8) tg4_body<W_INT8, 4, true>(L, P, smem);
-    else tg4_body<W_NF4, 4, true>(L, P, smem);
+    else tg4_body<W_NF4, 4, true>(L, P, smem);   // W_NF4 and W_SF4: one body, the code book by P.fmt
 }
 
 
@@ -4438,25 +4446,39 @@ __global__ void quant_nf4_kernel(const _Float16 *raw, int rows, int K, unsigned 
         scales[(((long)strip * NG + (blk >> 2)) * 16 + r16) * 4 + (blk & 3)] = amh;
     }
 }
-static float *g_nf4_mid_dev[16] = {nullptr};
-void launch_quant_nf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!g_nf4_mid_dev[dev & 15]) {
-        // exact fp32 midpoints, computed like the oracle: (Q[i+1] + Q[i]) * 0.5f
-        static const float Q[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
+// the float32 code books of the two 4-bit formats; the kernels' fp16 byte tables (nf4_f16_bits) are these rounded once
+static const float kNf4Table[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
                                     -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
                                     0.07958029955625534f, 0.16093020141124725f, 0.24611230194568634f, 0.33791524171829224f,
                                     0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f};
+// SF4: NF4's construction over Student's t with 5 degrees of freedom (pinned by tests/golden/sf4_table.json)
+static const float kSf4Table[16] = {-1.0f, -0.6277806758880615f, -0.4547361135482788f, -0.33433082699775696f,
+                                    -0.23743444681167603f, -0.15289874374866486f, -0.07498248666524887f, 0.0f,
+                                    0.06551308929920197f, 0.13296476006507874f, 0.2046610713005066f, 0.2838347852230072f,
+                                    0.37580493092536926f, 0.49107569456100464f, 0.6567812561988831f, 1.0f};
+static float *g_nf4_mid_dev[16] = {nullptr};
+static float *g_sf4_mid_dev[16] = {nullptr};
+static void launch_quant_4bit(const float (&Q)[16], float *(&mid_dev)[16], const _Float16 *raw, int rows, int K, void *out, void *scales,
+                              hipStream_t s) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!mid_dev[dev & 15]) {
+        // exact fp32 midpoints, computed like the oracle: (Q[i+1] + Q[i]) * 0.5f
         float mids[15];
         for (int i = 0; i < 15; ++i) mids[i] = (Q[i + 1] + Q[i]) * 0.5f;
         float *d = nullptr;
         (void)hipMalloc(&d, sizeof(mids));
         (void)hipMemcpy(d, mids, sizeof(mids), hipMemcpyHostToDevice);
-        g_nf4_mid_dev[dev & 15] = d;
+        mid_dev[dev & 15] = d;
     }
     hipLaunchKernelGGL(quant_nf4_kernel, dim3(2048), dim3(256), 0, s, raw, rows, K, (unsigned char *)out,
-                       (_Float16 *)scales, (const float *)g_nf4_mid_dev[dev & 15]);
+                       (_Float16 *)scales, (const float *)mid_dev[dev & 15]);
+}
+void launch_quant_nf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s) {
+    launch_quant_4bit(kNf4Table, g_nf4_mid_dev, raw, rows, K, out, scales, s);
+}
+void launch_quant_sf4(const _Float16 *raw, int rows, int K, void *out, void *scales, hipStream_t s) {
+    launch_quant_4bit(kSf4Table, g_sf4_mid_dev, raw, rows, K, out, scales, s);
 }
 
 __global__ void f16_to_f32_kernel(const _Float16 *in, float *out, long n, int op) {

@@ -231,10 +231,11 @@ class ModelVersion(enum.IntEnum):
     V7 = 7
 
 
-class Quant(enum.IntEnum):       # `Quant` lib.rs:689-704 (SF4 unsupported)
+class Quant(enum.IntEnum):       # `Quant` lib.rs:689-704, all four values (SF4: NF4 storage, Student-t code book)
     NONE = 0
     Int8 = 1
     NF4 = 2
+    SF4 = 3
 
 
 class Precision(enum.IntEnum):   # reload.rs:89-94 (+ the raw mode of ABI 7, include/rwkv_abi.h)

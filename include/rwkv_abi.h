@@ -53,7 +53,9 @@ extern "C" {
                               *    another thread streams the tokens of a running rwkv_gen_run and cancels slots inside it
                               *    additive under 9: rwkv_gen_set_capture, rwkv_gen_take_item, rwkv_gen_item_free / _state / _back / _from_host,
                               *    rwkv_gen_arm_item, RWKV_GEN_CAPTURE_PROMPT / _FINISH: resident generation fills the prefix cache (the state and raw
-                              *    row at the prompt's end and at a stop) and arms a slot from a cached item */
+                              *    row at the prompt's end and at a stop) and arms a slot from a cached item
+                              *    additive under 9 (no new symbol, no struct changed): RWKV_QUANT_SF4 — `Quant::SF4` models load: NF4's storage read
+                              *    through the Student-t code book; rwkv_bench_gemm takes fmt 3 */
 
 typedef int32_t rwkv_status;
 enum {
@@ -98,7 +100,10 @@ rwkv_status rwkv_model_info_from_st(const uint8_t *st_bytes, size_t st_len, rwkv
  * LoRA adapters are rejected (RWKV_ERR_UNSUPPORTED).  The format is this library's own (versioned), not web-rwkv's CBOR. */
 
 /* ---- `create_context` lib.rs:351-368 + `load_runtime` lib.rs:391-516 ---------------------- */
-enum { RWKV_QUANT_NONE = 0, RWKV_QUANT_INT8 = 1, RWKV_QUANT_NF4 = 2 };   /* `Quant` lib.rs:689-704 */
+/* `Quant` lib.rs:689-704, all four values.  The formats are this library's own (web-rwkv's layouts and tables cannot be read here):
+ * INT8 128-element blocks {a, b}; NF4 and SF4 64-element blocks, fp16 absmax, a 16-entry code book — NF4's the normal quantiles of
+ * QLoRA, SF4's the same construction over Student's t with 5 degrees of freedom (Dotzel et al. 2024).  Any other value: RWKV_ERR_UNSUPPORTED. */
+enum { RWKV_QUANT_NONE = 0, RWKV_QUANT_INT8 = 1, RWKV_QUANT_NF4 = 2, RWKV_QUANT_SF4 = 3 };
 /* `Precision` reload.rs:89-94, passed by `load_runtime` lib.rs:503-515.  GEMM operands are f16 with fp32 accumulation in every mode:
  *   FP16 (the reference's default, and this library's): f16 operands, except that the launches whose input rounding carries a model's
  *        error at depth read the operand as a hi + lo f16 pair (V5 / V6: the time-mix projections and first-stage LoRAs; V7: those, the
@@ -140,7 +145,7 @@ rwkv_status rwkv_engine_info(const rwkv_engine *e, rwkv_model_info *out);
 int32_t rwkv_engine_device(const rwkv_engine *e);               /* HIP device ordinal in use */
 int32_t rwkv_engine_max_batch(const rwkv_engine *e);
 int32_t rwkv_engine_token_chunk_size(const rwkv_engine *e);     /* the load-time `token_chunk_size` (lib.rs:221-223): rows one rwkv_infer call emits at most per Full slot */
-/* bytes of weights resident in HBM at their storage width (fp16 / int8+scales / nf4+absmax),
+/* bytes of weights resident in HBM at their storage width (fp16 / int8+scales / nf4 or sf4+absmax),
  * embedding table excluded: the W_q of SURVEY 8(d).  For roofline accounting. */
 uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e);
 
@@ -735,7 +740,7 @@ rwkv_status rwkv_profile_infer(rwkv_engine *e, const rwkv_slot_input *in, rwkv_s
 rwkv_status rwkv_decode_greedy(rwkv_engine *e, int32_t n_slots, const uint32_t *first_tokens,
                                int32_t n_steps, uint32_t *out_tokens, float *elapsed_ms);
 
-/* kernel microbench: one [rows x K] GEMM problem in weight format `fmt` (0 fp16, 1 int8, 2 nf4) against T
+/* kernel microbench: one [rows x K] GEMM problem in weight format `fmt` (0 fp16, 1 int8, 2 nf4, 3 sf4) against T
  * activation rows; `nmat` distinct weight copies are rotated so re-reads miss the Infinity Cache.
  * ksw = 0 lets the planner choose the in-block K split.  Returns microseconds per launch. */
 rwkv_status rwkv_bench_gemm(int32_t rows, int32_t K, int32_t fmt, int32_t T, int32_t hilo, int32_t ksw,

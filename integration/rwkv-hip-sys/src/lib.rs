@@ -18,6 +18,7 @@ pub const RWKV_ERR_NO_STATE: rwkv_status = -6;
 pub const RWKV_QUANT_NONE: i32 = 0;
 pub const RWKV_QUANT_INT8: i32 = 1;
 pub const RWKV_QUANT_NF4: i32 = 2;
+pub const RWKV_QUANT_SF4: i32 = 3;
 pub const RWKV_PRECISION_FP16: i32 = 0;
 pub const RWKV_PRECISION_FP32: i32 = 1;
 pub const RWKV_PRECISION_FP16_RAW: i32 = 2;

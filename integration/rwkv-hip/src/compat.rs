@@ -117,7 +117,7 @@ impl<'a> ModelBuilder<'a> {
     /// lib.rs:465: layers `0..quant` get `quant_type`
     pub fn quant(mut self, layers: usize, quant: Quant) -> Result<Self, Error> {
         let q = match quant { Quant::None => QuantType::None, Quant::Int8 => QuantType::Int8, Quant::NF4 => QuantType::NF4,
-                              Quant::SF4 => return Err(Error { code: -3, message: "SF4 is not supported by this backend".into() }) };
+                              Quant::SF4 => QuantType::SF4 };
         self.quant = (layers, q); Ok(self)
     }
     /// `LoraBlend::full(alpha)` (lib.rs:466-482)
