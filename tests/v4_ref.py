@@ -63,20 +63,48 @@ def synth_v4(name, seed=20251024):
 
 def blend_lora(tensors, lora, alpha):
     """`LoraBlend::full(alpha)` on the matrices of `blocks.N.*`: W += alpha * B A^T with `X.lora.0` = A [in, r] and `X.lora.1` = B [out, r],
-    in fp32 on the fp16 values and rounded back to fp16 once, before any quantisation (oracle/rwkv_ref.py RwkvRef does the same)."""
+    in fp32 on the fp16 values and rounded back to fp16 once, before any quantisation (oracle/rwkv_ref.py RwkvRef does the same).
+    Any other tensor of a block that the file holds under the model's own name (`time_decay`, `time_first`, a mix vector) is blended
+    whole, v = alpha * l + (1 - alpha) * v in fp32 on the fp16 values, and STAYS fp32 (the loader blends first and transforms after:
+    V4's -exp(time_decay) is taken of the blend); V4Ref reads a float32 tensor as it is."""
     out = dict(tensors)
     for k, v in tensors.items():
+        if not re.fullmatch(r"blocks\.[0-9]+\..+", k):
+            continue
         stem = k[:-len(".weight")] if k.endswith(".weight") else k
-        if re.fullmatch(r"blocks\.[0-9]+\..+", k) and stem + ".lora.0" in lora and np.ndim(v) == 2:
+        if stem + ".lora.0" in lora and np.ndim(v) == 2:
             A = np.asarray(lora[stem + ".lora.0"], np.float16).astype(np.float32)
             B = np.asarray(lora[stem + ".lora.1"], np.float16).astype(np.float32)
             out[k] = (np.asarray(v, np.float16).astype(np.float32) + np.float32(alpha) * (B @ A.T)).astype(np.float16)
+        elif k in lora:
+            base = np.asarray(v, np.float16).astype(np.float32)
+            out[k] = np.float32(alpha) * np.asarray(lora[k], np.float16).astype(np.float32).reshape(base.shape) + (np.float32(1.0) - np.float32(alpha)) * base
     return out
 
 
+class _RowSums(np.ndarray):
+    """A matrix whose product with a vector is numpy's own pairwise sum of every row instead of the BLAS's (`V4Ref(pairwise_sums=True)`)."""
+
+    def __matmul__(self, x):
+        return (np.asarray(self) * np.asarray(x)).sum(axis=1)
+
+
 class V4Ref:
-    def __init__(self, tensors, quant_layers=0, quant_type=R.QUANT_NONE, dtype=np.float64):
+    """`clip_operands`: every activation a matrix multiplies is clamped to +-65504 first, the engine's saturation contract as
+    `oracle.rwkv_ref.RwkvRef` states it.  `round_operands`: names of the launch classes (OPERAND_CLASSES) whose activation operand is rounded
+    to f16 on the way in, after the clamp: what Precision::Fp16 does to every class it does not promote (V4: all but `att`, FP16_PLAIN).
+    `self.probe`, when set to a callable `(name, layer, array)`, is shown, in this order per layer, `emb_row` (layer -1), `wdec` (the per-channel w), `k`,
+    `pp_step` (pp and pp + w), `e_state` (the two e1 of a token: row 0 the output half's, row 1 the state update's), `wkv_out` and `relu2` (the
+    operand of ffn.value).  `pairwise_sums`: matrix-vector products are numpy's pairwise row sums, so that a float32 evaluation gives the
+    same figures whichever kernel the BLAS picks for a CPU.  All four are off by default and then touch nothing."""
+    OPERAND_CLASSES = ("att", "wo", "ffn1", "fv", "head")
+    FP16_PLAIN = ("wo", "ffn1", "fv", "head")                       # promote_for_version(4) promotes CLS_ATT only
+
+    def __init__(self, tensors, quant_layers=0, quant_type=R.QUANT_NONE, dtype=np.float64, clip_operands=False, round_operands=(),
+                 pairwise_sums=False):
+        assert set(round_operands) <= set(self.OPERAND_CLASSES), round_operands
         self.dt = dtype
+        self.clip_operands, self.round_operands, self.probe = clip_operands, tuple(round_operands), None
         L = sum(1 for k in tensors if k.endswith(".ln1.weight"))
         V, C = tensors["emb.weight"].shape
         F = tensors["blocks.0.ffn.key.weight"].shape[0]
@@ -84,11 +112,14 @@ class V4Ref:
         qn = {f"blocks.{l}.{n}" for l in range(min(quant_layers, L)) for n in QUANT_NAMES} if quant_type != R.QUANT_NONE else set()
         self.w = {}
         for k, v in tensors.items():
-            v16 = np.asarray(v, np.float16)
+            if np.asarray(v).dtype == np.float32 and np.squeeze(v).ndim == 1:   # a vector `blend_lora` blended: fp32, as the loader keeps it
+                v16 = np.asarray(v)
+            else:
+                v16 = np.asarray(v, np.float16)
             if k in qn:
                 v16 = R.fake_quant(v16, quant_type)
             a = v16.astype(dtype)
-            self.w[k] = a if a.ndim == 2 else a.reshape(-1)
+            self.w[k] = (a.view(_RowSums) if pairwise_sums and k != "emb.weight" else a) if a.ndim == 2 else a.reshape(-1)
         self.k_absmax = 0.0                                          # largest |k| any token has produced so far (what the range test aims at)
 
     def init_state(self):
@@ -103,17 +134,31 @@ class V4Ref:
         return (x - m) / np.sqrt(v + self.dt(LN_EPS)) * w + b
 
     def _sigmoid(self, x):
-        return self.dt(1) / (self.dt(1) + np.exp(-x))
+        with np.errstate(over="ignore"):                            # exp(-x) = inf gives the exact 0 it should
+            return self.dt(1) / (self.dt(1) + np.exp(-x))
+
+    def _opd(self, x, cls):
+        """A GEMM's activation operand of launch class `cls` (see `clip_operands`, `round_operands`)."""
+        if self.clip_operands:
+            x = np.clip(x, self.dt(-65504.0), self.dt(65504.0))
+        if cls in self.round_operands:
+            x = x.astype(np.float16).astype(self.dt)
+        return x
+
+    def _show(self, name, layer, a):
+        if self.probe is not None:
+            self.probe(name, layer, a)
 
     def _token(self, token, s, want_logits=True):
         w = self.w
+        self._show("emb_row", -1, w["emb.weight"][token])
         x = self._ln(w["emb.weight"][token], w["blocks.0.ln0.weight"], w["blocks.0.ln0.bias"])
         for l in range(self.info.num_layer):
             p, a, f = f"blocks.{l}.", f"blocks.{l}.att.", f"blocks.{l}.ffn."
             xx = self._ln(x, w[p + "ln1.weight"], w[p + "ln1.bias"])
             sx = s[5 * l].copy()
             s[5 * l] = xx
-            mix = lambda mu: xx * mu + sx * (1 - mu)
+            mix = lambda mu: self._opd(xx * mu + sx * (1 - mu), "att")
             r = self._sigmoid(w[a + "receptance.weight"] @ mix(w[a + "time_mix_r"]))
             k = w[a + "key.weight"] @ mix(w[a + "time_mix_k"])
             v = w[a + "value.weight"] @ mix(w[a + "time_mix_v"])
@@ -124,20 +169,25 @@ class V4Ref:
             q = np.maximum(pp, ww)
             e1, e2 = np.exp(pp - q), np.exp(ww - q)
             wkv = (e1 * aa + e2 * v) / (e1 * bb + e2)
+            e_out = e1
             ww = pp + wd
             q = np.maximum(ww, k)
             e1, e2 = np.exp(ww - q), np.exp(k - q)
+            if self.probe is not None:
+                for name, arr in (("wdec", wd), ("k", k), ("pp_step", np.stack([pp, ww])), ("e_state", np.stack([e_out, e1])), ("wkv_out", wkv)):
+                    self.probe(name, l, arr)
             s[5 * l + 1], s[5 * l + 2], s[5 * l + 3] = e1 * aa + e2 * v, e1 * bb + e2, q
-            x = x + w[a + "output.weight"] @ (r * wkv)
+            x = x + w[a + "output.weight"] @ self._opd(r * wkv, "wo")
             xx = self._ln(x, w[p + "ln2.weight"], w[p + "ln2.bias"])
             sx = s[5 * l + 4].copy()
             s[5 * l + 4] = xx
-            mix = lambda mu: xx * mu + sx * (1 - mu)
+            mix = lambda mu: self._opd(xx * mu + sx * (1 - mu), "ffn1")
             kk = np.maximum(w[f + "key.weight"] @ mix(w[f + "time_mix_k"]), 0) ** 2
-            x = x + self._sigmoid(w[f + "receptance.weight"] @ mix(w[f + "time_mix_r"])) * (w[f + "value.weight"] @ kk)
+            self._show("relu2", l, kk)
+            x = x + self._sigmoid(w[f + "receptance.weight"] @ mix(w[f + "time_mix_r"])) * (w[f + "value.weight"] @ self._opd(kk, "fv"))
         if not want_logits:
             return None
-        return w["head.weight"] @ self._ln(x, w["ln_out.weight"], w["ln_out.bias"])
+        return w["head.weight"] @ self._opd(self._ln(x, w["ln_out.weight"], w["ln_out.bias"]), "head")
 
     def forward(self, tokens, state, full=False):
         """Consume `tokens` in order, `state` [5L][C] is updated in place.  Returns the logits of the last token [1, V], or with `full` one
