@@ -49,6 +49,8 @@ GROUPS = ("pre", "post", "stops", "mask", "pda", "topn", "state", "publish", "to
 VOCABS = (16, 1024, 16384, 16400, 65536)                           # gen_pre, gen_post's penalty pass, gen_inject: 16 blocks x 256 threads x float4 = 16384 a pass
 MASK_VOCABS = (16, 272, 65536)                                     # gen_mask, gen_pda_mask: min(ceil(V / 256), 256) blocks of 256 ids
 SX_STRIDES, WKV_STRIDES = (64, 65600), (64, 131136)                # gen_freeze, gen_capture: 64 blocks x 256 x float4 = 65536 floats a pass
+WIDE_B = 72                                                        # the wide worlds (geom): more rows than a wavefront has lanes, slot ids past 64
+TOKEN_ROWS = (0, 1, 256, 257, 300)                                 # gen_tokens, gen_handover: ceil(T / 256) blocks of 256 rows
 
 SLOT_DT = np.dtype([("top_p", "<f4"), ("top_k", "<i4"), ("temperature", "<f4"), ("tau", "<f4"), ("kind", "<i4"), ("presence", "<f4"), ("frequency", "<f4"),
                     ("decay", "<f4"), ("miro_target", "<f4"), ("miro_rate", "<f4"), ("seed", "<u8"), ("stream", "<u4"), ("draws", "<u4"), ("max_tokens", "<i4"),
@@ -658,7 +660,24 @@ def check_case(c, d, res, line, ratios=None):
 # ------------------------------------------------------------------------------------------------
 def geom(B, mixed):
     """(row_slot, out_rows, riders): a non-identity arrangement with gaps, n_rows < max_batch where max_batch > 1; with five slots a finished
-    rider (slot 1) between two live rows; mixed: non-adjacent step rows out of a longer step, one slot in mid-prefill without a logits row."""
+    rider (slot 1) between two live rows; mixed: non-adjacent step rows out of a longer step, one slot in mid-prefill without a logits row.
+    72 slots, the width of a server's engine: 33 logits rows (past a wavefront's 32) over a scattered slot list that reaches into the second word
+    of a slot mask (63, 64, 71), two finished riders; mixed: 70 step rows — 33 decode rows around a 20-token prompt that ends and 17 rows of a
+    slot in mid-prefill — and 34 output rows."""
+    if B == WIDE_B:
+        wide = [71, 63, 64] + [s for s in ((5 * i + 2) % WIDE_B for i in range(WIDE_B)) if s not in (71, 63, 64, 10, 40)][:30]
+        riders = [wide[1], wide[17]]
+        if not mixed:
+            return wide, None, riders
+        rs, orows = [], []
+        for i, s in enumerate(wide):
+            if i in (10, 22):                                      # slot 10: a prompt that ends here (its last row is sampled); slot 40: in mid-prefill, no logits row
+                n, slot = ((20, 10), (17, 40))[i == 22]
+                rs += [slot] * n
+                orows += [len(rs) - 1] if i == 10 else []
+            orows.append(len(rs))
+            rs.append(s)
+        return rs, orows, riders
     if not mixed:
         return {1: ([0], None, []), 3: ([2, 0], None, []), 5: ([4, 1, 3], None, [1])}[B]
     return {1: ([0, 0, 0], [2], []), 3: ([2, 2, 1, 0, 0], [1, 4], []), 5: ([4, 4, 1, 0, 3, 3, 0], [1, 2, 5], [1])}[B]
@@ -1006,7 +1025,7 @@ def stops_world(name, V, B, mixed, scenes):
     return W, p
 
 
-STEP_SCENES = ("penalties_bias_stop", "topn_capture_rider", "mixed_prompt_item_prefill", "dfa_beside_pda", "watch_cancel")
+STEP_SCENES = ("penalties_bias_stop", "topn_capture_rider", "mixed_prompt_item_prefill", "dfa_beside_pda", "watch_cancel", "wide_72")
 
 
 def step_world(name, scene):
@@ -1015,7 +1034,7 @@ def step_world(name, scene):
     compensation x = 1.5 - ((-p) + b) is exact."""
     V, N = 1024, 3
     mixed = scene == "mixed_prompt_item_prefill"
-    B = 5 if scene in ("penalties_bias_stop", "mixed_prompt_item_prefill") else 3
+    B = WIDE_B if scene == "wide_72" else 5 if scene in ("penalties_bias_stop", "mixed_prompt_item_prefill") else 3
     W, rng, p, riders = base_world(name, V, B, mixed, run_step=-1)
     steps = N + 1
     p.update(steps=steps, n_steps=N, nsx=64, nw=64, first_row=p["n_rows"])
@@ -1049,6 +1068,10 @@ def step_world(name, scene):
         s["has_bias"][slots[0]] = 1
         bias = rng.choice([0.0, 0.25, -0.5, 0.125], (B, V)).astype(F32)
         W["bias"] = bias
+    if scene == "wide_72":                                         # 33 rows of 72 slots: every sampler kind, a bias on every second slot, the two riders from the start
+        s["kind"], s["has_bias"] = np.arange(B) % 3, np.arange(B) % 2
+        W["bias"] = rng.choice([0.0, 0.25, -0.5, 0.125], (B, V)).astype(F32)
+        s["max_tokens"][slots[2]] = 2                              # finishes in step 1 (LENGTH), is frozen there and rides in step 2
     if scene == "topn_capture_rider":
         s["kind"][slots[0]], s["kind"][slots[1]] = 1, 0
         s["max_tokens"][slots[1]] = 2                              # finishes in step 1 (LENGTH) and rides in step 2
@@ -1324,10 +1347,17 @@ def all_cases():
     for j, V in enumerate(VOCABS):
         for B in (5, 3) if V in (16, 16400) else (5,):
             cs.append(_case(f"inject_V{V}_B{B}", "state", "gen_inject", state_world, "gen_inject", V, B, 1, 64, 64, j + B, V=V, B=B, mixed=1))
+    for mixed in (0, 1):                                           # the wide worlds: 72 slots, 33 logits rows decode-only, 34 of 70 step rows mixed
+        B = WIDE_B
+        cs.append(_case(f"pre_V1024_B{B}_m{mixed}", "pre", "gen_pre", pre_world, 1024, B, mixed, 2 * mixed, V=1024, B=B, mixed=mixed))
+        cs.append(_case(f"post_V1024_B{B}_m{mixed}", "post", "gen_post", post_world, 1024, B, mixed, 3 + mixed, V=1024, B=B, mixed=mixed))
+        cs.append(_case(f"mask_V272_B{B}_m{mixed}_n272", "mask", "gen_mask", mask_world, 272, B, mixed, 272, V=272, B=B, mixed=mixed, n_tok=272))
+        cs.append(_case(f"freeze_sx64_w64_B{B}_m{mixed}", "state", "gen_freeze", state_world, "gen_freeze", 16, B, mixed, 64, 64, mixed, nsx=64, nw=64, B=B, mixed=mixed))
+        cs.append(_case(f"capture_sx64_w64_B{B}_m{mixed}", "state", "gen_capture", state_world, "gen_capture", 16, B, mixed, 64, 64, 1 + mixed, nsx=64, nw=64, B=B, mixed=mixed))
     for B in (1, 3, 257):
         for var in range(6):
             cs.append(_case(f"publish_B{B}_v{var}", "publish", "gen_publish", publish_world, B, var, B=B, var=var))
-    for T in (0, 1, 256, 257):
+    for T in TOKEN_ROWS:
         cs.append(_case(f"tokens_T{T}", "tokens", "gen_tokens", tokens_world, "gen_tokens", T, 0, T=T))
         if T:
             for to_held in (0, 1):
@@ -1372,10 +1402,10 @@ def coverage(cases):
 
 WANTED = ([f"kind:{k}" for k in KIND_NAME] + [f"{k}:V{V}" for k in ("gen_pre", "gen_post", "gen_inject") for V in VOCABS]
           + [f"{k}:V{V}" for k in ("gen_mask", "gen_pda_mask") for V in MASK_VOCABS] + [f"{k}:V{V}" for k in ("gen_topn", "topn_pair") for V in (16, 272, 65536)]
-          + [f"{k}:B{B}" for k in ("gen_pre", "gen_post", "gen_mask", "gen_freeze", "gen_capture") for B in (1, 3, 5)] + [f"gen_publish:B{B}" for B in (1, 3, 257)]
+          + [f"{k}:B{B}" for k in ("gen_pre", "gen_post", "gen_mask", "gen_freeze", "gen_capture") for B in (1, 3, 5, WIDE_B)] + [f"gen_publish:B{B}" for B in (1, 3, 257)]
           + [f"{k}:mixed{m}" for k in ("gen_pre", "gen_post", "gen_mask", "gen_pda_mask", "gen_topn", "gen_freeze", "gen_capture") for m in (0, 1)]
           + [f"{k}:nsx{n}" for k in ("gen_freeze", "gen_capture") for n in SX_STRIDES] + [f"{k}:nw{n}" for k in ("gen_freeze", "gen_capture") for n in WKV_STRIDES]
-          + [f"publish:var{v}" for v in range(6)] + [f"gen_tokens:T{T}" for T in (0, 1, 256, 257)] + [f"gen_handover:T{T}" for T in (1, 256, 257)]
+          + [f"publish:var{v}" for v in range(6)] + [f"gen_tokens:T{T}" for T in TOKEN_ROWS] + [f"gen_handover:T{T}" for T in TOKEN_ROWS if T]
           + [f"stops:{s}:mixed{m}" for s in STOP_SCENES for m in (0, 1)] 
           + ["gen_post:dfa", "gen_post:topn", "gen_post:pda", "gen_pda_mask:bracket", "gen_pda_mask:json"] + [f"step:{s}" for s in STEP_SCENES])
 

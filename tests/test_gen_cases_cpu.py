@@ -39,7 +39,7 @@ def test_the_table_covers_what_it_must(cases):
     for k in ("gen_freeze", "gen_capture"):
         assert {c.p["nsx"] for c in kinds(k)} == {64, 65600} and {c.p["nw"] for c in kinds(k)} == {64, 131136}
     assert {c.p["max_batch"] for c in kinds("gen_publish")} == {1, 3, 257}
-    assert {c.p["T"] for c in kinds("gen_tokens")} == {0, 1, 256, 257} and {c.p["T"] for c in kinds("gen_handover")} == {1, 256, 257}
+    assert {c.p["T"] for c in kinds("gen_tokens")} == {0, 1, 256, 257, 300} and {c.p["T"] for c in kinds("gen_handover")} == {1, 256, 257, 300}
     assert all(c.p["max_batch"] <= 5 for c in cases if c.p["V"] == 65536)
     at = {}
     for c in kinds("gen_post"):
@@ -49,6 +49,30 @@ def test_the_table_covers_what_it_must(cases):
     live = lambda c: [s for s in G.row_slots(c.o["world"](), c.p)]
     five = [c for c in kinds("gen_pre", "gen_post") if c.p["max_batch"] == 5]
     assert five and all(c.o["world"]()["slots"][live(c)[1]]["finish"] != 0 and live(c) != sorted(live(c)) for c in five)   # a rider between two live rows
+
+
+def test_the_wide_worlds_are_what_the_table_says(cases):
+    """72 slots: 33 logits rows over a scattered slot list with 63, 64 and 71 and two finished riders; mixed, 70 step rows, 34 output rows and
+    one slot in mid-prefill.  One such case of each geometry per launcher, and rows past one block of gen_tokens / gen_handover."""
+    B = G.WIDE_B
+    rs, orows, riders = G.geom(B, 0)
+    assert orows is None and len(rs) == len(set(rs)) == 33 and {63, 64, 71} <= set(rs) and rs != sorted(rs) and max(rs) < B
+    assert len(riders) == 2 and set(riders) < set(rs) and sum(s >= 64 for s in rs) >= 3 and min(rs) < 32
+    ms, mo, mr = G.geom(B, 1)
+    out_slots = [ms[r] for r in mo]
+    assert len(ms) == 70 and len(mo) == len(set(out_slots)) == 34 and mo == sorted(mo) and {63, 64, 71} <= set(out_slots) and mr == riders
+    assert set(ms) - set(out_slots) == {40} and ms.count(40) == 17                            # in mid-prefill: step rows, no logits row
+    assert ms.count(10) == 20 and ms[mo[out_slots.index(10)]] == 10 and ms[mo[out_slots.index(10)] + 1] != 10   # a prompt that ends: its last row is sampled
+    assert all(ms.count(s) == 1 for s in out_slots if s != 10) and any(b - a > 1 for a, b in zip(mo, mo[1:]))
+    wide = [c for c in cases if c.p["max_batch"] == B]
+    assert sorted((G.KIND_NAME[c.kind], c.p["mixed"]) for c in wide) == sorted([(k, m) for k in ("gen_pre", "gen_post", "gen_mask", "gen_freeze", "gen_capture") for m in (0, 1)]
+                                                                              + [("step", 0)])
+    for c in wide:
+        W, p = c.o["world"](), c.p
+        assert (p["n_rows"], p["T"]) == ((34, 70) if p["mixed"] else (33, 33)) and G.row_slots(W, p) == (out_slots if p["mixed"] else rs), c.name
+        if G.KIND_NAME[c.kind] in ("gen_pre", "gen_post", "gen_mask", "gen_capture", "step"):
+            assert sorted(s for s in range(B) if W["slots"][s]["finish"]) == sorted(riders), c.name
+    assert any(c.p["T"] == 300 for c in cases if c.group == "tokens") and -(-300 // 256) == 2
 
 
 def test_the_draw_is_rwkv_gen_uniform(built_lib):

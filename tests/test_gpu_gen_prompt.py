@@ -81,29 +81,53 @@ def reference(eng, slot, toks, smp, n, stream=None, states=None):
 
 
 class Job:
-    """one slot of the lock-step reference: `pending` is the prompt tail or, once decoding, the one token it consumes next"""
+    """one slot of the lock-step reference: `pending` is the prompt tail or, once decoding, the one token it consumes next.  A slot that
+    comes with a past — armed from an item, whose first draw was made from the item's row — starts at draw `draws` with `emitted`, the
+    (token, prob) pairs it has already put out; `smp` has seen them."""
 
-    def __init__(self, pending, smp, n, stream, in_prompt, stops=()):
+    def __init__(self, pending, smp, n, stream, in_prompt, stops=(), draws=0, emitted=()):
         self.pending, self.smp, self.n, self.stream, self.in_prompt, self.stops = list(pending), smp, n, stream, in_prompt, set(stops)
-        self.draws, self.out, self.fin, self.fin_seen, self.state = 0, [], 0, False, None
+        self.draws, self.out, self.fin, self.fin_seen, self.state = int(draws), list(emitted), 0, False, None
 
 
-def lockstep(eng, jobs, steps):
+def lockstep(eng, jobs, steps, pseudo=(), rows=None):
     """`steps` resident steps restated with per-token calls: which slots are in a step is decided as rwkv_gen_run decides it (from
     what the HOST knows: prompts pending, max_tokens less what was emitted for certain; who finished is learnt when the run ends).
-    Returns (tokens, probs) shaped like gen_run's; jobs[b].state is the slab the state rule promises for slot b."""
+    Returns (tokens, probs) shaped like gen_run's; jobs[b].state is the slab the state rule promises for slot b.
+    `pseudo`: slots armed from an item (rwkv_gen_arm_item).  Their first draw — the last entry of the Job's `emitted`, not restated
+    here — is made in the first step of this call from a row that no forward pass computes: it takes one row of the chunk all the
+    same, so the prompts of that step share what is left, and the slot decodes from the step behind it.
+    `rows` (a list) receives per step (step rows + rows spoken for, decode rows among them)."""
     B = eng.max_batch
     T = np.full((steps, B), PAD, np.uint32)
     P = np.full((steps, B), np.nan, np.float32)
     live = [b for b in sorted(jobs) if not jobs[b].fin_seen]
     remain = {b: jobs[b].n - len(jobs[b].out) for b in live}
+    pseudo = [b for b in pseudo if b in live]
 
-    def one_step(k, slots):
-        inp = rt.RnnInput([rt.RnnInputBatch(list(jobs[b].pending) if b in slots else []) for b in range(B)])
+    def one_step(k, slots, reserve=0):
+        pend = {b: list(jobs[b].pending) for b in slots}
+        cut = set()
+        if reserve:
+            # infer_sample splits the whole chunk; with rows spoken for the split is made here (rwkv_plan_chunk over the smaller budget)
+            # and every slot is handed its share alone.  A share that is not the whole prompt looks like one to infer_sample: the row it
+            # draws for it is nobody's (one more row under the head, the forward pass has the step's rows)
+            take = rt.plan_chunk([len(pend.get(b, ())) for b in range(B)], eng.token_chunk_size - reserve)
+            cut = {b for b in slots if take[b] < len(pend[b])}
+            given = {b: pend[b][:take[b]] for b in slots}
+        else:
+            given = pend
+        inp = rt.RnnInput([rt.RnnInputBatch(list(given[b]) if b in slots else []) for b in range(B)])
         us = [rt.gen_uniform(SEED, jobs[b].stream, jobs[b].draws) if b in slots else 0.0 for b in range(B)]
         inp, res = eng.infer_sample(inp, [jobs[b].smp if b in slots else None for b in range(B)], us)
+        if rows is not None:
+            rows.append((sum(len(given[b]) - len(inp.batches[b].tokens) for b in slots) + reserve, sum(not jobs[b].in_prompt for b in slots)))
         for b in slots:
             j = jobs[b]
+            if b in cut:
+                assert not inp.batches[b].tokens
+                j.pending = pend[b][len(given[b]):]
+                continue
             if res[b] is None:
                 j.pending = list(inp.batches[b].tokens)
                 continue
@@ -122,14 +146,15 @@ def lockstep(eng, jobs, steps):
     k = 0
     while k < steps:
         pro = [b for b in live if jobs[b].in_prompt]
-        dec = [b for b in live if not jobs[b].in_prompt and remain[b] > 0]
-        if pro:
-            one_step(k, dec + pro)
+        dec = [b for b in live if not jobs[b].in_prompt and remain[b] > 0 and b not in pseudo]
+        if pro or pseudo:
+            one_step(k, dec + pro, len(pseudo))
             for b in dec:
                 remain[b] -= 1
             for b in pro:
                 if not jobs[b].in_prompt:
                     remain[b] -= 1
+            pseudo = []                                                # drew in this step; `remain` never counted that draw
             k += 1
         elif not dec:
             break
