@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librwkv_hip.so")
 SOURCES = ["rwkv_kernels.hip", "rwkv_engine.cpp", "tokenizer.cpp", "rwkv_dfa.cpp", "rwkv_pda.cpp"]
-DEPS = SOURCES + ["rwkv_kernels.h", "gemm_plan.h", "graph_cache.h", "gen_stop.h", "gen_dfa.h", "rwkv_dfa.h", "gen_pda.h", "gen_watch.h", "rwkv_pda.h", "safetensors.hpp", "rwkv_abi.map", os.path.join("..", "..", "include", "rwkv_abi.h"),
+DEPS = SOURCES + ["rwkv_kernels.h", "gemm_plan.h", "graph_cache.h", "gen_host.h", "gen_stop.h", "gen_dfa.h", "rwkv_dfa.h", "gen_pda.h", "gen_watch.h", "rwkv_pda.h", "safetensors.hpp", "rwkv_abi.map", os.path.join("..", "..", "include", "rwkv_abi.h"),
                os.path.join("..", "..", "include", "rwkv_runtime.hpp"), os.path.join("..", "..", "include", "rwkv_scheduler.hpp"),
                os.path.join("..", "..", "include", "rwkv_router.hpp"),
                os.path.join("..", "..", "harness", "decode_loop.cpp"), os.path.join("..", "..", "harness", "serve_loop.cpp"),

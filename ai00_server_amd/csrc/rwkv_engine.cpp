@@ -24,6 +24,7 @@
 
 #include "../../include/rwkv_abi.h"
 #include "gemm_plan.h"
+#include "gen_host.h"
 #include "graph_cache.h"
 #include "rwkv_dfa.h"
 #include "rwkv_pda.h"
@@ -267,8 +268,7 @@ struct MetaView {
 // (the kernels read the rows and write the outputs in place, through the block's device-visible alias: dv_*)
 struct SampStage { SampleRow *rows; int *adj_row, *adj_tok; float *adj_val; int *out_tok; float *out_prob; const SampleRow *dv_rows; int *dv_out_tok; float *dv_out_prob; };
 
-// which sampler kernels a set of rows needs, as bits (also the last word of a generation graph's key)
-enum : unsigned { NEEDS_NT = 1, NEEDS_MIRO = 2, NEEDS_WIDE = 4 };   // nucleus / typical, mirostat, rows of sample_wide_kernel (any kind)
+// which sampler kernels a set of rows needs: the NEEDS_* bits
 static unsigned sampler_need(int kind, bool wide = false) { return wide ? NEEDS_WIDE : kind == RWKV_SAMPLER_MIROSTAT ? NEEDS_MIRO : NEEDS_NT; }
 // Mirostat below 13 bits of surprise admits fewer than 2^13 tokens (p >= 2^-max_surprise each, plus one): nucleus_kernel's buffer is exact there
 constexpr float MIRO_WIDE_SURPRISE = 13.0f;
@@ -301,6 +301,42 @@ static void gen_item_destroy(rwkv_gen_item *it) {
     (void)hipFree(it->state); (void)hipFree(it->row);
     delete it;
 }
+
+// What the host keeps per slot of resident generation (rwkv_engine::gen_slots).  The has_stops / constraint / topn / capture words are host
+// knowledge of what the slot's device entries hold: they select the kernels of a step (feats).
+enum class GenConstraint : char { None, Dfa, Pda };            // a slot holds a byte automaton or a stack automaton, never both
+struct GenSlotHost {
+    GenSlot g{};                                               // mirror of d_gen[slot], read back after every run
+    bool armed = false;
+    std::vector<uint32_t> prompt;                              // rwkv_gen_arm_prompt: the slot's prompt tail, and how much of it the steps so far
+    size_t ppos = 0;                                           //   have consumed (each mixed step's slice rides in its plan upload)
+    float *shadow = nullptr;                                   // sxa | sxf | wkv of the step it finished in (dalloc, by the slot's first arm)
+    GenConstraint constraint = GenConstraint::None;
+    void *table = nullptr;                                     // the constraint's planes on the device (trans | flags, or next | act | flags); not in `allocs`
+    bool has_stops = false;
+    int topn = 0;                                              // places it lists, 0 = none (d_gen_topn_n holds the same)
+    unsigned capture = 0, cap_done = 0, cap_taken = 0;         // RWKV_GEN_CAPTURE_* asked for / PROMPT written / handed over
+    std::array<rwkv_gen_item *, 2> cap_item{nullptr, nullptr}; // the PROMPT and the FINISH item until they are taken
+    float *inj_row = nullptr;                                  // [V] the row of the item that armed it (dalloc, by the slot's first rwkv_gen_arm_item)
+    bool inj = false;                                          // its first draw, from that row, is still to come
+    size_t prompt_left() const { return armed ? prompt.size() - ppos : 0; }
+    uint64_t feats() const {                                   // what the slot adds to a step it has a row in
+        return (has_stops ? FEAT_STOPS : 0) | (constraint == GenConstraint::Dfa ? FEAT_DFA : 0) | (constraint == GenConstraint::Pda ? FEAT_PDA : 0) |
+               (topn ? FEAT_TOPN : 0) | (capture & ~cap_taken & RWKV_GEN_CAPTURE_FINISH ? FEAT_CAPTURE : 0);
+    }
+    void drop_items() { for (rwkv_gen_item *&it : cap_item) { gen_item_destroy(it); it = nullptr; } }   // asked for, never taken
+    // What ends with a request (gen_arm, gen_disarm_slot); the device entries are rewritten by the next arm, nothing reads them before.
+    // What stays: `g` (gen_arm overwrites it; a disarmed slot's finish word is the watch's to drop), `topn` (gen_arm clears it with the
+    // device's word), `shadow` and `inj_row` (allocated once per slot), `table` (freed behind a stream synchronise only: gen_drop_table).
+    void reset_request() {
+        drop_items();
+        capture = cap_done = cap_taken = 0;
+        armed = has_stops = inj = false;
+        constraint = GenConstraint::None;
+        prompt.clear();
+        ppos = 0;
+    }
+};
 
 struct rwkv_engine {
     rwkv_model_info info{};
@@ -338,6 +374,14 @@ struct rwkv_engine {
     // state (internal layout)
     float *sxa = nullptr, *sxf = nullptr, *wkv = nullptr;
     long sx_slot_stride = 0, wkv_slot_stride = 0;
+    // views (they own nothing): a slot's state, and a contiguous sxa | sxf | wkv block (a slot's shadow, an item's `state`)
+    rwkv_dstate slot_state(int slot) const { return {device, sxa + slot * sx_slot_stride, sxf + slot * sx_slot_stride, wkv + slot * wkv_slot_stride}; }
+    rwkv_dstate block_state(float *block) const { return {device, block, block + sx_slot_stride, block + 2 * sx_slot_stride}; }
+    void copy_state(const rwkv_dstate &dst, const rwkv_dstate &src) {   // on s_main, not waited for
+        HIP_CHECK(hipMemcpyAsync(dst.sxa, src.sxa, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(dst.sxf, src.sxf, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        HIP_CHECK(hipMemcpyAsync(dst.wkv, src.wkv, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+    }
     // The state as the ABI shows it has slab_rows() rows of C floats per layer: the two shift rows around the layer's WKV rows.  V5 / V6 / V7: 64
     // WKV rows, the H 64 x 64 head matrices (wkv_layer_floats = H * 4096).  V4: three, aa / bb / pp (wkv_layer_floats = 3 * C).
     int slab_rows() const { return info.version == 4 ? 5 : 66; }
@@ -403,15 +447,10 @@ struct rwkv_engine {
     // device-resident sampled generation (rwkv_gen_*): per-slot contexts, dense penalty / bias rows, the step's SampleRow array and the
     // output ring live on the device; everything is allocated by the first rwkv_gen_arm
     static constexpr int GEN_RING_STEPS = 1024;                  // steps one enqueue covers (longer runs are split)
-    std::vector<GenSlot> gen_host;                               // mirror of d_gen, read back after every run
-    std::vector<char> gen_armed;
-    std::vector<std::vector<uint32_t>> gen_prompt;               // rwkv_gen_arm_prompt: the slot's prompt tail, and how much of it the steps
-    std::vector<size_t> gen_ppos;                                //   so far have consumed (each mixed step's slice rides in its plan upload)
-    std::vector<float *> gen_shadow;                             // per slot: sxa | sxf | wkv of the step it finished in
+    std::vector<GenSlotHost> gen_slots;                          // [max_batch] by gen_init; empty: the engine never generated
     GenSlot *d_gen = nullptr;
     // stop STRINGS (rwkv_gen_set_token_bytes / _set_stops): the engine's token-bytes table and, beside d_gen, one GenStop per slot
     GenStop *d_gen_stop = nullptr;
-    std::vector<char> gen_has_stops;                             // per slot: it carries stop strings (host knowledge: selects the kernels of a step)
     unsigned *d_tok_off = nullptr;                               // [n_tok + 1]; not in `allocs`: a new table replaces it
     unsigned char *d_tok_bytes = nullptr;
     int n_tok = 0;
@@ -420,23 +459,19 @@ struct rwkv_engine {
     size_t gen_stop_tail(int slot, uint8_t *out, size_t cap);
     // the byte-automaton constraint (rwkv_gen_set_constraint): beside d_gen, one GenDfa per slot; the slot's table lives in a buffer of its own
     GenDfa *d_gen_dfa = nullptr;
-    std::vector<char> gen_has_dfa;                               // per slot: it carries a constraint (host knowledge: selects the kernels of a step)
-    std::vector<void *> gen_dfa_buf;                             // per slot: trans | flags on the device; not in `allocs`: a new constraint replaces it
     unsigned short *d_tok_end = nullptr;                         // [chunk][V] gen_mask -> gen_post; allocated by the first constraint
     uint8_t tok_single[256] = {};                                // the token table holds the single-byte token c (the liveness rule)
     void gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, int halt_mode);
     int gen_constraint_state(int slot);
-    void gen_drop_dfa_buf(int slot) { if (gen_dfa_buf[(size_t)slot]) { (void)hipFree(gen_dfa_buf[(size_t)slot]); gen_dfa_buf[(size_t)slot] = nullptr; } }
-    bool gen_any_dfa(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_dfa[(size_t)b]) return true; return false; }
     // the stack-automaton constraint (rwkv_gen_set_pda): beside d_gen_dfa, one GenPda per slot; a slot holds a DFA or a stack constraint, never both
     GenPda *d_gen_pda = nullptr;
-    std::vector<char> gen_has_pda;                               // per slot: it carries a stack constraint (host knowledge: selects the kernels of a step)
-    std::vector<void *> gen_pda_buf;                             // per slot: next | act | flags on the device; not in `allocs`: a new constraint replaces it
     void gen_set_pda(int slot, const rwkv_pda *pda, int state, const uint16_t *stack, int depth, int halt_mode);
     void gen_pda_config(int slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth);
-    void gen_drop_pda_buf(int slot) { if (gen_pda_buf[(size_t)slot]) { (void)hipFree(gen_pda_buf[(size_t)slot]); gen_pda_buf[(size_t)slot] = nullptr; } }
-    bool gen_any_pda(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_pda[(size_t)b]) return true; return false; }
-    bool gen_any_stops(const std::vector<int> &slots) const { for (int b : slots) if (gen_has_stops[(size_t)b]) return true; return false; }
+    // what both kinds share: the refusals, the table's upload into one buffer, the slot's entry, the swap (`fill`: the caller's own part)
+    struct Plane { const void *src; size_t bytes; };
+    template <class Entry, class Fill>
+    void gen_install(int slot, GenConstraint kind, bool present, Entry *d_entries, Fill fill);
+    void gen_drop_table(GenSlotHost &s) { if (s.table) { (void)hipFree(s.table); s.table = nullptr; } }   // behind a stream synchronise only
     float *d_gen_pen = nullptr, *d_gen_bias = nullptr, *d_gen_prob = nullptr;
     float **d_gen_shadow = nullptr;
     SampleRow *d_gen_rows = nullptr;
@@ -444,14 +479,12 @@ struct rwkv_engine {
     int *d_gen_held = nullptr;                                   // [max_batch] the token a running slot consumes next (its last emitted one)
     unsigned *d_gen_out = nullptr, *h_gen_out = nullptr;         // [2][GEN_RING_STEPS][max_batch]: tokens, then probabilities
     // top-n lists of the raw rows (rwkv_gen_set_topn / rwkv_gen_run_topn): everything below is allocated by the first rwkv_gen_set_topn
-    std::vector<int> gen_topn;                                   // per slot: places it lists, 0 = none (host knowledge: selects the kernels of a step)
-    int *d_gen_topn_n = nullptr;                                 // [max_batch] the same, for gen_topn_kernel
+    int *d_gen_topn_n = nullptr;                                 // [max_batch] GenSlotHost::topn, for gen_topn_kernel; assigned last: marks the block as complete
     unsigned *d_gen_top_ids = nullptr, *h_gen_top_ids = nullptr; // [GEN_RING_STEPS][max_batch][TOPN_MAX]
     float *d_gen_top_logp = nullptr, *h_gen_top_logp = nullptr;  // the same shape
     float *d_gen_tok_logp = nullptr, *h_gen_tok_logp = nullptr;  // [GEN_RING_STEPS][max_batch]
-    float *d_gen_side_ms = nullptr, *d_gen_side_rows = nullptr;  // [max_batch][2], [max_batch][V]: gen_topn -> gen_post
+    float *d_gen_side_ms = nullptr, *d_gen_side_rows = nullptr;  // [max_batch][2], [max_batch][V]: the top-n kernel -> gen_post
     void gen_set_topn(int slot, int n);
-    bool gen_any_topn(const std::vector<int> &slots) const { if (gen_topn.empty()) return false; for (int b : slots) if (gen_topn[(size_t)b]) return true; return false; }
     GraphCacheOf<std::vector<uint64_t>> gen_graphs{64, {}};      // one captured step per set of rows (slot mask + sampler kernels it needs)
     // the watch (rwkv_gen_watch_*, gen_watch.h): at most one.  Captured steps hold the ADDRESS of d_gen_watch, never the ring's: open
     // rewrites the descriptor, so a step captured under one watch publishes into the next; steps captured with no watch open do not
@@ -462,47 +495,33 @@ struct rwkv_engine {
     void gen_watch_close(rwkv_gen_watch *w);
     bool gen_cancel_set(int slot) const { return gen_watch && __atomic_load_n(gen_watch->cancel() + slot, __ATOMIC_ACQUIRE) != 0; }
     void gen_cancel_clear(int slot) { if (gen_watch) __atomic_store_n(gen_watch->cancel() + slot, 0u, __ATOMIC_RELEASE); }
-    // captures and items (rwkv_gen_set_capture / _take_item / _arm_item): beside d_gen, one GenCap per slot.  The host keeps what each
-    // slot was asked for, the items that wait to be taken, and which of them are complete or gone; a step launches gen_capture only
-    // when one of its slots captures (bit 37 of a decode graph's key)
+    // captures and items (rwkv_gen_set_capture / _take_item / _arm_item): beside d_gen, one GenCap per slot; a step launches the capture
+    // kernel only when one of its slots captures (FEAT_CAPTURE)
     GenCap *d_gen_cap = nullptr;
-    std::vector<unsigned> gen_capture, gen_cap_done, gen_cap_taken;   // per slot: RWKV_GEN_CAPTURE_* asked for / PROMPT written / handed over
-    std::vector<std::array<rwkv_gen_item *, 2>> gen_cap_item;         // per slot: the PROMPT and the FINISH item until they are taken
-    std::vector<float *> gen_inj_row;                                 // per slot: [V] the row of the item that armed it (allocated by its first rwkv_gen_arm_item)
-    std::vector<char> gen_inj;                                        // per slot: its first draw, from that row, is still to come
     rwkv_gen_item *gen_item_new() const;
     bool gen_item_fits(const rwkv_gen_item *it) const {
         return it && it->st.device == device && it->version == info.version && it->L == info.num_layer && it->C == info.num_emb &&
                it->V == info.num_vocab && it->nsx == sx_slot_stride && it->nw == wkv_slot_stride;
     }
     void gen_cap_upload(int slot);
-    void gen_drop_captures(int slot) {                                // host side; the device copy is rewritten by the next arm, nothing reads it before
-        for (rwkv_gen_item *&it : gen_cap_item[(size_t)slot]) { gen_item_destroy(it); it = nullptr; }
-        gen_capture[(size_t)slot] = gen_cap_done[(size_t)slot] = gen_cap_taken[(size_t)slot] = 0;
-        gen_inj[(size_t)slot] = 0;
-    }
-    bool gen_any_capture(const std::vector<int> &slots, unsigned bits) const { for (int b : slots) if (gen_capture[(size_t)b] & ~gen_cap_taken[(size_t)b] & bits) return true; return false; }
     void gen_set_capture(int slot, unsigned what);
     rwkv_gen_item *gen_take_item(int slot, unsigned which);
     void gen_arm_item(int slot, const rwkv_gen_item *it, const rwkv_gen_params &p);
     void gen_init();
     void gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *prompt, size_t n_prompt, bool from_item = false);
-    void gen_disarm_slot(int slot) {
+    void gen_disarm_slot(int slot) {                             // callable on an engine that never generated (rwkv_state_load / _write)
         gen_cancel_clear(slot);
-        if (gen_armed.empty()) return;
-        gen_drop_captures(slot);
-        gen_armed[(size_t)slot] = 0;
-        gen_has_stops[(size_t)slot] = 0;                           // the device copy is cleared by the next arm; nothing reads it before
-        gen_has_dfa[(size_t)slot] = 0;                             // likewise; the table's buffer is freed by the next arm / constraint / the destructor
-        gen_has_pda[(size_t)slot] = 0;                             // likewise
-        gen_prompt[(size_t)slot].clear();
-        gen_ppos[(size_t)slot] = 0;
+        if (!gen_slots.empty()) gen_slots[(size_t)slot].reset_request();
     }
-    size_t gen_prompt_left(int slot) const { return gen_armed.empty() || !gen_armed[(size_t)slot] ? 0 : gen_prompt[(size_t)slot].size() - gen_ppos[(size_t)slot]; }
-    GenArgs gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda, bool cap = false) const;
-    unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_host[(size_t)b].kind, gen_host[(size_t)b].wide != 0); return k; }
+    bool gen_is_armed(int slot) const { return !gen_slots.empty() && gen_slots[(size_t)slot].armed; }
+    bool gen_is_live(int slot) const { return gen_is_armed(slot) && !gen_slots[(size_t)slot].g.finish; }   // armed and unfinished
+    size_t gen_prompt_left(int slot) const { return gen_slots.empty() ? 0 : gen_slots[(size_t)slot].prompt_left(); }
+    GenArgs gen_args(int n_rows, uint64_t feats) const;
+    unsigned gen_needs(const std::vector<int> &slots) const { unsigned k = 0; for (int b : slots) k |= sampler_need(gen_slots[(size_t)b].g.kind, gen_slots[(size_t)b].g.wide != 0); return k; }
+    // the FEAT_* word of a step over these slots' rows: what each slot adds, and the open watch
+    uint64_t gen_feats(const std::vector<int> &slots) const { uint64_t f = gen_watch ? FEAT_WATCH : 0; for (int b : slots) f |= gen_slots[(size_t)b].feats(); return f; }
     void gen_sample(const GenArgs &a, unsigned needs);
-    void gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda, bool cap);
+    void gen_step(const StepPlan &pl, unsigned needs, uint64_t feats);
     void gen_decode_steps(const std::vector<int> &rows, int n);
     void gen_mixed_step(const std::vector<int> &dec, const std::vector<int> &pro, const std::vector<int> &inj, std::vector<int> &remain);
     void gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, int32_t *n_emitted, int32_t *finish, int n_top = 0,
@@ -543,9 +562,7 @@ struct rwkv_engine {
         if (gen_watch) { (void)hipHostFree(gen_watch->ring); delete gen_watch; gen_watch = nullptr; }   // the destructor closes an open watch
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
-        for (void *p : gen_dfa_buf) if (p) (void)hipFree(p);
-        for (void *p : gen_pda_buf) if (p) (void)hipFree(p);
-        for (auto &pair : gen_cap_item) for (rwkv_gen_item *it : pair) gen_item_destroy(it);   // asked for, never taken
+        for (GenSlotHost &s : gen_slots) { gen_drop_table(s); s.drop_items(); }
         if (d_tok_end) (void)hipFree(d_tok_end);
         if (d_tok_off) (void)hipFree(d_tok_off);
         if (d_tok_bytes) (void)hipFree(d_tok_bytes);
@@ -1701,24 +1718,15 @@ static_assert(RWKV_GEN_CANCELLED == GEN_FIN_CANCELLED && RWKV_GEN_WATCH_MAX_STEP
 void rwkv_engine::gen_init() {
     if (d_gen) return;
     const size_t B = (size_t)max_batch, V = (size_t)info.num_vocab;
-    gen_host.assign(B, GenSlot{});
-    gen_armed.assign(B, 0);
-    gen_has_stops.assign(B, 0);
-    gen_has_dfa.assign(B, 0);
-    gen_dfa_buf.assign(B, nullptr);
+    gen_slots.assign(B, GenSlotHost{});
     d_gen_dfa = dalloc<GenDfa>(B);
     HIP_CHECK(hipMemset(d_gen_dfa, 0, B * sizeof(GenDfa)));
-    gen_has_pda.assign(B, 0);
-    gen_pda_buf.assign(B, nullptr);
     d_gen_pda = dalloc<GenPda>(B);
     HIP_CHECK(hipMemset(d_gen_pda, 0, B * sizeof(GenPda)));
     d_gen_stop = dalloc<GenStop>(B);
     HIP_CHECK(hipMemset(d_gen_stop, 0, B * sizeof(GenStop)));
-    gen_prompt.assign(B, {});
-    gen_ppos.assign(B, 0);
     d_gen_held = dalloc<int>(B);
     HIP_CHECK(hipMemset(d_gen_held, 0, B * sizeof(int)));
-    gen_shadow.assign(B, nullptr);
     d_gen_pen = dalloc<float>(B * V);
     d_gen_bias = dalloc<float>(B * V);
     d_gen_shadow = dalloc<float *>(B);
@@ -1730,10 +1738,6 @@ void rwkv_engine::gen_init() {
     d_gen_out = dalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
     h_gen_out = hostalloc<unsigned>(2 * (size_t)GEN_RING_STEPS * B);
     HIP_CHECK(hipMemset(d_gen_shadow, 0, B * sizeof(float *)));
-    gen_capture.assign(B, 0); gen_cap_done.assign(B, 0); gen_cap_taken.assign(B, 0);
-    gen_cap_item.assign(B, {nullptr, nullptr});
-    gen_inj_row.assign(B, nullptr);
-    gen_inj.assign(B, 0);
     d_gen_cap = dalloc<GenCap>(B);
     HIP_CHECK(hipMemset(d_gen_cap, 0, B * sizeof(GenCap)));
     d_gen = dalloc<GenSlot>(B);                                   // last: marks the block as complete
@@ -1758,9 +1762,10 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
         throw RwkvError(RWKV_ERR_INVALID, "null penalty / bias / stop array");
     gen_init();
     const size_t b = (size_t)slot;
-    if (!gen_shadow[b]) {                                          // the slot's first arm: room for its state at the step it will finish in
-        gen_shadow[b] = dalloc<float>((size_t)(2 * sx_slot_stride + wkv_slot_stride));
-        HIP_CHECK(hipMemcpy(d_gen_shadow + b, &gen_shadow[b], sizeof(float *), hipMemcpyHostToDevice));
+    GenSlotHost &s = gen_slots[b];
+    if (!s.shadow) {                                               // the slot's first arm: room for its state at the step it will finish in
+        s.shadow = dalloc<float>((size_t)(2 * sx_slot_stride + wkv_slot_stride));
+        HIP_CHECK(hipMemcpy(d_gen_shadow + b, &s.shadow, sizeof(float *), hipMemcpyHostToDevice));
     }
     GenSlot g{};
     g.top_p = p.top_p; g.top_k = miro ? 1 : std::min(p.top_k, info.num_vocab); g.temperature = miro ? 1.0f : p.temperature; g.tau = p.tau; g.kind = p.kind;
@@ -1790,20 +1795,15 @@ void rwkv_engine::gen_arm(int slot, const rwkv_gen_params &p, const uint32_t *pr
     const int first = prompt || from_item ? 0 : (int)p.first_token;   // with a prompt, or an item, the slot's first draw fills it
     HIP_CHECK(hipMemcpyAsync(d_gen_held + b, &first, sizeof(int), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
-    gen_host[b] = g;
-    gen_has_stops[b] = 0;
-    gen_has_dfa[b] = 0;
-    gen_has_pda[b] = 0;
-    if (!gen_topn.empty() && gen_topn[b]) {                        // re-arming: the slot lists nothing until rwkv_gen_set_topn says so again
-        gen_topn[b] = 0;
+    s.g = g;
+    if (s.topn) {                                                  // re-arming: the slot lists nothing until rwkv_gen_set_topn says so again
+        s.topn = 0;
         HIP_CHECK(hipMemset(d_gen_topn_n + b, 0, sizeof(int)));
     }
-    gen_drop_dfa_buf(slot);                                        // behind the synchronize: no step is in flight
-    gen_drop_pda_buf(slot);
-    gen_drop_captures(slot);                                       // an item nobody took goes with the request that asked for it
-    gen_prompt[b].assign(prompt, prompt + n_prompt);
-    gen_ppos[b] = 0;
-    gen_armed[b] = 1;
+    gen_drop_table(s);                                             // behind the synchronize: no step is in flight
+    s.reset_request();                                             // an item nobody took goes with the request that asked for it
+    s.prompt.assign(prompt, prompt + n_prompt);
+    s.armed = true;
     gen_cancel_clear(slot);                                        // a flag set for the request that held the slot before is not this one's
 }
 
@@ -1820,9 +1820,9 @@ void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens,
     }
     if (total && !bytes) throw RwkvError(RWKV_ERR_INVALID, "token table: null bytes");
     if (total >= GEN_TOK_UNKNOWN) throw RwkvError(RWKV_ERR_UNSUPPORTED, "token table: more than 2 GiB of bytes");
-    for (char h : gen_has_stops) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has stop strings set");
-    for (char h : gen_has_dfa) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a constraint set");
-    for (char h : gen_has_pda) if (h) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a stack constraint set");
+    for (const GenSlotHost &s : gen_slots) if (s.has_stops) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has stop strings set");
+    for (const GenSlotHost &s : gen_slots) if (s.constraint == GenConstraint::Dfa) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a constraint set");
+    for (const GenSlotHost &s : gen_slots) if (s.constraint == GenConstraint::Pda) throw RwkvError(RWKV_ERR_INVALID, "token table: a slot has a stack constraint set");
     std::vector<unsigned> off(n + 1);
     size_t pos = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -1847,66 +1847,75 @@ void rwkv_engine::gen_set_token_bytes(const uint8_t *bytes, const int32_t *lens,
     }
 }
 
-// The byte-automaton constraint of an armed, unfinished slot (rwkv_gen_set_constraint): the table goes to the device, the GenDfa of the
-// slot points at it.  Between runs: the stream is idle, so the old table can go at once.
-void rwkv_engine::gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, int halt_mode) {
+// What rwkv_gen_set_constraint and rwkv_gen_set_pda share.  An armed, unfinished slot; with a table (`present`): no constraint of the other
+// kind, a token table, then fill(h, upload): the caller's own checks and its entry, where upload({plane, ...}) puts the planes one behind
+// the other into one fresh buffer and returns it.  Between runs: the stream is idle, so the old table can go at once.  NULL through the
+// call of the OTHER kind rewrites that kind's (already zero) entry and leaves the slot's constraint and its table alone.
+template <class Entry, class Fill>
+void rwkv_engine::gen_install(int slot, GenConstraint kind, bool present, Entry *d_entries, Fill fill) {
     HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs an armed, unfinished slot");
-    GenDfa h{};
-    void *buf = nullptr;
-    if (dfa) {
-        if (gen_has_pda[b]) throw RwkvError(RWKV_ERR_INVALID, "constraint: the slot has a stack constraint set (a slot holds one kind)");
+    if (!gen_is_live(slot)) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs an armed, unfinished slot");
+    GenSlotHost &s = gen_slots[(size_t)slot];
+    Entry h{};
+    void *buf = nullptr;                                           // the fresh table: upload (below) fills it, a failed entry copy frees it, the swap keeps it
+    if (present) {
+        if (s.constraint != GenConstraint::None && s.constraint != kind)
+            throw RwkvError(RWKV_ERR_INVALID, std::string("constraint: the slot has a ") + (s.constraint == GenConstraint::Pda ? "stack" : "DFA") + " constraint set (a slot holds one kind)");
         if (!d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs the token table: rwkv_gen_set_token_bytes");
+        fill(h, [&](std::initializer_list<Plane> planes) {
+            size_t total = 0, at = 0;
+            for (const Plane &p : planes) total += p.bytes;
+            HIP_CHECK(hipMalloc(&buf, total));
+            for (const Plane &p : planes) {
+                if (hipMemcpy((char *)buf + at, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                    (void)hipFree(buf);
+                    throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the table failed");
+                }
+                at += p.bytes;
+            }
+            return (const char *)buf;
+        });
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    if (hipMemcpy(d_entries + slot, &h, sizeof(Entry), hipMemcpyHostToDevice) != hipSuccess) {
+        if (buf) (void)hipFree(buf);
+        throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the slot's entry failed");
+    }
+    if (!present && s.constraint != kind) return;
+    gen_drop_table(s);
+    s.table = buf;
+    s.constraint = present ? kind : GenConstraint::None;
+}
+
+// The byte-automaton constraint (rwkv_gen_set_constraint): the table goes to the device, the GenDfa of the slot points at it.
+void rwkv_engine::gen_set_constraint(int slot, const rwkv_dfa *dfa, int state, int halt_mode) {
+    gen_install(slot, GenConstraint::Dfa, dfa != nullptr, d_gen_dfa, [&](GenDfa &h, auto upload) {
         if (state < 1 || state >= dfa->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: state 0 (dead) or out of range");
         if (halt_mode != RWKV_DFA_HALT_FINAL && halt_mode != RWKV_DFA_HALT_ACCEPT) throw RwkvError(RWKV_ERR_INVALID, "constraint: unknown halt mode");
         if (!dfa_never_stuck(*dfa, state, halt_mode, tok_single))
             throw RwkvError(RWKV_ERR_UNSUPPORTED, "constraint: a reachable state has no single-byte token that leads on (a row could be masked whole)");
         const size_t tbytes = (size_t)dfa->n_states * 256 * sizeof(uint16_t), fbytes = (size_t)dfa->n_states;
         if (!d_tok_end) HIP_CHECK(hipMalloc((void **)&d_tok_end, (size_t)chunk * (size_t)info.num_vocab * sizeof(unsigned short)));
-        HIP_CHECK(hipMalloc(&buf, tbytes + fbytes));
-        if (hipMemcpy(buf, dfa->trans.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy((char *)buf + tbytes, dfa->flags.data(), fbytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(buf);
-            throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the table failed");
-        }
-        h.trans = (const unsigned short *)buf;
-        h.flags = (const unsigned char *)buf + tbytes;
-        h.state = state;
-        h.mode = halt_mode;
-    }
-    HIP_CHECK(hipStreamSynchronize(s_main));
-    if (hipMemcpy(d_gen_dfa + b, &h, sizeof(GenDfa), hipMemcpyHostToDevice) != hipSuccess) {
-        if (buf) (void)hipFree(buf);
-        throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the slot's entry failed");
-    }
-    gen_drop_dfa_buf(slot);
-    gen_dfa_buf[b] = buf;
-    gen_has_dfa[b] = dfa ? 1 : 0;
+        const char *buf = upload({{dfa->trans.data(), tbytes}, {dfa->flags.data(), fbytes}});
+        h.trans = (const unsigned short *)buf; h.flags = (const unsigned char *)buf + tbytes;
+        h.state = state; h.mode = halt_mode;
+    });
 }
 
 int rwkv_engine::gen_constraint_state(int slot) {
     HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
-    if (!gen_has_dfa[b]) return 0;
+    if (!gen_is_armed(slot)) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    if (gen_slots[(size_t)slot].constraint != GenConstraint::Dfa) return 0;
     GenDfa h{};
-    HIP_CHECK(hipMemcpyAsync(&h, d_gen_dfa + b, sizeof(GenDfa), hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipMemcpyAsync(&h, d_gen_dfa + slot, sizeof(GenDfa), hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     return h.state;
 }
 
-// The stack-automaton constraint of an armed, unfinished slot (rwkv_gen_set_pda): the two planes and the flags go to the device, the GenPda
-// of the slot points at them and carries the configuration.  Between runs: the stream is idle, so the old table can go at once.
+// The stack-automaton constraint (rwkv_gen_set_pda): the two planes and the flags go to the device, the GenPda of the slot points at them
+// and carries the configuration.
 void rwkv_engine::gen_set_pda(int slot, const rwkv_pda *pda, int state, const uint16_t *stack, int depth, int halt_mode) {
-    HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs an armed, unfinished slot");
-    GenPda h{};
-    void *buf = nullptr;
-    if (pda) {
-        if (gen_has_dfa[b]) throw RwkvError(RWKV_ERR_INVALID, "constraint: the slot has a DFA constraint set (a slot holds one kind)");
-        if (!d_tok_off) throw RwkvError(RWKV_ERR_INVALID, "a constraint needs the token table: rwkv_gen_set_token_bytes");
+    gen_install(slot, GenConstraint::Pda, pda != nullptr, d_gen_pda, [&](GenPda &h, auto upload) {
         if (state < 1 || state >= pda->n_states) throw RwkvError(RWKV_ERR_INVALID, "constraint: state 0 (dead) or out of range");
         if (depth < 0 || depth > pda->max_depth || (depth && !stack)) throw RwkvError(RWKV_ERR_INVALID, "constraint: depth outside 0 .. max_depth, or a null stack");
         for (int i = 0; i < depth; ++i)
@@ -1915,41 +1924,21 @@ void rwkv_engine::gen_set_pda(int slot, const rwkv_pda *pda, int state, const ui
         if (!pda_never_stuck(*pda, state, stack, depth, tok_single))
             throw RwkvError(RWKV_ERR_UNSUPPORTED, "constraint: a reachable state has no single-byte token with a plain transition that leads on (a row could be masked whole)");
         const size_t tbytes = (size_t)pda->n_states * 256 * sizeof(uint16_t), fbytes = (size_t)pda->n_states;
-        HIP_CHECK(hipMalloc(&buf, 2 * tbytes + fbytes));
-        if (hipMemcpy(buf, pda->next.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy((char *)buf + tbytes, pda->act.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy((char *)buf + 2 * tbytes, pda->flags.data(), fbytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(buf);
-            throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the table failed");
-        }
-        h.next = (const unsigned short *)buf;
-        h.act = (const unsigned short *)((const char *)buf + tbytes);
-        h.flags = (const unsigned char *)buf + 2 * tbytes;
-        h.state = state;
-        h.depth = depth;
-        h.mode = halt_mode;
-        h.max_depth = pda->max_depth;
+        const char *buf = upload({{pda->next.data(), tbytes}, {pda->act.data(), tbytes}, {pda->flags.data(), fbytes}});
+        h.next = (const unsigned short *)buf; h.act = (const unsigned short *)(buf + tbytes); h.flags = (const unsigned char *)buf + 2 * tbytes;
+        h.state = state; h.depth = depth; h.mode = halt_mode; h.max_depth = pda->max_depth;
         for (int i = 0; i < depth; ++i) h.stack[i] = stack[i];
-    }
-    HIP_CHECK(hipStreamSynchronize(s_main));
-    if (hipMemcpy(d_gen_pda + b, &h, sizeof(GenPda), hipMemcpyHostToDevice) != hipSuccess) {
-        if (buf) (void)hipFree(buf);
-        throw RwkvError(RWKV_ERR_DEVICE, "constraint: copying the slot's entry failed");
-    }
-    gen_drop_pda_buf(slot);
-    gen_pda_buf[b] = buf;
-    gen_has_pda[b] = pda ? 1 : 0;
+    });
 }
 
 void rwkv_engine::gen_pda_config(int slot, int32_t *state, uint16_t *stack, size_t cap, int32_t *depth) {
     HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    if (!gen_is_armed(slot)) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
     *state = 0;
     *depth = 0;
-    if (!gen_has_pda[b]) return;
+    if (gen_slots[(size_t)slot].constraint != GenConstraint::Pda) return;
     GenPda h{};
-    HIP_CHECK(hipMemcpyAsync(&h, d_gen_pda + b, sizeof(GenPda), hipMemcpyDeviceToHost, s_main));
+    HIP_CHECK(hipMemcpyAsync(&h, d_gen_pda + slot, sizeof(GenPda), hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
     *state = h.state;
     *depth = std::min(std::max(h.depth, 0), (int)GEN_PDA_MAX_DEPTH);
@@ -1960,7 +1949,7 @@ void rwkv_engine::gen_pda_config(int slot, int32_t *state, uint16_t *stack, size
 void rwkv_engine::gen_set_stops(int slot, const rwkv_gen_stops &s) {
     HIP_CHECK(hipSetDevice(device));
     const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "stop strings need an armed, unfinished slot");
+    if (!gen_is_live(slot)) throw RwkvError(RWKV_ERR_INVALID, "stop strings need an armed, unfinished slot");
     if ((s.n && (!s.strs || !s.lens)) || (s.n_tail && !s.tail)) throw RwkvError(RWKV_ERR_INVALID, "null stop-string array");
     if (s.n > RWKV_GEN_MAX_STOP_STR) throw RwkvError(RWKV_ERR_UNSUPPORTED, "at most RWKV_GEN_MAX_STOP_STR stop strings");
     if (s.n_tail > RWKV_GEN_STOP_BUF) throw RwkvError(RWKV_ERR_UNSUPPORTED, "the tail is longer than RWKV_GEN_STOP_BUF");
@@ -1980,13 +1969,13 @@ void rwkv_engine::gen_set_stops(int slot, const rwkv_gen_stops &s) {
     if (s.n_tail) std::memcpy(h[0].buf, s.tail, s.n_tail);
     HIP_CHECK(hipMemcpyAsync(d_gen_stop + b, h.data(), sizeof(GenStop), hipMemcpyHostToDevice, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
-    gen_has_stops[b] = s.n ? 1 : 0;
+    gen_slots[b].has_stops = s.n != 0;
 }
 
 size_t rwkv_engine::gen_stop_tail(int slot, uint8_t *out, size_t cap) {
     HIP_CHECK(hipSetDevice(device));
     const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b]) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
+    if (!gen_is_armed(slot)) throw RwkvError(RWKV_ERR_INVALID, "slot is not armed");
     std::vector<GenStop> h(1);
     HIP_CHECK(hipMemcpyAsync(h.data(), d_gen_stop + b, sizeof(GenStop), hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipStreamSynchronize(s_main));
@@ -1999,23 +1988,23 @@ size_t rwkv_engine::gen_stop_tail(int slot, uint8_t *out, size_t cap) {
 void rwkv_engine::gen_set_topn(int slot, int n) {
     HIP_CHECK(hipSetDevice(device));
     const size_t b = (size_t)slot, B = (size_t)max_batch, V = (size_t)info.num_vocab;
-    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "top-n lists need an armed, unfinished slot");
+    if (!gen_is_live(slot)) throw RwkvError(RWKV_ERR_INVALID, "top-n lists need an armed, unfinished slot");
     if (n < 0 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 0.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
-    if (gen_topn.empty()) {
+    if (!d_gen_topn_n) {
         if (n == 0) return;
         const size_t ring = (size_t)GEN_RING_STEPS * B;
-        d_gen_topn_n = dalloc<int>(B);
-        HIP_CHECK(hipMemset(d_gen_topn_n, 0, B * sizeof(int)));
         d_gen_top_ids = dalloc<unsigned>(ring * TOPN_MAX); h_gen_top_ids = hostalloc<unsigned>(ring * TOPN_MAX);
         d_gen_top_logp = dalloc<float>(ring * TOPN_MAX); h_gen_top_logp = hostalloc<float>(ring * TOPN_MAX);
         d_gen_tok_logp = dalloc<float>(ring); h_gen_tok_logp = hostalloc<float>(ring);
         d_gen_side_ms = dalloc<float>(B * 2);
         d_gen_side_rows = dalloc<float>(B * V);
-        gen_topn.assign(B, 0);                                     // last: marks the block as complete
+        int *topn_n = dalloc<int>(B);
+        HIP_CHECK(hipMemset(topn_n, 0, B * sizeof(int)));
+        d_gen_topn_n = topn_n;                                     // last: marks the block as complete
     }
     HIP_CHECK(hipStreamSynchronize(s_main));
     HIP_CHECK(hipMemcpy(d_gen_topn_n + b, &n, sizeof(int), hipMemcpyHostToDevice));
-    gen_topn[b] = n;
+    gen_slots[b].topn = n;
 }
 
 // A watch: the block is mapped and coherent like h_tok (uncached on the device: a store is the host's to see at once, a load is the
@@ -2063,65 +2052,63 @@ rwkv_gen_item *rwkv_engine::gen_item_new() const {
     it->nsx = sx_slot_stride; it->nw = wkv_slot_stride;
     HIP_CHECK(hipMalloc((void **)&it->state, (size_t)(2 * it->nsx + it->nw) * 4));
     HIP_CHECK(hipMalloc((void **)&it->row, (size_t)it->V * 4));
-    it->st.sxa = it->state; it->st.sxf = it->state + it->nsx; it->st.wkv = it->state + 2 * it->nsx;
+    it->st = block_state(it->state);
     return it.release();
 }
 // the slot's GenCap as the host knows it.  Between runs: the stream is idle.
 void rwkv_engine::gen_cap_upload(int slot) {
-    const size_t b = (size_t)slot;
+    const GenSlotHost &s = gen_slots[(size_t)slot];
     GenCap c{};
-    if (const rwkv_gen_item *it = gen_cap_item[b][0]) { c.p_state = it->state; c.p_row = it->row; }
-    if (const rwkv_gen_item *it = gen_cap_item[b][1]) c.f_row = it->row;
-    if (gen_inj[b]) c.inj_row = gen_inj_row[b];
+    if (const rwkv_gen_item *it = s.cap_item[0]) { c.p_state = it->state; c.p_row = it->row; }
+    if (const rwkv_gen_item *it = s.cap_item[1]) c.f_row = it->row;
+    if (s.inj) c.inj_row = s.inj_row;
     HIP_CHECK(hipStreamSynchronize(s_main));
-    HIP_CHECK(hipMemcpy(d_gen_cap + b, &c, sizeof c, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_gen_cap + slot, &c, sizeof c, hipMemcpyHostToDevice));
 }
 void rwkv_engine::gen_set_capture(int slot, unsigned what) {
     HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
-    if (gen_armed.empty() || !gen_armed[b] || gen_host[b].finish) throw RwkvError(RWKV_ERR_INVALID, "a capture needs an armed, unfinished slot");
+    if (!gen_is_live(slot)) throw RwkvError(RWKV_ERR_INVALID, "a capture needs an armed, unfinished slot");
     if (what & ~(unsigned)(RWKV_GEN_CAPTURE_PROMPT | RWKV_GEN_CAPTURE_FINISH)) throw RwkvError(RWKV_ERR_INVALID, "unknown capture bit");
     if ((what & RWKV_GEN_CAPTURE_PROMPT) && gen_prompt_left(slot) == 0)
         throw RwkvError(RWKV_ERR_INVALID, "RWKV_GEN_CAPTURE_PROMPT: the slot has no prompt left, its end has passed");
+    GenSlotHost &s = gen_slots[(size_t)slot];
     std::array<rwkv_gen_item *, 2> fresh{nullptr, nullptr};         // everything is allocated before anything changes
     try {
-        for (int i = 0; i < 2; ++i) if ((what >> i & 1) && !gen_cap_item[b][(size_t)i]) fresh[(size_t)i] = gen_item_new();
+        for (int i = 0; i < 2; ++i) if ((what >> i & 1) && !s.cap_item[(size_t)i]) fresh[(size_t)i] = gen_item_new();
     } catch (...) {
         for (rwkv_gen_item *it : fresh) gen_item_destroy(it);
         throw;
     }
     HIP_CHECK(hipStreamSynchronize(s_main));
     for (int i = 0; i < 2; ++i) {
-        rwkv_gen_item *&it = gen_cap_item[b][(size_t)i];
-        if (fresh[(size_t)i]) { it = fresh[(size_t)i]; gen_cap_taken[b] &= ~(1u << i); gen_cap_done[b] &= ~(1u << i); }
-        else if (!(what >> i & 1)) { gen_item_destroy(it); it = nullptr; gen_cap_taken[b] &= ~(1u << i); gen_cap_done[b] &= ~(1u << i); }
+        rwkv_gen_item *&it = s.cap_item[(size_t)i];
+        if (fresh[(size_t)i]) { it = fresh[(size_t)i]; s.cap_taken &= ~(1u << i); s.cap_done &= ~(1u << i); }
+        else if (!(what >> i & 1)) { gen_item_destroy(it); it = nullptr; s.cap_taken &= ~(1u << i); s.cap_done &= ~(1u << i); }
     }
-    gen_capture[b] = what;
+    s.capture = what;
     gen_cap_upload(slot);
 }
 rwkv_gen_item *rwkv_engine::gen_take_item(int slot, unsigned which) {
     HIP_CHECK(hipSetDevice(device));
-    const size_t b = (size_t)slot;
     if (which != RWKV_GEN_CAPTURE_PROMPT && which != RWKV_GEN_CAPTURE_FINISH) throw RwkvError(RWKV_ERR_INVALID, "`which` must be exactly one RWKV_GEN_CAPTURE_* bit");
-    if (gen_armed.empty() || !(gen_capture[b] & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot was not asked to capture this item");
-    if (gen_cap_taken[b] & which) throw RwkvError(RWKV_ERR_INVALID, "the item was already taken");
+    if (gen_slots.empty() || !(gen_slots[(size_t)slot].capture & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot was not asked to capture this item");
+    GenSlotHost &s = gen_slots[(size_t)slot];
+    if (s.cap_taken & which) throw RwkvError(RWKV_ERR_INVALID, "the item was already taken");
     const int i = which == RWKV_GEN_CAPTURE_PROMPT ? 0 : 1;
-    rwkv_gen_item *it = gen_cap_item[b][(size_t)i];
+    rwkv_gen_item *it = s.cap_item[(size_t)i];
     if (i == 0) {
-        if (!(gen_cap_done[b] & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot's prompt is not exhausted yet");
+        if (!(s.cap_done & which)) throw RwkvError(RWKV_ERR_INVALID, "the slot's prompt is not exhausted yet");
     } else {
-        const int fin = gen_host[b].finish;
+        const int fin = s.g.finish;
         if (!fin) throw RwkvError(RWKV_ERR_INVALID, "the slot is still running");
-        if (fin == RWKV_GEN_CANCELLED && gen_prompt_left(slot)) throw RwkvError(RWKV_ERR_INVALID, "the slot was cancelled inside its prompt: it never drew");
+        if (fin == RWKV_GEN_CANCELLED && s.prompt_left()) throw RwkvError(RWKV_ERR_INVALID, "the slot was cancelled inside its prompt: it never drew");
         // the state rule's state: gen_freeze kept it, the end of the run put it back into the slot, and nothing has run the slot since
-        HIP_CHECK(hipMemcpyAsync(it->st.sxa, sxa + slot * sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-        HIP_CHECK(hipMemcpyAsync(it->st.sxf, sxf + slot * sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-        HIP_CHECK(hipMemcpyAsync(it->st.wkv, wkv + slot * wkv_slot_stride, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+        copy_state(it->st, slot_state(slot));
         HIP_CHECK(hipStreamSynchronize(s_main));
     }
-    gen_cap_item[b][(size_t)i] = nullptr;
-    gen_cap_taken[b] |= which;
-    try { gen_cap_upload(slot); } catch (...) { gen_cap_item[b][(size_t)i] = it; gen_cap_taken[b] &= ~which; throw; }   // no step may write what the caller owns
+    s.cap_item[(size_t)i] = nullptr;
+    s.cap_taken |= which;
+    try { gen_cap_upload(slot); } catch (...) { s.cap_item[(size_t)i] = it; s.cap_taken &= ~which; throw; }   // no step may write what the caller owns
     return it;
 }
 // rwkv_gen_arm_prompt for a prompt that is wholly cached: the slot takes the item's state, and the item's row waits in a buffer of the
@@ -2132,14 +2119,12 @@ void rwkv_engine::gen_arm_item(int slot, const rwkv_gen_item *it, const rwkv_gen
     // the refusals of rwkv_gen_arm, all as RWKV_ERR_INVALID: an item is a resident-only object, there is no other path to name
     try { gen_arm(slot, p, nullptr, 0, true); }
     catch (const RwkvError &err) { if (err.code == RWKV_ERR_UNSUPPORTED) throw RwkvError(RWKV_ERR_INVALID, err.what()); throw; }
-    const size_t b = (size_t)slot;
+    GenSlotHost &s = gen_slots[(size_t)slot];
     try {
-        if (!gen_inj_row[b]) gen_inj_row[b] = dalloc<float>((size_t)info.num_vocab);
-        HIP_CHECK(hipMemcpyAsync(gen_inj_row[b], it->row, (size_t)it->V * 4, hipMemcpyDeviceToDevice, s_main));
-        HIP_CHECK(hipMemcpyAsync(sxa + slot * sx_slot_stride, it->st.sxa, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-        HIP_CHECK(hipMemcpyAsync(sxf + slot * sx_slot_stride, it->st.sxf, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-        HIP_CHECK(hipMemcpyAsync(wkv + slot * wkv_slot_stride, it->st.wkv, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-        gen_inj[b] = 1;
+        if (!s.inj_row) s.inj_row = dalloc<float>((size_t)info.num_vocab);
+        HIP_CHECK(hipMemcpyAsync(s.inj_row, it->row, (size_t)it->V * 4, hipMemcpyDeviceToDevice, s_main));
+        copy_state(slot_state(slot), it->st);
+        s.inj = true;
         gen_cap_upload(slot);
     } catch (...) {
         gen_disarm_slot(slot);
@@ -2147,30 +2132,31 @@ void rwkv_engine::gen_arm_item(int slot, const rwkv_gen_item *it, const rwkv_gen
     }
 }
 
-GenArgs rwkv_engine::gen_args(int n_rows, bool stops, bool dfa, bool topn, bool pda, bool cap) const {
+// the non-null pointers of GenArgs say what the step's features (FEAT_*) are: gen_sample picks its launches from them
+GenArgs rwkv_engine::gen_args(int n_rows, uint64_t feats) const {
     GenArgs a{};
-    if (cap) a.cap = d_gen_cap;
-    if (topn) {
+    if (feats & FEAT_CAPTURE) a.cap = d_gen_cap;
+    if (feats & FEAT_TOPN) {
         a.topn_n = d_gen_topn_n; a.top_ids = d_gen_top_ids; a.top_logp = d_gen_top_logp; a.tok_logp = d_gen_tok_logp;
         a.side_ms = d_gen_side_ms; a.side_rows = d_gen_side_rows;
     }
-    if (stops) a.stops = d_gen_stop;
-    if (dfa) { a.dfa = d_gen_dfa; a.tok_end = d_tok_end; }
-    if (pda) a.pda = d_gen_pda;
-    if (stops || dfa || pda) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
+    if (feats & FEAT_STOPS) a.stops = d_gen_stop;
+    if (feats & FEAT_DFA) { a.dfa = d_gen_dfa; a.tok_end = d_tok_end; }
+    if (feats & FEAT_PDA) a.pda = d_gen_pda;
+    if (feats & (FEAT_STOPS | FEAT_DFA | FEAT_PDA)) { a.tok_off = d_tok_off; a.tok_bytes = d_tok_bytes; a.n_tok = n_tok; }
     a.slots = d_gen; a.row_slot = dm.slot; a.logits = logits; a.penalty = d_gen_pen; a.bias = d_gen_bias;
     a.rows = d_gen_rows; a.samp_tok = d_gen_tok; a.samp_prob = d_gen_prob; a.feedback = d_tok_feedback;
     a.out_tok = d_gen_out; a.out_prob = (float *)(d_gen_out + (size_t)GEN_RING_STEPS * max_batch);
     a.run_step = d_gen_runstep; a.max_batch = max_batch; a.V = info.num_vocab; a.n_rows = n_rows;
     a.sxa = sxa; a.sxf = sxf; a.wkv = wkv; a.sx_slot_stride = sx_slot_stride; a.wkv_slot_stride = wkv_slot_stride;
     a.shadow = d_gen_shadow;
-    a.watch = gen_watch ? d_gen_watch : nullptr;
+    if (feats & FEAT_WATCH) a.watch = d_gen_watch;
     return a;
 }
 
 // the sampler stage of a generation step over the a.n_rows rows of the logits block: the state machine around nucleus_kernel
 void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
-    if (a.cap) launch(FAM_COPY, [&] { launch_gen_capture(a, s_main); });   // the raw rows, like gen_topn: in front of gen_pre
+    if (a.cap) launch(FAM_COPY, [&] { launch_gen_capture(a, s_main); });   // the raw rows, like the top-n kernel's: in front of gen_pre
     if (a.topn_n) launch(FAM_SAMPLE, [&] { launch_gen_topn(a, s_main); });   // the raw rows: gen_pre edits the block in place
     launch(FAM_SAMPLE, [&] { launch_gen_pre(a, s_main); });
     if (a.dfa) launch(FAM_SAMPLE, [&] { launch_gen_mask(a, s_main); });   // `transform` (run.rs:676-679) of the constrained rows
@@ -2182,37 +2168,29 @@ void rwkv_engine::gen_sample(const GenArgs &a, unsigned needs) {
 }
 
 // one decode step of the rows of `pl` that feeds itself: forward pass on the feedback tokens, then the sampler stage
-void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, bool stops, bool dfa, bool topn, bool pda, bool cap) {
+void rwkv_engine::gen_step(const StepPlan &pl, unsigned needs, uint64_t feats) {
     run_layers(pl.T, pl.n_seq, pl.n_out, d_tok_feedback, pl.dense);
-    gen_sample(gen_args(pl.T, stops, dfa, topn, pda, cap), needs);
+    gen_sample(gen_args(pl.T, feats), needs);
 }
 
 // `n` decode-only steps of the slots `rows` (ascending): one captured graph per set of rows, fed from and handed back to d_gen_held
 void rwkv_engine::gen_decode_steps(const std::vector<int> &rows, int n) {
     if ((int)rows.size() > chunk) throw RwkvError(RWKV_ERR_INVALID, "more armed slots than token_chunk_size");
     const unsigned needs = gen_needs(rows);
-    const bool stops = gen_any_stops(rows);                        // a slot of this row set has stop strings: gen_post_kernel<., true>
-    const bool dfa = gen_any_dfa(rows);                            // a slot of this row set has a constraint: gen_mask_kernel joins the step
-    const bool topn = gen_any_topn(rows);                          // a slot of this row set lists: gen_topn_kernel joins the step
-    const bool pda = gen_any_pda(rows);                            // a slot of this row set has a stack constraint: gen_pda_mask_kernel joins the step
-    const bool cap = gen_any_capture(rows, RWKV_GEN_CAPTURE_FINISH);   // a slot of this row set keeps its rows for a FINISH item: gen_capture_kernel joins the step
+    const uint64_t feats = gen_feats(rows);
     // the step's plan: one token per row, every row emitted (the token ids come from the feedback buffer, not from the plan)
     StepPlan pl;
     plan_step(one_token_each(rows, nullptr).data(), pl);
     upload_plan(pl);
     step_max_rows = 1;
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, false, s_main);
-    std::vector<uint64_t> key((size_t)(max_batch + 63) / 64 + 1, 0);
-    for (int b : rows) key[(size_t)b / 64] |= 1ull << (b % 64);
-    key.back() = needs | (stops ? 1ull << 32 : 0) | (dfa ? 1ull << 33 : 0) | (topn ? 1ull << 34 : 0) | (pda ? 1ull << 35 : 0) |
-                 (gen_watch ? 1ull << 36 : 0) |                    // a step under a watch launches gen_publish as well
-                 (cap ? 1ull << 37 : 0);
+    const std::vector<uint64_t> key = gen_step_key(max_batch, rows, needs, feats);
     int s0 = 0;
     hipGraphExec_t *exec = gen_graphs.find(key);
     if (!exec) {
         // as in run_plan: a set of rows runs its first step directly, the steps after it go through the captured graph
-        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, stops, dfa, topn, pda, cap); s0 = 1; }
-        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, stops, dfa, topn, pda, cap); }));
+        if (!gen_graphs.should_capture(key)) { gen_step(pl, needs, feats); s0 = 1; }
+        if (s0 < n) exec = &gen_graphs.insert(key, capture(s_main, [&] { gen_step(pl, needs, feats); }));
     }
     for (int s = s0; s < n; ++s) HIP_CHECK(hipGraphLaunch(*exec, s_main));
     launch_gen_handover(d_tok_feedback, d_gen_held, dm.slot, pl.T, true, s_main);
@@ -2229,16 +2207,16 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     const int B = max_batch;
     // dec.size() < chunk: gen_run checked, before its first step, that all live slots together fit one chunk
     std::vector<rwkv_slot_input> in = one_token_each(dec, nullptr);
-    for (int b : pro) in[(size_t)b] = rwkv_slot_input{gen_prompt[(size_t)b].data() + gen_ppos[(size_t)b], gen_prompt_left(b), RWKV_OPTION_LAST, 0};
+    for (int b : pro) in[(size_t)b] = rwkv_slot_input{gen_slots[(size_t)b].prompt.data() + gen_slots[(size_t)b].ppos, gen_prompt_left(b), RWKV_OPTION_LAST, 0};
     StepPlan pl;
     plan_step(in.data(), pl, (int)inj.size());
     for (int i = 0; i < pl.n_seq; ++i) if (!gen_prompt_left(pl.seq_slot[i])) pl.token[(size_t)pl.seq_begin[i]] = -1;   // a decode row; gen_tokens_kernel: held[slot]
-    std::vector<int> drawn;                                        // the slots that sample here: every decode row, every prompt that ends
+    std::vector<int> drawn;                                        // the slots that sample here: every decode row, every prompt that ends, every item's row
     for (int b = 0; b < B; ++b) if (pl.slot_out_rows[(size_t)b]) drawn.push_back(b);
-    bool cap = gen_any_capture(drawn, RWKV_GEN_CAPTURE_FINISH) || gen_any_capture(inj, RWKV_GEN_CAPTURE_FINISH);
-    for (int b : pro)                                              // the prompts that end here and are to be kept: complete once this step has run
-        if (pl.slot_out_rows[(size_t)b] && (gen_capture[(size_t)b] & RWKV_GEN_CAPTURE_PROMPT)) { gen_cap_done[(size_t)b] |= RWKV_GEN_CAPTURE_PROMPT; cap = true; }
     drawn.insert(drawn.end(), inj.begin(), inj.end());
+    uint64_t feats = gen_feats(drawn);
+    for (int b : pro)                                              // the prompts that end here and are to be kept: complete once this step has run
+        if (pl.slot_out_rows[(size_t)b] && (gen_slots[(size_t)b].capture & RWKV_GEN_CAPTURE_PROMPT)) { gen_slots[(size_t)b].cap_done |= RWKV_GEN_CAPTURE_PROMPT; feats |= FEAT_CAPTURE; }
     const int n_rows = pl.n_out + (int)inj.size();
     upload_plan(pl, inj);
     uploaded_id = 0;                                               // the uploaded token row is not the plan's: nobody may skip an upload on it
@@ -2246,22 +2224,22 @@ void rwkv_engine::gen_mixed_step(const std::vector<int> &dec, const std::vector<
     step_max_rows = pl.max_rows();
     if (pl.T > 0) run_layers(pl.T, pl.n_seq, pl.n_out, dm.token, pl.dense);
     if (n_rows > 0) {
-        GenArgs a = gen_args(n_rows, gen_any_stops(drawn), gen_any_dfa(drawn), gen_any_topn(drawn), gen_any_pda(drawn), cap || !inj.empty());
+        GenArgs a = gen_args(n_rows, inj.empty() ? feats : feats | FEAT_CAPTURE);   // gen_inject reads a.cap as well
         a.out_rows = dm.out_rows;
         a.held = d_gen_held;
         if (!inj.empty()) launch(FAM_COPY, [&] { launch_gen_inject(a, pl.n_out, s_main); });
-        if (!cap) a.cap = nullptr;                                 // gen_inject alone needed it
+        if (!(feats & FEAT_CAPTURE)) a.cap = nullptr;              // gen_inject alone needed it
         gen_sample(a, gen_needs(drawn));
     } else if (gen_watch) {                                        // a step without a row still publishes its (all padding) record
-        const GenArgs a = gen_args(0, false, false, false, false);
+        const GenArgs a = gen_args(0, FEAT_WATCH);
         launch(FAM_SAMPLE, [&] { launch_gen_publish(a, s_main); });
     }
     for (int b : dec) remain[(size_t)b] -= 1;
     for (int b : pro) {
-        gen_ppos[(size_t)b] += (size_t)pl.slot_consumed[(size_t)b];
+        gen_slots[(size_t)b].ppos += (size_t)pl.slot_consumed[(size_t)b];
         if (pl.slot_out_rows[(size_t)b]) remain[(size_t)b] -= 1;      // the prompt ended: its last row was the slot's first draw
     }
-    for (int b : inj) { gen_inj[(size_t)b] = 0; remain[(size_t)b] -= 1; }
+    for (int b : inj) { gen_slots[(size_t)b].inj = false; remain[(size_t)b] -= 1; }
 }
 
 // n_top > 0 (rwkv_gen_run_topn): the three top-n outputs are filled as well, n_top places per step and slot.
@@ -2272,9 +2250,9 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
     const int B = max_batch;
     const float nan = std::nanf("");
     if (n_top) {                                                   // refused before the first step, and before anything is written
-        for (int b = 0; b < B && !gen_topn.empty(); ++b)
-            if (gen_armed[(size_t)b] && !gen_host[(size_t)b].finish && gen_topn[(size_t)b] > n_top)
-                throw RwkvError(RWKV_ERR_INVALID, "slot " + std::to_string(b) + " lists " + std::to_string(gen_topn[(size_t)b]) + " places, n_top is " + std::to_string(n_top));
+        for (int b = 0; b < B; ++b)
+            if (gen_is_live(b) && gen_slots[(size_t)b].topn > n_top)
+                throw RwkvError(RWKV_ERR_INVALID, "slot " + std::to_string(b) + " lists " + std::to_string(gen_slots[(size_t)b].topn) + " places, n_top is " + std::to_string(n_top));
         std::fill(out_tok_logp, out_tok_logp + (size_t)n_steps * B, nan);
         std::fill(out_top_ids, out_top_ids + (size_t)n_steps * B * n_top, RWKV_TOPN_NONE);
         std::fill(out_top_logp, out_top_logp + (size_t)n_steps * B * n_top, nan);
@@ -2284,20 +2262,21 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
     if (n_emitted) std::fill(n_emitted, n_emitted + B, 0);
     if (finish) std::fill(finish, finish + B, (int32_t)RWKV_GEN_RUNNING);
     const size_t ring = (size_t)GEN_RING_STEPS * B;
-    for (int done = 0; done < n_steps && !gen_armed.empty();) {
+    for (int done = 0; done < n_steps && !gen_slots.empty();) {
         // One enqueue: up to a ring of steps with no wait in between.  The host knows which slots are in their prompt and when each
         // prompt ends (the plan says so); what it cannot know is who finished on the device, so a slot rides until the enqueue ends or
         // until it can emit nothing more (`remain`: max_tokens less what it has emitted for certain).
         const int nb = std::min(n_steps - done, (int)GEN_RING_STEPS);
         std::vector<int> live, remain((size_t)B, 0), cancelled;
         for (int b = 0; b < B; ++b) {
-            if (gen_watch && !gen_armed[(size_t)b] && gen_host[(size_t)b].finish) {   // a record shows 0 for a slot that is not armed: drop the word
-                gen_host[(size_t)b].finish = RWKV_GEN_RUNNING;                        // its last request left behind (nothing else reads it)
+            GenSlotHost &s = gen_slots[(size_t)b];
+            if (gen_watch && !s.armed && s.g.finish) {                 // a record shows 0 for a slot that is not armed: drop the word
+                s.g.finish = RWKV_GEN_RUNNING;                         // its last request left behind (nothing else reads it)
                 HIP_CHECK(hipMemsetAsync(&d_gen[b].finish, 0, sizeof(int), s_main));
             }
-            if (!gen_armed[(size_t)b] || gen_host[(size_t)b].finish) continue;
+            if (!s.armed || s.g.finish) continue;
             live.push_back(b);
-            remain[(size_t)b] = gen_host[(size_t)b].max_tokens - gen_host[(size_t)b].emitted;
+            remain[(size_t)b] = s.g.max_tokens - s.g.emitted;
         }
         if (live.empty()) break;
         // refused before anything is enqueued (a throw from the middle of an enqueue would lose the steps already run): every live slot
@@ -2306,7 +2285,7 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         HIP_CHECK(hipMemsetAsync(d_gen_runstep, 0xFF, 4, s_main));                          // -1: the first kernel of a step counts up
         HIP_CHECK(hipMemsetAsync(d_gen_out, 0xFF, (size_t)nb * B * 4, s_main));             // 0xFFFFFFFF: nothing emitted
         HIP_CHECK(hipMemsetAsync(d_gen_out + ring, 0xFF, (size_t)nb * B * 4, s_main));      // ... and the same bits are a NaN
-        const bool lists = gen_any_topn(live);                     // the top-n planes of the ring: RWKV_TOPN_NONE / NaN until a slot lists
+        const bool lists = gen_feats(live) & FEAT_TOPN;            // the top-n planes of the ring: RWKV_TOPN_NONE / NaN until a slot lists
         if (lists) {
             HIP_CHECK(hipMemsetAsync(d_gen_top_ids, 0xFF, (size_t)nb * B * TOPN_MAX * 4, s_main));
             HIP_CHECK(hipMemsetAsync(d_gen_top_logp, 0xFF, (size_t)nb * B * TOPN_MAX * 4, s_main));
@@ -2324,7 +2303,7 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
             std::vector<int> dec, pro, inj;                        // ascending slot order
             for (int b : live) {
                 if (gen_prompt_left(b)) pro.push_back(b);
-                else if (gen_inj[(size_t)b]) inj.push_back(b);         // armed from an item: its first draw needs no forward row
+                else if (gen_slots[(size_t)b].inj) inj.push_back(b);         // armed from an item: its first draw needs no forward row
                 else if (remain[(size_t)b] > 0) dec.push_back(b);
             }
             if (!pro.empty() || !inj.empty()) {
@@ -2355,7 +2334,7 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
         HIP_CHECK(hipStreamSynchronize(s_main));
         for (int b : cancelled) {                                  // the stream is idle (as where gen_set_topn writes its word); not in `live`: no restore
             const int fin = RWKV_GEN_CANCELLED;
-            gen_host[(size_t)b].finish = fin;
+            gen_slots[(size_t)b].g.finish = fin;
             HIP_CHECK(hipMemcpy(&d_gen[b].finish, &fin, sizeof(int), hipMemcpyHostToDevice));
         }
         if (k == 0) break;
@@ -2366,7 +2345,7 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
             for (int b : live) {
                 const size_t cell = (size_t)s * B + (size_t)b, to = ((size_t)(done + s) * B + (size_t)b) * (size_t)n_top;
                 if (h_gen_out[cell] == 0xFFFFFFFFu) continue;
-                const int n = gen_topn.empty() ? 0 : gen_topn[(size_t)b];
+                const int n = gen_slots[(size_t)b].topn;
                 if (n) {
                     out_tok_logp[(size_t)(done + s) * B + (size_t)b] = h_gen_tok_logp[cell];
                     std::memcpy(out_top_ids + to, h_gen_top_ids + cell * TOPN_MAX, (size_t)n * 4);
@@ -2376,23 +2355,20 @@ void rwkv_engine::gen_run(int n_steps, uint32_t *out_tokens, float *out_probs, i
             }
         bool restored = false;
         for (int b : live) {
-            const size_t sb = (size_t)b;
-            const int got = back[sb].emitted - gen_host[sb].emitted;
-            gen_host[sb] = back[sb];
+            GenSlotHost &s = gen_slots[(size_t)b];
+            const int got = back[(size_t)b].emitted - s.g.emitted;
+            s.g = back[(size_t)b];
             if (n_emitted) n_emitted[b] += got;
-            if (back[sb].finish) {
+            if (s.g.finish) {
                 // the slot rode the steps behind the one it finished in: its state goes back to what it was there (the state rule)
-                const float *sh = gen_shadow[sb];
-                HIP_CHECK(hipMemcpyAsync(sxa + b * sx_slot_stride, sh, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-                HIP_CHECK(hipMemcpyAsync(sxf + b * sx_slot_stride, sh + sx_slot_stride, (size_t)sx_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
-                HIP_CHECK(hipMemcpyAsync(wkv + b * wkv_slot_stride, sh + 2 * sx_slot_stride, (size_t)wkv_slot_stride * 4, hipMemcpyDeviceToDevice, s_main));
+                copy_state(slot_state(b), block_state(s.shadow));
                 restored = true;
             }
         }
         if (restored) HIP_CHECK(hipStreamSynchronize(s_main));
         done += k;
     }
-    if (finish) for (int b = 0; b < B && !gen_armed.empty(); ++b) if (gen_armed[(size_t)b]) finish[b] = gen_host[(size_t)b].finish;
+    if (finish) for (int b = 0; b < B; ++b) if (gen_is_armed(b)) finish[b] = gen_slots[(size_t)b].g.finish;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2601,9 +2577,9 @@ rwkv_status rwkv_state_init(const rwkv_engine *e, float *dst) {
         e->fill_init_state(dst);                            // v5/v6/v7: all-zero; v4: -1e30 in the pp rows
     });
 }
-static StatePackArgs pack_args(rwkv_engine *e, float *sxa, float *sxf, float *wkv, int to_slab, int layer_only) {
+static StatePackArgs pack_args(rwkv_engine *e, const rwkv_dstate &st, int to_slab, int layer_only) {
     StatePackArgs a{};
-    a.slab = e->slab_dev; a.sxa = sxa; a.sxf = sxf; a.wkv = wkv;
+    a.slab = e->slab_dev; a.sxa = st.sxa; a.sxf = st.sxf; a.wkv = st.wkv;
     a.L = e->info.num_layer; a.C = e->info.num_emb; a.H = e->info.num_head;
     a.transposed = e->info.version != 7; a.to_slab = to_slab; a.layer_only = layer_only;
     a.v4 = e->info.version == 4;
@@ -2622,8 +2598,7 @@ rwkv_status rwkv_state_load(rwkv_engine *e, int32_t slot, const float *src) {
         const size_t n = rwkv_state_len(e);
         std::memcpy(e->slab_host, src, n * 4);
         HIP_CHECK(hipMemcpyAsync(e->slab_dev, e->slab_host, n * 4, hipMemcpyHostToDevice, e->s_main));
-        launch_state_pack(pack_args(e, e->sxa + slot * e->sx_slot_stride, e->sxf + slot * e->sx_slot_stride,
-                                    e->wkv + slot * e->wkv_slot_stride, 0, -1), e->s_main);
+        launch_state_pack(pack_args(e, e->slot_state(slot), 0, -1), e->s_main);
         HIP_CHECK(hipStreamSynchronize(e->s_main));
     });
 }
@@ -2633,8 +2608,7 @@ rwkv_status rwkv_state_back(rwkv_engine *e, int32_t slot, float *dst) {
         if (!dst) throw RwkvError(RWKV_ERR_INVALID, "null dst");
         HIP_CHECK(hipSetDevice(e->device));
         const size_t n = rwkv_state_len(e);
-        launch_state_pack(pack_args(e, e->sxa + slot * e->sx_slot_stride, e->sxf + slot * e->sx_slot_stride,
-                                    e->wkv + slot * e->wkv_slot_stride, 1, -1), e->s_main);
+        launch_state_pack(pack_args(e, e->slot_state(slot), 1, -1), e->s_main);
         HIP_CHECK(hipMemcpyAsync(e->slab_host, e->slab_dev, n * 4, hipMemcpyDeviceToHost, e->s_main));
         HIP_CHECK(hipStreamSynchronize(e->s_main));
         std::memcpy(dst, e->slab_host, n * 4);
@@ -2646,8 +2620,7 @@ rwkv_status rwkv_state_back_layer(rwkv_engine *e, int32_t slot, int32_t layer, f
         if (!dst || layer < 0 || layer >= e->info.num_layer) throw RwkvError(RWKV_ERR_INVALID, "bad layer/dst");
         HIP_CHECK(hipSetDevice(e->device));
         const size_t n = (size_t)e->wkv_layer_floats();       // the layer's WKV rows: [64][C], V4 [3][C]
-        launch_state_pack(pack_args(e, e->sxa + slot * e->sx_slot_stride, e->sxf + slot * e->sx_slot_stride,
-                                    e->wkv + slot * e->wkv_slot_stride, 1, layer), e->s_main);
+        launch_state_pack(pack_args(e, e->slot_state(slot), 1, layer), e->s_main);
         HIP_CHECK(hipMemcpyAsync(e->slab_host, e->slab_dev, n * 4, hipMemcpyDeviceToHost, e->s_main));
         HIP_CHECK(hipStreamSynchronize(e->s_main));
         std::memcpy(dst, e->slab_host, n * 4);
@@ -2677,8 +2650,7 @@ rwkv_status rwkv_state_back_layer_async(rwkv_engine *e, int32_t slot, int32_t la
         // the pack reads the slot as the compute stream left it ...
         HIP_CHECK(hipEventRecord(e->ev_copy_a, e->s_main));
         HIP_CHECK(hipStreamWaitEvent(e->s_copy, e->ev_copy_a, 0));
-        StatePackArgs a = pack_args(e, e->sxa + slot * e->sx_slot_stride, e->sxf + slot * e->sx_slot_stride,
-                                    e->wkv + slot * e->wkv_slot_stride, 1, layer);
+        StatePackArgs a = pack_args(e, e->slot_state(slot), 1, layer);
         a.slab = e->emb_stage + (size_t)slot * n;                // per-slot staging: the copy stream is in order, so a slot's staging
         launch_state_pack(a, e->s_copy);                         // area is free again before its next pack runs
         // ... and whatever the compute stream does to the slot next waits for the pack (microseconds), not for the PCIe copy
@@ -2705,9 +2677,7 @@ rwkv_status rwkv_state_read(rwkv_engine *e, int32_t slot, rwkv_dstate **snap) {
         HIP_CHECK(hipMalloc((void **)&s->sxa, nsx));
         HIP_CHECK(hipMalloc((void **)&s->sxf, nsx));
         HIP_CHECK(hipMalloc((void **)&s->wkv, nw));
-        HIP_CHECK(hipMemcpyAsync(s->sxa, e->sxa + slot * e->sx_slot_stride, nsx, hipMemcpyDeviceToDevice, e->s_main));
-        HIP_CHECK(hipMemcpyAsync(s->sxf, e->sxf + slot * e->sx_slot_stride, nsx, hipMemcpyDeviceToDevice, e->s_main));
-        HIP_CHECK(hipMemcpyAsync(s->wkv, e->wkv + slot * e->wkv_slot_stride, nw, hipMemcpyDeviceToDevice, e->s_main));
+        e->copy_state(*s, e->slot_state(slot));
         HIP_CHECK(hipStreamSynchronize(e->s_main));
         *snap = s.release();
     });
@@ -2718,10 +2688,7 @@ rwkv_status rwkv_state_write(rwkv_engine *e, int32_t slot, const rwkv_dstate *s)
         if (!s) throw RwkvError(RWKV_ERR_INVALID, "null snap");
         HIP_CHECK(hipSetDevice(e->device));
         e->gen_disarm_slot(slot);
-        const size_t nsx = (size_t)e->sx_slot_stride * 4, nw = (size_t)e->wkv_slot_stride * 4;
-        HIP_CHECK(hipMemcpyAsync(e->sxa + slot * e->sx_slot_stride, s->sxa, nsx, hipMemcpyDeviceToDevice, e->s_main));
-        HIP_CHECK(hipMemcpyAsync(e->sxf + slot * e->sx_slot_stride, s->sxf, nsx, hipMemcpyDeviceToDevice, e->s_main));
-        HIP_CHECK(hipMemcpyAsync(e->wkv + slot * e->wkv_slot_stride, s->wkv, nw, hipMemcpyDeviceToDevice, e->s_main));
+        e->copy_state(e->slot_state(slot), *s);
         HIP_CHECK(hipStreamSynchronize(e->s_main));
     });
 }
@@ -2942,7 +2909,7 @@ rwkv_status rwkv_gen_item_back(rwkv_engine *e, const rwkv_gen_item *it, float *s
         HIP_CHECK(hipSetDevice(e->device));
         if (state_dst) {
             const size_t n = rwkv_state_len(e);
-            launch_state_pack(pack_args(e, it->st.sxa, it->st.sxf, it->st.wkv, 1, -1), e->s_main);   // to_slab: the item is only read
+            launch_state_pack(pack_args(e, it->st, 1, -1), e->s_main);   // to_slab: the item is only read
             HIP_CHECK(hipMemcpyAsync(e->slab_host, e->slab_dev, n * 4, hipMemcpyDeviceToHost, e->s_main));
             HIP_CHECK(hipStreamSynchronize(e->s_main));
             std::memcpy(state_dst, e->slab_host, n * 4);
@@ -2958,7 +2925,7 @@ rwkv_status rwkv_gen_item_from_host(rwkv_engine *e, const float *state, const fl
         const size_t n = rwkv_state_len(e);
         std::memcpy(e->slab_host, state, n * 4);
         HIP_CHECK(hipMemcpyAsync(e->slab_dev, e->slab_host, n * 4, hipMemcpyHostToDevice, e->s_main));
-        launch_state_pack(pack_args(e, it->st.sxa, it->st.sxf, it->st.wkv, 0, -1), e->s_main);
+        launch_state_pack(pack_args(e, it->st, 0, -1), e->s_main);
         HIP_CHECK(hipStreamSynchronize(e->s_main));
         HIP_CHECK(hipMemcpy(it->row, row, (size_t)it->V * 4, hipMemcpyHostToDevice));
         *out = it.release();

@@ -413,10 +413,14 @@ def test_the_refusals_and_what_clears_a_constraint():
     assert A.gen_pda_config(0) == (q, st) and A.gen_constraint_state(0) == 0
     assert code(lambda: A.gen_set_constraint(0, dfa)) == -1              # a slot holds a DFA or a stack constraint
     assert code(lambda: A.gen_set_token_bytes(tab)) == -1                # a slot walks the table
+    A.gen_set_constraint(0, None)                                        # NULL through the call of the other kind leaves it alone
+    assert A.gen_pda_config(0) == (q, st)
     A.gen_set_pda(0, None)                                               # NULL clears it
     assert A.gen_pda_config(0) == (0, [])
     A.gen_set_constraint(0, dfa)
     assert code(lambda: A.gen_set_pda(0, pda)) == -1                     # ... the other way round
+    A.gen_set_pda(0, None)
+    assert dfa.start != 0 and A.gen_constraint_state(0) == dfa.start     # ... in both: the state it was set with
     A.gen_set_constraint(0, None)
     A.gen_set_token_bytes(tab)
     no_colon = [None if w == b":" else w for w in tab]
