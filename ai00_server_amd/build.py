@@ -47,7 +47,9 @@ def needs_build() -> bool:
     return open(STAMP).read().strip() != _sources_digest()
 
 
-KERNEL_PARTS = 6      # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
+KERNEL_PARTS = 7      # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
+# part 6 (the WKV chunk-scan form) is compiled without packed fp32 instructions; the older parts keep the flags they were measured with
+PART_FLAGS = {6: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
@@ -64,7 +66,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if src == "rwkv_kernels.hip":
             for k in range(KERNEL_PARTS):
                 obj = os.path.join(CSRC, f"{stem}.p{k}.o")
-                jobs.append((base + [f"-DRWKV_PART={k}", "-c", os.path.join(CSRC, src), "-o", obj], obj))
+                jobs.append((base + PART_FLAGS.get(k, []) + [f"-DRWKV_PART={k}", "-c", os.path.join(CSRC, src), "-o", obj], obj))
         else:
             obj = os.path.join(CSRC, stem + ".o")
             jobs.append((base + ["-c", os.path.join(CSRC, src), "-o", obj], obj))

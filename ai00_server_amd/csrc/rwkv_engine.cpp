@@ -240,6 +240,7 @@ struct LayerW {
     const DMat *W2[5];              // v6 time_mix_w2 [C x Dm] x5
     const DMat *D1;                 // v6 time_decay_w1 [Dd x C]
     const _Float16 *D2;             // v6 time_decay_w2 raw [C][Dd]
+    const float *ldec;              // v5, safetensors loads only: -exp(decay), the log of wdec taken from time_decay (the WKV scan form)
     // v7
     const DMat *w1, *w2, *a1, *a2, *v1, *v2, *g1, *g2;
     const float *w0, *a0, *v0, *k_k, *k_a, *r_k;
@@ -619,6 +620,9 @@ struct rwkv_engine {
     void log_gemm(const std::vector<ProbSpec> &ps, int T, int fam, const char *kind, int variant, int grid, int ksplit, int threads);
     void log_row(const char *kernel, int T, long grid, double bytes);   // RWKV_LAUNCH_LOG: algorithmic bytes of a non-GEMM launch of layer 0 / 1
     int step_max_rows = 0;                                // most rows any sequence has in the step being enqueued (run_plan)
+    int wkv_form = RWKV_WKV_RECURRENT;                    // rwkv_engine_set_wkv_form: RWKV_WKV_SCAN sends multi-row steps through launch_wkv_scan
+    WkvScanWs scan_ws{};                                  // its workspace, shared by every layer; allocated when the form is first switched on
+    void set_wkv_form(int form);
     float *lnp_xx_att = nullptr;                          // normalised rows published by the V6 mix's LN-prologue launch (for the commit)
     void plan_step(const rwkv_slot_input *in, StepPlan &pl, int reserve = 0);   // reserve: rows of the chunk that are spoken for (gen_mixed_step)
     void upload_plan(const StepPlan &pl, const std::vector<int> &pseudo = {});
@@ -771,8 +775,10 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         HIP_CHECK(hipMemcpyAsync(raw, t.data, t.nbytes, hipMemcpyHostToDevice, s_main));
     };
     // `want` = the element count the kernels will read (0: unchecked): a short tensor must fail the load, not a kernel
-    auto load_vec = [&](const std::string &name, int op = 0, size_t want = 0) -> const float * {
+    // side: a second transform of a vector that is already loaded under `name` — not registered (a prefab keeps one image per name), not counted
+    auto load_vec = [&](const std::string &name, int op = 0, size_t want = 0, bool side = false) -> const float * {
         if (pf) {
+            if (side) return nullptr;                               // the image holds the first transform only
             const PfEntry &e = prefab.get(name, 0);
             if (want && e.h.n_elems != want) throw RwkvError(RWKV_ERR_FORMAT, name + ": unexpected size");
             float *v = dalloc<float>((size_t)e.h.n_elems);
@@ -804,6 +810,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
         if (blended) { if (op) launch_vec_op(v, t.numel(), op, s_main); }
         else launch_f16_to_f32(raw, v, t.numel(), op, s_main);
         HIP_CHECK(hipStreamSynchronize(s_main));
+        if (side) return v;
         vecs[name] = v; vec_meta[name] = {(size_t)t.numel(), true};
         weight_bytes += (uint64_t)t.numel() * 2;
         return v;
@@ -962,6 +969,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
             const char *n4[] = {"k", "v", "r", "g"};
             for (int i = 0; i < 4; ++i) w.mu[i] = load_vec(p + "att.time_mix_" + n4[i], 0, nC);
             w.wdec = load_vec(p + "att.time_decay", 1, nC);  // exp(-exp(decay)), static per channel
+            w.ldec = load_vec(p + "att.time_decay", 2, nC, true);   // -exp(decay): its logarithm, exact where wdec rounds to 1
         } else if (info.version == 6) {
             const char *n6[] = {"x", "w", "k", "v", "r", "g"};
             for (int i = 0; i < 6; ++i) w.mu[i] = load_vec(p + "att.time_mix_" + n6[i], 0, nC);
@@ -1395,11 +1403,23 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
             k.lnx_w = w.lnxw; k.lnx_b = w.lnxb;
             k.yhi = aY.hi; k.ylo = aY.lo; k.ldh = C;
             k.max_rows = step_max_rows;
-            launch(FAM_WKV, [&] { launch_wkv(k, T > n_seq, s_main); });
-            // state tiles in and out (2 x 16 KiB per (slot, head)), the projections of every row in, the gated output operand out
-            log_row(T > n_seq ? "wkv_chunk_kernel" : "wkv_kernel", T, (long)n_seq * H,
-                    (double)n_seq * H * 32768.0 + (double)T * C * 4.0 * (info.version == 7 ? (l > 0 ? 8 : 6) : 4) +
-                        (info.version == 6 ? (double)T * Dd * 4.0 + (double)C * Dd * 2.0 : 0.0) + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            k.ldec = w.ldec; k.T = T;
+            if (wkv_form == RWKV_WKV_SCAN && T > n_seq) {
+                launch(FAM_WKV, [&] { launch_wkv_scan(k, scan_ws, s_main); });
+                // A: r / k / v (and td, D2) in; the chunk records, the decayed-r rows and the intra outputs out.  B: the state in and out, every
+                // record in, its 64 x 64 part out again.  C: the records, both row arrays and the gate in, the output operand out.
+                const long nchunk = wkv_scan_chunks(T, n_seq);
+                const double recs = (double)nchunk * H * WKV_SCAN_REC * 4.0, rows = (double)T * C * 4.0;
+                log_row("wkv_scan_local_kernel", T, nchunk * H, 3.0 * rows + (info.version == 6 ? (double)T * Dd * 4.0 + (double)C * Dd * 2.0 : 0.0) + recs + 2.0 * rows);
+                log_row("wkv_scan_carry_kernel", T, (long)n_seq * H, (double)n_seq * H * 32768.0 + 2.0 * recs);
+                log_row("wkv_scan_out_kernel", T, nchunk * H, recs + 3.0 * rows + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            } else {
+                launch(FAM_WKV, [&] { launch_wkv(k, T > n_seq, s_main); });
+                // state tiles in and out (2 x 16 KiB per (slot, head)), the projections of every row in, the gated output operand out
+                log_row(T > n_seq ? "wkv_chunk_kernel" : "wkv_kernel", T, (long)n_seq * H,
+                        (double)n_seq * H * 32768.0 + (double)T * C * 4.0 * (info.version == 7 ? (l > 0 ? 8 : 6) : 4) +
+                            (info.version == 6 ? (double)T * Dd * 4.0 + (double)C * Dd * 2.0 : 0.0) + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            }
         }
         {
             ProbSpec s = prob(w.Wo, aY, ACT_NONE, P, C);
@@ -2454,6 +2474,36 @@ int32_t rwkv_engine_device(const rwkv_engine *e) { return e ? e->device : -1; }
 int32_t rwkv_engine_max_batch(const rwkv_engine *e) { return e ? e->max_batch : 0; }
 int32_t rwkv_engine_token_chunk_size(const rwkv_engine *e) { return e ? e->chunk : 0; }
 uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e) { return e ? e->weight_bytes : 0; }
+
+// The form is not part of a step graph's key: switching it drops every captured step that may hold a WKV launch of the other form.
+void rwkv_engine::set_wkv_form(int form) {
+    if (form != RWKV_WKV_RECURRENT && form != RWKV_WKV_SCAN) throw RwkvError(RWKV_ERR_INVALID, "wkv form must be RWKV_WKV_RECURRENT or RWKV_WKV_SCAN");
+    if (form == wkv_form) return;
+    HIP_CHECK(hipSetDevice(device));
+    if (form == RWKV_WKV_SCAN) {
+        WkvArgs k{};
+        k.version = info.version; k.Dd = Dd;
+        k.ldec = layers.empty() ? nullptr : layers[0].ldec;
+        if (!wkv_scan_supported(k))
+            throw RwkvError(RWKV_ERR_UNSUPPORTED, "the WKV scan form serves V5 models loaded from safetensors and V6 models with a decay LoRA dim of 64 or 128");
+        if (!scan_ws.chunks) {
+            const size_t TC = (size_t)chunk * info.num_emb;
+            scan_ws.rt = dalloc<float>(TC);
+            scan_ws.oi = dalloc<float>(TC);
+            scan_ws.chunks = dalloc<float>((size_t)wkv_scan_chunks(chunk, max_batch) * info.num_head * WKV_SCAN_REC);
+        }
+    }
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    graphs.clear(); gen_graphs.clear();
+    wkv_form = form;
+}
+rwkv_status rwkv_engine_set_wkv_form(rwkv_engine *e, int32_t form) {
+    return guard([&] {
+        if (!e) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        e->set_wkv_form(form);
+    });
+}
+int32_t rwkv_engine_wkv_form(const rwkv_engine *e) { return e ? e->wkv_form : -1; }
 
 // Blocks handed out by rwkv_host_alloc, base -> bytes: the asynchronous read-back checks that the rows it is asked to write END inside the
 // block they start in (a pinned block that is too small, or a large offset into it, must come back as RWKV_ERR_INVALID, not as a DMA

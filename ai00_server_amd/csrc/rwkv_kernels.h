@@ -242,8 +242,23 @@ struct WkvArgs {
     _Float16 *yhi, *ylo;
     int ldh;
     int max_rows;                   // most rows any sequence has in this step (0: unknown): <= 8 selects the short-chunk form of wkv_chunk_kernel
+    // the chunk-scan form (launch_wkv_scan) only
+    const float *ldec;              // v5: the log decay -exp(time_decay) [C], computed from time_decay itself (logf of wdec is 0 wherever w rounds to 1)
+    int T;                          // rows of this step (with n_seq it bounds the number of 64-token chunks: the grid of the scan launches)
 };
 void launch_wkv(const WkvArgs &a, bool multi_row, hipStream_t s);   // multi_row: some sequence has > 1 row in this step
+
+// The chunk-scan (matrix) form of the V5 / V6 recurrence for multi-row steps: three launches over 64-token chunks, the products on the MFMA pipe
+// (rwkv_kernels.hip, part 6).  Sums in another order than launch_wkv: fp32-class agreement, not bit equality.
+constexpr int WKV_SCAN_CHUNK = 64;
+constexpr int WKV_SCAN_REC = 4096 + 64;                            // floats per (chunk, head): dS / entry state [p][q], then D = e^(sum of log decays) [q]
+struct WkvScanWs {
+    float *chunks;                  // [wkv_scan_chunks(T, n_seq)][H][WKV_SCAN_REC]
+    float *rt, *oi;                 // [T][C] each: r * e^(prefix log decay) rows; the intra-chunk outputs
+};
+inline long wkv_scan_chunks(int T, int n_seq) { return (T + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK + n_seq; }   // >= sum over sequences of ceil(len / 64)
+bool wkv_scan_supported(const WkvArgs &a);                          // version 5 (with ldec); version 6 with Dd 64 or 128
+void launch_wkv_scan(const WkvArgs &a, const WkvScanWs &ws, hipStream_t s);   // serves every sequence of the step, one-row ones included
 
 // RWKV-4: the per-channel WKV recurrence with a running maximum (aa, bb, pp); no heads, no gate, no group norm.  One thread per channel.
 struct Wkv4Args {

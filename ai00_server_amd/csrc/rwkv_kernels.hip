@@ -4529,4 +4529,359 @@ void launch_lora_blend(_Float16 *W, const _Float16 *B, const _Float16 *A, int ro
 }
 
 #endif  // part 4: state pack, softmax / arg-max / samplers, load-time kernels
+
+#if RWKV_PART_ON(6)
+// =====================================================================================
+// WKV in chunk-scan (matrix) form for V5 / V6 multi-row steps (opt-in: rwkv_engine_set_wkv_form).  wkv_chunk_kernel walks a sequence token by
+// token in one block per (sequence, head); here the step's rows are cut into 64-token chunks, every chunk is a block, and the recurrence
+// inside a chunk is written as matrix products on the MFMA pipe.  With l_t = log w_t <= 0 per channel q and [a, b) = sum of l_j over a <= j < b:
+//   o_t[p]   = sum_q r_tq e^[0,t) S0[p][q]  +  sum_{s<t} A_ts v_s[p]  +  (sum_q r_tq u_q k_tq) v_t[p],   A_ts = sum_q r_tq k_sq e^[s+1,t)
+//   S_out[p][q] = e^[0,64) S0[p][q] + sum_s v_s[p] k_sq e^[s+1,64)
+// Every exponent is a sum of log decays, so every factor is <= 1: w == 0 and w == 1 are ordinary values (no 1/w anywhere), and underflow
+// to 0 is the limit the recurrence itself reaches.  The exponents are running sums from the nearer end (never a difference of two prefixes:
+// a channel that decays hard early would cancel the bits of the small sums behind it).
+//   A  wkv_scan_local_kernel  (chunk, head): everything that does not need S0.  16-token sub-blocks I, J: for I > J
+//        A_ts = sum_q (r_tq e^[16(J+1),t)) (k_sq e^[s+1,16(J+1))), a 16 x 16 x 64 product per pair; inside a sub-block (s <= t) there is no such
+//        split, those 544 entries are evaluated directly (one wave per t, lanes = channels, a wave sum per entry).  Then o = A v and
+//        dS = sum_s v_s (k_s e^[s+1,64))^T as 64 x 64 x 64 products.  Out: dS, D = e^[0,64), the intra outputs, the rows r_t e^[0,t).
+//   B  wkv_scan_carry_kernel  (sequence, head): S_{c+1} = D_c S_c + dS_c over the sequence's chunks, elementwise; S_c replaces dS_c.
+//   C  wkv_scan_out_kernel    (chunk, head): o_t += (r_t e^[0,t)) S_c, then GroupNorm / gate / operand emit as wkv_chunk_kernel's phase C.
+// No block waits for another one: the three launches are ordered by the stream.  A block finds its (sequence, chunk) by walking seq_len.
+// MFMA operands: fp32 values as an f16 (hi, lo) pair, three products (hi hi, hi lo, lo hi) per fragment, each fragment scaled by the power
+// of two that puts its largest magnitude in [2^13, 2^14) — hi is a normal f16 and lo keeps its bits whatever the values are (states reach
+// thousands) — and unscaled in fp32 on the accumulator: 22 bits of every operand.  Fragments are split in registers from fp32 LDS rows
+// (8 consecutive k per lane: two 16-byte reads; row stride 68 floats).
+// =====================================================================================
+constexpr int SCAN_LD = 68;
+__device__ __forceinline__ float wave_max(float v) {
+    v = fmaxf(v, dpp_f32<0xB1>(v));
+    v = fmaxf(v, dpp_f32<0x4E>(v));
+    v = fmaxf(v, dpp_f32<0x124>(v));
+    v = fmaxf(v, dpp_f32<0x128>(v));
+    return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)),
+                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16))),
+                 fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)),
+                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48))));
+}
+struct ScanFrag { f16x8 hi, lo; float inv; };
+// one A or B fragment of v_mfma_f32_16x16x32_f16 from 8 consecutive fp32 (16-byte aligned); the whole wave must be active
+__device__ __forceinline__ ScanFrag scan_frag(const float *p) {
+    const float4 x0 = *(const float4 *)p, x1 = *(const float4 *)(p + 4);
+    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    float m = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x[e]));
+    m = wave_max(m);
+    // m = 1.f x 2^(ex - 127): scale = 2^(140 - ex) puts it in [2^13, 2^14).  The clamp keeps scale and 1 / scale finite powers of two for a
+    // fragment of zeros (and for values beyond 2^63, which are no activations)
+    const int ex = min(max((int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xff), 27), 190);
+    const float scale = __builtin_bit_cast(float, (unsigned)(267 - ex) << 23);
+    ScanFrag f;
+    f.inv = __builtin_bit_cast(float, (unsigned)(ex - 13) << 23);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float y = x[e] * scale;
+        const _Float16 h = (_Float16)y;
+        f.hi[e] = h;
+        f.lo[e] = (_Float16)(y - (float)h);
+    }
+    return f;
+}
+__device__ __forceinline__ void scan_mma(f32x4 &tot, const ScanFrag &a, const ScanFrag &b) {
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, b.hi, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.lo, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, acc, 0, 0, 0);
+    const float s = a.inv * b.inv;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tot[i] = fmaf(acc[i], s, tot[i]);
+}
+// block b of launches A and C -> (sequence, chunk inside it); false: the grid bound ceil(T / 64) + n_seq left this block without a chunk
+__device__ __forceinline__ bool scan_locate(const WkvArgs &a, int b, int &seq, int &c) {
+    for (int i = 0; i < a.n_seq; ++i) {
+        const int nc = (a.seq_len[i] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+        if (b < nc) { seq = i; c = b; return true; }
+        b -= nc;
+    }
+    return false;
+}
+
+template <int VER, int DD>
+__global__ __launch_bounds__(256) void wkv_scan_local_kernel(const WkvArgs a, const WkvScanWs ws) {
+    constexpr int LD = SCAN_LD;
+    // r, k, log decay rows [t][q]; v transposed [p][s]; k e^[s+1,64) transposed [q][s] (later: the matrix A [t][s]); k e^[s+1, sub-block end) [s][q];
+    // r e^[16(J+1),t) [t - 16(J+1)][q] for J = 0 (48 rows), 1 (32), 2 (16); the sub-blocks' decay totals
+    __shared__ __attribute__((aligned(16))) float s_r[64][LD], s_k[64][LD], s_l[64][LD], s_vt[64][LD], s_kht[64][LD], s_kb[64][LD], s_q[96][LD];
+    __shared__ float s_bt[4][64];
+    float (*s_am)[LD] = s_kht;
+    int seq, c;
+    if (!scan_locate(a, blockIdx.x, seq, c)) return;
+    const int h = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row0 = a.seq_begin[seq] + c * 64, n = min(64, a.seq_len[seq] - c * 64);
+    const int C = a.C, cb = h * 64;
+    float *rec = ws.chunks + ((long)blockIdx.x * a.H + h) * WKV_SCAN_REC;
+
+    // ---- the chunk's rows; rows n.. are zeros with log decay 0: they add nothing to dS and leave D alone
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, t = idx >> 4, c4 = (idx & 15) * 4;
+        float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f), k4 = r4, v4 = r4, l4 = r4;
+        if (t < n) {
+            const long rb = (long)(row0 + t) * C + cb + c4;
+            r4 = *(const float4 *)(a.r + rb); k4 = *(const float4 *)(a.k + rb); v4 = *(const float4 *)(a.v + rb);
+            if (VER == 5) l4 = *(const float4 *)(a.ldec + cb + c4);
+        }
+        *(float4 *)(&s_r[t][c4]) = r4;
+        *(float4 *)(&s_k[t][c4]) = k4;
+        s_vt[c4][t] = v4.x; s_vt[c4 + 1][t] = v4.y; s_vt[c4 + 2][t] = v4.z; s_vt[c4 + 3][t] = v4.w;
+        // below -104 e^l is 0 in fp32 already; the floor keeps the sums finite (-inf - -inf has no value)
+        if (VER == 5) *(float4 *)(&s_l[t][c4]) = make_float4(fmaxf(l4.x, -128.f), fmaxf(l4.y, -128.f), fmaxf(l4.z, -128.f), fmaxf(l4.w, -128.f));
+    }
+    if (VER == 6) {
+        // decay LoRA stage 2 on the matrix pipe, as in wkv_chunk_kernel: wave w owns channels 16w .. 16w+15, four 16-token tiles; the outer
+        // exp is not applied: l = -exp(decay + D2 td)
+        constexpr int KS = DD / 32;
+        const int Dd = a.Dd;
+        f16x8 af[KS];
+        const _Float16 *d2 = a.D2 + (long)(cb + wave * 16 + (lane & 15)) * Dd + (lane >> 4) * 8;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) af[ks] = *(const f16x8 *)(d2 + ks * 32);
+        const float4 dec4 = *(const float4 *)(a.wdec_or_decay + cb + wave * 16 + (lane >> 4) * 4);
+#pragma unroll
+        for (int tile = 0; tile < 4; ++tile) {
+            const int tt = tile * 16 + (lane & 15);
+            const float *tdp = a.td + (long)(row0 + min(tt, n - 1)) * Dd + (lane >> 4) * 8;
+            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const float4 t0k = *(const float4 *)(tdp + ks * 32), t1k = *(const float4 *)(tdp + ks * 32 + 4);
+                const float tv[8] = {t0k.x, t0k.y, t0k.z, t0k.w, t1k.x, t1k.y, t1k.z, t1k.w};
+                f16x8 bh, bl;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { _Float16 hh, ll; split_hilo(tv[e], hh, ll); bh[e] = hh; bl[e] = ll; }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks], bh, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks], bl, acc, 0, 0, 0);
+            }
+            float4 lv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tt < n) {
+                lv.x = fmaxf(-expf(dec4.x + acc[0]), -128.f); lv.y = fmaxf(-expf(dec4.y + acc[1]), -128.f);
+                lv.z = fmaxf(-expf(dec4.z + acc[2]), -128.f); lv.w = fmaxf(-expf(dec4.w + acc[3]), -128.f);
+            }
+            *(float4 *)(&s_l[tt][wave * 16 + (lane >> 4) * 4]) = lv;
+        }
+    }
+    __syncthreads();
+
+    // ---- running sums of the log decays: thread = (sub-block I = wave, channel q = lane), 16 tokens each way
+    {
+        const int I = wave, q = lane;
+        float bt = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) bt += s_l[16 * I + j][q];
+        s_bt[I][q] = bt;
+        __syncthreads();
+        const float b0 = s_bt[0][q], b1 = s_bt[1][q], b2 = s_bt[2][q], b3 = s_bt[3][q];
+        const float head = I == 0 ? 0.f : I == 1 ? b0 : I == 2 ? b0 + b1 : b0 + b1 + b2;      // [0, 16 I)
+        const float tail = I == 3 ? 0.f : I == 2 ? b3 : I == 1 ? b2 + b3 : b1 + b2 + b3;      // [16 (I + 1), 64)
+        float ls = 0.f;                                                                     // [s + 1, 16 (I + 1))
+        for (int j = 15; j >= 0; --j) {
+            const int s = 16 * I + j;
+            const float kk = s_k[s][q];
+            s_kb[s][q] = kk * expf(ls);
+            s_kht[q][s] = kk * expf(ls + tail);
+            ls += s_l[s][q];
+        }
+        float lp = 0.f;                                                                     // [16 I, t)
+        for (int j = 0; j < 16; ++j) {
+            const int t = 16 * I + j;
+            const float rr = s_r[t][q];
+            if (t < n) ws.rt[(long)(row0 + t) * C + cb + q] = rr * expf(head + lp);
+            if (I >= 1) s_q[t - 16][q] = rr * expf(lp + (I == 2 ? b1 : I == 3 ? b1 + b2 : 0.f));
+            if (I >= 2) s_q[48 + t - 32][q] = rr * expf(lp + (I == 3 ? b2 : 0.f));
+            if (I == 3) s_q[80 + t - 48][q] = rr * expf(lp);
+            lp += s_l[t][q];
+        }
+        if (I == 3) rec[4096 + q] = expf(head + bt);
+    }
+    __syncthreads();
+
+    // ---- dS[p][q] = sum_s vt[p][s] kht[q][s]: wave w owns rows p = 16w ..
+    {
+        ScanFrag av[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) av[ks] = scan_frag(&s_vt[16 * wave + (lane & 15)][ks * 32 + (lane >> 4) * 8]);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            f32x4 tot = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) scan_mma(tot, av[ks], scan_frag(&s_kht[16 * nt + (lane & 15)][ks * 32 + (lane >> 4) * 8]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rec[(16 * wave + (lane >> 4) * 4 + i) * 64 + 16 * nt + (lane & 15)] = tot[i];
+        }
+    }
+    __syncthreads();                                           // kht is read: its rows become the matrix A [t][s], zero above the diagonal
+    for (int i = tid; i < 64 * LD; i += 256) (&s_am[0][0])[i] = 0.f;
+    __syncthreads();
+
+    // ---- the diagonal sub-blocks, s <= t, directly: wave w takes t = w, w + 4, ...; lane = channel; s walks down from t with the exponent
+    //      [s + 1, t) as a running sum; lane s - s0 keeps entry (t, s).  s == t is the bonus sum_q r u k.
+    {
+        const float uq = a.u[cb + lane];
+        for (int t = wave; t < 64; t += 4) {
+            const int s0 = t & ~15;
+            const float rt = s_r[t][lane];
+            float mine = wave_sum(rt * uq * s_k[t][lane]);
+            if (lane != t - s0) mine = 0.f;
+            float e = 0.f;
+            for (int s = t - 1; s >= s0; --s) {
+                const float v = wave_sum(rt * s_k[s][lane] * expf(e));
+                if (lane == s - s0) mine = v;
+                e += s_l[s][lane];
+            }
+            if (lane <= t - s0) s_am[t][s0 + lane] = mine;
+        }
+    }
+    // ---- the six sub-block pairs I > J on the matrix pipe: A[16 I ..][16 J ..] = q_J rows of I x kb rows of J
+    for (int pi = wave; pi < 6; pi += 4) {
+        const int J = pi < 3 ? 0 : pi < 5 ? 1 : 2, I = pi < 3 ? pi + 1 : pi < 5 ? pi - 1 : 3;
+        const int qb = (J == 0 ? 0 : J == 1 ? 48 : 80) + 16 * (I - J - 1);
+        f32x4 tot = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+            scan_mma(tot, scan_frag(&s_q[qb + (lane & 15)][ks * 32 + (lane >> 4) * 8]), scan_frag(&s_kb[16 * J + (lane & 15)][ks * 32 + (lane >> 4) * 8]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s_am[16 * I + (lane >> 4) * 4 + i][16 * J + (lane & 15)] = tot[i];
+    }
+    __syncthreads();
+
+    // ---- o[t][p] = sum_s A[t][s] vt[p][s]: wave w owns rows t = 16w ..; s beyond 16w + 15 is zero (the second 32 only for w >= 2)
+    {
+        const int nks = (wave >> 1) + 1;
+        ScanFrag aa[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) if (ks < nks) aa[ks] = scan_frag(&s_am[16 * wave + (lane & 15)][ks * 32 + (lane >> 4) * 8]);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            f32x4 tot = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) if (ks < nks) scan_mma(tot, aa[ks], scan_frag(&s_vt[16 * nt + (lane & 15)][ks * 32 + (lane >> 4) * 8]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = 16 * wave + (lane >> 4) * 4 + i;
+                if (t < n) ws.oi[(long)(row0 + t) * C + cb + 16 * nt + (lane & 15)] = tot[i];
+            }
+        }
+    }
+}
+
+// S_{c+1} = D_c S_c + dS_c over the chunks of one (sequence, head); thread (ig, jg) owns T[p = aa*16+ig][q = jg*4 .. +4] like the recurrent kernels
+__global__ __launch_bounds__(256) void wkv_scan_carry_kernel(const WkvArgs a, const WkvScanWs ws) {
+    const int seq = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, ig = tid >> 4, jg = tid & 15;
+    int g = 0;
+    for (int i = 0; i < seq; ++i) g += (a.seq_len[i] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+    const int nc = (a.seq_len[seq] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+    float *st = a.state + (long)a.seq_slot[seq] * a.slot_stride + (long)h * 4096;
+    float4 S[4];
+#pragma unroll
+    for (int aa = 0; aa < 4; ++aa) S[aa] = __builtin_bit_cast(float4, __builtin_nontemporal_load((const f32x4 *)(st + (aa * 16 + ig) * 64 + jg * 4)));
+    for (int c = 0; c < nc; ++c) {
+        float *rec = ws.chunks + ((long)(g + c) * a.H + h) * WKV_SCAN_REC;
+        const float4 d = *(const float4 *)(rec + 4096 + jg * 4);
+#pragma unroll
+        for (int aa = 0; aa < 4; ++aa) {
+            float4 *e = (float4 *)(rec + (aa * 16 + ig) * 64 + jg * 4);
+            const float4 ds = *e;
+            *e = S[aa];                                        // the state this chunk starts from, for wkv_scan_out_kernel
+            S[aa] = make_float4(fmaf(d.x, S[aa].x, ds.x), fmaf(d.y, S[aa].y, ds.y), fmaf(d.z, S[aa].z, ds.z), fmaf(d.w, S[aa].w, ds.w));
+        }
+    }
+#pragma unroll
+    for (int aa = 0; aa < 4; ++aa) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, S[aa]), (f32x4 *)(st + (aa * 16 + ig) * 64 + jg * 4));
+}
+
+__global__ __launch_bounds__(256) void wkv_scan_out_kernel(const WkvArgs a, const WkvScanWs ws) {
+    constexpr int LD = SCAN_LD;
+    __shared__ __attribute__((aligned(16))) float s_rt[64][LD], s_s[64][LD], s_o[64][LD];
+    int seq, c;
+    if (!scan_locate(a, blockIdx.x, seq, c)) return;
+    const int h = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row0 = a.seq_begin[seq] + c * 64, n = min(64, a.seq_len[seq] - c * 64);
+    const int C = a.C, cb = h * 64;
+    const float *rec = ws.chunks + ((long)blockIdx.x * a.H + h) * WKV_SCAN_REC;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, t = idx >> 4, c4 = (idx & 15) * 4;
+        *(float4 *)(&s_rt[t][c4]) = t < n ? *(const float4 *)(ws.rt + (long)(row0 + t) * C + cb + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *(float4 *)(&s_s[t][c4]) = *(const float4 *)(rec + t * 64 + c4);
+    }
+    __syncthreads();
+    // ---- o[t][p] = intra[t][p] + sum_q rt[t][q] S[p][q]: wave w owns rows t = 16w ..
+    {
+        ScanFrag ar[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) ar[ks] = scan_frag(&s_rt[16 * wave + (lane & 15)][ks * 32 + (lane >> 4) * 8]);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            f32x4 tot = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) scan_mma(tot, ar[ks], scan_frag(&s_s[16 * nt + (lane & 15)][ks * 32 + (lane >> 4) * 8]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = 16 * wave + (lane >> 4) * 4 + i, p = 16 * nt + (lane & 15);
+                s_o[t][p] = tot[i] + (t < n ? ws.oi[(long)(row0 + t) * C + cb + p] : 0.f);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- wkv_chunk_kernel's phase C on 64 tokens: GroupNorm over the head (eps 64e-5), gate, operand emit; thread = (token, 8 channels), two passes
+    auto sum8 = [](float v) {
+        v = quad_sum(v);
+        return v + __shfl_xor(v, 4, 64);
+    };
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int tt = (tid >> 3) + 32 * pass, c8 = (tid & 7) * 8;
+        if (tt < n) {                                             // the 8 lanes of a token take the branch together
+            const int t = row0 + tt;
+            const float4 g0 = *(const float4 *)(a.g + (long)t * C + cb + c8), g1 = *(const float4 *)(a.g + (long)t * C + cb + c8 + 4);
+            const float4 o0 = *(const float4 *)(&s_o[tt][c8]), o1 = *(const float4 *)(&s_o[tt][c8 + 4]);
+            float o[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            float sm = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm += o[e];
+            const float mean = sum8(sm) * (1.0f / 64.0f);
+            float sq = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { o[e] -= mean; sq += o[e] * o[e]; }
+            const float rstd = 1.0f / sqrtf(sum8(sq) * (1.0f / 64.0f) + 64e-5f);
+            f16x8 hh, ll;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float y = (o[e] * rstd * a.lnx_w[cb + c8 + e] + a.lnx_b[cb + c8 + e]) * gg[e];
+                _Float16 hv, lv;
+                split_hilo(y, hv, lv);
+                hh[e] = hv; ll[e] = lv;
+            }
+            const long yo = opd_off(t, cb + c8, a.ldh);           // 8 consecutive k of one token: one 16-byte piece
+            *(f16x8 *)(a.yhi + yo) = hh;
+            if (a.ylo) *(f16x8 *)(a.ylo + yo) = ll;
+        }
+    }
+}
+
+bool wkv_scan_supported(const WkvArgs &a) {
+    return (a.version == 5 && a.ldec != nullptr) || (a.version == 6 && (a.Dd == 64 || a.Dd == 128));
+}
+void launch_wkv_scan(const WkvArgs &a, const WkvScanWs &ws, hipStream_t s) {
+    const dim3 chunks((unsigned)wkv_scan_chunks(a.T, a.n_seq), a.H);
+    if (a.version == 5) hipLaunchKernelGGL((wkv_scan_local_kernel<5, 64>), chunks, dim3(256), 0, s, a, ws);
+    else if (a.Dd == 64) hipLaunchKernelGGL((wkv_scan_local_kernel<6, 64>), chunks, dim3(256), 0, s, a, ws);
+    else hipLaunchKernelGGL((wkv_scan_local_kernel<6, 128>), chunks, dim3(256), 0, s, a, ws);
+    hipLaunchKernelGGL(wkv_scan_carry_kernel, dim3(a.n_seq, a.H), dim3(256), 0, s, a, ws);
+    hipLaunchKernelGGL(wkv_scan_out_kernel, chunks, dim3(256), 0, s, a, ws);
+}
+#endif  // part 6: WKV chunk-scan form
 }  // namespace rwkv

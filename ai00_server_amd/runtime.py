@@ -94,6 +94,8 @@ ABI_SYMBOLS = {
     "rwkv_engine_max_batch": (C.c_int32, [C.c_void_p]),
     "rwkv_engine_token_chunk_size": (C.c_int32, [C.c_void_p]),
     "rwkv_engine_weight_bytes": (C.c_uint64, [C.c_void_p]),
+    "rwkv_engine_set_wkv_form": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "rwkv_engine_wkv_form": (C.c_int32, [C.c_void_p]),
     "rwkv_infer": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(_SlotOutC)]),
     "rwkv_host_alloc": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "rwkv_host_free": (None, [C.c_void_p]),
@@ -242,6 +244,11 @@ class Precision(enum.IntEnum):   # reload.rs:89-94 (+ the raw mode of ABI 7, inc
     Fp16 = 0                     # f16 operands, the error-carrying launches hi + lo: within 1e-3 at 32 layers (the default)
     Fp32 = 1                     # hi + lo operands everywhere (fp32-class)
     Fp16Raw = 2                  # f16 operands everywhere: fastest, not tolerance-holding at depth
+
+
+class WkvForm(enum.IntEnum):     # rwkv_engine_set_wkv_form: the V5 / V6 WKV of multi-row (prefill) steps
+    Recurrent = 0                # token by token, one block per (sequence, head): the default
+    Scan = 1                     # 64-token chunks as matrix products on the MFMA pipe; fp32-class agreement, not bit equality
 
 
 class RnnOption(enum.IntEnum):   # run.rs:716, 819
@@ -750,8 +757,15 @@ class ModelBuilder:
         return self
 
     def build(self, max_batch: int = 8, token_chunk_size: int = 128,
-              precision: Precision = Precision.Fp16) -> "Runtime":
-        return Runtime(self, max_batch, token_chunk_size, precision)
+              precision: Precision = Precision.Fp16, wkv_form: WkvForm = WkvForm.Recurrent) -> "Runtime":
+        rt = Runtime(self, max_batch, token_chunk_size, precision)
+        if wkv_form != WkvForm.Recurrent:
+            try:
+                rt.set_wkv_form(wkv_form)
+            except RwkvError:
+                rt.close()
+                raise
+        return rt
 
 
 class Runtime:
@@ -811,6 +825,15 @@ class Runtime:
     @property
     def device(self) -> int:
         return lib().rwkv_engine_device(self._h)
+
+    @property
+    def wkv_form(self) -> WkvForm:
+        return WkvForm(lib().rwkv_engine_wkv_form(self._h))
+
+    def set_wkv_form(self, form: WkvForm):
+        """RwkvError (-3, RWKV_ERR_UNSUPPORTED) on an engine the scan form does not serve (V4, V7, V6 with another decay LoRA dim, V5 from a
+        prefab image); the engine keeps the form it had."""
+        _check(lib().rwkv_engine_set_wkv_form(self._h, int(form)))
 
     @property
     def weight_bytes(self) -> int:

@@ -148,6 +148,20 @@ int32_t rwkv_engine_token_chunk_size(const rwkv_engine *e);     /* the load-time
 /* bytes of weights resident in HBM at their storage width (fp16 / int8+scales / nf4 or sf4+absmax),
  * embedding table excluded: the W_q of SURVEY 8(d).  For roofline accounting. */
 uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e);
+/* The form of the V5 / V6 WKV recurrence in steps where a sequence has several rows (prefill); one-row steps are not affected.
+ *   RWKV_WKV_RECURRENT (the default): one block per (sequence, head) walks the sequence's rows token by token.
+ *   RWKV_WKV_SCAN: the rows are cut into 64-token chunks, one block per (chunk, head) evaluates the recurrence inside a chunk as matrix
+ *     products on the MFMA pipe, and a short elementwise pass carries the state from chunk to chunk: a single long prompt occupies
+ *     prompt_length / 64 x heads blocks instead of `heads`.  It sums in another order than the recurrent form: logits and states agree with it
+ *     (and with an fp32 evaluation) within the bounds of rwkv_load_desc.precision, not bit for bit.
+ * RWKV_WKV_SCAN on a V4 or V7 engine, on a V6 engine whose decay LoRA dim is not 64 or 128, or on a V5 engine loaded from a prefab image
+ * (which holds exp(-exp(time_decay)) only, and its logarithm is lost where that rounds to 1): RWKV_ERR_UNSUPPORTED, and nothing changes —
+ * there is no silent fallback.  Any other value: RWKV_ERR_INVALID.  The first switch to RWKV_WKV_SCAN allocates the workspace
+ * ((token_chunk_size / 64 + max_batch) x heads x 4160 + 2 x token_chunk_size x num_emb floats); every switch drops the captured step graphs.
+ * Thread contract of rwkv_infer, between calls. */
+enum { RWKV_WKV_RECURRENT = 0, RWKV_WKV_SCAN = 1 };
+rwkv_status rwkv_engine_set_wkv_form(rwkv_engine *e, int32_t form);
+int32_t rwkv_engine_wkv_form(const rwkv_engine *e);            /* RWKV_WKV_* in force */
 
 /* ---- `runtime.infer(RnnInput) -> (RnnInput, RnnOutput)` run.rs:1134-1156 ------------------ */
 enum { RWKV_OPTION_LAST = 0, RWKV_OPTION_FULL = 1,              /* RnnOption, run.rs:716,819 */

@@ -28,6 +28,7 @@ enum class RnnOption : int32_t { Last = RWKV_OPTION_LAST, Full = RWKV_OPTION_FUL
 enum class Quant : int32_t { None = RWKV_QUANT_NONE, Int8 = RWKV_QUANT_INT8, NF4 = RWKV_QUANT_NF4, SF4 = RWKV_QUANT_SF4 };
 // reload.rs:89-94; Fp16Raw is this library's extension (ABI 7): f16 operands on EVERY launch — the fastest mode, outside 1e-3 at 32 layers
 enum class Precision : int32_t { Fp16 = RWKV_PRECISION_FP16, Fp32 = RWKV_PRECISION_FP32, Fp16Raw = RWKV_PRECISION_FP16_RAW };
+enum class WkvForm : int32_t { Recurrent = RWKV_WKV_RECURRENT, Scan = RWKV_WKV_SCAN };   // rwkv_engine_set_wkv_form
 using ModelInfo = rwkv_model_info;
 
 struct Loader {
@@ -182,6 +183,9 @@ class Runtime {
         max_batch = rwkv_engine_max_batch(e);
         token_chunk_size = rwkv_engine_token_chunk_size(e);      // what the engine was built with: sizes the buffers of Full requests
     }
+    // the WKV form of multi-row steps; an engine the scan form does not serve throws (RWKV_ERR_UNSUPPORTED) and keeps its form
+    void set_wkv_form(WkvForm f) { check(rwkv_engine_set_wkv_form(e_.get(), (int32_t)f)); }
+    WkvForm wkv_form() const { return (WkvForm)rwkv_engine_wkv_form(e_.get()); }
     // runtime.infer(input) -> output; `input` is consumed in place (tokens drained by n_consumed)
     std::vector<RnnOutputBatch> infer(RnnInput &input) {
         if ((int)input.batches.size() != max_batch) throw std::invalid_argument("RnnInput must have max_batch entries");
@@ -521,12 +525,14 @@ class ModelBuilder {
     ModelBuilder(const uint8_t *st, size_t len, int adapter = RWKV_ADAPTER_AUTO) { d_.st_bytes = st; d_.st_len = len; d_.adapter = adapter; }
     ModelBuilder &quant(int layers, Quant q) { d_.quant_layers = layers; d_.quant_type = (int32_t)q; return *this; }
     ModelBuilder &lora(const uint8_t *st, size_t len, float alpha) { lora_.push_back({st, len, alpha}); return *this; }
-    Runtime build(int max_batch = 8, int token_chunk_size = 128, Precision p = Precision::Fp16) {
+    Runtime build(int max_batch = 8, int token_chunk_size = 128, Precision p = Precision::Fp16, WkvForm form = WkvForm::Recurrent) {
         d_.max_batch = max_batch; d_.token_chunk_size = token_chunk_size; d_.precision = (int32_t)p;
         d_.lora = lora_.empty() ? nullptr : lora_.data(); d_.n_lora = lora_.size();
         rwkv_engine *e = nullptr;
         check(rwkv_engine_create(&d_, &e));
-        return Runtime(e);
+        Runtime rt(e);
+        if (form != WkvForm::Recurrent) rt.set_wkv_form(form);
+        return rt;
     }
    private:
     rwkv_load_desc d_{};

@@ -22,6 +22,8 @@ pub const RWKV_QUANT_SF4: i32 = 3;
 pub const RWKV_PRECISION_FP16: i32 = 0;
 pub const RWKV_PRECISION_FP32: i32 = 1;
 pub const RWKV_PRECISION_FP16_RAW: i32 = 2;
+pub const RWKV_WKV_RECURRENT: i32 = 0;
+pub const RWKV_WKV_SCAN: i32 = 1;
 pub const RWKV_ADAPTER_AUTO: i32 = -1;
 pub const RWKV_ADAPTER_ECONOMICAL: i32 = -2;
 pub const RWKV_OPTION_LAST: i32 = 0;
@@ -113,6 +115,8 @@ extern "C" {
     pub fn rwkv_engine_max_batch(e: *const rwkv_engine) -> i32;
     pub fn rwkv_engine_token_chunk_size(e: *const rwkv_engine) -> i32;
     pub fn rwkv_engine_weight_bytes(e: *const rwkv_engine) -> u64;
+    pub fn rwkv_engine_set_wkv_form(e: *mut rwkv_engine, form: i32) -> rwkv_status;
+    pub fn rwkv_engine_wkv_form(e: *const rwkv_engine) -> i32;
     // runtime.infer  (run.rs:1128-1156) and the pinned buffers its logits land in
     pub fn rwkv_infer(e: *mut rwkv_engine, inp: *const rwkv_slot_input, out: *mut rwkv_slot_output) -> rwkv_status;
     pub fn rwkv_host_alloc(bytes: usize, out: *mut *mut c_void) -> rwkv_status;
