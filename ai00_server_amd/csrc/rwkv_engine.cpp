@@ -622,6 +622,7 @@ struct rwkv_engine {
     int step_max_rows = 0;                                // most rows any sequence has in the step being enqueued (run_plan)
     int wkv_form = RWKV_WKV_RECURRENT;                    // rwkv_engine_set_wkv_form: RWKV_WKV_SCAN sends multi-row steps through launch_wkv_scan
     WkvScanWs scan_ws{};                                  // its workspace, shared by every layer; allocated when the form is first switched on
+    Wkv7ScanWs scan7_ws{};                                // RWKV_WKV_SCAN_DELTA's workspace (V7), likewise
     void set_wkv_form(int form);
     float *lnp_xx_att = nullptr;                          // normalised rows published by the V6 mix's LN-prologue launch (for the commit)
     void plan_step(const rwkv_slot_input *in, StepPlan &pl, int reserve = 0);   // reserve: rows of the chunk that are spoken for (gen_mixed_step)
@@ -1413,6 +1414,16 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
                 log_row("wkv_scan_local_kernel", T, nchunk * H, 3.0 * rows + (info.version == 6 ? (double)T * Dd * 4.0 + (double)C * Dd * 2.0 : 0.0) + recs + 2.0 * rows);
                 log_row("wkv_scan_carry_kernel", T, (long)n_seq * H, (double)n_seq * H * 32768.0 + 2.0 * recs);
                 log_row("wkv_scan_out_kernel", T, nchunk * H, recs + 3.0 * rows + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            } else if (wkv_form == RWKV_WKV_SCAN_DELTA && T > n_seq) {
+                launch(FAM_WKV, [&] { launch_wkv7_scan(k, scan7_ws, s_main); });
+                // A: r / k / v / a / w (and v_first, the value gate) in; the records, the decayed-r rows, N_rk V and the bonus out.  B: the state in and
+                // out; W, U_loc, B~, dS_v and D of every record in, SA and the entry state out.  C: the entry state, SA, N_rb, both row arrays, v and
+                // the gate in, the output operand out.
+                const long nchunk = wkv_scan_chunks(T, n_seq);
+                const double mats = (double)nchunk * H * 4096.0 * 4.0, rows = (double)T * C * 4.0;
+                log_row("wkv7_scan_local_kernel", T, nchunk * H, (l > 0 ? 7.0 : 6.0) * rows + 5.0 * mats + 2.0 * rows + (double)T * H * 4.0);
+                log_row("wkv7_scan_carry_kernel", T, (long)n_seq * H, (double)n_seq * H * 32768.0 + 6.0 * mats);
+                log_row("wkv7_scan_out_kernel", T, nchunk * H, 3.0 * mats + (l > 0 ? 6.0 : 4.0) * rows + (double)T * H * 4.0 + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
             } else {
                 launch(FAM_WKV, [&] { launch_wkv(k, T > n_seq, s_main); });
                 // state tiles in and out (2 x 16 KiB per (slot, head)), the projections of every row in, the gated output operand out
@@ -2477,7 +2488,8 @@ uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e) { return e ? e->weight_b
 
 // The form is not part of a step graph's key: switching it drops every captured step that may hold a WKV launch of the other form.
 void rwkv_engine::set_wkv_form(int form) {
-    if (form != RWKV_WKV_RECURRENT && form != RWKV_WKV_SCAN) throw RwkvError(RWKV_ERR_INVALID, "wkv form must be RWKV_WKV_RECURRENT or RWKV_WKV_SCAN");
+    if (form != RWKV_WKV_RECURRENT && form != RWKV_WKV_SCAN && form != RWKV_WKV_SCAN_DELTA)
+        throw RwkvError(RWKV_ERR_INVALID, "wkv form must be RWKV_WKV_RECURRENT, RWKV_WKV_SCAN or RWKV_WKV_SCAN_DELTA");
     if (form == wkv_form) return;
     HIP_CHECK(hipSetDevice(device));
     if (form == RWKV_WKV_SCAN) {
@@ -2491,6 +2503,16 @@ void rwkv_engine::set_wkv_form(int form) {
             scan_ws.rt = dalloc<float>(TC);
             scan_ws.oi = dalloc<float>(TC);
             scan_ws.chunks = dalloc<float>((size_t)wkv_scan_chunks(chunk, max_batch) * info.num_head * WKV_SCAN_REC);
+        }
+    }
+    if (form == RWKV_WKV_SCAN_DELTA) {
+        if (info.version != 7) throw RwkvError(RWKV_ERR_UNSUPPORTED, "the WKV delta-rule scan form serves V7 models");
+        if (!scan7_ws.chunks) {
+            const size_t TC = (size_t)chunk * info.num_emb;
+            scan7_ws.rt = dalloc<float>(TC);
+            scan7_ws.oi = dalloc<float>(TC);
+            scan7_ws.bonus = dalloc<float>((size_t)chunk * info.num_head);
+            scan7_ws.chunks = dalloc<float>((size_t)wkv_scan_chunks(chunk, max_batch) * info.num_head * WKV7_SCAN_REC);
         }
     }
     HIP_CHECK(hipStreamSynchronize(s_main));

@@ -260,6 +260,19 @@ inline long wkv_scan_chunks(int T, int n_seq) { return (T + WKV_SCAN_CHUNK - 1) 
 bool wkv_scan_supported(const WkvArgs &a);                          // version 5 (with ldec); version 6 with Dd 64 or 128
 void launch_wkv_scan(const WkvArgs &a, const WkvScanWs &ws, hipStream_t s);   // serves every sequence of the step, one-row ones included
 
+// The chunked matrix form of the V7 recurrence (a diagonal plus a rank-1 factor per token): a triangular solve inside the 64-token chunk and two
+// 64 x 64 x 64 products per chunk in the carry (rwkv_kernels.hip, part 7).  Another summation order than launch_wkv and than launch_wkv_scan.
+// Floats per (chunk, head), all row-major 64 x 64: W [t][j]; U_loc, after the carry SA [t][p]; B~ [t][j]; dS_v, after the carry the chunk's entry
+// state [p][j]; N_rb [t][s] (s <= t written); then D = e^(sum of log decays) [j].
+constexpr int WKV7_REC_W = 0, WKV7_REC_U = 4096, WKV7_REC_B = 8192, WKV7_REC_DS = 12288, WKV7_REC_N = 16384, WKV7_REC_D = 20480;
+constexpr int WKV7_SCAN_REC = 5 * 4096 + 64;
+struct Wkv7ScanWs {
+    float *chunks;                  // [wkv_scan_chunks(T, n_seq)][H][WKV7_SCAN_REC]
+    float *rt, *oi;                 // [T][C] each: r * e^(inclusive prefix log decay) rows; N_rk V rows
+    float *bonus;                   // [T][H]: sum_j r k r_k with the transformed k
+};
+void launch_wkv7_scan(const WkvArgs &a, const Wkv7ScanWs &ws, hipStream_t s);   // version 7 only; serves every sequence of the step
+
 // RWKV-4: the per-channel WKV recurrence with a running maximum (aa, bb, pp); no heads, no gate, no group norm.  One thread per channel.
 struct Wkv4Args {
     int C;

@@ -19,7 +19,7 @@
 #include <algorithm>
 
 
-// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..4, in parallel: one pass takes
+// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..7, in parallel: one pass takes
 // ~3 minutes, the parts ~1); without RWKV_PART everything is one translation unit (trace builds of scripts/build_variant.py,
 // whose `__device__` probe buffers cannot span translation units).
 #ifdef RWKV_PART
@@ -4530,7 +4530,7 @@ void launch_lora_blend(_Float16 *W, const _Float16 *B, const _Float16 *A, int ro
 
 #endif  // part 4: state pack, softmax / arg-max / samplers, load-time kernels
 
-#if RWKV_PART_ON(6)
+#if RWKV_PART_ON(6) || RWKV_PART_ON(7)      // the fragment helpers below also serve part 7 (the V7 form)
 // =====================================================================================
 // WKV in chunk-scan (matrix) form for V5 / V6 multi-row steps (opt-in: rwkv_engine_set_wkv_form).  wkv_chunk_kernel walks a sequence token by
 // token in one block per (sequence, head); here the step's rows are cut into 64-token chunks, every chunk is a block, and the recurrence
@@ -4605,6 +4605,8 @@ __device__ __forceinline__ bool scan_locate(const WkvArgs &a, int b, int &seq, i
     }
     return false;
 }
+#endif
+#if RWKV_PART_ON(6)
 
 template <int VER, int DD>
 __global__ __launch_bounds__(256) void wkv_scan_local_kernel(const WkvArgs a, const WkvScanWs ws) {
@@ -4884,4 +4886,490 @@ void launch_wkv_scan(const WkvArgs &a, const WkvScanWs &ws, hipStream_t s) {
     hipLaunchKernelGGL(wkv_scan_out_kernel, chunks, dim3(256), 0, s, a, ws);
 }
 #endif  // part 6: WKV chunk-scan form
+
+#if RWKV_PART_ON(7)
+// =====================================================================================
+// WKV of V7 in chunked matrix form for multi-row steps (opt-in: rwkv_engine_set_wkv_form, RWKV_WKV_SCAN_DELTA).  Per token the walk does
+//   sa = S a_t;  S <- S diag(w_t) + sa b_t^T + v_t k_t^T;  o_t = S r_t      (a = -kappa, b = kappa * a7, k and v transformed as in wkv_chunk_kernel)
+// the state is multiplied by a diagonal plus a rank-1 matrix, so a chunk is not a sum of decayed outer products: the sa rows of a chunk obey a unit
+// lower triangular system.  With l_t = log w_t, [x, y) = sum of l_j over x <= j < y, and a 64-token chunk entered with S0:
+//   M_ab[t][s] = sum_j a_tj b_sj e^[s+1,t)  (s < t),  M_ak likewise with k;   N_rb[t][s] = sum_j r_tj b_sj e^[s+1,t+1)  (s <= t),  N_rk likewise
+//   (I - M_ab) [W | U_loc] = [a_t e^[0,t) | M_ak V];   SA = U_loc + W S0^T;   O = (r_t e^[0,t+1)) S0^T + N_rb SA + N_rk V
+//   S_out = S0 diag(e^[0,64)) + SA^T B~ + V^T K~,   B~_s = b_s e^[s+1,64),  K~_s = k_s e^[s+1,64)
+// w is in [0.545, 1], so no exponent is below -38.9 and nothing underflows; the rule of the V5 / V6 form is kept all the same: exponents are
+// running sums from the nearer end, a pair of 16-token sub-blocks I > J is split at sub-block boundaries into factors <= 1 (a or r to the start
+// of I, b or k to the end of J, the sub-blocks between them as a third factor on the a / r side), the diagonal sub-blocks are evaluated directly.
+//   A  wkv7_scan_local_kernel  (chunk, head): all of the above that does not need S0, the solve by block forward substitution.
+//   B  wkv7_scan_carry_kernel  (sequence, head): SA_c = U_loc + W S_c^T and S_{c+1} = S_c D + SA_c^T B~ + dS_v, two 64^3 products per chunk, S in fp32
+//        registers; SA_c replaces U_loc and S_c replaces dS_v in the record.
+//   C  wkv7_scan_out_kernel    (chunk, head): O, then phase C of the walk with the bonus.
+// Every array is row-major [token][channel] in LDS and in the records.  A product that contracts over tokens takes its fragments down a column
+// (scan_frag_col: 8 LDS reads a row apart, two lanes per bank at the 68-float stride) instead of keeping transposed copies: launch A holds nine
+// 64 x 68 arrays as it is.
+// =====================================================================================
+// scan_frag's split, on 8 values that are in registers already
+__device__ __forceinline__ ScanFrag scan_split(const float (&x)[8]) {
+    float m = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(x[e]));
+    m = wave_max(m);
+    const int ex = min(max((int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xff), 27), 190);
+    const float scale = __builtin_bit_cast(float, (unsigned)(267 - ex) << 23);
+    ScanFrag f;
+    f.inv = __builtin_bit_cast(float, (unsigned)(ex - 13) << 23);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float y = x[e] * scale;
+        const _Float16 h = (_Float16)y;
+        f.hi[e] = h;
+        f.lo[e] = (_Float16)(y - (float)h);
+    }
+    return f;
+}
+// a fragment whose 8 k values lie one row apart: p[0], p[SCAN_LD], ...
+__device__ __forceinline__ ScanFrag scan_frag_col(const float *p) {
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = p[e * SCAN_LD];
+    return scan_split(x);
+}
+// 8 consecutive values times 8 consecutive factors (both 16-byte aligned)
+__device__ __forceinline__ ScanFrag scan_frag_mul(const float *p, const float *f) {
+    const float4 x0 = *(const float4 *)p, x1 = *(const float4 *)(p + 4), f0 = *(const float4 *)f, f1 = *(const float4 *)(f + 4);
+    const float x[8] = {x0.x * f0.x, x0.y * f0.y, x0.z * f0.z, x0.w * f0.w, x1.x * f1.x, x1.y * f1.y, x1.z * f1.z, x1.w * f1.w};
+    return scan_split(x);
+}
+
+__global__ __launch_bounds__(256) void wkv7_scan_local_kernel(const WkvArgs a, const Wkv7ScanWs ws) {
+    constexpr int LD = SCAN_LD;
+    // r, k, a, b, l rows [t][j] and v [t][p]: raw for the diagonal sub-blocks, then r, k, a, b decayed in place; three score matrices [t][s] (N_rb goes
+    // straight to the record).  X = [W | U_loc] takes the place of l and r once they are dead.
+    __shared__ __attribute__((aligned(16))) float s_r[64][LD], s_k[64][LD], s_a[64][LD], s_b[64][LD], s_l[64][LD], s_v[64][LD];
+    __shared__ __attribute__((aligned(16))) float s_mab[64][LD], s_mak[64][LD], s_nrk[64][LD];
+    // per sub-block I and channel: sum of l; e^[0,16 I); e^[16 (I + 1),64); and e^ of the sub-blocks between J and I for (J, I) = (0,2), (0,3), (1,3)
+    __shared__ __attribute__((aligned(16))) float s_bt[4][64], s_eh[4][64], s_et[4][64], s_eb[3][64];
+    float (*s_xw)[LD] = s_l, (*s_xu)[LD] = s_r;
+    int seq, c;
+    if (!scan_locate(a, blockIdx.x, seq, c)) return;
+    const int h = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row0 = a.seq_begin[seq] + c * 64, n = min(64, a.seq_len[seq] - c * 64);
+    const int C = a.C, cb = h * 64;
+    const int tr = (lane >> 4) * 4, tc = lane & 15, k8 = (lane >> 4) * 8;           // MFMA tile: 4 rows from tr, column tc; a fragment's 8 k from k8
+    float *rec = ws.chunks + ((long)blockIdx.x * a.H + h) * WKV7_SCAN_REC;
+
+    // ---- the chunk's rows with the walk's per-token transforms: wave w takes tokens w, w + 4, ..., lane = channel, 8 tokens' loads and norms at a time.
+    //      Rows n.. are zeros with l = 0: they add nothing to any product and leave D alone.
+    for (int i = tid; i < 64 * LD; i += 256) { (&s_mab[0][0])[i] = 0.f; (&s_mak[0][0])[i] = 0.f; (&s_nrk[0][0])[i] = 0.f; }
+    {
+        const float kk_p = a.k_k[cb + lane], ka_p = a.k_a[cb + lane], rk_p = a.r_k[cb + lane];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            float q0[8], q1[8], q2[8], q3[8], q4[8], q5[8], q6[8], kk[8], ss[8], bs[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const long rb = (long)(row0 + min(wave + 4 * (8 * half + i), n - 1)) * C + cb + lane;
+                q0[i] = a.r[rb]; q1[i] = a.k[rb]; q2[i] = a.v[rb]; q3[i] = a.a7[rb]; q4[i] = a.w7[rb];
+                if (a.layer != 0) { q5[i] = a.v_first[rb]; q6[i] = a.vg7[rb]; }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { kk[i] = q1[i] * kk_p; ss[i] = kk[i] * kk[i]; }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ss[i] = wave_sum(ss[i]);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                q1[i] = q1[i] * (1.0f + (q3[i] - 1.0f) * ka_p);
+                bs[i] = wave_sum(q0[i] * q1[i] * rk_p);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int tt = wave + 4 * (8 * half + i);
+                const bool on = tt < n;
+                const float kn = kk[i] / fmaxf(sqrtf(ss[i]), 1e-12f);
+                float v = q2[i];
+                if (a.layer == 0) { if (on) a.v_first[(long)(row0 + tt) * C + cb + lane] = v; }
+                else v = v + (q5[i] - v) * q6[i];
+                s_r[tt][lane] = on ? q0[i] : 0.f;
+                s_k[tt][lane] = on ? q1[i] : 0.f;
+                s_v[tt][lane] = on ? v : 0.f;
+                s_l[tt][lane] = on ? logf(q4[i]) : 0.f;
+                s_a[tt][lane] = on ? -kn : 0.f;
+                s_b[tt][lane] = on ? kn * q3[i] : 0.f;
+                if (on && lane == 0) ws.bonus[(long)(row0 + tt) * a.H + h] = bs[i];
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- the diagonal sub-blocks directly, from the raw rows: thread = (t, a quarter of the channels); s walks down from t with the exponent [s+1,t) as
+    //      a running sum per channel; the four lanes of a t add up and each stores one of the four matrices.  N has s == t, M does not.
+    {
+        const int t = tid >> 2, g = tid & 3, s0 = t & ~15, j0 = 16 * g;
+        float av[16], rv[16], wv[16], e[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) { av[jj] = s_a[t][j0 + jj]; rv[jj] = s_r[t][j0 + jj]; wv[jj] = expf(s_l[t][j0 + jj]); e[jj] = 0.f; }
+        for (int d = 0; d <= t - s0; ++d) {
+            const int s = t - d;
+            float mb = 0.f, mk = 0.f, nb = 0.f, nk = 0.f;
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) {
+                const float bv = s_b[s][j0 + jj], kv = s_k[s][j0 + jj];
+                if (d == 0) { nb = fmaf(rv[jj], bv, nb); nk = fmaf(rv[jj], kv, nk); }
+                else {
+                    const float em = expf(e[jj]), am = av[jj] * em, rn = rv[jj] * (em * wv[jj]);
+                    mb = fmaf(am, bv, mb); mk = fmaf(am, kv, mk); nb = fmaf(rn, bv, nb); nk = fmaf(rn, kv, nk);
+                    e[jj] += s_l[s][j0 + jj];
+                }
+            }
+            mb = quad_sum(mb); mk = quad_sum(mk); nb = quad_sum(nb); nk = quad_sum(nk);
+            if (g == 0) s_mab[t][s] = mb;
+            else if (g == 1) s_mak[t][s] = mk;
+            else if (g == 2) s_nrk[t][s] = nk;
+            else rec[WKV7_REC_N + t * 64 + s] = nb;
+        }
+    }
+    __syncthreads();
+
+    // ---- running sums of l and the decayed rows, in place: thread = (sub-block I = wave, channel q = lane), 16 tokens each way
+    {
+        const int I = wave, q = lane;
+        float bt = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) bt += s_l[16 * I + j][q];
+        s_bt[I][q] = bt;
+        __syncthreads();
+        const float b0 = s_bt[0][q], b1 = s_bt[1][q], b2 = s_bt[2][q], b3 = s_bt[3][q];
+        const float head = I == 0 ? 0.f : I == 1 ? b0 : I == 2 ? b0 + b1 : b0 + b1 + b2;      // [0, 16 I)
+        const float tail = I == 3 ? 0.f : I == 2 ? b3 : I == 1 ? b2 + b3 : b1 + b2 + b3;      // [16 (I + 1), 64)
+        s_eh[I][q] = expf(head);
+        s_et[I][q] = expf(tail);
+        if (I == 0) { s_eb[0][q] = expf(b1); s_eb[1][q] = expf(b1 + b2); s_eb[2][q] = expf(b2); }
+        if (I == 3) rec[WKV7_REC_D + q] = expf(head + bt);
+        float ls = 0.f;                                                                     // [s + 1, 16 (I + 1))
+        for (int j = 15; j >= 0; --j) {
+            const int s = 16 * I + j;
+            const float bb = s_b[s][q], ex = expf(ls);
+            s_k[s][q] *= ex;
+            s_b[s][q] = bb * ex;
+            rec[WKV7_REC_B + s * 64 + q] = bb * expf(ls + tail);
+            ls += s_l[s][q];
+        }
+        float lp = 0.f;                                                                     // [16 I, t), then [16 I, t]
+        for (int j = 0; j < 16; ++j) {
+            const int t = 16 * I + j;
+            const float rr = s_r[t][q];
+            s_a[t][q] *= expf(lp);
+            lp += s_l[t][q];
+            s_r[t][q] = rr * expf(lp);
+            if (t < n) ws.rt[(long)(row0 + t) * C + cb + q] = rr * expf(head + lp);
+        }
+    }
+    __syncthreads();                                           // l is read: its rows become the W half of X, zero until a sub-block is solved
+    for (int i = tid; i < 64 * LD; i += 256) (&s_xw[0][0])[i] = 0.f;
+
+    // ---- the six sub-block pairs I > J on the matrix pipe, four products each from two A-side fragments: (a, r rows of I) x (b, k rows of J)
+    for (int pi = wave; pi < 6; pi += 4) {
+        const int J = pi < 3 ? 0 : pi < 5 ? 1 : 2, I = pi < 3 ? pi + 1 : pi < 5 ? pi - 1 : 3;
+        f32x4 mab = (f32x4){0.f, 0.f, 0.f, 0.f}, mak = mab, nrb = mab, nrk = mab;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int ko = ks * 32 + k8;
+            ScanFrag fa, fr;
+            if (I - J == 1) { fa = scan_frag(&s_a[16 * I + tc][ko]); fr = scan_frag(&s_r[16 * I + tc][ko]); }
+            else {
+                const float *eb = &s_eb[J == 0 ? I - 2 : 2][ko];
+                fa = scan_frag_mul(&s_a[16 * I + tc][ko], eb); fr = scan_frag_mul(&s_r[16 * I + tc][ko], eb);
+            }
+            const ScanFrag fb = scan_frag(&s_b[16 * J + tc][ko]), fk = scan_frag(&s_k[16 * J + tc][ko]);
+            scan_mma(mab, fa, fb); scan_mma(mak, fa, fk); scan_mma(nrb, fr, fb); scan_mma(nrk, fr, fk);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = 16 * I + tr + i, s = 16 * J + tc;
+            s_mab[t][s] = mab[i]; s_mak[t][s] = mak[i]; s_nrk[t][s] = nrk[i];
+            rec[WKV7_REC_N + t * 64 + s] = nrb[i];
+        }
+    }
+    __syncthreads();                                           // the decayed r rows are read: they become the U half of X
+    for (int i = tid; i < 64 * LD; i += 256) (&s_xu[0][0])[i] = 0.f;
+    __syncthreads();
+
+    // ---- (I - M_ab) X = [a e^[0,t) | M_ak V] by block forward substitution.  Wave w owns columns 16w .. 16w+15 of W and of U_loc.  Per sub-block I:
+    //      X_I = RHS_I + M_ab[I][..] X on the matrix pipe (the rows of X from 16 I on are still zero, so the diagonal block of M_ab adds nothing),
+    //      then the unit triangular 16 x 16 block on the VALU: a thread per column, 16 dependent steps, M_ab entries as LDS broadcasts.
+    for (int I = 0; I < 4; ++I) {
+        f32x4 xw, xu = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xw[i] = s_a[16 * I + tr + i][16 * wave + tc] * s_eh[I][16 * wave + tc];
+        for (int ks = 0; ks < (I + 1) >> 1; ++ks) {             // s < 16 I
+            const ScanFrag fm = scan_frag(&s_mab[16 * I + tc][ks * 32 + k8]);
+            scan_mma(xw, fm, scan_frag_col(&s_xw[ks * 32 + k8][16 * wave + tc]));
+            scan_mma(xu, fm, scan_frag_col(&s_xu[ks * 32 + k8][16 * wave + tc]));
+        }
+        for (int ks = 0; ks < (I >> 1) + 1; ++ks)               // s < 16 (I + 1): M_ak is zero from the diagonal on
+            scan_mma(xu, scan_frag(&s_mak[16 * I + tc][ks * 32 + k8]), scan_frag_col(&s_v[ks * 32 + k8][16 * wave + tc]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { s_xw[16 * I + tr + i][16 * wave + tc] = xw[i]; s_xu[16 * I + tr + i][16 * wave + tc] = xu[i]; }
+        __syncthreads();
+        if (lane < 32) {
+            float (*X)[LD] = lane < 16 ? s_xw : s_xu;
+            const int col = 16 * wave + tc;
+            float x[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float acc = X[16 * I + i][col];
+#pragma unroll
+                for (int j = 0; j < i; ++j) acc = fmaf(s_mab[16 * I + i][16 * I + j], x[j], acc);
+                x[i] = acc;
+                X[16 * I + i][col] = acc;
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- the record's W and U_loc; O_loc = N_rk V (wave w owns rows t = 16w ..; s beyond 16w + 15 is zero); dS_v = V^T K~ (wave w owns rows p = 16w ..)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, t = idx >> 4, c4 = (idx & 15) * 4;
+        *(float4 *)(rec + WKV7_REC_W + t * 64 + c4) = *(const float4 *)(&s_xw[t][c4]);
+        *(float4 *)(rec + WKV7_REC_U + t * 64 + c4) = *(const float4 *)(&s_xu[t][c4]);
+    }
+    {
+        const int nks = (wave >> 1) + 1;
+        ScanFrag an[2], av[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            if (ks < nks) an[ks] = scan_frag(&s_nrk[16 * wave + tc][ks * 32 + k8]);
+            av[ks] = scan_frag_col(&s_v[ks * 32 + k8][16 * wave + tc]);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f}, ds = o;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int s8 = ks * 32 + k8, j = 16 * nt + tc;
+                const float et = s_et[s8 >> 4][j];                                         // a lane's 8 tokens lie in one sub-block
+                float kx[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) kx[e] = s_k[s8 + e][j] * et;
+                scan_mma(ds, av[ks], scan_split(kx));
+                if (ks < nks) scan_mma(o, an[ks], scan_frag_col(&s_v[s8][j]));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = 16 * wave + tr + i;
+                rec[WKV7_REC_DS + t * 64 + 16 * nt + tc] = ds[i];
+                if (t < n) ws.oi[(long)(row0 + t) * C + cb + 16 * nt + tc] = o[i];
+            }
+        }
+    }
+}
+
+// The only serial part: per chunk SA = U_loc + W S^T, then S <- S D + SA^T B~ + dS_v.  Wave w owns rows 16w .. of both results; S stays in the MFMA tile
+// layout (S[nt][i] = S[p = 16w + tr + i][j = 16 nt + tc]) in fp32 registers and goes to LDS as the operand of the first product.  The next chunk's
+// operands are requested into registers before the current chunk multiplies.  SA is stored over U_loc and the entry state over dS_v: a thread
+// overwrites only what it has itself read.
+__global__ __launch_bounds__(256) void wkv7_scan_carry_kernel(const WkvArgs a, const Wkv7ScanWs ws) {
+    constexpr int LD = SCAN_LD;
+    __shared__ __attribute__((aligned(16))) float s_s[64][LD], s_w[64][LD], s_sa[64][LD], s_bt[64][LD];
+    const int seq = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tr = 16 * wave + (lane >> 4) * 4, tc = lane & 15, k8 = (lane >> 4) * 8;
+    int g = 0;
+    for (int i = 0; i < seq; ++i) g += (a.seq_len[i] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+    const int nc = (a.seq_len[seq] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+    float *st = a.state + (long)a.seq_slot[seq] * a.slot_stride + (long)h * 4096;
+    f32x4 S[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) S[nt][i] = __builtin_nontemporal_load(st + (tr + i) * 64 + 16 * nt + tc);
+    f32x4 wq[4], bq[4];
+    const int fo0 = (tid >> 4) * 64 + (tid & 15) * 4;               // W and B~ go to LDS as they lie: thread = (row, 4 columns), 16 rows apart
+    if (nc > 0) {
+        const float *rec = ws.chunks + ((long)g * a.H + h) * WKV7_SCAN_REC;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { wq[i] = *(const f32x4 *)(rec + WKV7_REC_W + fo0 + 1024 * i); bq[i] = *(const f32x4 *)(rec + WKV7_REC_B + fo0 + 1024 * i); }
+    }
+    for (int c = 0; c < nc; ++c) {
+        float *rec = ws.chunks + ((long)(g + c) * a.H + h) * WKV7_SCAN_REC;
+        f32x4 u[4], ds[4];
+        float D[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + 256 * i, t = idx >> 4, c4 = (idx & 15) * 4;
+            *(f32x4 *)(&s_w[t][c4]) = wq[i];
+            *(f32x4 *)(&s_bt[t][c4]) = bq[i];
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {                          // this chunk's U_loc, dS_v and D: asked for here, used behind the products
+            D[nt] = rec[WKV7_REC_D + 16 * nt + tc];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                u[nt][i] = rec[WKV7_REC_U + (tr + i) * 64 + 16 * nt + tc];
+                ds[nt][i] = rec[WKV7_REC_DS + (tr + i) * 64 + 16 * nt + tc];
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                s_s[tr + i][16 * nt + tc] = S[nt][i];
+                rec[WKV7_REC_DS + (tr + i) * 64 + 16 * nt + tc] = S[nt][i];              // the state this chunk starts from, for wkv7_scan_out_kernel
+            }
+        if (c + 1 < nc) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                wq[i] = *(const f32x4 *)(rec + WKV7_SCAN_REC * (long)a.H + WKV7_REC_W + fo0 + 1024 * i);
+                bq[i] = *(const f32x4 *)(rec + WKV7_SCAN_REC * (long)a.H + WKV7_REC_B + fo0 + 1024 * i);
+            }
+        }
+        __syncthreads();
+        {
+            ScanFrag aw[2];
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) aw[ks] = scan_frag(&s_w[16 * wave + tc][ks * 32 + k8]);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                f32x4 tot = u[nt];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) scan_mma(tot, aw[ks], scan_frag(&s_s[16 * nt + tc][ks * 32 + k8]));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    s_sa[tr + i][16 * nt + tc] = tot[i];
+                    rec[WKV7_REC_U + (tr + i) * 64 + 16 * nt + tc] = tot[i];
+                }
+            }
+        }
+        __syncthreads();
+        {
+            ScanFrag as[2];
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) as[ks] = scan_frag_col(&s_sa[ks * 32 + k8][16 * wave + tc]);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                f32x4 tot = ds[nt];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) scan_mma(tot, as[ks], scan_frag_col(&s_bt[ks * 32 + k8][16 * nt + tc]));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) S[nt][i] = fmaf(S[nt][i], D[nt], tot[i]);
+            }
+        }
+        __syncthreads();                                       // the next chunk overwrites the operand rows
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) __builtin_nontemporal_store(S[nt][i], st + (tr + i) * 64 + 16 * nt + tc);
+}
+
+__global__ __launch_bounds__(256) void wkv7_scan_out_kernel(const WkvArgs a, const Wkv7ScanWs ws) {
+    constexpr int LD = SCAN_LD;
+    // r e^[0,t+1) rows [t][j] (later: the outputs [t][p], each wave over its own 16 rows), the entry state [p][j], N_rb [t][s], SA [s][p]
+    __shared__ __attribute__((aligned(16))) float s_rt[64][LD], s_s[64][LD], s_n[64][LD], s_sa[64][LD];
+    float (*s_o)[LD] = s_rt;
+    int seq, c;
+    if (!scan_locate(a, blockIdx.x, seq, c)) return;
+    const int h = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row0 = a.seq_begin[seq] + c * 64, n = min(64, a.seq_len[seq] - c * 64);
+    const int C = a.C, cb = h * 64;
+    const int tr = (lane >> 4) * 4, tc = lane & 15, k8 = (lane >> 4) * 8;
+    const float *rec = ws.chunks + ((long)blockIdx.x * a.H + h) * WKV7_SCAN_REC;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, t = idx >> 4, c4 = (idx & 15) * 4;
+        *(float4 *)(&s_rt[t][c4]) = t < n ? *(const float4 *)(ws.rt + (long)(row0 + t) * C + cb + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *(float4 *)(&s_s[t][c4]) = *(const float4 *)(rec + WKV7_REC_DS + t * 64 + c4);
+        *(float4 *)(&s_sa[t][c4]) = *(const float4 *)(rec + WKV7_REC_U + t * 64 + c4);
+        float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);           // launch A wrote s <= t only
+        if (c4 <= t) {
+            nv = *(const float4 *)(rec + WKV7_REC_N + t * 64 + c4);
+            if (c4 + 1 > t) nv.y = 0.f;
+            if (c4 + 2 > t) nv.z = 0.f;
+            if (c4 + 3 > t) nv.w = 0.f;
+        }
+        *(float4 *)(&s_n[t][c4]) = nv;
+    }
+    __syncthreads();
+    // ---- o[t][p] = O_loc[t][p] + sum_j rt[t][j] S[p][j] + sum_{s<=t} N_rb[t][s] SA[s][p]: wave w owns rows t = 16w ..
+    {
+        const int nks = (wave >> 1) + 1;
+        ScanFrag ar[2], an[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            ar[ks] = scan_frag(&s_rt[16 * wave + tc][ks * 32 + k8]);
+            if (ks < nks) an[ks] = scan_frag(&s_n[16 * wave + tc][ks * 32 + k8]);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            f32x4 tot = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                scan_mma(tot, ar[ks], scan_frag(&s_s[16 * nt + tc][ks * 32 + k8]));
+                if (ks < nks) scan_mma(tot, an[ks], scan_frag_col(&s_sa[ks * 32 + k8][16 * nt + tc]));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = 16 * wave + tr + i, p = 16 * nt + tc;
+                s_o[t][p] = tot[i] + (t < n ? ws.oi[(long)(row0 + t) * C + cb + p] : 0.f);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- wkv_chunk_kernel's phase C on 64 tokens: GroupNorm over the head (eps 64e-5), bonus, gate, operand emit; thread = (token, 8 channels), two passes
+    auto sum8 = [](float v) {
+        v = quad_sum(v);
+        return v + __shfl_xor(v, 4, 64);
+    };
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int tt = (tid >> 3) + 32 * pass, c8 = (tid & 7) * 8;
+        if (tt < n) {                                             // the 8 lanes of a token take the branch together
+            const int t = row0 + tt;
+            const long rb = (long)t * C + cb + c8;
+            const float4 g0 = *(const float4 *)(a.g + rb), g1 = *(const float4 *)(a.g + rb + 4);
+            const float4 v0 = *(const float4 *)(a.v + rb), v1 = *(const float4 *)(a.v + rb + 4);
+            const float4 o0 = *(const float4 *)(&s_o[tt][c8]), o1 = *(const float4 *)(&s_o[tt][c8 + 4]);
+            float o[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+            float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            if (a.layer != 0) {                                   // the transformed v, as launch A formed it
+                const float4 f0 = *(const float4 *)(a.v_first + rb), f1 = *(const float4 *)(a.v_first + rb + 4);
+                const float4 m0 = *(const float4 *)(a.vg7 + rb), m1 = *(const float4 *)(a.vg7 + rb + 4);
+                const float vf[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w}, vm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vv[e] = vv[e] + (vf[e] - vv[e]) * vm[e];
+            }
+            const float bonus = ws.bonus[(long)t * a.H + h];
+            float sm = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm += o[e];
+            const float mean = sum8(sm) * (1.0f / 64.0f);
+            float sq = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { o[e] -= mean; sq += o[e] * o[e]; }
+            const float rstd = 1.0f / sqrtf(sum8(sq) * (1.0f / 64.0f) + 64e-5f);
+            f16x8 hh, ll;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float y = (o[e] * rstd * a.lnx_w[cb + c8 + e] + a.lnx_b[cb + c8 + e] + bonus * vv[e]) * gg[e];
+                _Float16 hv, lv;
+                split_hilo(y, hv, lv);
+                hh[e] = hv; ll[e] = lv;
+            }
+            const long yo = opd_off(t, cb + c8, a.ldh);           // 8 consecutive k of one token: one 16-byte piece
+            *(f16x8 *)(a.yhi + yo) = hh;
+            if (a.ylo) *(f16x8 *)(a.ylo + yo) = ll;
+        }
+    }
+}
+
+void launch_wkv7_scan(const WkvArgs &a, const Wkv7ScanWs &ws, hipStream_t s) {
+    const dim3 chunks((unsigned)wkv_scan_chunks(a.T, a.n_seq), a.H);
+    hipLaunchKernelGGL(wkv7_scan_local_kernel, chunks, dim3(256), 0, s, a, ws);
+    hipLaunchKernelGGL(wkv7_scan_carry_kernel, dim3(a.n_seq, a.H), dim3(256), 0, s, a, ws);
+    hipLaunchKernelGGL(wkv7_scan_out_kernel, chunks, dim3(256), 0, s, a, ws);
+}
+#endif  // part 7: WKV chunked matrix form of V7
 }  // namespace rwkv
