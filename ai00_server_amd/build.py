@@ -47,11 +47,11 @@ def needs_build() -> bool:
     return open(STAMP).read().strip() != _sources_digest()
 
 
-KERNEL_PARTS = 8      # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
-# parts 6 and 7 (the WKV chunk-scan forms of V5 / V6 and of V7) are compiled without packed fp32 instructions; the older parts keep the flags they
+KERNEL_PARTS = 9      # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
+# parts 6 to 8 (the WKV scan forms of V5 / V6, of V7 and of V4) are compiled without packed fp32 instructions; the older parts keep the flags they
 # were measured with
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-PART_FLAGS = {6: NO_PACKED_FP32, 7: NO_PACKED_FP32}
+PART_FLAGS = {6: NO_PACKED_FP32, 7: NO_PACKED_FP32, 8: NO_PACKED_FP32}
 
 
 def build(force: bool = False, verbose: bool = True) -> str:

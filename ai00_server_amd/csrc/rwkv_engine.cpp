@@ -623,6 +623,7 @@ struct rwkv_engine {
     int wkv_form = RWKV_WKV_RECURRENT;                    // rwkv_engine_set_wkv_form: RWKV_WKV_SCAN sends multi-row steps through launch_wkv_scan
     WkvScanWs scan_ws{};                                  // its workspace, shared by every layer; allocated when the form is first switched on
     Wkv7ScanWs scan7_ws{};                                // RWKV_WKV_SCAN_DELTA's workspace (V7), likewise
+    Wkv4ScanWs scan4_ws{};                                // RWKV_WKV_SCAN_MAX's workspace (V4), likewise
     void set_wkv_form(int form);
     float *lnp_xx_att = nullptr;                          // normalised rows published by the V6 mix's LN-prologue launch (for the commit)
     void plan_step(const rwkv_slot_input *in, StepPlan &pl, int reserve = 0);   // reserve: rows of the chunk that are spoken for (gen_mixed_step)
@@ -1388,10 +1389,23 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
             k.state = wkv + (long)l * wkv_layer_floats(); k.slot_stride = wkv_slot_stride;
             k.r = fr; k.k = fk; k.v = fv; k.w = w.wdec; k.u = w.u;
             k.yhi = aY.hi; k.ylo = aY.lo; k.ldh = C;
-            launch(FAM_WKV, [&] { launch_wkv4(k, T > n_seq, s_main); });
-            // three state rows in and out per sequence, r / k / v of every row in, the Wo operand out
-            log_row(T > n_seq ? "wkv4_chunk_kernel" : "wkv4_kernel", T, T > n_seq ? (long)n_seq * (C / 64) : (long)n_seq * ((C + 255) / 256),
-                    (double)n_seq * C * 24.0 + 8.0 * C + (double)T * C * 12.0 + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            if (wkv_form == RWKV_WKV_SCAN_MAX && T > n_seq) {
+                Wkv4ScanWs ws = scan4_ws;
+                ws.T = T;
+                launch(FAM_WKV, [&] { launch_wkv4_scan(k, ws, s_main); });
+                // A: k / v of every row and w in, three floats per (segment, channel) out.  B: the state in and out, the summaries in, the entry states
+                // out.  C: the entry states, r / k / v of every row, u and w in, the Wo operand out.  Segments: at most 64 / SEG per chunk of the grid.
+                const long nchunk = wkv_scan_chunks(T, n_seq);
+                const double segs = (double)nchunk * (WKV_SCAN_CHUNK / WKV4_SCAN_SEG) * C * 12.0, rows = (double)T * C * 4.0;
+                log_row("wkv4_scan_local_kernel", T, nchunk * (C / 64), 2.0 * rows + 4.0 * C + segs);
+                log_row("wkv4_scan_carry_kernel", T, (long)n_seq * (C / 64), (double)n_seq * C * 24.0 + 4.0 * C + 2.0 * segs);
+                log_row("wkv4_scan_out_kernel", T, nchunk * (C / 64), segs + 3.0 * rows + 8.0 * C + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            } else {
+                launch(FAM_WKV, [&] { launch_wkv4(k, T > n_seq, s_main); });
+                // three state rows in and out per sequence, r / k / v of every row in, the Wo operand out
+                log_row(T > n_seq ? "wkv4_chunk_kernel" : "wkv4_kernel", T, T > n_seq ? (long)n_seq * (C / 64) : (long)n_seq * ((C + 255) / 256),
+                        (double)n_seq * C * 24.0 + 8.0 * C + (double)T * C * 12.0 + (double)T * C * 2.0 * (k.ylo ? 2 : 1));
+            }
         } else {
             WkvArgs k{};
             k.version = info.version; k.H = H; k.C = C; k.n_seq = n_seq;
@@ -2488,8 +2502,8 @@ uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e) { return e ? e->weight_b
 
 // The form is not part of a step graph's key: switching it drops every captured step that may hold a WKV launch of the other form.
 void rwkv_engine::set_wkv_form(int form) {
-    if (form != RWKV_WKV_RECURRENT && form != RWKV_WKV_SCAN && form != RWKV_WKV_SCAN_DELTA)
-        throw RwkvError(RWKV_ERR_INVALID, "wkv form must be RWKV_WKV_RECURRENT, RWKV_WKV_SCAN or RWKV_WKV_SCAN_DELTA");
+    if (form != RWKV_WKV_RECURRENT && form != RWKV_WKV_SCAN && form != RWKV_WKV_SCAN_DELTA && form != RWKV_WKV_SCAN_MAX)
+        throw RwkvError(RWKV_ERR_INVALID, "wkv form must be RWKV_WKV_RECURRENT, RWKV_WKV_SCAN, RWKV_WKV_SCAN_DELTA or RWKV_WKV_SCAN_MAX");
     if (form == wkv_form) return;
     HIP_CHECK(hipSetDevice(device));
     if (form == RWKV_WKV_SCAN) {
@@ -2513,6 +2527,14 @@ void rwkv_engine::set_wkv_form(int form) {
             scan7_ws.oi = dalloc<float>(TC);
             scan7_ws.bonus = dalloc<float>((size_t)chunk * info.num_head);
             scan7_ws.chunks = dalloc<float>((size_t)wkv_scan_chunks(chunk, max_batch) * info.num_head * WKV7_SCAN_REC);
+        }
+    }
+    if (form == RWKV_WKV_SCAN_MAX) {
+        if (info.version != 4) throw RwkvError(RWKV_ERR_UNSUPPORTED, "the WKV max-plus scan form serves V4 models");
+        if (!scan4_ws.sum) {
+            const size_t n = wkv4_scan_ws_floats(chunk, max_batch, info.num_emb);
+            scan4_ws.sum = dalloc<float>(n);
+            scan4_ws.ent = dalloc<float>(n);
         }
     }
     HIP_CHECK(hipStreamSynchronize(s_main));

@@ -290,6 +290,22 @@ struct Wkv4Args {
 };
 void launch_wkv4(const Wkv4Args &a, bool multi_row, hipStream_t s);   // multi_row: wkv4_chunk_kernel; else every sequence has one row: wkv4_kernel
 
+// The segmented-scan form of the V4 recurrence for multi-row steps: segments of WKV4_SCAN_SEG tokens are summarised independently, one thread per
+// (sequence, channel) carries the state across the summaries, and the segments are walked again from their entry states (rwkv_kernels.hip, part 8).
+// Another summation order than launch_wkv4: fp32-class agreement, not bit equality.  SEG was chosen by measurement.
+#ifndef WKV4_SCAN_SEG_OVERRIDE
+constexpr int WKV4_SCAN_SEG = 32;
+#else
+constexpr int WKV4_SCAN_SEG = WKV4_SCAN_SEG_OVERRIDE;              // 16 or 32: the A/B builds behind DESIGN 3.7.3
+#endif
+static_assert(WKV4_SCAN_SEG == 16 || WKV4_SCAN_SEG == 32, "a 64-token chunk is 4 or 2 segments");
+struct Wkv4ScanWs {
+    float *sum, *ent;               // [wkv_scan_chunks(T, n_seq)][64 / SEG][3][C] each: the segments' (A, B, P); the states (aa, bb, pp) entering them
+    int T;                          // rows of this step (with n_seq it bounds the number of 64-token chunks: the grid of launches A and C)
+};
+inline size_t wkv4_scan_ws_floats(int T, int n_seq, int C) { return (size_t)wkv_scan_chunks(T, n_seq) * (WKV_SCAN_CHUNK / WKV4_SCAN_SEG) * 3 * C; }   // per array
+void launch_wkv4_scan(const Wkv4Args &a, const Wkv4ScanWs &ws, hipStream_t s);   // serves every sequence of the step, one-row ones included; a.dense must be 0
+
 // ---- state slab <-> internal layout ---------------------------------------------------
 struct StatePackArgs {
     float *slab;                    // public [L][N+2][C]  (V4: [L][5][C])

@@ -7,7 +7,8 @@
 //   embed_kernel     K1             emb gather + ln0
 //   ln_out_kernel    K2             final LayerNorm on the rows whose logits are requested
 //   wkv_kernel       K8-K11,K13     WKV recurrence (+v6 decay LoRA stage 2, +v7 kappa/a/v-mix), GroupNorm, gate
-//   wkv4_kernel      (V4)           per-channel WKV-4 recurrence with a running maximum; wkv4_chunk_kernel walks a sequence's rows
+//   wkv4_kernel      (V4)           per-channel WKV-4 recurrence with a running maximum; wkv4_chunk_kernel walks a sequence's rows;
+//                                   wkv4_scan_*_kernel: the same rows as a segmented max-plus scan (opt-in)
 //   state_pack       K17            public slab [C,N+2,L,1] <-> internal state layout
 //   softmax / argmax K16            batched over the vocabulary
 //   tile/quant       K18,K19        load-time: raw fp16 -> tiled fp16 / int8 / nf4 ; LoRA blend
@@ -19,7 +20,7 @@
 #include <algorithm>
 
 
-// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..7, in parallel: one pass takes
+// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..8, in parallel: one pass takes
 // ~3 minutes, the parts ~1); without RWKV_PART everything is one translation unit (trace builds of scripts/build_variant.py,
 // whose `__device__` probe buffers cannot span translation units).
 #ifdef RWKV_PART
@@ -3028,6 +3029,8 @@ void launch_wkv(const WkvArgs &a, bool multi_row, hipStream_t s) {
     else hipLaunchKernelGGL(wkv_kernel, dim3(a.n_seq, a.H), dim3(256), 0, s, a);
 }
 
+#endif  // part 3: row kernels + WKV
+#if RWKV_PART_ON(3) || RWKV_PART_ON(8)      // wkv4_step / wkv4_emit also serve part 8 (the segmented-scan form of V4)
 // =====================================================================================
 // WKV-4 (RWKV-4): per channel, state (aa, bb, pp) = numerator, denominator and their common exponent (a running maximum, so that
 // neither sum overflows whatever k is).  With u = time_first, w = -exp(time_decay):
@@ -3064,6 +3067,8 @@ __device__ __forceinline__ void wkv4_emit(act_t byh, act_t byl, bool has_lo, int
         if (has_lo) __builtin_amdgcn_raw_buffer_store_b32(lb | (ln2 << 16), byl, (unsigned)(yo * 2), 0, ACT_SC1);
     }
 }
+#endif
+#if RWKV_PART_ON(3)
 // Decode form: every sequence of the step has ONE row.  One thread per (row, channel); aa / bb / pp are read and written once.
 __global__ __launch_bounds__(256) void wkv4_kernel(const Wkv4Args a) {
     const int c = blockIdx.x * 256 + threadIdx.x, seq = blockIdx.y, C = a.C;
@@ -3105,8 +3110,144 @@ void launch_wkv4(const Wkv4Args &a, bool multi_row, hipStream_t s) {
     if (multi_row) hipLaunchKernelGGL(wkv4_chunk_kernel, dim3(a.C / 64, a.n_seq), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(wkv4_kernel, dim3((a.C + 255) / 256, a.n_seq), dim3(256), 0, s, a);
 }
+#endif  // part 3: the WKV-4 walk
 
-#endif  // part 3: row kernels + WKV
+#if RWKV_PART_ON(8)
+// =====================================================================================
+// WKV-4 as a segmented scan over tokens for multi-row steps (opt-in: rwkv_engine_set_wkv_form, RWKV_WKV_SCAN_MAX).  wkv4_chunk_kernel gives a
+// whole sequence to one thread per channel: 2048 rows are 2048 dependent rounds of two exp pairs and a division on C / 64 waves.  The update of
+// (aa, bb, pp) is associative, so the rows are cut into segments that are walked independently.  Per channel, w = -exp(time_decay), u = time_first.
+//
+// A run of n consecutive tokens s = 0 .. n-1 is summarised by (A, B, P):
+//     P = max_s (k_s + (n-1-s) w)        A = sum_s e^(k_s + (n-1-s) w - P) v_s        B = the same sum with 1 for v_s
+// and the state (aa, bb, pp) is such a summary of everything before it.  Two adjacent runs, x on the left and y of n_y tokens on the right, combine to
+//     P = max(P_x + n_y w, P_y)          A = e^(P_x + n_y w - P) A_x + e^(P_y - P) A_y          B likewise
+// Every exponent is <= 0, as in wkv4_step.  P is the max-plus value the walk itself produces, pp = max(pp0 + t w, max_s (k_s + (t-1-s) w)), so the
+// scan leaves the state in the walk's own normalisation (the tests compare aa, bb and pp row by row).  A run starts from its first token (A = v_0,
+// B = 1, P = k_0): no sentinel.  An entry pp of -1e30 passes through the combine as through the walk: e^(pp + n w - P) is an exact 0.  n_y w is
+// (float)n * w, one rounding where the walk has n; expf and a true division for wkv4_step's reason.
+//
+// Three stream-ordered launches, no block waits for another.  A segment is SEG = WKV4_SCAN_SEG consecutive tokens of one sequence; lanes are
+// channels throughout (a wave = one segment x 64 consecutive channels), so every row load and every workspace access is one coalesced 256-byte
+// line as in the walk, and there is no cross-lane work except wkv4_emit's lane pairing.  No LDS.
+//   A  wkv4_scan_local_kernel   grid (chunks, C / 64), a block = one 64-token chunk x 64 channels, its 64 / SEG waves = the chunk's segments.  A wave
+//                               issues the k / v loads of ALL its rows (independent, where the walk has one row of lookahead), walks them from the
+//                               first-token summary and stores (A, B, P).  A ragged last segment covers the rows it has; waves past the last row leave.
+//   B  wkv4_scan_carry_kernel   grid (C / 64, n_seq), one thread per (sequence, channel): the slot's (aa, bb, pp), then per segment in order the state
+//                               ENTERING it is stored and combined with the segment's summary; the summaries of the next CARRY_AHEAD segments are in
+//                               flight.  One exp pair per SEG rows on the serial chain.  The final state goes to the slot; no rows, no write.
+//   C  wkv4_scan_out_kernel     grid and blocks of A.  A wave reads its segment's entry state and the r / k / v of all its rows up front, then runs
+//                               wkv4_step per row from that state and emits r * wkv (hi and lo) with wkv4_emit.  Whole waves are active: C % 64 == 0.
+// A block of A and C finds its (sequence, chunk) by walking seq_len like scan_locate; the grid bound wkv_scan_chunks(T, n_seq) needs no step
+// metadata of its own.  Workspace (Wkv4ScanWs), shared by all layers: per (segment, channel) three floats of summary and three of entry state,
+//     2 arrays x wkv_scan_chunks(token_chunk_size, max_batch) x (64 / SEG) x 3 x C floats,
+// indexed [chunk block][segment of the chunk][A, B, P][C]: the segments of a sequence are consecutive, which is all the carry needs.
+// =====================================================================================
+constexpr int WKV4_CARRY_AHEAD = 4;                    // 16 was measured slower: the ring then costs 110 VGPRs and the wait counter saturates
+__device__ __forceinline__ bool scan4_locate(const Wkv4Args &a, int b, int &seq, int &ch) {
+    for (int i = 0; i < a.n_seq; ++i) {
+        const int nc = (a.seq_len[i] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+        if (b < nc) { seq = i; ch = b; return true; }
+        b -= nc;
+    }
+    return false;
+}
+template <int SEG>
+__global__ __launch_bounds__(4096 / SEG) void wkv4_scan_local_kernel(const Wkv4Args a, const Wkv4ScanWs ws) {
+    int seq, ch;
+    if (!scan4_locate(a, blockIdx.x, seq, ch)) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), C = a.C, c = blockIdx.y * 64 + (threadIdx.x & 63);
+    const int t0 = ch * WKV_SCAN_CHUNK + wave * SEG, n = min(SEG, a.seq_len[seq] - t0);
+    if (n <= 0) return;
+    const act_t bk = act_buf(a.k), bv = act_buf(a.v);
+    const long rb = (long)(a.seq_begin[seq] + t0) * C + c;
+    float k[SEG], v[SEG];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i)
+        if (i < n) { k[i] = act_ld1(bk, rb + (long)i * C); v[i] = act_ld1(bv, rb + (long)i * C); }
+    const float w = a.w[c];
+    float A = v[0], B = 1.f, P = k[0];
+#pragma unroll
+    for (int i = 1; i < SEG; ++i)
+        if (i < n) {
+            const float ww = P + w, p = fmaxf(ww, k[i]);
+            const float e1 = expf(ww - p), e2 = expf(k[i] - p);
+            A = e1 * A + e2 * v[i];
+            B = e1 * B + e2;
+            P = p;
+        }
+    float *o = ws.sum + ((long)blockIdx.x * (WKV_SCAN_CHUNK / SEG) + wave) * 3 * C + c;
+    o[0] = A; o[C] = B; o[2 * C] = P;
+}
+template <int SEG>
+__global__ __launch_bounds__(64) void wkv4_scan_carry_kernel(const Wkv4Args a, const Wkv4ScanWs ws) {
+    constexpr int AH = WKV4_CARRY_AHEAD;
+    const int c = blockIdx.x * 64 + threadIdx.x, seq = blockIdx.y, C = a.C;
+    const int nrow = a.seq_len[seq], nseg = (nrow + SEG - 1) / SEG;
+    if (nseg == 0) return;
+    long g0 = 0;                                             // the sequence's first segment: its chunks follow those of the sequences before it
+    for (int i = 0; i < seq; ++i) g0 += (a.seq_len[i] + WKV_SCAN_CHUNK - 1) / WKV_SCAN_CHUNK;
+    g0 *= WKV_SCAN_CHUNK / SEG;
+    const float *sum = ws.sum + g0 * 3 * C + c;
+    float *ent = ws.ent + g0 * 3 * C + c;
+    float *st = a.state + (long)a.seq_slot[seq] * a.slot_stride + c;
+    const float w = a.w[c];
+    float aa = st[0], bb = st[C], pp = st[2 * C];
+    float A[AH], B[AH], P[AH];
+#pragma unroll
+    for (int i = 0; i < AH; ++i)
+        if (i < nseg) { const float *s = sum + (long)i * 3 * C; A[i] = s[0]; B[i] = s[C]; P[i] = s[2 * C]; }
+    for (int gb = 0; gb < nseg; gb += AH) {
+#pragma unroll
+        for (int i = 0; i < AH; ++i) {
+            const int g = gb + i;
+            if (g >= nseg) break;
+            const float sa = A[i], sb = B[i], sp = P[i];
+            if (g + AH < nseg) { const float *s = sum + (long)(g + AH) * 3 * C; A[i] = s[0]; B[i] = s[C]; P[i] = s[2 * C]; }
+            float *e = ent + (long)g * 3 * C;
+            e[0] = aa; e[C] = bb; e[2 * C] = pp;
+            const float ww = pp + (float)min(SEG, nrow - g * SEG) * w, p = fmaxf(ww, sp);
+            const float e1 = expf(ww - p), e2 = expf(sp - p);
+            aa = e1 * aa + e2 * sa;
+            bb = e1 * bb + e2 * sb;
+            pp = p;
+        }
+    }
+    st[0] = aa; st[C] = bb; st[2 * C] = pp;
+}
+template <int SEG>
+__global__ __launch_bounds__(4096 / SEG) void wkv4_scan_out_kernel(const Wkv4Args a, const Wkv4ScanWs ws) {
+    int seq, ch;
+    if (!scan4_locate(a, blockIdx.x, seq, ch)) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), C = a.C, c = blockIdx.y * 64 + (threadIdx.x & 63);
+    const int t0 = ch * WKV_SCAN_CHUNK + wave * SEG, n = min(SEG, a.seq_len[seq] - t0);
+    if (n <= 0) return;
+    const act_t br = act_buf(a.r), bk = act_buf(a.k), bv = act_buf(a.v), byh = act_buf(a.yhi), byl = act_buf(a.ylo);
+    const bool has_lo = a.ylo != nullptr;
+    const int row0 = a.seq_begin[seq] + t0;
+    const long rb = (long)row0 * C + c;
+    const float *e = ws.ent + ((long)blockIdx.x * (WKV_SCAN_CHUNK / SEG) + wave) * 3 * C + c;
+    float aa = e[0], bb = e[C], pp = e[2 * C];
+    float r[SEG], k[SEG], v[SEG];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i)
+        if (i < n) { r[i] = act_ld1(br, rb + (long)i * C); k[i] = act_ld1(bk, rb + (long)i * C); v[i] = act_ld1(bv, rb + (long)i * C); }
+    const float u = a.u[c], w = a.w[c];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i)
+        if (i < n) {
+            const float wkv = wkv4_step(aa, bb, pp, k[i], v[i], u, w);
+            wkv4_emit(byh, byl, has_lo, row0 + i, c, a.ldh, r[i] * wkv);
+        }
+}
+void launch_wkv4_scan(const Wkv4Args &a, const Wkv4ScanWs &ws, hipStream_t s) {
+    constexpr int SEG = WKV4_SCAN_SEG;
+    const dim3 chunks((unsigned)wkv_scan_chunks(ws.T, a.n_seq), a.C / 64), block(4096 / SEG);
+    hipLaunchKernelGGL(wkv4_scan_local_kernel<SEG>, chunks, block, 0, s, a, ws);
+    hipLaunchKernelGGL(wkv4_scan_carry_kernel<SEG>, dim3(a.C / 64, a.n_seq), dim3(64), 0, s, a, ws);
+    hipLaunchKernelGGL(wkv4_scan_out_kernel<SEG>, chunks, block, 0, s, a, ws);
+}
+#endif  // part 8: the segmented-scan form of WKV-4
 
 #if RWKV_PART_ON(4)
 // =====================================================================================

@@ -246,10 +246,11 @@ class Precision(enum.IntEnum):   # reload.rs:89-94 (+ the raw mode of ABI 7, inc
     Fp16Raw = 2                  # f16 operands everywhere: fastest, not tolerance-holding at depth
 
 
-class WkvForm(enum.IntEnum):     # rwkv_engine_set_wkv_form: the V5 / V6 / V7 WKV of multi-row (prefill) steps
+class WkvForm(enum.IntEnum):     # rwkv_engine_set_wkv_form: the WKV of multi-row (prefill) steps
     Recurrent = 0                # token by token, one block per (sequence, head): the default
     Scan = 1                     # V5 / V6: 64-token chunks as matrix products on the MFMA pipe; fp32-class agreement, not bit equality
     ScanDelta = 2                # V7: the same cut with a triangular solve per chunk and two matrix products per chunk in the carry
+    ScanMax = 3                  # V4: 32-token segments summarised independently (max-plus), a per-channel carry, then walked from their entry states
 
 
 class RnnOption(enum.IntEnum):   # run.rs:716, 819

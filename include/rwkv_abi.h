@@ -148,7 +148,7 @@ int32_t rwkv_engine_token_chunk_size(const rwkv_engine *e);     /* the load-time
 /* bytes of weights resident in HBM at their storage width (fp16 / int8+scales / nf4 or sf4+absmax),
  * embedding table excluded: the W_q of SURVEY 8(d).  For roofline accounting. */
 uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e);
-/* The form of the V5 / V6 / V7 WKV recurrence in steps where a sequence has several rows (prefill); one-row steps are not affected.
+/* The form of the WKV recurrence in steps where a sequence has several rows (prefill); one-row steps are not affected.
  *   RWKV_WKV_RECURRENT (the default): one block per (sequence, head) walks the sequence's rows token by token.
  *   RWKV_WKV_SCAN: the rows are cut into 64-token chunks, one block per (chunk, head) evaluates the recurrence inside a chunk as matrix
  *     products on the MFMA pipe, and a short elementwise pass carries the state from chunk to chunk: a single long prompt occupies
@@ -163,8 +163,14 @@ uint64_t rwkv_engine_weight_bytes(const rwkv_engine *e);
  *     The two SCAN values name two different summation orders, not one form with a parameter: RWKV_WKV_SCAN on a V7 engine and
  *     RWKV_WKV_SCAN_DELTA on a V4, V5 or V6 engine are RWKV_ERR_UNSUPPORTED, and the form in force stays.  A V7 engine loaded from a prefab image
  *     is served.  Workspace: (token_chunk_size / 64 + max_batch) x heads x 20544 + token_chunk_size x (2 x num_emb + heads) floats.
+ *   RWKV_WKV_SCAN_MAX: the segmented scan of V4, whose per-channel state (aa, bb, pp) is a sum under a running maximum: the rows are cut into
+ *     32-token segments that are summarised independently (a max-plus / log-sum-exp summary of three floats per channel), one thread per
+ *     (sequence, channel) carries the state over the summaries, and every segment is then walked from the state that enters it: a single long
+ *     prompt occupies prompt_length / 32 x num_emb / 64 waves instead of num_emb / 64.  No matrix products: the recurrence has none.  A third
+ *     summation order, so a third value: RWKV_WKV_SCAN_MAX on a V5, V6 or V7 engine is RWKV_ERR_UNSUPPORTED, and the form in force stays.  A V4
+ *     engine loaded from a prefab image is served.  Workspace: (token_chunk_size / 64 + max_batch) x 12 x num_emb floats.
  * Thread contract of rwkv_infer, between calls. */
-enum { RWKV_WKV_RECURRENT = 0, RWKV_WKV_SCAN = 1, RWKV_WKV_SCAN_DELTA = 2 };
+enum { RWKV_WKV_RECURRENT = 0, RWKV_WKV_SCAN = 1, RWKV_WKV_SCAN_DELTA = 2, RWKV_WKV_SCAN_MAX = 3 };
 rwkv_status rwkv_engine_set_wkv_form(rwkv_engine *e, int32_t form);
 int32_t rwkv_engine_wkv_form(const rwkv_engine *e);            /* RWKV_WKV_* in force */
 

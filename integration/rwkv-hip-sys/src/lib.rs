@@ -25,6 +25,7 @@ pub const RWKV_PRECISION_FP16_RAW: i32 = 2;
 pub const RWKV_WKV_RECURRENT: i32 = 0;
 pub const RWKV_WKV_SCAN: i32 = 1;
 pub const RWKV_WKV_SCAN_DELTA: i32 = 2;
+pub const RWKV_WKV_SCAN_MAX: i32 = 3;
 pub const RWKV_ADAPTER_AUTO: i32 = -1;
 pub const RWKV_ADAPTER_ECONOMICAL: i32 = -2;
 pub const RWKV_OPTION_LAST: i32 = 0;

@@ -125,9 +125,10 @@ impl Engine {
         let (max_batch, token_chunk_size) = unsafe { (sys::rwkv_engine_max_batch(raw) as usize, sys::rwkv_engine_token_chunk_size(raw) as usize) };
         Ok(Self { raw, info, max_batch, token_chunk_size })
     }
-    /// The form of the V5 / V6 / V7 WKV recurrence in multi-row steps: `sys::RWKV_WKV_RECURRENT` (token by token, the default),
-    /// `sys::RWKV_WKV_SCAN` (V5 / V6: 64-token chunks as matrix products) or `sys::RWKV_WKV_SCAN_DELTA` (V7: the same cut with a triangular
-    /// solve per chunk and two matrix products per chunk in the carry).  An engine the asked form does not serve answers
+    /// The form of the WKV recurrence in multi-row steps: `sys::RWKV_WKV_RECURRENT` (token by token, the default),
+    /// `sys::RWKV_WKV_SCAN` (V5 / V6: 64-token chunks as matrix products), `sys::RWKV_WKV_SCAN_DELTA` (V7: the same cut with a triangular
+    /// solve per chunk and two matrix products per chunk in the carry) or `sys::RWKV_WKV_SCAN_MAX` (V4: 32-token segments summarised
+    /// independently under a running maximum, a per-channel carry, then walked from their entry states).  An engine the asked form does not serve answers
     /// `RWKV_ERR_UNSUPPORTED` and keeps its form.
     pub fn set_wkv_form(&mut self, form: i32) -> Result<()> { check(unsafe { sys::rwkv_engine_set_wkv_form(self.raw, form) }) }
     pub fn wkv_form(&self) -> i32 { unsafe { sys::rwkv_engine_wkv_form(self.raw) } }
