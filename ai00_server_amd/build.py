@@ -47,9 +47,9 @@ def needs_build() -> bool:
     return open(STAMP).read().strip() != _sources_digest()
 
 
-KERNEL_PARTS = 9      # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
-# parts 6 to 8 (the WKV scan forms of V5 / V6, of V7 and of V4) are compiled without packed fp32 instructions; the older parts keep the flags they
-# were measured with
+KERNEL_PARTS = 10     # rwkv_kernels.hip is compiled once per part (-DRWKV_PART=k), in parallel
+# parts 6 to 8 (the WKV scan forms of V5 / V6, of V7 and of V4) are compiled without packed fp32 instructions; the older parts and part 9 (head_score) keep
+# packed fp32: the older ones the flags they were measured with, part 9 the compiler's default
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 PART_FLAGS = {6: NO_PACKED_FP32, 7: NO_PACKED_FP32, 8: NO_PACKED_FP32}
 

@@ -408,6 +408,7 @@ struct rwkv_engine {
     // scoring (rwkv_infer_score on s_main, rwkv_score_rows on s_soft): one target in and one ln-probability out per logits row; pinned mirrors
     unsigned *d_score_tgt = nullptr, *h_score_tgt = nullptr, *d_soft_tgt = nullptr, *h_soft_tgt = nullptr;
     float *d_score_out = nullptr, *h_score_out = nullptr, *d_soft_score = nullptr, *h_soft_score = nullptr;
+    float *d_head_score_ws = nullptr;                          // rwkv_infer_score_fused: (m, s, x_target) per (row, vocabulary split) of head_score_kernel
     // top-n lists (rwkv_infer_topn on s_main, rwkv_topn_rows on s_soft): TOPN_MAX ids and ln-probabilities per logits row; pinned mirrors
     unsigned *d_topn_ids = nullptr, *h_topn_ids = nullptr, *d_soft_topn_ids = nullptr, *h_soft_topn_ids = nullptr;
     float *d_topn_logp = nullptr, *h_topn_logp = nullptr, *d_soft_topn_logp = nullptr, *h_soft_topn_logp = nullptr;
@@ -620,6 +621,10 @@ struct rwkv_engine {
     void log_gemm(const std::vector<ProbSpec> &ps, int T, int fam, const char *kind, int variant, int grid, int ksplit, int threads);
     void log_row(const char *kernel, int T, long grid, double bytes);   // RWKV_LAUNCH_LOG: algorithmic bytes of a non-GEMM launch of layer 0 / 1
     int step_max_rows = 0;                                // most rows any sequence has in the step being enqueued (run_plan)
+    bool step_score_fused = false;                        // the step being enqueued scores its rows in the head GEMM (infer_score, fused): part of the graph's identity
+    HeadScoreArgs head_score_args(int n_out) const {
+        return HeadScoreArgs{head->data, opO.hi, wide(CLS_HEAD) ? opO.lo : nullptr, opO.ld, info.num_vocab, info.num_emb, n_out, chunk, d_score_tgt, d_head_score_ws, d_score_out};
+    }
     int wkv_form = RWKV_WKV_RECURRENT;                    // rwkv_engine_set_wkv_form: RWKV_WKV_SCAN sends multi-row steps through launch_wkv_scan
     WkvScanWs scan_ws{};                                  // its workspace, shared by every layer; allocated when the form is first switched on
     Wkv7ScanWs scan7_ws{};                                // RWKV_WKV_SCAN_DELTA's workspace (V7), likewise
@@ -633,7 +638,7 @@ struct rwkv_engine {
     void run_plan(const StepPlan &pl);
     void infer_sample(const rwkv_slot_input *in, const rwkv_sample_params *sp, uint32_t *out_tokens, float *out_probs,
                       uint8_t *emitted, size_t *n_consumed);
-    void infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
+    void infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed, bool fused = false);
     void infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *out_ids, float *const *out_logp, const uint32_t *const *targets,
                     float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
     // the input of a step in which each of `slots` feeds one token and asks for its row (`Last`); tokens[i] belongs to slots[i], and steps whose
@@ -1077,6 +1082,8 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     soft_host = hostalloc<float>(soft_rows_cap * V);
     d_score_tgt = dalloc<unsigned>(chunk); d_score_out = dalloc<float>(chunk);
     h_score_tgt = hostalloc<unsigned>(chunk); h_score_out = hostalloc<float>(chunk);
+    d_head_score_ws = dalloc<float>((size_t)chunk * head_score_splits(V) * 3);
+    HIP_CHECK((hipError_t)head_score_prepare());
     d_soft_tgt = dalloc<unsigned>(soft_rows_cap); d_soft_score = dalloc<float>(soft_rows_cap);
     h_soft_tgt = hostalloc<unsigned>(soft_rows_cap); h_soft_score = hostalloc<float>(soft_rows_cap);
     d_topn_ids = dalloc<unsigned>((size_t)chunk * TOPN_MAX); d_topn_logp = dalloc<float>((size_t)chunk * TOPN_MAX);
@@ -1483,6 +1490,11 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
         if (!wide(CLS_HEAD)) aO.lo = nullptr;
         LnOutArgs o{cur, P, np, pstride, lnow, lnob, dense ? nullptr : dm.out_rows, aO.hi, aO.lo, C, C};
         launch(FAM_ROW, [&] { launch_ln_out(o, n_out, s_main); });
+        if (step_score_fused) {                                // the rows' targets are in d_score_tgt, their scores go to d_score_out; `logits` is not touched
+            const HeadScoreArgs hs = head_score_args(n_out);
+            launch(FAM_HEAD, [&] { launch_head_score(hs, s_main); });
+            return;
+        }
         std::vector<ProbSpec> ps(1);
         ps[0].W = head; ps[0].x = aO; ps[0].out = logits; ps[0].ldo = V;
         gemm(ps, n_out, FAM_HEAD, nullptr, CLS_HEAD);
@@ -1501,7 +1513,7 @@ void rwkv_engine::run_plan(const StepPlan &pl) {
     const int *tok_ptr = pl.dense ? dv_tok : dm.token;
     step_max_rows = pl.max_rows();
     const bool short_rows = step_max_rows <= 8;                  // picks the WKV form: part of the graph's identity
-    const uint64_t key = ((uint64_t)pl.dense << 63) | ((uint64_t)short_rows << 62) | ((uint64_t)pl.T << 40) | ((uint64_t)pl.n_seq << 20) | (uint64_t)pl.n_out;
+    const uint64_t key = ((uint64_t)pl.dense << 63) | ((uint64_t)short_rows << 62) | ((uint64_t)step_score_fused << 61) | ((uint64_t)pl.T << 40) | ((uint64_t)pl.n_seq << 20) | (uint64_t)pl.n_out;
     auto enqueue = [&] { run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense); };
     if (profiling) return enqueue();                            // timed launch by launch: event pairs, no graph
     hipGraphExec_t *exec = graphs.find(key);
@@ -1642,7 +1654,9 @@ void rwkv_engine::infer(const rwkv_slot_input *in, rwkv_slot_output *out) {
 
 // rwkv_infer_score: the step rwkv_infer would run with RWKV_OPTION_FULL on the scored slots (same plan, same step shape, same captured graph),
 // then score_rows_kernel over the n_out rows of `logits`; 4 bytes per row come back instead of the row (perplexity run.rs:699-755, Choose 936-982)
-void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed) {
+// fused (rwkv_infer_score_fused): the same plan and step, but its head is head_score_kernel, which reads the targets (uploaded in FRONT of the step) and
+// leaves the scores where score_rows_kernel would; the step's graph is a different one (run_plan's key), and `logits` is neither written nor read.
+void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed, bool fused) {
     HIP_CHECK(hipSetDevice(device));
     (void)hipGetLastError();                                   // as in infer(): the poll below must only see THIS call's errors
     const uint32_t V = (uint32_t)info.num_vocab;
@@ -1662,20 +1676,29 @@ void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *
             if (targets[b][i] >= V && targets[b][i] != RWKV_SCORE_SKIP)
                 throw RwkvError(RWKV_ERR_INVALID, "target " + std::to_string(targets[b][i]) + " of slot " + std::to_string(b) + " is not a token of this vocabulary");
     }
+    if (fused)                                                 // a step scores at most `chunk` rows: what holds for those holds for every plan
+        if (const char *why = head_score_check(head_score_args(chunk))) throw RwkvError(RWKV_ERR_INVALID, why);
     for (int b = 0; b < max_batch; ++b) if (in[b].n_tokens) gen_disarm_slot(b);
     StepPlan pl;
     plan_step(full.data(), pl);
     if (pl.T == 0) return;
     for (int b = 0; b < max_batch; ++b)                        // a Full slot emits one row per consumed token: rows and targets line up
         if (targets[b]) std::memcpy(h_score_tgt + pl.slot_out_begin[b], targets[b], (size_t)pl.slot_out_rows[b] * 4);
-    run_plan(pl);
+    if (fused && pl.n_out > 0) {
+        HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+    }
+    step_score_fused = fused;
+    try { run_plan(pl); } catch (...) { step_score_fused = false; throw; }
+    step_score_fused = false;
     for (int b = 0; b < max_batch; ++b) n_consumed[b] = (size_t)pl.slot_consumed[b];
     if (pl.n_out == 0) {                                       // only state-only slots rode: not waited for, like a row-less rwkv_infer
         HIP_CHECK(hipPeekAtLastError());
         return;
     }
-    HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
-    launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+    if (!fused) {
+        HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+        launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+    }
     HIP_CHECK(hipMemcpyAsync(h_score_out, d_score_out, (size_t)pl.n_out * 4, hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipPeekAtLastError());
     HIP_CHECK(hipStreamSynchronize(s_main));
@@ -2610,6 +2633,15 @@ rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const ui
         if (!e || !in || !targets || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
         use_knobs(e->kn);
         e->infer_score(in, targets, out_logp, n_consumed);
+    });
+}
+
+rwkv_status rwkv_infer_score_fused(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp,
+                                   size_t *n_consumed) {
+    return guard([&] {
+        if (!e || !in || !targets || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        use_knobs(e->kn);
+        e->infer_score(in, targets, out_logp, n_consumed, true);
     });
 }
 

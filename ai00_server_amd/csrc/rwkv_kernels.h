@@ -329,6 +329,43 @@ constexpr int TOPN_MAX = 32;
 constexpr unsigned TOPN_NONE = 0xFFFFFFFFu;
 void launch_topn_rows(const float *logits, int n, unsigned *out_ids, float *out_logp, int n_rows, int V, hipStream_t s, float *side_ms = nullptr,
                       float *side_rows = nullptr);
+// ---- head_score: out[r] = ln softmax(x[r] W^T)[targets[r]] inside the head GEMM; the logits exist only as accumulator tiles (rwkv_kernels.hip, part 9).
+// A block owns one tile of rows (HEAD_SCORE_ROWS, or twice that on steps with more rows: the same arithmetic per row) and one of `splits` contiguous
+// ranges of vocabulary strip groups; it leaves (m, sum of exp(x - m), x[target] or -inf) per (row, split) in `ws`, and head_score_combine_kernel merges
+// a row's partials in a fixed order.  The split count is a function of V alone: a row's bits depend on its operand, its target, V and K, not on the step.
+constexpr int HEAD_SCORE_ROWS = 64;            // row-tile height of steps of up to 64 rows; 128 above
+constexpr int HEAD_SCORE_GROUP = 128;          // vocabulary rows per strip group: 4 waves x 2 strips of 16
+constexpr int HEAD_SCORE_MAX_SPLITS = 256;
+inline int head_score_groups_per_block(int V) {
+    const int groups = (V + HEAD_SCORE_GROUP - 1) / HEAD_SCORE_GROUP;
+    return (groups + HEAD_SCORE_MAX_SPLITS - 1) / HEAD_SCORE_MAX_SPLITS;
+}
+inline int head_score_splits(int V) {
+    const int groups = (V + HEAD_SCORE_GROUP - 1) / HEAD_SCORE_GROUP, gpb = head_score_groups_per_block(V);
+    return (groups + gpb - 1) / gpb;
+}
+struct HeadScoreArgs {
+    const void *W;                  // the head, tiled fp16 [V x K]
+    const _Float16 *xhi, *xlo;      // ln_out's operand (opd_off order, ldx k per row); xlo null: hi only
+    int ldx, V, K;
+    int n_rows, rows_cap;           // rows of this launch; rows targets, ws and out were allocated for.  The operand holds ceil16(rows_cap) rows, the
+                                    // pad zero-filled (the engine's alloc_opd): the kernel loads whole 16-row tiles, up to ceil16(n_rows) rows
+    const unsigned *targets;        // [n_rows] token ids; >= V: not scored (NaN)
+    float *ws;                      // [rows_cap][head_score_splits(V)][3]
+    float *out;                     // [n_rows]
+};
+// null when every index the two kernels form lies inside what the caller allocated (the operand tile-padded as above), else what is wrong
+inline const char *head_score_check(const HeadScoreArgs &a) {
+    if (!a.W || !a.xhi || !a.targets || !a.ws || !a.out) return "head_score: null array";
+    if (a.V < 16 || a.V % 16) return "head_score: num_vocab must be a positive multiple of 16";
+    if (a.K < 64 || a.K % 64) return "head_score: the inner dimension must be a positive multiple of 64";
+    if (a.ldx < a.K || a.ldx % 32) return "head_score: operand rows shorter than the inner dimension";
+    if (a.n_rows < 1 || a.n_rows > a.rows_cap) return "head_score: row count outside the allocation";
+    return nullptr;
+}
+int head_score_prepare();                                           // once per device, outside stream capture: the LDS ceiling of the 128-row hi + lo form; a hipError_t
+void launch_head_score(const HeadScoreArgs &a, hipStream_t s);      // throws nothing: the caller runs head_score_check first
+
 // on-device sampling front-end (f-1): V <= 65536.  nucleus_kernel takes top_k <= 256 and Mirostat with fewer than 8192 candidates,
 // sample_wide_kernel the rows that carry SAMPLE_WIDE in `kind` (any top_k, any max_surprise); each row is written by exactly one of them
 constexpr int SAMPLE_WIDE = 4;

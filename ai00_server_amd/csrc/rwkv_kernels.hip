@@ -20,7 +20,7 @@
 #include <algorithm>
 
 
-// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..8, in parallel: one pass takes
+// Build parts: the product build compiles this file once per part (-DRWKV_PART=k, k = 0..9, in parallel: one pass takes
 // ~3 minutes, the parts ~1); without RWKV_PART everything is one translation unit (trace builds of scripts/build_variant.py,
 // whose `__device__` probe buffers cannot span translation units).
 #ifdef RWKV_PART
@@ -3312,6 +3312,8 @@ void launch_softmax(const float *in, float *out, int n_rows, int V, hipStream_t 
 // row's bits, the target and V alone.  -inf entries (masked tokens) count as zero; a row holding +inf or NaN gives NaN.
 // =====================================================================================
 constexpr int SCORE_THREADS = 256;
+#endif
+#if RWKV_PART_ON(4) || RWKV_PART_ON(9)      // the online (m, s) pair and its merge also serve part 9 (head_score)
 struct ScorePair { float m, s; };
 // one more element into a pair: exactly one exp (of -|x - m|); x = -inf adds nothing, the first finite x after -inf starts the sum at 1
 __device__ __forceinline__ void score_push(ScorePair &p, float x) {
@@ -3327,6 +3329,8 @@ __device__ __forceinline__ ScorePair score_merge(ScorePair a, ScorePair b) {
     const float t = ml == -INFINITY ? 0.f : expf(ml - mh);
     return ScorePair{mh, a.m == b.m ? a.s + b.s : sh + sl * t};
 }
+#endif
+#if RWKV_PART_ON(4)
 // One pass over a row in score_rows_kernel's thread mapping: lane t of the block reads 16 bytes at float4 index base + u * SCORE_THREADS + t and
 // pushes component c into its pair p[c]; `bad` collects +inf / NaN.  `each(i, e)` sees every float4 the lane reads (index i < n4, its four values).
 // score_rows_kernel and topn_rows_kernel both run THIS loop and score_block_merge below: that is why their (m, S) agree bit for bit.
@@ -5513,4 +5517,203 @@ void launch_wkv7_scan(const WkvArgs &a, const Wkv7ScanWs &ws, hipStream_t s) {
     hipLaunchKernelGGL(wkv7_scan_out_kernel, chunks, dim3(256), 0, s, a, ws);
 }
 #endif  // part 7: WKV chunked matrix form of V7
+
+#if RWKV_PART_ON(9)
+// =====================================================================================
+// head_score: ln softmax(x W_head^T)[target] of every row of a step with the softmax statistics taken in the head GEMM's epilogue — the logits are
+// accumulator tiles and nothing else (rwkv_infer_score_fused).
+//
+// Block = 4 waves = (row tile rt of RT = 16 NTL rows, split sp).  A split is a contiguous range of strip GROUPS; a group is 8 strips = 128 vocabulary
+// rows, wave w owns strips {2w, 2w + 1} of it against all NTL token tiles (8 NTL accumulator registers).  K streams in chunks of 64 (K % 64 == 0: no
+// tail): the operand chunk of the row tile goes global -> LDS by global_load_lds, already in B-fragment order (opd_off), double buffered; the wave's
+// four 1 KiB weight tiles of the next chunk are in flight to registers while this chunk is multiplied.  One barrier per chunk, and the (group, chunk)
+// pairs of the block form ONE pipelined sequence: the first chunk of the next group is loaded under the last chunk of this one.
+// After a group's last chunk the tile is folded, never stored.  Per token column: the lane's 8 values -> max, xor-shuffle over the four lane groups
+// that share the column -> the wave's m; sum of exp(x - m) in register order, the same shuffles -> the wave's s; lanes 0..15 park (m, s) in LDS and
+// thread t < RT merges the four waves' pairs ((w0, w1), (w2, w3)) and then the result into row t's running pair (score_merge: the rescale
+// s = s e^(m_old - m_new) + s_new e^(m_new' - m_new)).  The lane whose accumulator element IS x[r][target] stores it to LDS (one lane of the grid per row).
+// Strips past V (a partial last group) are loaded clamped and folded as -inf; token tiles past the step are clamped to its last tile and never written.
+// Every step of this is a function of the row's own MFMA column: neither the other rows of the tile nor NTL enter a row's bits.
+// =====================================================================================
+constexpr int HS_WAVES = 4, HS_SPW = 2, HS_KC = 64, HS_KTC = HS_KC / 32, HS_STRIPS = HS_WAVES * HS_SPW;
+static_assert(HS_STRIPS * 16 == HEAD_SCORE_GROUP, "a group is what the four waves cover");
+constexpr size_t hs_lds_bytes(bool hilo, int ntl) {
+    return (size_t)2 * (hilo ? 2 : 1) * ntl * HS_KTC * 1024 + (size_t)HS_WAVES * ntl * 16 * sizeof(ScorePair) + (size_t)ntl * 16 * sizeof(float);
+}
+__device__ __forceinline__ void hs_glds16(const _Float16 *g, _Float16 *lds) {   // lane l -> lds + 16 l bytes; `lds` is wave-uniform
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)g,
+                                     (__attribute__((address_space(3))) void *)(uintptr_t)(uint32_t)(uintptr_t)lds, 16, 0, 0);
+}
+
+template <bool HILO, int NTL>
+__global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const HeadScoreArgs a, const int gpb, const int splits) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int RT = NTL * 16, PART = NTL * HS_KTC * 512, NP = HILO ? 2 : 1;   // PART: halfs per (buffer, hi | lo)
+    _Float16 *xs = (_Float16 *)smem;                              // [buf][hi | lo][token tile][k-tile][lane][8]
+    ScorePair *red = (ScorePair *)(xs + 2 * NP * PART);           // [wave][RT]
+    float *s_xt = (float *)(red + HS_WAVES * RT);                 // [RT]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nstrips = a.V >> 4, ngroups = (nstrips + HS_STRIPS - 1) / HS_STRIPS;
+    const int nrt = (a.n_rows + RT - 1) / RT;
+    const int rt = (int)blockIdx.x % nrt, sp = (int)blockIdx.x / nrt;   // row tile fastest: the blocks that share a weight range are dispatched together
+    const int g0 = sp * gpb, g1 = min(g0 + gpb, ngroups);
+    const int t0 = rt * RT, last_tile = (a.n_rows - 1) >> 4;
+    const int KT = a.K >> 5, nchunk = a.K / HS_KC, total = (g1 - g0) * nchunk;
+
+    unsigned tgt[NTL];
+#pragma unroll
+    for (int nt = 0; nt < NTL; ++nt) {
+        const int row = t0 + nt * 16 + (lane & 15);
+        tgt[nt] = row < a.n_rows ? a.targets[row] : 0xFFFFFFFFu;
+    }
+    ScorePair run{-INFINITY, 0.f};                                // row t0 + tid's pair over the groups folded so far (threads < RT)
+    if (tid < RT) s_xt[tid] = -INFINITY;                          // published by the first barrier below
+
+    f32x4 acc[HS_SPW][NTL];
+#pragma unroll
+    for (int h = 0; h < HS_SPW; ++h)
+#pragma unroll
+        for (int nt = 0; nt < NTL; ++nt) acc[h][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    struct WRegs { u32x4 q[HS_SPW][HS_KTC]; };
+    auto wload = [&](WRegs &w, int g, int c) {
+#pragma unroll
+        for (int h = 0; h < HS_SPW; ++h) {
+            const int sidx = min(g * HS_STRIPS + wave * HS_SPW + h, nstrips - 1);
+            const u32x4 *base = (const u32x4 *)a.W + ((long)sidx * KT + c * HS_KTC) * 64 + lane;
+#pragma unroll
+            for (int j = 0; j < HS_KTC; ++j) w.q[h][j] = base[j * 64];      // default policy: the other row tiles of this split find the range in L2
+        }
+    };
+    // fragment tile i = (token tile i / KTC, k-tile i % KTC) of chunk c: one 1 KiB direct-to-LDS load, issued by wave i % 4
+    auto xissue = [&](int c, int buf) {
+        _Float16 *bh = xs + buf * NP * PART;
+#pragma unroll
+        for (int j = 0; j < NTL * HS_KTC / HS_WAVES; ++j) {
+            const int i = wave + j * HS_WAVES;
+            const int ttile = min((t0 >> 4) + i / HS_KTC, last_tile);
+            const long xo = ((long)ttile * (a.ldx >> 5) + c * HS_KTC + i % HS_KTC) * 512 + lane * 8;
+            hs_glds16(a.xhi + xo, bh + i * 512);
+            if constexpr (HILO) hs_glds16(a.xlo + xo, bh + PART + i * 512);
+        }
+    };
+    auto mma = [&](const WRegs &w, int buf) {
+        const _Float16 *bh = xs + buf * NP * PART;
+#pragma unroll
+        for (int ks = 0; ks < HS_KTC; ++ks) {
+            f16x8 xv[NTL], xc[HILO ? NTL : 1];
+#pragma unroll
+            for (int nt = 0; nt < NTL; ++nt) {
+                const int off = ((nt * HS_KTC + ks) * 64 + lane) * 8;
+                xv[nt] = *(const f16x8 *)(bh + off);
+                if constexpr (HILO) xc[nt] = *(const f16x8 *)(bh + PART + off);
+            }
+#pragma unroll
+            for (int nt = 0; nt < NTL; ++nt)
+#pragma unroll
+                for (int h = 0; h < HS_SPW; ++h) {
+                    const f16x8 af = __builtin_bit_cast(f16x8, w.q[h][ks]);
+                    acc[h][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, xv[nt], acc[h][nt], 0, 0, 0);
+                    if constexpr (HILO) acc[h][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, xc[nt], acc[h][nt], 0, 0, 0);
+                }
+        }
+    };
+    // acc[h][nt][r] = x[token t0 + 16 nt + (lane & 15)][vocabulary row (8 g + 2 wave + h) 16 + (lane >> 4) 4 + r]
+    auto fold = [&](int g) {
+        const int s0 = g * HS_STRIPS + wave * HS_SPW;
+#pragma unroll
+        for (int nt = 0; nt < NTL; ++nt) {
+            float x[HS_SPW * 4];
+            bool bad = false;
+            float m = -INFINITY;
+#pragma unroll
+            for (int h = 0; h < HS_SPW; ++h) {
+                const bool live = s0 + h < nstrips;
+                const unsigned d = tgt[nt] - (unsigned)((s0 + h) * 16 + (lane >> 4) * 4);   // < 4: this lane holds the target's logit
+                if (live && d < 4u) s_xt[nt * 16 + (lane & 15)] = d == 0 ? acc[h][nt][0] : d == 1 ? acc[h][nt][1] : d == 2 ? acc[h][nt][2] : acc[h][nt][3];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = live ? acc[h][nt][r] : -INFINITY;
+                    x[h * 4 + r] = v;
+                    bad |= !(v < INFINITY);                        // +inf or NaN
+                    m = fmaxf(m, v);
+                }
+                acc[h][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < HS_SPW * 4; ++i) s += x[i] == -INFINITY ? 0.f : expf(x[i] - m);
+            if (bad) s = __builtin_nanf("");                       // rides the additions and every merge
+            s += __shfl_xor(s, 16, 64);
+            s += __shfl_xor(s, 32, 64);
+            if (lane < 16) red[wave * RT + nt * 16 + lane] = ScorePair{m, s};
+        }
+        __syncthreads();
+        if (tid < RT)
+            run = score_merge(run, score_merge(score_merge(red[tid], red[RT + tid]), score_merge(red[2 * RT + tid], red[3 * RT + tid])));
+    };
+
+    WRegs cur, nxt;
+    wload(cur, g0, 0);
+    xissue(0, 0);
+    nxt = cur;
+    __syncthreads();
+    for (int it = 0; it < total; ++it) {
+        const int c = it % nchunk;
+        if (it + 1 < total) {                                     // the other buffer: every wave has left the chunk that read it (the barrier below)
+            wload(nxt, g0 + (it + 1) / nchunk, (it + 1) % nchunk);
+            xissue((it + 1) % nchunk, (it + 1) & 1);
+        }
+        mma(cur, it & 1);
+        if (c == nchunk - 1) fold(g0 + it / nchunk);              // block-uniform; `red` is rewritten one barrier later at the earliest
+        __syncthreads();
+        cur = nxt;
+    }
+    if (tid < RT && t0 + tid < a.n_rows) {
+        float *o = a.ws + ((long)(t0 + tid) * splits + sp) * 3;
+        o[0] = run.m;
+        o[1] = run.s;
+        o[2] = s_xt[tid];
+    }
+}
+
+// one wave per row: lane l merges partials l, l + 64, ... in order, then the xor butterfly (score_merge is symmetric bit for bit, so the lanes agree)
+__global__ __launch_bounds__(256) void head_score_combine_kernel(const float *ws, const unsigned *targets, float *out, int n_rows, int splits, int V) {
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n_rows) return;
+    ScorePair p{-INFINITY, 0.f};
+    float xt = -INFINITY;
+    for (int i = lane; i < splits; i += 64) {
+        const float *q = ws + ((long)row * splits + i) * 3;
+        p = score_merge(p, ScorePair{q[0], q[1]});
+        xt = fmaxf(xt, q[2]);                                      // one split holds the value, the others -inf
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        p = score_merge(p, ScorePair{__shfl_xor(p.m, k, 64), __shfl_xor(p.s, k, 64)});
+        xt = fmaxf(xt, __shfl_xor(xt, k, 64));
+    }
+    if (lane == 0)                                                // as score_rows_kernel: not scored -> NaN; poisoned -> NaN; a target at -inf -> -inf
+        out[row] = targets[row] >= (unsigned)V ? __builtin_nanf("") : p.s != p.s ? p.s : xt == -INFINITY ? -INFINITY : (xt - p.m) - logf(p.s);
+}
+
+int head_score_prepare() {                                         // 128-row tiles with hi + lo need 68.5 KiB of LDS
+    return (int)hipFuncSetAttribute((const void *)head_score_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_lds_bytes(true, 8));
+}
+void launch_head_score(const HeadScoreArgs &a, hipStream_t s) {
+    const bool hilo = a.xlo != nullptr;
+    const int ntl = a.n_rows > HEAD_SCORE_ROWS ? 8 : 4;
+    const int splits = head_score_splits(a.V), gpb = head_score_groups_per_block(a.V);
+    const dim3 grid((unsigned)(((a.n_rows + ntl * 16 - 1) / (ntl * 16)) * splits)), block(HS_WAVES * 64);
+    const size_t lds = hs_lds_bytes(hilo, ntl);
+    if (hilo && ntl == 8) hipLaunchKernelGGL((head_score_kernel<true, 8>), grid, block, lds, s, a, gpb, splits);
+    else if (hilo) hipLaunchKernelGGL((head_score_kernel<true, 4>), grid, block, lds, s, a, gpb, splits);
+    else if (ntl == 8) hipLaunchKernelGGL((head_score_kernel<false, 8>), grid, block, lds, s, a, gpb, splits);
+    else hipLaunchKernelGGL((head_score_kernel<false, 4>), grid, block, lds, s, a, gpb, splits);
+    hipLaunchKernelGGL(head_score_combine_kernel, dim3((a.n_rows + 3) / 4), dim3(256), 0, s, a.ws, a.targets, a.out, a.n_rows, splits, a.V);
+}
+#endif  // part 9: head_score
 }  // namespace rwkv

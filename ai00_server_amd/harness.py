@@ -101,12 +101,13 @@ def perplexity(loop: InferLoop, batch: int, tokens, head: float | None = None) -
     return float(-sum(math.log(x) for x in p) / len(toks))
 
 
-def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = None) -> float:
+def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = None, fused: bool = False) -> float:
     """`perplexity` with the realised tokens scored on the device (`Runtime.infer_score`, rwkv_infer_score): tokens' = [0] + tokens, or
     tokens when `head` (the probability of tokens[0]) is given; every row's target is the next token, the last row is `SCORE_SKIP`;
     ppl = -(sum ln p [+ ln head]) / len(tokens').  4 bytes per token come back instead of a logits row.  Takes an `InferLoop` (whose
     queues must be drained) or a runtime.  Unlike `perplexity` — and run.rs:737-740 — the device subtracts the row maximum before it
-    exponentiates, so logits beyond ~88 still score finitely; where `perplexity` is finite the two agree to fp32."""
+    exponentiates, so logits beyond ~88 still score finitely; where `perplexity` is finite the two agree to fp32.  `fused=True` scores
+    inside the head GEMM (`Runtime.infer_score_fused`): no logits array on the device either, another summation order."""
     rt = getattr(loop_or_runtime, "rt", loop_or_runtime)
     toks = list(tokens) if head is not None else [0] + list(tokens)
     targets = [None] * rt.max_batch
@@ -114,7 +115,7 @@ def perplexity_scored(loop_or_runtime, batch: int, tokens, head: float | None = 
     inp = RnnInput([RnnInputBatch(toks if b == batch else [], RnnOption.Full) for b in range(rt.max_batch)])
     acc = math.log(head) if head is not None else 0.0
     while inp.num_token() > 0:
-        inp, targets, scores = rt.infer_score(inp, targets)
+        inp, targets, scores = (rt.infer_score_fused if fused else rt.infer_score)(inp, targets)
         lp = np.asarray(scores[batch], dtype=np.float64)
         if not len(inp.batches[batch].tokens):                    # the request's last row is the skipped one
             lp = lp[:-1]

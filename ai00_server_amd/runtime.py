@@ -104,6 +104,8 @@ ABI_SYMBOLS = {
     "rwkv_score_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
     "rwkv_infer_score": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
                                      C.POINTER(C.c_size_t)]),
+    "rwkv_infer_score_fused": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
+                                           C.POINTER(C.c_size_t)]),
     "rwkv_topn_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
     "rwkv_infer_topn": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.c_int32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
                                     C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -935,6 +937,14 @@ class Runtime:
         rides state-only with `RnnOption.NoOutput`) or one target per pending token of slot b: `targets[b][i]` (a token id, or `SCORE_SKIP`) is
         scored on the row that consuming `tokens[b][i]` produces.  Returns (inp, targets, scores): tokens and targets drained by what the call
         consumed, `scores[b]` the float32 ln-probabilities of the rows it consumed (NaN where skipped; empty for a slot that is not scored)."""
+        return self._infer_score(lib().rwkv_infer_score, inp, targets)
+
+    def infer_score_fused(self, inp: RnnInput, targets: list):
+        """`infer_score` with the scores taken inside the head GEMM (rwkv_infer_score_fused): the same arguments and returns, no logits array
+        on the device; another summation order, so values within the fused path's own bound of float64, not `infer_score`'s bits."""
+        return self._infer_score(lib().rwkv_infer_score_fused, inp, targets)
+
+    def _infer_score(self, entry, inp: RnnInput, targets: list):
         B = self.max_batch
         if len(inp.batches) != B or len(targets) != B:
             raise RwkvError(-1, f"infer_score needs max_batch={B} entries")
@@ -957,7 +967,7 @@ class Runtime:
                     op[b] = out.ctypes.data_as(C.POINTER(C.c_float))
             scores.append(out)
         consumed = (C.c_size_t * B)()
-        _check(lib().rwkv_infer_score(self._h, ins, tp, op, consumed))
+        _check(entry(self._h, ins, tp, op, consumed))
         del keep
         rest = []
         for b, ib in enumerate(inp.batches):

@@ -54,6 +54,8 @@ extern "C" {
                               *    additive under 9: rwkv_gen_set_capture, rwkv_gen_take_item, rwkv_gen_item_free / _state / _back / _from_host,
                               *    rwkv_gen_arm_item, RWKV_GEN_CAPTURE_PROMPT / _FINISH: resident generation fills the prefix cache (the state and raw
                               *    row at the prompt's end and at a stop) and arms a slot from a cached item
+                              *    additive under 9: rwkv_infer_score_fused: rwkv_infer_score with the softmax statistics taken in the head GEMM's
+                              *    epilogue, no logits array in between (another summation order: its own bound, not rwkv_score_rows' bits)
                               *    additive under 9 (no new symbol, no struct changed): RWKV_QUANT_SF4 — `Quant::SF4` models load: NF4's storage read
                               *    through the Student-t code book; rwkv_bench_gemm takes fmt 3 */
 
@@ -274,6 +276,13 @@ rwkv_status rwkv_score_rows(rwkv_engine *e, const float *const *in, const uint32
  * call in which only state-only slots ride returns when the step is queued, as rwkv_infer does); errors as for a row-emitting rwkv_infer.  Thread
  * contract of rwkv_infer; tokens for an armed generation slot disarm it. */
 rwkv_status rwkv_infer_score(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
+/* rwkv_infer_score with the scores taken INSIDE the head GEMM: same arguments, plan, step shapes, n_consumed, refusals and thread contract, but no
+ * [rows, num_vocab] logits array is written or read (at token_chunk_size 2048 and num_vocab 65536 that is 512 MiB each way per step): every output
+ * tile of the head is reduced to (max, sum of exp, target logit) where it is computed.  Another summation order than rwkv_infer_score, so another
+ * value: each logp is within the bound measured for this path of a float64 evaluation, not rwkv_score_rows' bits.  A row's result
+ * depends on its own operand bits, its target, num_vocab and the model's dimensions, not on the rows that ride along or on its place in the step.
+ * RWKV_SCORE_SKIP, rows holding +inf or NaN, huge logits and targets >= num_vocab behave as described above. */
+rwkv_status rwkv_infer_score_fused(rwkv_engine *e, const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed);
 
 /* ---- top-n lists on the device: what the `top_logprobs` of a completion, a classifier over a few label tokens or a per-token
  * uncertainty estimate need of a logits row is the n most likely tokens and their ln-probabilities.  For a row x[0 .. num_vocab) and

@@ -239,6 +239,16 @@ class Runtime {
     // the row that consuming tokens[b][i] produces); a slot with no targets must have no tokens or RnnOption::None.  `input` and `targets`
     // are consumed in place; returns per slot the ln-probabilities of the rows this call consumed (NaN where skipped).  No row crosses PCIe.
     std::vector<std::vector<float>> infer_score(RnnInput &input, std::vector<std::vector<uint32_t>> &targets) {
+        return infer_score_by(rwkv_infer_score, input, targets);
+    }
+    // rwkv_infer_score_fused: infer_score() with the scores taken inside the head GEMM, no logits array on the device; another summation order, so
+    // its own bound against float64 instead of score_rows()'s bits.
+    std::vector<std::vector<float>> infer_score_fused(RnnInput &input, std::vector<std::vector<uint32_t>> &targets) {
+        return infer_score_by(rwkv_infer_score_fused, input, targets);
+    }
+
+   private:
+    std::vector<std::vector<float>> infer_score_by(decltype(&rwkv_infer_score) entry, RnnInput &input, std::vector<std::vector<uint32_t>> &targets) {
         if ((int)input.batches.size() != max_batch || (int)targets.size() != max_batch) throw std::invalid_argument("infer_score: need max_batch entries");
         std::vector<rwkv_slot_input> in((size_t)max_batch);
         std::vector<const uint32_t *> tp((size_t)max_batch, nullptr);
@@ -254,7 +264,7 @@ class Runtime {
             tp[b] = targets[b].data();
             op[b] = out[b].data();
         }
-        check(rwkv_infer_score(e_.get(), in.data(), tp.data(), op.data(), consumed.data()));
+        check(entry(e_.get(), in.data(), tp.data(), op.data(), consumed.data()));
         for (size_t b = 0; b < (size_t)max_batch; ++b) {
             auto &t = input.batches[b].tokens;
             t.erase(t.begin(), t.begin() + (long)consumed[b]);
@@ -264,6 +274,8 @@ class Runtime {
         }
         return out;
     }
+
+   public:
     // rwkv_score_rows: ln softmax(rows[i])[targets[i]] of host rows on the device (RWKV_SCORE_SKIP -> NaN) — Choose's `head` term (run.rs:971-972).
     // The softmax task's stream and thread, like softmax() below.
     std::vector<float> score_rows(const std::vector<std::vector<float>> &rows, const std::vector<uint32_t> &targets) {

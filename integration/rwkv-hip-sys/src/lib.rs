@@ -143,6 +143,9 @@ extern "C" {
     pub fn rwkv_score_rows(e: *mut rwkv_engine, inp: *const *const f32, targets: *const u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
     pub fn rwkv_infer_score(e: *mut rwkv_engine, inp: *const rwkv_slot_input, targets: *const *const u32, out_logp: *const *mut c_float,
                             n_consumed: *mut usize) -> rwkv_status;
+    // the same call with the scores taken inside the head GEMM: no logits array on the device, its own bound instead of rwkv_score_rows' bits
+    pub fn rwkv_infer_score_fused(e: *mut rwkv_engine, inp: *const rwkv_slot_input, targets: *const *const u32, out_logp: *const *mut c_float,
+                                  n_consumed: *mut usize) -> rwkv_status;
     // top-n lists on the device: the `top_logprobs` of a completion
     pub fn rwkv_topn_rows(e: *mut rwkv_engine, inp: *const *const f32, n: i32, out_ids: *mut u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
     pub fn rwkv_infer_topn(e: *mut rwkv_engine, inp: *const rwkv_slot_input, n: i32, out_ids: *const *mut u32, out_logp: *const *mut c_float,
