@@ -409,6 +409,10 @@ struct rwkv_engine {
     unsigned *d_score_tgt = nullptr, *h_score_tgt = nullptr, *d_soft_tgt = nullptr, *h_soft_tgt = nullptr;
     float *d_score_out = nullptr, *h_score_out = nullptr, *d_soft_score = nullptr, *h_soft_score = nullptr;
     float *d_head_score_ws = nullptr;                          // rwkv_infer_score_fused: (m, s, x_target) per (row, vocabulary split) of head_score_kernel
+    // rwkv_infer_topn_fused: head_topn_kernel's list of every (row, vocabulary split), chunk x head_score_splits(V) x n composites of 8 bytes.
+    // Allocated by the first fused call for the n it asks for and replaced when a larger n comes (head_topn_reserve); never part of load().
+    unsigned long long *d_head_topn_lists = nullptr;
+    int head_topn_cap_n = 0;                                   // the n it was sized for
     // top-n lists (rwkv_infer_topn on s_main, rwkv_topn_rows on s_soft): TOPN_MAX ids and ln-probabilities per logits row; pinned mirrors
     unsigned *d_topn_ids = nullptr, *h_topn_ids = nullptr, *d_soft_topn_ids = nullptr, *h_soft_topn_ids = nullptr;
     float *d_topn_logp = nullptr, *h_topn_logp = nullptr, *d_soft_topn_logp = nullptr, *h_soft_topn_logp = nullptr;
@@ -445,6 +449,8 @@ struct rwkv_engine {
 
     // captured steps (graph_cache.h holds the policy: captured on second sight, least recently used evicted)
     GraphCacheOf<uint64_t> graphs{64, {}};                     // run_plan: keyed by step shape
+    GraphCacheOf<uint64_t> topn_graphs{64, {}};                // run_plan under rwkv_infer_topn_fused: the same key, every graph for lists of topn_graphs_n places
+    int topn_graphs_n = 0;
     std::optional<GraphCacheOf<int>> greedy_graphs;            // rwkv_decode_greedy: step + arg-max feedback, keyed by slot count; room for every count
     // device-resident sampled generation (rwkv_gen_*): per-slot contexts, dense penalty / bias rows, the step's SampleRow array and the
     // output ring live on the device; everything is allocated by the first rwkv_gen_arm
@@ -560,7 +566,7 @@ struct rwkv_engine {
         if (s_main) (void)hipStreamSynchronize(s_main);
         if (s_soft) (void)hipStreamSynchronize(s_soft);
         if (s_copy) (void)hipStreamSynchronize(s_copy);
-        graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
+        graphs.clear(); topn_graphs.clear(); gen_graphs.clear(); greedy_graphs.reset();   // while the streams they were captured on still exist
         if (gen_watch) { (void)hipHostFree(gen_watch->ring); delete gen_watch; gen_watch = nullptr; }   // the destructor closes an open watch
         for (auto ev : prof_ev) (void)hipEventDestroy(ev);
         for (void *p : allocs) (void)hipFree(p);
@@ -625,6 +631,11 @@ struct rwkv_engine {
     HeadScoreArgs head_score_args(int n_out) const {
         return HeadScoreArgs{head->data, opO.hi, wide(CLS_HEAD) ? opO.lo : nullptr, opO.ld, info.num_vocab, info.num_emb, n_out, chunk, d_score_tgt, d_head_score_ws, d_score_out};
     }
+    int step_topn_fused = 0;                              // > 0: the step being enqueued lists its rows' n = this many best in the head GEMM (infer_topn, fused): part of the graph's identity
+    HeadTopnArgs head_topn_args(int n_out, int n) const {
+        return HeadTopnArgs{head_score_args(n_out), n, d_head_topn_lists, head_topn_list_entries(chunk, info.num_vocab, head_topn_cap_n), d_topn_ids, d_topn_logp};
+    }
+    void head_topn_reserve(int n);
     int wkv_form = RWKV_WKV_RECURRENT;                    // rwkv_engine_set_wkv_form: RWKV_WKV_SCAN sends multi-row steps through launch_wkv_scan
     WkvScanWs scan_ws{};                                  // its workspace, shared by every layer; allocated when the form is first switched on
     Wkv7ScanWs scan7_ws{};                                // RWKV_WKV_SCAN_DELTA's workspace (V7), likewise
@@ -640,7 +651,7 @@ struct rwkv_engine {
                       uint8_t *emitted, size_t *n_consumed);
     void infer_score(const rwkv_slot_input *in, const uint32_t *const *targets, float *const *out_logp, size_t *n_consumed, bool fused = false);
     void infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *out_ids, float *const *out_logp, const uint32_t *const *targets,
-                    float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
+                    float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed, bool fused = false);
     // the input of a step in which each of `slots` feeds one token and asks for its row (`Last`); tokens[i] belongs to slots[i], and steps whose
     // ids come from the device (the feedback buffer, held tokens) pass nullptr: the plan then carries a zero nobody reads
     std::vector<rwkv_slot_input> one_token_each(const std::vector<int> &slots, const uint32_t *tokens) const {
@@ -1084,6 +1095,7 @@ void rwkv_engine::load(const rwkv_load_desc &d) {
     h_score_tgt = hostalloc<unsigned>(chunk); h_score_out = hostalloc<float>(chunk);
     d_head_score_ws = dalloc<float>((size_t)chunk * head_score_splits(V) * 3);
     HIP_CHECK((hipError_t)head_score_prepare());
+    HIP_CHECK((hipError_t)head_topn_prepare());
     d_soft_tgt = dalloc<unsigned>(soft_rows_cap); d_soft_score = dalloc<float>(soft_rows_cap);
     h_soft_tgt = hostalloc<unsigned>(soft_rows_cap); h_soft_score = hostalloc<float>(soft_rows_cap);
     d_topn_ids = dalloc<unsigned>((size_t)chunk * TOPN_MAX); d_topn_logp = dalloc<float>((size_t)chunk * TOPN_MAX);
@@ -1495,6 +1507,11 @@ void rwkv_engine::run_layers(int T, int n_seq, int n_out, const int *d_token, bo
             launch(FAM_HEAD, [&] { launch_head_score(hs, s_main); });
             return;
         }
+        if (step_topn_fused) {                                 // likewise, and the rows' lists go to d_topn_ids / d_topn_logp
+            const HeadTopnArgs ht = head_topn_args(n_out, step_topn_fused);
+            launch(FAM_HEAD, [&] { launch_head_topn(ht, s_main); });
+            return;
+        }
         std::vector<ProbSpec> ps(1);
         ps[0].W = head; ps[0].x = aO; ps[0].out = logits; ps[0].ldo = V;
         gemm(ps, n_out, FAM_HEAD, nullptr, CLS_HEAD);
@@ -1516,11 +1533,12 @@ void rwkv_engine::run_plan(const StepPlan &pl) {
     const uint64_t key = ((uint64_t)pl.dense << 63) | ((uint64_t)short_rows << 62) | ((uint64_t)step_score_fused << 61) | ((uint64_t)pl.T << 40) | ((uint64_t)pl.n_seq << 20) | (uint64_t)pl.n_out;
     auto enqueue = [&] { run_layers(pl.T, pl.n_seq, pl.n_out, tok_ptr, pl.dense); };
     if (profiling) return enqueue();                            // timed launch by launch: event pairs, no graph
-    hipGraphExec_t *exec = graphs.find(key);
+    auto &cache = step_topn_fused ? topn_graphs : graphs;       // the key has no room for n: the listing steps keep a cache of their own, of one n at a time
+    hipGraphExec_t *exec = cache.find(key);
     if (!exec) {
         // a shape's first step runs directly (graph_cache.h says why; the launchers' one-time attribute calls also happen here, outside a capture)
-        if (!graphs.should_capture(key)) return enqueue();
-        exec = &graphs.insert(key, capture(s_main, enqueue));
+        if (!cache.should_capture(key)) return enqueue();
+        exec = &cache.insert(key, capture(s_main, enqueue));
     }
     HIP_CHECK(hipGraphLaunch(*exec, s_main));
 }
@@ -1706,12 +1724,35 @@ void rwkv_engine::infer_score(const rwkv_slot_input *in, const uint32_t *const *
         if (targets[b] && pl.slot_out_rows[b]) std::memcpy(out_logp[b], h_score_out + pl.slot_out_begin[b], (size_t)pl.slot_out_rows[b] * 4);
 }
 
+// The list workspace of head_topn_kernel for lists of n places; outside any capture.  The listing steps' graphs hold n and the workspace: another n
+// drops them (they are captured again on their second visit), and a larger n than the block was sized for replaces it, behind a drained stream.
+void rwkv_engine::head_topn_reserve(int n) {
+    if (n == topn_graphs_n && n <= head_topn_cap_n) return;
+    HIP_CHECK(hipStreamSynchronize(s_main));
+    topn_graphs.clear();
+    topn_graphs_n = 0;                                         // no n is in force until the block for it stands: a failed allocation is met again by the next call
+    if (n > head_topn_cap_n) {
+        if (void *old = d_head_topn_lists) {
+            d_head_topn_lists = nullptr;
+            head_topn_cap_n = 0;
+            allocs.erase(std::find(allocs.begin(), allocs.end(), old));
+            HIP_CHECK(hipFree(old));
+        }
+        d_head_topn_lists = dalloc<unsigned long long>(head_topn_list_entries(chunk, info.num_vocab, n));
+        head_topn_cap_n = n;
+    }
+    topn_graphs_n = n;
+}
+
 // rwkv_infer_topn: rwkv_infer's step (the caller's options, hence its plan, step shape and captured graph), then topn_rows_kernel over the n_out
 // rows of `logits`: n ids and n ln-probabilities per row come back instead of the row.  Slots with targets are scored as well, by the launch
 // rwkv_infer_score makes, on the same block (the `echo` case: the realised token's ln-probability beside the alternatives, in one pass).
+// fused (rwkv_infer_topn_fused): the same refusals, plan and step, but its head is head_topn_kernel, which reads the targets (uploaded in FRONT of the
+// step, RWKV_SCORE_SKIP on every row that is not scored) and leaves lists and scores where the two row kernels would; the step's graph is a different
+// one (run_plan's cache of listing steps), and `logits` is neither written nor read.
 static_assert(RWKV_TOPN_MAX == TOPN_MAX && RWKV_TOPN_NONE == TOPN_NONE, "rwkv_abi.h and rwkv_kernels.h disagree");
 void rwkv_engine::infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *out_ids, float *const *out_logp, const uint32_t *const *targets,
-                             float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed) {
+                             float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed, bool fused) {
     HIP_CHECK(hipSetDevice(device));
     (void)hipGetLastError();                                   // as in infer(): the poll below must only see THIS call's errors
     const uint32_t V = (uint32_t)info.num_vocab;
@@ -1739,28 +1780,40 @@ void rwkv_engine::infer_topn(const rwkv_slot_input *in, int n, uint32_t *const *
                 throw RwkvError(RWKV_ERR_INVALID, "target " + std::to_string(targets[b][i]) + " of slot " + std::to_string(b) + " is not a token of this vocabulary");
         any_targets |= in[b].n_tokens > 0;
     }
+    if (fused) {                                               // a step lists at most `chunk` rows: what holds for those holds for every plan
+        if (const char *why = head_topn_check_args(head_topn_args(chunk, n))) throw RwkvError(RWKV_ERR_INVALID, why);   // before anything changes
+        head_topn_reserve(n);
+        if (const char *why = head_topn_check(head_topn_args(chunk, n))) throw RwkvError(RWKV_ERR_INVALID, why);        // the workspace as it now stands
+    }
     for (int b = 0; b < max_batch; ++b) if (in[b].n_tokens) gen_disarm_slot(b);
     StepPlan pl;
     plan_step(in, pl);
     if (pl.T == 0) return;
-    if (any_targets) {
+    if (any_targets || fused) {
         for (int r = 0; r < pl.n_out; ++r) h_score_tgt[r] = RWKV_SCORE_SKIP;   // rows of slots without targets are not scored
         for (int b = 0; b < max_batch; ++b)                    // a Full slot emits one row per consumed token: rows and targets line up
-            if (targets[b] && pl.slot_out_rows[b]) std::memcpy(h_score_tgt + pl.slot_out_begin[b], targets[b], (size_t)pl.slot_out_rows[b] * 4);
+            if (targets && targets[b] && pl.slot_out_rows[b]) std::memcpy(h_score_tgt + pl.slot_out_begin[b], targets[b], (size_t)pl.slot_out_rows[b] * 4);
     }
-    run_plan(pl);
+    if (fused && pl.n_out > 0) {
+        HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+    }
+    step_topn_fused = fused ? n : 0;
+    try { run_plan(pl); } catch (...) { step_topn_fused = 0; throw; }
+    step_topn_fused = 0;
     for (int b = 0; b < max_batch; ++b) n_consumed[b] = (size_t)pl.slot_consumed[b];
     if (pl.n_out == 0) {                                       // no slot reached a row: not waited for, like a row-less rwkv_infer
         HIP_CHECK(hipPeekAtLastError());
         return;
     }
     const size_t cells = (size_t)pl.n_out * (size_t)n;
-    launch(FAM_SAMPLE, [&] { launch_topn_rows(logits, n, d_topn_ids, d_topn_logp, pl.n_out, (int)V, s_main); });
+    if (!fused) launch(FAM_SAMPLE, [&] { launch_topn_rows(logits, n, d_topn_ids, d_topn_logp, pl.n_out, (int)V, s_main); });
     HIP_CHECK(hipMemcpyAsync(h_topn_ids, d_topn_ids, cells * 4, hipMemcpyDeviceToHost, s_main));
     HIP_CHECK(hipMemcpyAsync(h_topn_logp, d_topn_logp, cells * 4, hipMemcpyDeviceToHost, s_main));
     if (any_targets) {
-        HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
-        launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+        if (!fused) {
+            HIP_CHECK(hipMemcpyAsync(d_score_tgt, h_score_tgt, (size_t)pl.n_out * 4, hipMemcpyHostToDevice, s_main));
+            launch(FAM_SAMPLE, [&] { launch_score_rows(logits, d_score_tgt, d_score_out, pl.n_out, (int)V, s_main); });
+        }
         HIP_CHECK(hipMemcpyAsync(h_score_out, d_score_out, (size_t)pl.n_out * 4, hipMemcpyDeviceToHost, s_main));
     }
     HIP_CHECK(hipPeekAtLastError());
@@ -2561,7 +2614,7 @@ void rwkv_engine::set_wkv_form(int form) {
         }
     }
     HIP_CHECK(hipStreamSynchronize(s_main));
-    graphs.clear(); gen_graphs.clear();
+    graphs.clear(); topn_graphs.clear(); gen_graphs.clear();
     wkv_form = form;
 }
 rwkv_status rwkv_engine_set_wkv_form(rwkv_engine *e, int32_t form) {
@@ -2652,6 +2705,16 @@ rwkv_status rwkv_infer_topn(rwkv_engine *e, const rwkv_slot_input *in, int32_t n
         if (n < 1 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 1.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
         use_knobs(e->kn);
         e->infer_topn(in, n, out_ids, out_logp, targets, out_tok_logp, n_rows, n_consumed);
+    });
+}
+
+rwkv_status rwkv_infer_topn_fused(rwkv_engine *e, const rwkv_slot_input *in, int32_t n, uint32_t *const *out_ids, float *const *out_logp,
+                                  const uint32_t *const *targets, float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed) {
+    return guard([&] {
+        if (!e || !in || !out_ids || !out_logp || !n_rows || !n_consumed) throw RwkvError(RWKV_ERR_INVALID, "null argument");
+        if (n < 1 || n > RWKV_TOPN_MAX) throw RwkvError(RWKV_ERR_INVALID, "n must be 1.." + std::to_string(RWKV_TOPN_MAX) + ", got " + std::to_string(n));
+        use_knobs(e->kn);
+        e->infer_topn(in, n, out_ids, out_logp, targets, out_tok_logp, n_rows, n_consumed, true);
     });
 }
 

@@ -365,6 +365,34 @@ inline const char *head_score_check(const HeadScoreArgs &a) {
 }
 int head_score_prepare();                                           // once per device, outside stream capture: the LDS ceiling of the 128-row hi + lo form; a hipError_t
 void launch_head_score(const HeadScoreArgs &a, hipStream_t s);      // throws nothing: the caller runs head_score_check first
+// ---- head_topn: head_score's launch with the n most likely tokens of every row kept as well (rwkv_kernels.hip, part 9).  Same blocks, same K loop,
+// same fold: hs.out[r] is launch_head_score's value bit for bit.  out_ids / out_logp [n_rows][n]: the n largest logits of the row as the
+// accumulators hold them, descending, ties to the lower id, each with (x - m) - ln s on head_score's (m, s); fewer than n entries above -inf:
+// (TOPN_NONE, -inf) in the places left; +inf or NaN in the row: (TOPN_NONE, NaN) in all.  A row's list depends on its operand, n, V and K alone.
+struct HeadTopnArgs {
+    HeadScoreArgs hs;               // hs.targets: >= V where a row is not scored (the kernel reads every row's); hs.out [n_rows]: the target's logp
+    int n;                          // places per list, 1..TOPN_MAX
+    unsigned long long *lists;      // [rows_cap][head_score_splits(V)][n] composites: every block's list of every row
+    size_t lists_cap;               // entries `lists` was allocated for
+    unsigned *out_ids;              // [n_rows][n]
+    float *out_logp;                // [n_rows][n]
+};
+inline size_t head_topn_list_entries(int rows, int V, int n) { return (size_t)rows * (size_t)head_score_splits(V) * (size_t)n; }
+// everything but the list workspace, which the engine allocates for the n of the call: what can be refused before that
+inline const char *head_topn_check_args(const HeadTopnArgs &a) {
+    if (const char *why = head_score_check(a.hs)) return why;
+    if (a.n < 1 || a.n > TOPN_MAX) return "head_topn: n outside 1..TOPN_MAX";
+    if (!a.out_ids || !a.out_logp) return "head_topn: null array";
+    return nullptr;
+}
+inline const char *head_topn_check(const HeadTopnArgs &a) {
+    if (const char *why = head_topn_check_args(a)) return why;
+    if (!a.lists) return "head_topn: no list workspace";
+    if (head_topn_list_entries(a.hs.rows_cap, a.hs.V, a.n) > a.lists_cap) return "head_topn: list workspace smaller than rows x splits x n";
+    return nullptr;
+}
+int head_topn_prepare();                                            // once per device, outside stream capture: the LDS ceilings of the 128-row forms; a hipError_t
+void launch_head_topn(const HeadTopnArgs &a, hipStream_t s);        // throws nothing: the caller runs head_topn_check first
 
 // on-device sampling front-end (f-1): V <= 65536.  nucleus_kernel takes top_k <= 256 and Mirostat with fewer than 8192 candidates,
 // sample_wide_kernel the rows that carry SAMPLE_WIDE in `kind` (any top_k, any max_surprise); each row is written by exactly one of them

@@ -3418,6 +3418,8 @@ void launch_score_rows(const float *logits, const unsigned *targets, float *out,
 // The slot a candidate lands in varies from run to run, the SET and hence every output does not.
 // =====================================================================================
 constexpr int TOPN_CAND = 1024;                                   // candidate slots in LDS (8 KiB); TOPN_MAX, TOPN_NONE: rwkv_kernels.h
+#endif
+#if RWKV_PART_ON(4) || RWKV_PART_ON(9)      // the composite key also orders part 9's lists (head_topn)
 typedef unsigned long long u64;
 // (key << 32) | ~id; 0 for an entry that is no candidate (-inf).  Larger float <-> larger key; -0 takes +0's key.
 __device__ __forceinline__ u64 topn_comp(float x, int id) {
@@ -3427,6 +3429,8 @@ __device__ __forceinline__ u64 topn_comp(float x, int id) {
     const unsigned key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // a finite negative float maps to >= 0x00800000: a live key is never 0
     return ((u64)key << 32) | (u64)(0xFFFFFFFFu - (unsigned)id);
 }
+#endif
+#if RWKV_PART_ON(4)
 // f(composite) over the whole row, in pass 1's thread mapping
 template <class F>
 __device__ __forceinline__ void topn_for_each(const float4 *x4, int n4, F &&f) {
@@ -5545,13 +5549,23 @@ __device__ __forceinline__ void hs_glds16(const _Float16 *g, _Float16 *lds) {   
                                      (__attribute__((address_space(3))) void *)(uintptr_t)(uint32_t)(uintptr_t)lds, 16, 0, 0);
 }
 
-template <bool HILO, int NTL>
-__global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const HeadScoreArgs a, const int gpb, const int splits) {
+// The block of head_score_kernel (TOPN false) and of head_topn_kernel (TOPN true: see head_topn below; `n` places per list, `lists` the per-(row, split)
+// lists in global memory).  ONE body: the K loop, the fold and the partials the two kernels write are the same code, so their (m, s, x_target) are the
+// same bits; everything the lists add sits under `if constexpr (TOPN)` and reads the accumulators without changing them.
+constexpr int HT_STAGE = 16;                   // head_topn: staged entries per token and round
+__device__ __forceinline__ u64 ht_readlane(u64 v, int l) {         // `l` is wave-uniform
+    return ((u64)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)v, l);
+}
+template <bool HILO, int NTL, bool TOPN>
+__device__ __forceinline__ void hs_block(const HeadScoreArgs &a, const int gpb, const int splits, const int n, u64 *lists) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RT = NTL * 16, PART = NTL * HS_KTC * 512, NP = HILO ? 2 : 1;   // PART: halfs per (buffer, hi | lo)
     _Float16 *xs = (_Float16 *)smem;                              // [buf][hi | lo][token tile][k-tile][lane][8]
     ScorePair *red = (ScorePair *)(xs + 2 * NP * PART);           // [wave][RT]
     float *s_xt = (float *)(red + HS_WAVES * RT);                 // [RT]
+    u64 *list = (u64 *)(s_xt + RT);                               // TOPN: [RT][n] composites, descending, 0 = empty place
+    int *cnt = (int *)(list + (TOPN ? RT * n : 0));               // TOPN: [RT] entries staged for the token; [RT] its overflow flag; the block's flag
+    int *ovt = cnt + RT, *ovf = ovt + RT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nstrips = a.V >> 4, ngroups = (nstrips + HS_STRIPS - 1) / HS_STRIPS;
@@ -5569,6 +5583,11 @@ __global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const Head
     }
     ScorePair run{-INFINITY, 0.f};                                // row t0 + tid's pair over the groups folded so far (threads < RT)
     if (tid < RT) s_xt[tid] = -INFINITY;                          // published by the first barrier below
+    if constexpr (TOPN) {
+        for (int i = tid; i < RT * n; i += HS_WAVES * 64) list[i] = 0ull;
+        if (tid < RT) { cnt[tid] = 0; ovt[tid] = 0; }
+        if (tid == 0) *ovf = 0;
+    }
 
     f32x4 acc[HS_SPW][NTL];
 #pragma unroll
@@ -5620,7 +5639,75 @@ __global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const Head
         }
     };
     // acc[h][nt][r] = x[token t0 + 16 nt + (lane & 15)][vocabulary row (8 g + 2 wave + h) 16 + (lane >> 4) 4 + r]
-    auto fold = [&](int g) {
+    // TOPN, ahead of the fold: the tile's values that beat their token's n-th best join its list (head_topn below says how).  `buf` is the operand
+    // buffer the group's last chunk was multiplied from: nothing loads into it before the K loop's next barrier, so it stages the survivors.
+    auto offer = [&](u64 *stage, int nt, int h, int s0, bool only_overflowed) {
+        const int t = nt * 16 + (lane & 15);
+        if (only_overflowed && !ovt[t]) return;
+        const u64 thr = list[t * n + n - 1];                       // 0 while the list has places left: every live composite is above it
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const u64 c = topn_comp(acc[h][nt][r], (s0 + h) * 16 + (lane >> 4) * 4 + r);
+            if (c > thr) {
+                const int slot = atomicAdd(&cnt[t], 1);
+                if (slot < HT_STAGE) stage[t * HT_STAGE + slot] = c;
+            }
+        }
+    };
+    // wave w merges the staged entries of tokens w, w + 4, ...: lane i < n holds place i of the list, lane 32 + j staged entry j.  Composites are
+    // distinct, so a key's place in the union is the number of keys above it: a list key keeps its place plus the staged keys above it (the list is
+    // sorted), a staged key counts the lanes above it with one ballot.  The places below n are the new list: a function of the SET of keys.
+    auto merge = [&](const u64 *stage) {
+        for (int t = wave; t < RT; t += HS_WAVES) {
+            const int c = __builtin_amdgcn_readfirstlane(cnt[t]);
+            if (c == 0) continue;
+            if (lane == 0) cnt[t] = 0;
+            if (c > HT_STAGE) {                                    // more than the stage holds (the first pass only): the token is redone a strip at a time
+                if (lane == 0) { ovt[t] = 1; *ovf = 1; }
+                continue;
+            }
+            const u64 key = lane < n ? list[t * n + lane] : (lane >= 32 && lane < 32 + c) ? stage[t * HT_STAGE + lane - 32] : 0ull;
+            int place = lane;
+            for (int j = 0; j < c; ++j) {
+                const u64 sj = ht_readlane(key, 32 + j);
+                const u64 above = __ballot(key > sj);
+                if (lane == 32 + j) place = __popcll(above);
+                else if (lane < 32) place += sj > key;
+            }
+            if (key != 0ull && place < n) list[t * n + place] = key;
+        }
+    };
+    auto select = [&](int g, int buf) {
+        u64 *stage = (u64 *)(xs + buf * NP * PART);               // [RT][HT_STAGE]: NTL 2 KiB of the buffer's NP NTL 2 KiB
+        const int s0 = g * HS_STRIPS + wave * HS_SPW;
+        __syncthreads();                                          // every wave has multiplied the last chunk: the buffer is free
+#pragma unroll
+        for (int nt = 0; nt < NTL; ++nt)
+#pragma unroll
+            for (int h = 0; h < HS_SPW; ++h)
+                if (s0 + h < nstrips) offer(stage, nt, h, s0, false);   // a clamped strip past V repeats the last one: it is no candidate
+        __syncthreads();
+        merge(stage);
+        __syncthreads();
+        if (*ovf) {                                               // block-uniform.  One (wave, strip) a round: 4 lanes x 4 values = HT_STAGE entries per token at most
+#pragma unroll 1
+            for (int q = 0; q < HS_WAVES; ++q)
+#pragma unroll
+                for (int h = 0; h < HS_SPW; ++h) {
+                    if (wave == q && s0 + h < nstrips) {
+#pragma unroll
+                        for (int nt = 0; nt < NTL; ++nt) offer(stage, nt, h, s0, true);
+                    }
+                    __syncthreads();
+                    merge(stage);
+                    __syncthreads();
+                }
+            if (tid < RT) ovt[tid] = 0;
+            if (tid == 0) *ovf = 0;                               // read again after the fold's barrier at the earliest
+        }
+    };
+    auto fold = [&](int g, int buf) {
+        if constexpr (TOPN) select(g, buf);
         const int s0 = g * HS_STRIPS + wave * HS_SPW;
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt) {
@@ -5668,7 +5755,7 @@ __global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const Head
             xissue((it + 1) % nchunk, (it + 1) & 1);
         }
         mma(cur, it & 1);
-        if (c == nchunk - 1) fold(g0 + it / nchunk);              // block-uniform; `red` is rewritten one barrier later at the earliest
+        if (c == nchunk - 1) fold(g0 + it / nchunk, it & 1);      // block-uniform; `red` is rewritten one barrier later at the earliest
         __syncthreads();
         cur = nxt;
     }
@@ -5678,14 +5765,21 @@ __global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const Head
         o[1] = run.s;
         o[2] = s_xt[tid];
     }
+    if constexpr (TOPN)                                           // the last merge is behind the K loop's closing barrier
+        for (int i = tid; i < RT * n; i += HS_WAVES * 64)
+            if (t0 + i / n < a.n_rows) lists[((long)(t0 + i / n) * splits + sp) * n + i % n] = list[i];
 }
 
-// one wave per row: lane l merges partials l, l + 64, ... in order, then the xor butterfly (score_merge is symmetric bit for bit, so the lanes agree)
-__global__ __launch_bounds__(256) void head_score_combine_kernel(const float *ws, const unsigned *targets, float *out, int n_rows, int splits, int V) {
-    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n_rows) return;
-    ScorePair p{-INFINITY, 0.f};
-    float xt = -INFINITY;
+template <bool HILO, int NTL>
+__global__ __launch_bounds__(HS_WAVES * 64, 2) void head_score_kernel(const HeadScoreArgs a, const int gpb, const int splits) {
+    hs_block<HILO, NTL, false>(a, gpb, splits, 0, nullptr);
+}
+
+// one wave per row: lane l merges partials l, l + 64, ... in order, then the xor butterfly (score_merge is symmetric bit for bit, so the lanes agree).
+// head_score_combine_kernel and head_topn_combine_kernel both run THIS merge and THIS expression.
+__device__ __forceinline__ void hs_combine_row(const float *ws, int row, int splits, int lane, ScorePair &p, float &xt) {
+    p = ScorePair{-INFINITY, 0.f};
+    xt = -INFINITY;
     for (int i = lane; i < splits; i += 64) {
         const float *q = ws + ((long)row * splits + i) * 3;
         p = score_merge(p, ScorePair{q[0], q[1]});
@@ -5696,8 +5790,18 @@ __global__ __launch_bounds__(256) void head_score_combine_kernel(const float *ws
         p = score_merge(p, ScorePair{__shfl_xor(p.m, k, 64), __shfl_xor(p.s, k, 64)});
         xt = fmaxf(xt, __shfl_xor(xt, k, 64));
     }
-    if (lane == 0)                                                // as score_rows_kernel: not scored -> NaN; poisoned -> NaN; a target at -inf -> -inf
-        out[row] = targets[row] >= (unsigned)V ? __builtin_nanf("") : p.s != p.s ? p.s : xt == -INFINITY ? -INFINITY : (xt - p.m) - logf(p.s);
+}
+// as score_rows_kernel: not scored -> NaN; poisoned -> NaN; a target at -inf -> -inf
+__device__ __forceinline__ float hs_target_logp(unsigned target, int V, ScorePair p, float xt) {
+    return target >= (unsigned)V ? __builtin_nanf("") : p.s != p.s ? p.s : xt == -INFINITY ? -INFINITY : (xt - p.m) - logf(p.s);
+}
+__global__ __launch_bounds__(256) void head_score_combine_kernel(const float *ws, const unsigned *targets, float *out, int n_rows, int splits, int V) {
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n_rows) return;
+    ScorePair p;
+    float xt;
+    hs_combine_row(ws, row, splits, lane, p, xt);
+    if (lane == 0) out[row] = hs_target_logp(targets[row], V, p, xt);
 }
 
 int head_score_prepare() {                                         // 128-row tiles with hi + lo need 68.5 KiB of LDS
@@ -5715,5 +5819,94 @@ void launch_head_score(const HeadScoreArgs &a, hipStream_t s) {
     else hipLaunchKernelGGL((head_score_kernel<false, 4>), grid, block, lds, s, a, gpb, splits);
     hipLaunchKernelGGL(head_score_combine_kernel, dim3((a.n_rows + 3) / 4), dim3(256), 0, s, a.ws, a.targets, a.out, a.n_rows, splits, a.V);
 }
-#endif  // part 9: head_score
+
+// =====================================================================================
+// head_topn: the n most likely tokens of every row of a step, with their ln-probabilities and the target's, inside the head GEMM — head_score's
+// block (hs_block above, TOPN) plus a selection over every finished 128 x RT accumulator tile before it is dropped (rwkv_infer_topn_fused).
+//
+// An entry is topn_comp's composite (order-preserving key of the logit << 32 | ~id): distinct per token, so "the n largest composites" is "logit
+// descending, ties to the lower id" and a list is a function of the SET of candidates, not of the order lanes hand them in.  Each token of the tile
+// keeps its n best so far in LDS, sorted; place n - 1 is its threshold.  Per group:
+//   offer   every lane compares its 8 values per token with the token's threshold; a survivor takes a slot of the token's stage (an LDS atomic) —
+//           after a block's first group few values pass (n / (values seen) of them on a row without structure);
+//   merge   a wave per token ranks list + staged entries (<= 32 + HT_STAGE keys, one per lane) and rewrites the list; tokens with nothing staged cost
+//           one LDS read;
+//   redo    a token that staged more than HT_STAGE entries (always in a block's first group, where the list is empty; every group when logits rise
+//           with the id) is merged again from its unchanged list, one (wave, strip) = 16 candidates a round, eight rounds with the threshold
+//           tightening in between: the stage cannot overflow, whatever the values.
+// The stage is the operand buffer the group's last chunk came from (free until the K loop's next barrier), so the lists cost RT n 8 + RT 8 + 16
+// bytes of LDS over hs_lds_bytes: <true, 8> (128-row tiles, hi + lo) 69.5 KiB + n KiB — 101.5 KiB at n = 32 (one block per CU of 160 KiB), 74.5 KiB
+// at n = 5; two blocks per CU fit up to n = 10.  <false, 8>: 37.5 KiB + n KiB, <true, 4>: 34.75 KiB + n / 2 KiB, <false, 4>: 18.75 KiB + n / 2 KiB: two
+// blocks at every n.
+// At the end of its range the block writes its n composites per row beside head_score's (m, s, x_target); head_topn_combine_kernel merges the
+// splits' lists and emits (x - m) - ln s per entry with head_score_combine_kernel's (m, s).  The logit is read back from the composite's key: the
+// accumulator's bits, except that -0 is listed as +0 (which changes no logp unless m = 0 and s = 1).
+// =====================================================================================
+constexpr size_t ht_lds_bytes(bool hilo, int ntl, int n) { return hs_lds_bytes(hilo, ntl) + (size_t)ntl * 16 * ((size_t)n * 8 + 8) + 16; }
+static_assert(HT_STAGE * 8 * 16 <= HS_KTC * 1024, "a token tile's stage fits the operand buffer of a token tile");
+static_assert(TOPN_MAX <= 32 && HT_STAGE <= 32, "merge: list in lanes 0..31, stage in lanes 32..63");
+
+template <bool HILO, int NTL>
+__global__ __launch_bounds__(HS_WAVES * 64, 2) void head_topn_kernel(const HeadTopnArgs a, const int gpb, const int splits) {
+    hs_block<HILO, NTL, true>(a.hs, gpb, splits, a.n, a.lists);
+}
+
+// one wave per row.  (m, s, x_target): head_score_combine_kernel's merge.  Lists: lane i < n holds place i of the running list; the splits' entries are
+// read 64 at a time and those above the running threshold inserted one by one (a ballot gives the place, the tail moves down a lane).  Each split's
+// list is sorted, so after the first splits whole reads pass without an insertion.
+__global__ __launch_bounds__(256) void head_topn_combine_kernel(const HeadTopnArgs a, const int splits) {
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int n = a.n, V = a.hs.V;
+    if (row >= a.hs.n_rows) return;
+    ScorePair p;
+    float xt;
+    hs_combine_row(a.hs.ws, row, splits, lane, p, xt);
+    if (lane == 0) a.hs.out[row] = hs_target_logp(a.hs.targets[row], V, p, xt);
+    if (p.s != p.s) {                                             // +inf or NaN in the row (wave-uniform): nothing is listed
+        if (lane < n) { a.out_ids[(long)row * n + lane] = TOPN_NONE; a.out_logp[(long)row * n + lane] = p.s; }
+        return;
+    }
+    const u64 *src = a.lists + (long)row * splits * n;
+    const int total = splits * n;
+    u64 mine = 0ull, thr = 0ull;
+    for (int base = 0; base < total; base += 64) {
+        const u64 k = base + lane < total ? src[base + lane] : 0ull;
+        u64 pass = __ballot(k > thr);
+        while (pass) {
+            const int j = __ffsll((long long)pass) - 1;
+            pass &= pass - 1;
+            const u64 s = ht_readlane(k, j);
+            if (s <= thr) continue;                                // the threshold rose since the ballot
+            const int place = __popcll(__ballot(mine > s));
+            const u64 up = __shfl_up(mine, 1, 64);
+            mine = lane >= n ? 0ull : lane < place ? mine : lane == place ? s : up;
+            thr = ht_readlane(mine, n - 1);
+        }
+    }
+    if (lane < n) {
+        const unsigned key = (unsigned)(mine >> 32);
+        const float x = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+        a.out_ids[(long)row * n + lane] = mine ? 0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull) : TOPN_NONE;
+        a.out_logp[(long)row * n + lane] = mine ? (x - p.m) - logf(p.s) : -INFINITY;
+    }
+}
+
+int head_topn_prepare() {                                         // the 128-row forms pass 64 KiB of LDS: 101.5 KiB with hi + lo, 69.5 KiB without, at TOPN_MAX places
+    const hipError_t e = hipFuncSetAttribute((const void *)head_topn_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ht_lds_bytes(true, 8, TOPN_MAX));
+    if (e != hipSuccess) return (int)e;
+    return (int)hipFuncSetAttribute((const void *)head_topn_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ht_lds_bytes(false, 8, TOPN_MAX));
+}
+void launch_head_topn(const HeadTopnArgs &a, hipStream_t s) {
+    const bool hilo = a.hs.xlo != nullptr;
+    const int ntl = a.hs.n_rows > HEAD_SCORE_ROWS ? 8 : 4;
+    const int splits = head_score_splits(a.hs.V), gpb = head_score_groups_per_block(a.hs.V);
+    const dim3 grid((unsigned)(((a.hs.n_rows + ntl * 16 - 1) / (ntl * 16)) * splits)), block(HS_WAVES * 64);
+    const size_t lds = ht_lds_bytes(hilo, ntl, a.n);
+    if (hilo && ntl == 8) hipLaunchKernelGGL((head_topn_kernel<true, 8>), grid, block, lds, s, a, gpb, splits);
+    else if (hilo) hipLaunchKernelGGL((head_topn_kernel<true, 4>), grid, block, lds, s, a, gpb, splits);
+    else if (ntl == 8) hipLaunchKernelGGL((head_topn_kernel<false, 8>), grid, block, lds, s, a, gpb, splits);
+    else hipLaunchKernelGGL((head_topn_kernel<false, 4>), grid, block, lds, s, a, gpb, splits);
+    hipLaunchKernelGGL(head_topn_combine_kernel, dim3((a.hs.n_rows + 3) / 4), dim3(256), 0, s, a, splits);
+}
+#endif  // part 9: head_score, head_topn
 }  // namespace rwkv

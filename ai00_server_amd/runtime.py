@@ -109,6 +109,9 @@ ABI_SYMBOLS = {
     "rwkv_topn_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t]),
     "rwkv_infer_topn": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.c_int32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
                                     C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rwkv_infer_topn_fused": (C.c_int32, [C.c_void_p, C.POINTER(_SlotInC), C.c_int32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)),
+                                          C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_size_t)]),
     "rwkv_gen_set_topn": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "rwkv_gen_run_topn": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
@@ -1012,6 +1015,15 @@ class Runtime:
         token of a `Full` slot (a token id or `SCORE_SKIP`): the realised token is scored on its row as `infer_score` does.
         Returns (inp, targets, lists): tokens and targets drained by what the call consumed; `lists[b]` is None for a slot that did not
         list, else (ids uint32 [rows, n], logp float32 [rows, n], tok_logp float32 [rows] or None)."""
+        return self._infer_topn(lib().rwkv_infer_topn, inp, n, targets, listing)
+
+    def infer_topn_fused(self, inp: RnnInput, n: int, targets=None, listing=None):
+        """`infer_topn` with the lists and scores taken inside the head GEMM (rwkv_infer_topn_fused): the same arguments and returns, no logits
+        array on the device.  Every logp is `infer_score_fused`'s value for that row and id, bit for bit; ids are ordered by this path's own
+        logits, so tokens whose logits differ by less than the two paths do may change places against `infer_topn`."""
+        return self._infer_topn(lib().rwkv_infer_topn_fused, inp, n, targets, listing)
+
+    def _infer_topn(self, entry, inp: RnnInput, n: int, targets, listing):
         B = self.max_batch
         if len(inp.batches) != B or (targets is not None and len(targets) != B) or (listing is not None and len(listing) != B):
             raise RwkvError(-1, f"infer_topn needs max_batch={B} entries")
@@ -1041,7 +1053,7 @@ class Runtime:
                 op[b] = o[2].ctypes.data_as(C.POINTER(C.c_float))
             outs.append(o)
         n_rows, consumed = (C.c_size_t * B)(), (C.c_size_t * B)()
-        _check(lib().rwkv_infer_topn(self._h, ins, int(n), ip, lp, tp if targets is not None else None, op if targets is not None else None, n_rows, consumed))
+        _check(entry(self._h, ins, int(n), ip, lp, tp if targets is not None else None, op if targets is not None else None, n_rows, consumed))
         del keep
         rest = None if targets is None else []
         for b, ib in enumerate(inp.batches):

@@ -56,6 +56,8 @@ extern "C" {
                               *    row at the prompt's end and at a stop) and arms a slot from a cached item
                               *    additive under 9: rwkv_infer_score_fused: rwkv_infer_score with the softmax statistics taken in the head GEMM's
                               *    epilogue, no logits array in between (another summation order: its own bound, not rwkv_score_rows' bits)
+                              *    additive under 9: rwkv_infer_topn_fused: rwkv_infer_topn with the lists and the scores taken in the head GEMM's
+                              *    epilogue, no logits array in between (rwkv_infer_score_fused's bits, its own order among near-ties)
                               *    additive under 9 (no new symbol, no struct changed): RWKV_QUANT_SF4 — `Quant::SF4` models load: NF4's storage read
                               *    through the Student-t code book; rwkv_bench_gemm takes fmt 3 */
 
@@ -313,6 +315,25 @@ rwkv_status rwkv_topn_rows(rwkv_engine *e, const float *const *in, int32_t n, ui
  * rwkv_infer does); errors, thread contract and disarming rule of rwkv_infer. */
 rwkv_status rwkv_infer_topn(rwkv_engine *e, const rwkv_slot_input *in, int32_t n, uint32_t *const *out_ids, float *const *out_logp,
                             const uint32_t *const *targets, float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
+/* rwkv_infer_topn with the lists taken INSIDE the head GEMM: same arguments, plan, rwkv_plan_chunk split, step shapes, meaning of the options,
+ * n_rows, n_consumed, refusals, thread contract and disarming rule; the lists are for the same rows as rwkv_infer_topn's at the same occupancy.
+ * What differs:
+ *  - no [rows, num_vocab] logits array is written or read by the step (at token_chunk_size 2048 and num_vocab 65536 that is 512 MiB each way):
+ *    every output tile of the head is reduced to the softmax statistics and the tile's candidates for each row's list where it is computed.
+ *  - order: by the logits as THIS path's accumulators hold them, descending, ties to the lower id (-0 equals +0).  The accumulators are another
+ *    summation order than the plain head's, so two tokens whose logits differ by less than the difference of the two paths may change places
+ *    against rwkv_infer_topn; nothing else may.
+ *  - bits: every listed logp and every out_tok_logp is (x - m) - ln s with (m, s) reduced exactly as rwkv_infer_score_fused reduces them (the
+ *    same kernel code, vocabulary split and merge order).  out_tok_logp is bit for bit rwkv_infer_score_fused's value for the same call, a listed
+ *    id's logp bit for bit what rwkv_infer_score_fused gives with that id as target, and both are within that path's bound of a float64
+ *    evaluation, not rwkv_score_rows' bits.
+ *  - a row's list depends on its own operand bits, n, num_vocab and the model's dimensions, not on the rows that ride along or on its place in
+ *    the step.
+ * Fewer than n entries above -inf leave (RWKV_TOPN_NONE, -inf) in the places left, a row holding +inf or NaN gives (RWKV_TOPN_NONE, NaN) in
+ * all n places, RWKV_SCORE_SKIP a quiet NaN, as above.  The first call allocates rows x splits x n x 8 bytes of list workspace on the device
+ * (token_chunk_size rows, up to 256 vocabulary splits: 128 MiB at 2048 rows and n = 32) and a call with a larger n replaces it. */
+rwkv_status rwkv_infer_topn_fused(rwkv_engine *e, const rwkv_slot_input *in, int32_t n, uint32_t *const *out_ids, float *const *out_logp,
+                                  const uint32_t *const *targets, float *const *out_tok_logp, size_t *n_rows, size_t *n_consumed);
 
 /* ---- on-device sampling front-end: what `sample()` run.rs:664-697 + NucleusSampler::sample
  * (sampler/nucleus.rs:69-101) do with three PCIe hops and a 65,536-element CPU sort, done on the device.

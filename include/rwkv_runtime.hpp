@@ -307,6 +307,16 @@ class Runtime {
     // of which targets[b] is empty or holds one target per pending token of a Full slot (a token id or RWKV_SCORE_SKIP): the realised token
     // is scored on its row exactly as infer_score() does.  `input` and `targets` are consumed in place.  No row crosses PCIe.
     std::vector<TopLists> infer_topn(RnnInput &input, int n, std::vector<std::vector<uint32_t>> &targets) {
+        return infer_topn_by(rwkv_infer_topn, input, n, targets);
+    }
+    // rwkv_infer_topn_fused: infer_topn() with the lists and scores taken inside the head GEMM, no logits array on the device.  Every logp is
+    // infer_score_fused()'s value for that row and id, bit for bit; tokens whose logits differ by less than the two paths do may change places.
+    std::vector<TopLists> infer_topn_fused(RnnInput &input, int n, std::vector<std::vector<uint32_t>> &targets) {
+        return infer_topn_by(rwkv_infer_topn_fused, input, n, targets);
+    }
+
+   private:
+    std::vector<TopLists> infer_topn_by(decltype(&rwkv_infer_topn) entry, RnnInput &input, int n, std::vector<std::vector<uint32_t>> &targets) {
         if ((int)input.batches.size() != max_batch || (!targets.empty() && (int)targets.size() != max_batch)) throw std::invalid_argument("infer_topn: need max_batch entries");
         if (n < 1 || n > RWKV_TOPN_MAX) throw std::invalid_argument("infer_topn: n must be 1..RWKV_TOPN_MAX");
         std::vector<rwkv_slot_input> in((size_t)max_batch);
@@ -332,8 +342,8 @@ class Runtime {
             tp[b] = targets[b].data();
             op[b] = out[b].tok_logp.data();
         }
-        check(rwkv_infer_topn(e_.get(), in.data(), n, ip.data(), lp.data(), targets.empty() ? nullptr : tp.data(), targets.empty() ? nullptr : op.data(),
-                              n_rows.data(), consumed.data()));
+        check(entry(e_.get(), in.data(), n, ip.data(), lp.data(), targets.empty() ? nullptr : tp.data(), targets.empty() ? nullptr : op.data(),
+                    n_rows.data(), consumed.data()));
         for (size_t b = 0; b < (size_t)max_batch; ++b) {
             auto &t = input.batches[b].tokens;
             t.erase(t.begin(), t.begin() + (long)consumed[b]);
@@ -346,6 +356,8 @@ class Runtime {
         }
         return out;
     }
+
+   public:
     // Device-resident sampled generation (rwkv_gen_arm / _run / _disarm): arm a slot with `sampler.gen_params_for(...)`
     // (include/rwkv_sampler.hpp), then every gen_run generates up to n_steps tokens per armed slot without a host turn-around.
     void gen_arm(int slot, const rwkv_gen_params &p) { check(rwkv_gen_arm(e_.get(), slot, &p)); }

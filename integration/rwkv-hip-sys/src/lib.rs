@@ -150,6 +150,9 @@ extern "C" {
     pub fn rwkv_topn_rows(e: *mut rwkv_engine, inp: *const *const f32, n: i32, out_ids: *mut u32, out_logp: *mut c_float, n_rows: usize) -> rwkv_status;
     pub fn rwkv_infer_topn(e: *mut rwkv_engine, inp: *const rwkv_slot_input, n: i32, out_ids: *const *mut u32, out_logp: *const *mut c_float,
                            targets: *const *const u32, out_tok_logp: *const *mut c_float, n_rows: *mut usize, n_consumed: *mut usize) -> rwkv_status;
+    // the same call with the lists and scores taken inside the head GEMM: no logits array on the device, rwkv_infer_score_fused's bits
+    pub fn rwkv_infer_topn_fused(e: *mut rwkv_engine, inp: *const rwkv_slot_input, n: i32, out_ids: *const *mut u32, out_logp: *const *mut c_float,
+                                 targets: *const *const u32, out_tok_logp: *const *mut c_float, n_rows: *mut usize, n_consumed: *mut usize) -> rwkv_status;
     pub fn rwkv_gen_set_topn(e: *mut rwkv_engine, slot: i32, n: i32) -> rwkv_status;
     pub fn rwkv_gen_run_topn(e: *mut rwkv_engine, n_steps: i32, out_tokens: *mut u32, out_probs: *mut c_float, n_emitted: *mut i32, finish: *mut i32,
                              n_top: i32, out_tok_logp: *mut c_float, out_top_ids: *mut u32, out_top_logp: *mut c_float) -> rwkv_status;
