@@ -355,4 +355,25 @@ inline GemmPlan plan_gemm(GemmLaunch &Lh, const ProbShape *ps, int n, int T, boo
     return {GEMM_DECODE, Lh.single_shot, Lh.total_blocks + (has_commit ? 1 : 0), Lh.threads, np};
 }
 
+// Geometry of the one-launch forms of v6_mix_kernel (v6_mix_supported: T <= 32, C % 256 == 0): grid (gx strip groups, 5 mixes, gz token tiles
+// of NT x 16 rows), 512 threads; strip group g owns strips [g sq + min(g, sr), + sq + (g < sr)), one per wave.  launch_v6_mix executes it.
+//  * T <= 16, and T <= LNP_MAX_T with the LayerNorm prologue (lnp_bytes: its extra LDS): one token tile, groups of 8 strips;
+//  * 17 .. 32 rows: the token-tile form — a block owns one 16-token tile, so its phase 1 pulls W1_c and HALF of z, and the groups are sized for
+//    one block per CU: the most groups that keep 5 x 2 x gx <= 256 (25: at C = 2560 groups of 6 or 7 strips), never more than 8 strips a group.
+//    Alternating bench processes, V6-3B Int8: 2.273 -> 2.231 ms per step at 32 slots, 2.136 -> 2.093 at 20, 2.105 -> 2.070 at 17
+//    (profiles/r21_v6_mix_decode_ab.jsonl).
+struct V6MixPlan { int NT, gx, gz, sq, sr; size_t lds; };
+inline V6MixPlan v6_mix_plan(int T, int C, int Dm, size_t lnp_bytes) {
+    const int S = C >> 4, gmin = (S + 7) / 8;                           // strips; groups of at most 8 (a block has 8 waves)
+    V6MixPlan p{1, gmin, 1, 8, 0, 0};
+    if (T > 16) {
+        p.gz = 2;
+        p.gx = std::max(gmin, std::min(S, 256 / (5 * p.gz)));
+    }
+    p.sq = S / p.gx;
+    p.sr = S % p.gx;
+    p.lds = (size_t)8 * 4 * p.NT * 64 * 16 + (size_t)2 * p.NT * 16 * (Dm + 8) * 2 + lnp_bytes;     // K partials [8][4][NT][64] f32x4, m_c hi + lo
+    return p;
+}
+
 }  // namespace rwkv

@@ -164,6 +164,7 @@ struct V6MixArgs {
     _Float16 *mg_hi = nullptr, *mg_lo = nullptr;   // scratch for the two-launch form (>= 512 rows): m_c tiles [5][T/32][32][Dm]
     float *mp = nullptr;                           // fp32 partials of phase 1 sliced over K (192 .. 511 rows): [ksp][5][T][Dm]
     int ksp = 1, ksp_min_t = 192, ksp_blocks = 160, ksp_max = 16;   // slices (set by launch_v6_mix); rule parameters (engine knobs)
+    int sq = 8, sr = 0;             // one-launch forms of T <= 32 (set by launch_v6_mix from v6_mix_plan): strip group g owns sq + (g < sr) strips
 };
 bool v6_mix_supported(int T, int C, int Dm);
 bool v6_mix_wide_supported(int T, int C, int Dm);                   // steps with more than 32 rows: block = (mix, 32-token tile), all strips

@@ -829,6 +829,12 @@ void launch_gemm(const GemmLaunch &L, bool hilo, hipStream_t s) {
 // Dm x C fp16 = 164 KiB from L2, recomputed by the C/128 blocks of that c), park the partials in LDS, reduce,
 // apply tanh and keep m_c in LDS as the f16 (hi, lo) operand; then wave w multiplies strip w of W2_c (K = Dm)
 // with it and applies the lerp epilogue, emitting the five GEMM operands.
+// TOKEN TILES (17 .. 32 rows; gemm_plan.h v6_mix_plan): grid (25, 5, 2) at C = 2560 — a block owns one mix, ONE 16-token tile and a group of
+// 6 or 7 strips, so its phase 1 pulls W1_c + half of z (246 KB instead of 328 KB through one CU) and 250 of the 256 CUs have a block.  The K
+// split over the waves, the order of the LDS reduce, the tanh, the (hi, lo) rounding of m_c and the epilogue are per token what they were: only
+// the ownership of (token tile, strip) pairs differs, and the outputs are the same bits.  rocprofv3: 7.63 -> 6.64 us per launch; alternating
+// bench processes 2.273 -> 2.231 ms per 32-slot step (profiles/r21_v6_mix_decode_*).  (An earlier split of these rows into 200 blocks that kept
+// groups of 8 strips lost: 2.250 -> 2.267 ms, profiles/r3_exp_ab_v6mix_ksw8.log.)
 // =====================================================================================
 // WIDE (steps with more than 32 rows, prefill included): grid (1, 5, ceil(T/32)) — a block owns one mix c and one 32-token
 // tile, computes m_c for its tokens once and then walks ALL strips of W2_c (8 waves, strip = wave, wave+8, ...).  Per block:
@@ -863,20 +869,33 @@ __global__ __launch_bounds__(512) void v6_mix_kernel(const V6MixArgs a) {
 
     TRACE_K(0, 0);
     // phase-2 operands of this wave (W2 strip, mu, xx, dx): independent of phase 1, so fetched first — their L2/MALL
-    // latency hides behind phase 1 instead of following its barrier
-    const int strip = sg * 8 + wave;                              // >= C/16: idle in phase 2
+    // latency hides behind phase 1 instead of following its barrier.
+    const int nstrip = WIDE ? 8 : a.sq + (sg < a.sr ? 1 : 0);     // strips of this group (v6_mix_plan); waves beyond them idle in phase 2
+    const int strip = WIDE ? sg * 8 + wave : sg * a.sq + min(sg, a.sr) + wave;
     const int strip_c = min(strip, (C >> 4) - 1);
     const int row0 = strip_c * 16 + (lane >> 4) * 4;
     u32x4 w2t[DS / 2];
     float4 xxv[NT], dxv[NT];
     float4 mu = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (!WIDE) {
+    const act_t bxx = act_buf(a.xx), bdx = act_buf(a.dx), bzh = act_buf(a.zhi), bzl = act_buf(a.zlo);
+    const act_t boh = act_buf(a.ohi[c]), bol = act_buf(a.olo[c]);
+    auto fetch_w2 = [&]() {
 #pragma unroll
         for (int ks = 0; ks < DS / 2; ++ks) w2t[ks] = ((const u32x4 *)a.W2[c])[((long)strip_c * (DS / 2) + ks) * 64 + lane];
         mu = *(const float4 *)(a.mu[c] + row0);
+    };
+    auto fetch_rows = [&]() {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            int t = t0 + nt * 16 + (lane & 15);
+            t = t < T ? t : T - 1;
+            xxv[nt] = act_ld4(bxx, (long)t * C + row0);
+            dxv[nt] = act_ld4(bdx, (long)t * C + row0);
+        }
+    };
+    if constexpr (!WIDE) {
+        fetch_w2();
     }
-    const act_t bxx = act_buf(a.xx), bdx = act_buf(a.dx), bzh = act_buf(a.zhi), bzl = act_buf(a.zlo);
-    const act_t boh = act_buf(a.ohi[c]), bol = act_buf(a.olo[c]);
     // LNP (single-token steps): LayerNorm + token shift are redone here by every block (ln_prologue_*): z arrives in LDS in
     // fragment order, xx and dx for the epilogue come from the prologue's LDS rows
     float *xx_l = (float *)(m_lo + NT * 16 * mstride);
@@ -915,13 +934,7 @@ __global__ __launch_bounds__(512) void v6_mix_kernel(const V6MixArgs a) {
             dxv[nt] = make_float4(pr.x - x.x, pr.y - x.y, pr.z - x.z, pr.w - x.w);
         }
     } else if constexpr (!WIDE) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            int t = t0 + nt * 16 + (lane & 15);
-            t = t < T ? t : T - 1;
-            xxv[nt] = act_ld4(bxx, (long)t * C + row0);
-            dxv[nt] = act_ld4(bdx, (long)t * C + row0);
-        }
+        fetch_rows();
     }
     // ---- phase 1: partial m_c over this wave's K slice
     f32x4 acc[DS][NT];
@@ -1060,7 +1073,7 @@ __global__ __launch_bounds__(512) void v6_mix_kernel(const V6MixArgs a) {
             cur = nxt;
         }
     } else {
-        if (strip < (C >> 4)) do_strip(strip, w2t, mu, xxv, dxv);
+        if (wave < nstrip && strip < (C >> 4)) do_strip(strip, w2t, mu, xxv, dxv);
     }
     TRACE_K(0, 4);
 }
@@ -1188,14 +1201,10 @@ void launch_v6_mix(const V6MixArgs &a, bool hilo, hipStream_t s) {
     // (the wide form — 40 blocks that each walk every strip — for 17..32 rows too: 2.250 -> 2.36 ms per 32-slot step,
     // profiles/r3_exp_ab_v6mix_wide_for_32_rows.log; 100 blocks of 8 strips is the measured optimum between that and the 200-block split)
     const bool wide = a.T > 32;                                // v6_mix_wide_supported: one block per (mix, 32-token tile)
-    // (17..32 rows as two NT = 1 token tiles — 200 workgroups that each pull W1_c + half of z — was measured and dropped: every
-    // workgroup still pulls all of W1_c, so the launch's L2 traffic grows by half: 2.250 -> 2.267 ms per 32-slot step,
-    // profiles/r3_exp_ab_v6mix_ksw8.log.)
-    const int NT = (a.T <= 16 && !wide) ? 1 : 2;
     const bool lnp = a.lnp.x_in != nullptr;                    // host: T <= LNP_MAX_T, !hilo, C <= 4096 (v6_mix_ln_supported)
-    const size_t lds = (size_t)8 * 4 * NT * 64 * 16 + (size_t)2 * NT * 16 * (a.Dm + 8) * 2 + (lnp ? lnp_lds_bytes(LNP_MAX_T, a.C, hilo) : 0);
-    dim3 grid((a.C / 16 + 7) / 8, 5, 1), block(512);
+    dim3 grid(1, 5, 1), block(512);
     if (wide) {
+        const size_t lds = (size_t)8 * 4 * 2 * 64 * 16 + (size_t)2 * 2 * 16 * (a.Dm + 8) * 2;
         const int ntile = (a.T + 31) / 32;
         grid = dim3(std::max(1, std::min(8, 256 / (5 * ntile))), 5, ntile);   // fill the chip when the step has few token tiles
         V6MixArgs b = a;
@@ -1228,11 +1237,17 @@ void launch_v6_mix(const V6MixArgs &a, bool hilo, hipStream_t s) {
         (void)hipFuncSetAttribute((const void *)v6_mix_kernel<1, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done[dev & 15] = true;
     }
-#define V6L(nt, h, ds, ln) hipLaunchKernelGGL((v6_mix_kernel<nt, h, ds, ln>), grid, block, lds, s, a)
+    // (17 .. 32 rows are two 16-token tiles of the NT = 1 kernel, v6_mix_plan: the NT = 2 instantiations serve the wide and split forms only)
+    const V6MixPlan pl = v6_mix_plan(a.T, a.C, a.Dm, lnp ? lnp_lds_bytes(LNP_MAX_T, a.C, hilo) : 0);
+    V6MixArgs b = a;
+    b.sq = pl.sq;
+    b.sr = pl.sr;
+    grid = dim3(pl.gx, 5, pl.gz);
+#define V6L(h, ds, ln) hipLaunchKernelGGL((v6_mix_kernel<1, h, ds, ln>), grid, block, pl.lds, s, b)
     const int DS = a.Dm >> 4;
-    if (lnp) { if (DS == 2) V6L(1, false, 2, true); else V6L(1, false, 4, true); }
-    else if (hilo) { if (NT == 1) { if (DS == 2) V6L(1, true, 2, false); else V6L(1, true, 4, false); } else { if (DS == 2) V6L(2, true, 2, false); else V6L(2, true, 4, false); } }
-    else      { if (NT == 1) { if (DS == 2) V6L(1, false, 2, false); else V6L(1, false, 4, false); } else { if (DS == 2) V6L(2, false, 2, false); else V6L(2, false, 4, false); } }
+    if (lnp) { if (DS == 2) V6L(false, 2, true); else V6L(false, 4, true); }
+    else if (hilo) { if (DS == 2) V6L(true, 2, false); else V6L(true, 4, false); }
+    else { if (DS == 2) V6L(false, 2, false); else V6L(false, 4, false); }
 #undef V6L
 }
 bool v6_mix_ln_supported(int T, int C, int Dm, bool hilo, int np) {
